@@ -78,7 +78,13 @@ def parse():
     ap.add_argument("--dry-launch", action="store_true",
                     help="self-test of the --gpus N launcher: the ranks rendezvous over gloo on the CPU, reduce their ranks and "
                          "rank 0 prints one JSON line; no GPU is touched (tests/test_bench_launcher.py)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: its entity rows, the visible "
+                         "id list, its particles) as DIR/<name>.npy, float32 / float64, under 64 MB (seeded row samples)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -475,6 +481,46 @@ class RankStep:
         self.xch.submit()
 
 
+DUMP_SEED = 0
+DUMP_ROWS = 200_000          # rows kept of a 2-D output (of the matrices: 200 000 x 16 floats, 12.8 MB)
+DUMP_IDS = 1 << 20           # ids kept of the visible list (float64: 8 MB)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _dump_sample(out, prefix, arrays, cap):
+    """Put `arrays` (same leading length) into `out`; beyond `cap` rows, the same seeded sample of rows of each, the row
+    numbers as `<prefix>_rows`.  The sample depends on the length alone, so equal runs sample equal rows."""
+    n = next(iter(arrays.values())).shape[0]
+    if n > cap:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+        out[prefix + "_rows"] = rows.astype(np.float64)
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    out.update(arrays)
+
+
+def dump_outputs(path, batch, visible, pbatch):
+    """--dump-outputs: the arrays a caller of the timed step receives after its last step -- world matrices, inverses,
+    AABBs and centres of every entity row, the ascending visible id list (global with an exchange), and the particles'
+    positions and velocities when the step updates particles.  Ids go out as float64 (exact), the rest as float32."""
+    import torch
+    torch.cuda.synchronize()
+    ent = batch.download()
+    out = {"visible_count": np.asarray([visible.size], np.float64)}
+    _dump_sample(out, "entity", {"entity_" + k: np.ascontiguousarray(ent[k], np.float32)
+                                 for k in ("mx", "inv_mx", "aabb", "center")}, DUMP_ROWS)
+    _dump_sample(out, "visible", {"visible": visible.astype(np.float64)}, DUMP_IDS)
+    if pbatch is not None:
+        p = pbatch.download()
+        _dump_sample(out, "particle", {"particle_pos": np.ascontiguousarray(p["pos"], np.float32),
+                                       "particle_vel": np.ascontiguousarray(p["vel"], np.float32)}, DUMP_ROWS)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return total
+
+
 def main():
     args = parse()
     if args.c5:
@@ -560,6 +606,10 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = world * n_real * args.steps / elapsed
     visible = int((xch.last()[0] if use_dist else batch.visible_count).item())
+    dumped = None
+    if args.dump_outputs and rank == 0:                      # before any later pass touches the step's buffers
+        ids = xch.last()[1] if use_dist else batch.visible
+        dumped = dump_outputs(args.dump_outputs, batch, ids[:visible].cpu().numpy().view(np.uint32), pbatch)
 
     # ---- N > 1, no explicit sizing: BASELINE configs[4]'s per-rank share as a SECOND timed leg of the same run, the same
     #      process group and the same communicator (16 M entities + 2 M particles at 8 GPUs).  The headline above stays
@@ -653,6 +703,8 @@ def main():
             out["ms_per_step_per_rank"] = rank_ms
         if c5 is not None:
             out["c5"] = c5
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
         extra = None
         if args.snapshot:
             out["data"] = "snapshot"
