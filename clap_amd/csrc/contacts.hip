@@ -480,7 +480,11 @@ extern "C" int clapgpu_contacts_geoms_both(void *stream, clapgpu_bp *bp, const c
     // as many workgroups as are resident at once: a wavefront then walks its chunks with the next one's inputs in flight
     static uint32_t cached;
     const uint32_t resident = resident_workgroups(reinterpret_cast<const void *>(k_contacts_geoms_both), &cached);
-    hipLaunchKernelGGL(k_contacts_geoms_both, dim3(blocks < resident ? blocks : resident), dim3(PB), 0, s, geoms_k(bodies), geoms_k(statics),
+    uint32_t grid = blocks < resident ? blocks : resident;
+    // the tickets are the word's top 16 bits: with more than 2^16 workgroups none would see the last one (totals never
+    // stored, the word never reset).  The grid-stride loop covers any list with fewer.
+    if (grid > (1u << 16)) grid = 1u << 16;
+    hipLaunchKernelGGL(k_contacts_geoms_both, dim3(grid), dim3(PB), 0, s, geoms_k(bodies), geoms_k(statics),
                        reinterpret_cast<const uint2 *>(pairs), pair_total, capacity, contacts, contact_total,
                        reinterpret_cast<const uint2 *>(static_pairs), static_pair_total, statics->n ? static_capacity : 0u,
                        static_contacts, static_contact_total, body_flags,
