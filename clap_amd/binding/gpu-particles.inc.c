@@ -132,7 +132,7 @@ static int gp_rebuild(struct gpu_particles *gp)
     if (!gp->d.pos || n > gp->cap_n || gp->n_sys > gp->cap_sys_dev) {
         gp_free_device(gp);
         const uint32_t cap = gp_pow2(n, 4096), cap_rows = cap / 64, cap_sys = gp_pow2(gp->n_sys ? gp->n_sys : 1, 16);
-        const bool mapped = cap <= GP_MAPPED_MAX && !getenv("GPU_PARTICLES_STAGED");
+        const bool mapped = cap <= GP_MAPPED_MAX;
         const size_t sys_bytes = (size_t)cap_sys * sizeof(clapgpu_particle_system);
         if (mapped) {
             void *a_pos = NULL, *a_vel = NULL, *a_mx = NULL, *a_sys = NULL, *a_rng = NULL;

@@ -1084,6 +1084,7 @@ static int cmd_edge(void)
     CASE("every hook foreign: nothing batched", 0, { for (int i = 0; i < 20; i++) mk(i % 3, NONE, true, true); });
     CASE("a parent with 200 children (level layout)", 603, { mk(0, NONE, false, true); for (int i = 0; i < 200; i++) mk(1 + i % 3, 0, false, true); });
     CASE("a chain 40 deep", 120, { mk(0, NONE, false, true); for (uint32_t i = 1; i < 40; i++) mk(0, i - 1, false, true); });
+    CASE("a chain 1000 deep", 3000, { mk(0, NONE, false, true); for (uint32_t i = 1; i < 1000; i++) mk(0, i - 1, false, true); });
     CASE("never positioned: mx stays as made", 30, { for (int i = 0; i < 10; i++) mk(0, NONE, false, i & 1); });
     CASE("children of a hooked parent stay on the host", 3, { mk(0, NONE, true, true); mk(1, 0, false, true); mk(1, 1, false, true); mk(2, NONE, false, true); });
     CASE("dead entities in the list", 15, { for (int i = 0; i < 10; i++) mk(i % 4, NONE, false, true);

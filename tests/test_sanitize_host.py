@@ -54,9 +54,6 @@ def test_binding_and_mirror_under_asan_ubsan():
     assert _run(exe, "test", 200, 40, 13, "notify", "drawn")["mismatches"] == 0
     assert _run(exe, "test", 6000, 16, 33, "notify", "drawn", "steady")["mismatches"] == 0
     assert _run(exe, "test", 1500, 10, 2)["mismatches"] == 0
-    # re-tiled frames with the serial second half (GPU_SCENE_RETILE_BY_MASK=0: the A/B switch keeps working)
-    assert _run(exe, "test", 2500, 12, 1, "notify", "drawn", "steady", env={"GPU_SCENE_RETILE_BY_MASK": "0"})["mismatches"] == 0
-    assert _run(exe, "test", 1500, 10, 2, env={"GPU_SCENE_RETILE_BY_MASK": "0"})["mismatches"] == 0
     r = _run(exe, "test", 20000, 12, 1, "steady")               # no notifications, >= 16 384 entities: the frames whose queue stood go by the records
     assert r["mismatches"] == 0 and r["frames_by_the_records"] >= 6 and r["fast_frames"] == 0
     r = _run(exe, "test", 2000, 24, 1, "steady")                # ... a small queue is walked (one thread would lose by the records)

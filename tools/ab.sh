@@ -7,8 +7,7 @@
 # Log: gpurun_out/<log name>.log (copy what should be judged into profiles/); stdout: one summary line per run.
 # What round 5's one-off scripts did, e.g.:
 #     tools/ab.sh r06/churn -e GPU_SCENE_INCREMENTAL=1 -e GPU_SCENE_INCREMENTAL=0 -- "bench 1000000 5 100 notify drawn churn 10" "bench 100000 10 100 notify drawn churn 10"
-#     tools/ab.sh r06/replay -r 3 -e GPU_SCENE_REPLAY_MIN=0 -e GPU_SCENE_REPLAY_MIN=16384 -- "bench 10000 400 100"
-#     tools/ab.sh r06/retile -t -e GPU_SCENE_RETILE_BY_MASK=1 -e GPU_SCENE_RETILE_BY_MASK=0 -- "bench 1000000 5 100 notify churn 10"   (with GPU_SCENE_INCREMENTAL=0 exported)
+#     tools/ab.sh r06/replay -r 3 -e GPU_SCENE_REPLAY=0 -e GPU_SCENE_REPLAY=1 -- "bench 10000 400 100"
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 D=$R/oracle/_ref/clap_dropin
 name=$1; shift
