@@ -26,6 +26,9 @@ E_SKIP_CULLING = 1 << 14
 E_DIRTY = 1 << 16
 E_JOINT_ATTACHED = 1 << 17
 E_ALIVE = 1 << 31
+RAY_INVALID = 1 << 0
+RAY_UNRESOLVED = 1 << 1
+RAY_MOVED_TARGET = 1 << 2
 UPDATE_ALL_DIRTY = 1 << 0
 
 _ERR_NAMES = {ERR_NOMEM: "NOMEM", ERR_INVALID_ARGUMENTS: "INVALID_ARGUMENTS", ERR_NOT_SUPPORTED: "NOT_SUPPORTED",
@@ -258,6 +261,13 @@ SYMBOLS = {
                                            C.POINTER(C.c_uint32)]),
     "clapgpu_bodies_step_prebin": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.c_double, C.c_void_p]),
     "clapgpu_bp_invalidate": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "clapgpu_bp_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "clapgpu_bp_index_status": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "clapgpu_ray_cast": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_uint32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_bodies_ground_collide": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_uint32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_visible_compact_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_characters_update_clock": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),

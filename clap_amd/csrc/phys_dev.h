@@ -409,4 +409,24 @@ PHD int collide(const Geom &a, const Geom &b, CGeom &c0, CGeom &c1)
     return nc;
 }
 
+// phys_body_ground_collide (physics.c:695-744) in dReal: the ray's offset below the body and its ray_len
+PHD double ground_ray_len(double ray_off, double yoffset, double &roff)
+{
+    const double epsilon = 1e-3, safety = 0.05;
+    roff = ray_off - safety;
+    return yoffset - roff + epsilon;
+}
+
+// ... its three branches on a hit at depth `dist`: the return value, and the vertical move phys_body_move receives
+// (a vec3, so float); move = false: the body stays
+PHD bool ground_branch(double dist, double ray_len, bool grounded, float &dy, bool &move)
+{
+    move = false;
+    dy = 0.0f;
+    if (grounded && dist > ray_len) { dy = (float)(-(dist - ray_len)); move = true; }   // was grounded: down onto it
+    else if (dist < ray_len) { dy = (float)(ray_len - dist); move = true; }             // sinking in: up
+    else if (dist > ray_len) return false;                                              // airborne
+    return true;
+}
+
 } // namespace phd

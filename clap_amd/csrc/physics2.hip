@@ -15,6 +15,7 @@
 #include <vector>
 #include "common.h"
 #include "phys_dev.h"
+#include "bp_grid.h"
 
 namespace clapgpu {
 
@@ -256,26 +257,12 @@ constexpr int BP_EMIT_TILE = 1024;     // bodies per tile of the pair-offset sca
 #endif
 constexpr int CTRL_STATUS = 2, CTRL_EPOCH = 3, CTRL_CONTACT_WORD = 8;   // [8..9]: clapgpu_contacts_geoms_both's ticket + counts, zero between launches     // the frame counter lives on the device: a captured graph replays the same arguments
 
-__host__ __device__ __forceinline__ uint32_t block_hash(int32_t bx, int32_t by, int32_t bz, uint32_t mask)
-{
-    const uint32_t h = ((uint32_t)bx * 73856093u) ^ ((uint32_t)by * 19349663u) ^ ((uint32_t)bz * 83492791u);
-    return (h ^ (h >> 15)) & mask;
-}
-
-__host__ __device__ __forceinline__ int32_t cell_coord(double x, double cell)
-{
-    double c = floor(x / cell);
-    if (!(c > -5.0e8)) c = -5.0e8;                                       // also catches NaN
-    if (c > 5.0e8) c = 5.0e8;
-    return (int32_t)c;
-}
-
-__host__ __device__ __forceinline__ uint32_t cell_slot(int32_t cx, int32_t cy, int32_t cz, uint32_t mask)
-{
-    return block_hash(cx >> 2, cy >> 2, cz >> 2, mask) << 6 | (uint32_t)(cx & 3) | (uint32_t)(cy & 3) << 2 | (uint32_t)(cz & 3) << 4;
-}
+// block_hash, cell_coord, cell_slot: bp_grid.h (the ray cast looks cells up with the same functions)
 
 struct BpRec { double bb[6]; uint32_t idx; int32_t cell[3]; };    // 64 bytes; cell = the box centre's cell (dynamic records)
+static_assert(CTRL_EPOCH == CTRL_BIN_EPOCH, "bp_grid.h's view of the control words");
+static_assert(sizeof(BpRec) == sizeof(GridRec) && offsetof(BpRec, idx) == offsetof(GridRec, idx) &&
+              offsetof(BpRec, cell) == offsetof(GridRec, cell), "bp_grid.h's view of the records");
 
 struct BpK {
     uint32_t n;
@@ -815,6 +802,91 @@ void k_bp_emit(BpK k)
     }
 }
 
+// clapgpu_bp_index's fourth launch: the indexed boxes' bounds and "an edge exceeds `cell`" into the index's own control
+// words (bp_grid.h), which the host set to all ones in front of it.  The sticky bit 0 of CTRL_STATUS is not this flag: it
+// reports any oversized box since the object was made, this one the boxes of the current index only.
+constexpr int BP_BOUNDS_BLOCKS = 512;
+__global__ __launch_bounds__(PB)
+void k_bp_index_bounds(BpK k)
+{
+    __shared__ double red[6][PB / WAVE];
+    __shared__ uint32_t big[PB / WAVE];
+    const int lane = lane_id(), wave = threadIdx.x / WAVE;
+    double m[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };     // min xyz, max xyz
+    uint32_t over = 0;
+    for (uint32_t i = blockIdx.x * PB + threadIdx.x; i < k.n; i += gridDim.x * PB) {
+        double bb[6];
+        load_box(k.aabb, i, bb);
+        if (bb[1] - bb[0] > k.cell || bb[3] - bb[2] > k.cell || bb[5] - bb[4] > k.cell) over = 1;   // k_bp_bin's test
+        // finite coordinates only: a geom at infinity or NaN never hits (rays.hip), and the bounds stay finite
+        for (int a = 0; a < 3; a++) {
+            if (isfinite(bb[2 * a])) m[a] = fmin(m[a], bb[2 * a]);
+            if (isfinite(bb[2 * a + 1])) m[3 + a] = fmax(m[3 + a], bb[2 * a + 1]);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        for (int a = 0; a < 3; a++) { m[a] = fmin(m[a], __shfl_xor(m[a], o)); m[3 + a] = fmax(m[3 + a], __shfl_xor(m[3 + a], o)); }
+        over |= __shfl_xor(over, o);
+    }
+    if (lane == 0) {
+        for (int a = 0; a < 6; a++) red[a][wave] = m[a];
+        big[wave] = over;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && threadIdx.x == 0)                             // the grid this index looked at (stream order: after its bins)
+        k.ctrl[CTRL_INDEX_EPOCH] = k.ctrl[CTRL_EPOCH];
+    if (threadIdx.x < 7) {
+        unsigned long long *w = reinterpret_cast<unsigned long long *>(k.ctrl + CTRL_INDEX_WORD);
+        const int a = threadIdx.x;
+        if (a == INDEX_OVERSIZE) {
+            uint32_t o = 0;
+            for (int q = 0; q < PB / WAVE; q++) o |= big[q];
+            if (o) atomicMin(&w[INDEX_OVERSIZE], 0ull);
+        } else {
+            double v = red[a][0];
+            for (int q = 1; q < PB / WAVE; q++) v = a < 3 ? fmin(v, red[a][q]) : fmax(v, red[a][q]);
+            if (a < 3 ? v < INFINITY : v > -INFINITY)                         // not the identity: this block has a box (NaN skipped)
+                atomicMin(&w[a], a < 3 ? order_key(v) : ~order_key(v));
+        }
+    }
+}
+
+// clapgpu_bodies_ground_collide's second launch (rays.hip casts, this moves): phys_body_move of every body whose ray
+// said so, through a vec3 (float), then the geom as clapgpu_bodies_aabb writes it.  A ray whose hit body moved here is
+// flagged: it saw that body where it was before the call.
+__global__ __launch_bounds__(PB)
+void k_ground_apply(BodiesK b, const double *yoffset, uint32_t n, const uint32_t *body, const double *ray_off,
+                    const uint8_t *grounded, uint8_t *grounded_out, const double *dist, const int32_t *hit, uint32_t *flags,
+                    const uint32_t *moved)
+{
+    const uint32_t j = blockIdx.x * PB + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t f = flags[j];
+    const int32_t h = hit[j];
+    const uint32_t i = body[j];
+    if (i >= b.n) return;                                                   // flagged invalid by the ray launch
+    if ((moved[i] >> 1) > 1) {                                              // listed twice: none of its rays moves it
+        flags[j] = f | CLAPGPU_RAY_INVALID;
+        grounded_out[j] = 0;
+        return;
+    }
+    if (f || h == -1) return;                                               // invalid, unresolved or a miss: nothing moves
+    double roff;
+    const double ray_len = phd::ground_ray_len(ray_off[j], yoffset[i], roff);
+    float dy;
+    bool mv;
+    phd::ground_branch(dist[j], ray_len, grounded[j] != 0, dy, mv);
+    if (h >= 0 && (uint32_t)h < b.n && (moved[h] & 1u) && (moved[h] >> 1) == 1) flags[j] = f | CLAPGPU_RAY_MOVED_TARGET;
+    if (!mv) return;
+    const float d[3] = { 0.0f, dy, 0.0f };
+    double *pp = b.pos + 3 * (size_t)i;
+    const double p[3] = { pp[0] + d[0], pp[1] + d[1], pp[2] + d[2] };     // dBodySetPosition(pos + delta)
+    pp[0] = p[0]; pp[1] = p[1]; pp[2] = p[2];
+    const double q[4] = { b.quat[4 * (size_t)i], b.quat[4 * (size_t)i + 1], b.quat[4 * (size_t)i + 2], b.quat[4 * (size_t)i + 3] };
+    write_geom(b, i, p, q);
+}
+
 } // namespace clapgpu
 
 using namespace clapgpu;
@@ -950,6 +1022,11 @@ struct clapgpu_bp {
     // the next clapgpu_bp_collide over the same array skips its first launch
     const double *prebinned_aabb;
     uint32_t prebinned_n;
+    // clapgpu_bp_index: the grid now describes these boxes (cleared by everything that bins again)
+    bool indexed;
+    const double *indexed_aabb;
+    uint32_t indexed_n;
+    double s_bounds[6];            // union of the statics registered per block (not the large list); min > max: none
 };
 
 // The step + the NEXT broadphase's bin pass in one launch (the bin pass reads nothing but the box the step has in
@@ -961,6 +1038,7 @@ extern "C" int clapgpu_bodies_step_prebin(void *stream, const clapgpu_bodies *b,
     if (!w || !bp) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (!b->aabb || b->n > bp->n_max) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (b->n == 0) return CLAPGPU_OK;
+    bp->indexed = false;                                         // the step moves the boxes and rebins: the index is stale
     if (bp->prebinned_aabb) {                                    // a step binned already and no collide consumed it: start over
         rc = clapgpu_bp_invalidate(stream, bp);
         if (rc) return rc;
@@ -980,6 +1058,7 @@ extern "C" int clapgpu_bodies_step_prebin(void *stream, const clapgpu_bodies *b,
 extern "C" int clapgpu_bp_invalidate(void *stream, clapgpu_bp *bp)
 {
     if (!bp) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    bp->indexed = false;
     if (!bp->prebinned_aabb) return CLAPGPU_OK;
     bp->prebinned_aabb = nullptr; bp->prebinned_n = 0;
     CLAPGPU_HIP(hipMemsetAsync(bp->k.cell_cnt, 0, (size_t)bp->buckets * 64 * sizeof(uint32_t), as_stream(stream)));
@@ -1010,6 +1089,7 @@ extern "C" int clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, 
     std::vector<uint32_t> s_count(nb + 1, 0), s_entries, s_large;
     std::vector<std::pair<uint32_t, uint32_t>> ins;                               // (bucket, static)
     const double grow = cell * 0.5 * (1.0 + 1e-9);
+    for (int a = 0; a < 3; a++) { bp->s_bounds[a] = INFINITY; bp->s_bounds[3 + a] = -INFINITY; }
     for (uint32_t s = 0; s < n_static; s++) {
         const double *bb = static_aabb + 6 * (size_t)s;
         int32_t lo[3], hi[3];
@@ -1023,6 +1103,10 @@ extern "C" int clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, 
             if (blocks > 64) large = true;
         }
         if (large) { s_large.push_back(s); continue; }
+        for (int a = 0; a < 3; a++) {
+            bp->s_bounds[a] = fmin(bp->s_bounds[a], bb[2 * a]);
+            bp->s_bounds[3 + a] = fmax(bp->s_bounds[3 + a], bb[2 * a + 1]);
+        }
         const size_t first = ins.size();
         for (int32_t z = lo[2]; z <= hi[2]; z++)
             for (int32_t y = lo[1]; y <= hi[1]; y++)
@@ -1118,6 +1202,7 @@ extern "C" int clapgpu_bp_collide(void *stream, clapgpu_bp *bp, uint32_t n, cons
     if (!bp || !pair_total || (n && !aabb) || (capacity && !pairs) || (static_capacity && !static_pairs))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (n > bp->n_max) return CLAPGPU_ERR_TOO_LARGE;
+    bp->indexed = false;                                         // collide rebins: an index it leaves behind is not kept
     hipStream_t s = as_stream(stream);
     const bool statics = bp->n_static && static_pair_total;
     if (n == 0) {
@@ -1164,4 +1249,97 @@ __attribute__((visibility("hidden"))) unsigned long long *clapgpu_bp_contact_tic
 {
     static_assert((CTRL_CONTACT_WORD * sizeof(uint32_t)) % 8 == 0, "the ticket word is a 64-bit atomic");
     return reinterpret_cast<unsigned long long *>(bp->k.ctrl + CTRL_CONTACT_WORD);
+}
+
+// The first three launches of clapgpu_bp_collide (the grid of the current boxes in cell order) and the bounds of those
+// boxes: what clapgpu_ray_cast looks up.  The collide kernels are not run and keep their code.
+// Boxes a step pre-binned are indexed WITHOUT using up the prebin: k_bp_cells zeroes the counters it reads, so the index
+// bins the same boxes once more after its scatter.  The next collide -- eager, or captured in a graph whose collide has
+// no bin launch (FrameLoop.capture with prebin) -- then finds the counters it expects.  Ranks inside a cell may come out
+// in another order; the collide's lists are canonical whatever order the atomics took.
+extern "C" int clapgpu_bp_index(void *stream, clapgpu_bp *bp, uint32_t n, const double *aabb)
+{
+    if (!bp || (n && !aabb)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (n > bp->n_max) return CLAPGPU_ERR_TOO_LARGE;
+    bp->indexed = false;
+    hipStream_t s = as_stream(stream);
+    BpK k = bp->k;
+    k.n = n; k.aabb = aabb; k.n_tiles = (n + BP_EMIT_TILE - 1) / BP_EMIT_TILE;
+    CLAPGPU_HIP(hipMemsetAsync(k.ctrl + CTRL_INDEX_WORD, 0xff, INDEX_WORDS * sizeof(uint64_t), s));
+    if (n) {
+        const bool prebinned = bp->prebinned_aabb == aabb && bp->prebinned_n == n;
+        if (!prebinned) {
+            if (bp->prebinned_aabb) {                            // binned for other boxes: undo
+                int rc = clapgpu_bp_invalidate(stream, bp);
+                if (rc) return rc;
+            }
+            hipLaunchKernelGGL(k_bp_bin, dim3((n + PB - 1) / PB), dim3(PB), 0, s, k);
+            CLAPGPU_LAUNCH_CHECK("k_bp_bin");
+        }
+        hipLaunchKernelGGL(k_bp_cells, dim3((bp->buckets + BP_CELLS_BLOCK / WAVE - 1) / (BP_CELLS_BLOCK / WAVE)), dim3(BP_CELLS_BLOCK), 0, s, k);
+        CLAPGPU_LAUNCH_CHECK("k_bp_cells");
+        hipLaunchKernelGGL(k_bp_scatter, dim3((n + PB - 1) / PB), dim3(PB), 0, s, k);
+        CLAPGPU_LAUNCH_CHECK("k_bp_scatter");
+        if (prebinned) {                                         // the counters back, as the prebinning step left them
+            hipLaunchKernelGGL(k_bp_bin, dim3((n + PB - 1) / PB), dim3(PB), 0, s, k);
+            CLAPGPU_LAUNCH_CHECK("k_bp_bin");
+        }
+        const uint32_t blocks = (n + PB - 1) / PB;
+        hipLaunchKernelGGL(k_bp_index_bounds, dim3(blocks < BP_BOUNDS_BLOCKS ? blocks : BP_BOUNDS_BLOCKS), dim3(PB), 0, s, k);
+        CLAPGPU_LAUNCH_CHECK("k_bp_index_bounds");
+    } else {
+        int rc = clapgpu_bp_invalidate(stream, bp);              // no boxes: every cell is empty, as k_bp_cells leaves them
+        if (rc) return rc;
+    }
+    bp->indexed = true; bp->indexed_aabb = aabb; bp->indexed_n = n;
+    return CLAPGPU_OK;
+}
+
+// rays.hip's view of an index (bp_grid.h)
+__attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp *bp, uint32_t n, const double *aabb,
+                                                                 BpGridView *v)
+{
+    if (!bp || !bp->indexed || bp->indexed_n != n || (aabb && bp->indexed_aabb != aabb)) return false;
+    v->n = n; v->n_static = bp->n_static; v->cell = bp->cell; v->mask = bp->k.mask; v->n_large = bp->n_large;
+    v->cell_range = bp->k.cell_range;
+    v->recs = reinterpret_cast<const GridRec *>(bp->k.recs);
+    v->s_start = bp->k.s_start;
+    v->s_recs = reinterpret_cast<const GridRec *>(bp->k.s_recs);
+    v->s_lrecs = reinterpret_cast<const GridRec *>(bp->k.s_lrecs);
+    v->index = reinterpret_cast<const uint64_t *>(bp->k.ctrl + CTRL_INDEX_WORD);
+    v->ctrl = bp->k.ctrl;
+    memcpy(v->s_bounds, bp->s_bounds, sizeof(v->s_bounds));
+    return true;
+}
+
+// rays.hip's clapgpu_bodies_ground_collide: the moves
+__attribute__((visibility("hidden"))) int clapgpu_bodies_ground_apply(void *stream, const clapgpu_bodies *b, uint32_t n,
+                                                                      const uint32_t *body, const double *ray_off,
+                                                                      const uint8_t *grounded, uint8_t *grounded_out,
+                                                                      const double *dist, const int32_t *hit, uint32_t *flags,
+                                                                      const uint32_t *moved)
+{
+    int rc = check_bodies2(b);
+    if (rc) return rc;
+    if (n == 0) return CLAPGPU_OK;
+    hipLaunchKernelGGL(k_ground_apply, dim3((n + PB - 1) / PB), dim3(PB), 0, as_stream(stream), bodies_k(b), b->yoffset, n, body,
+                       ray_off, grounded, grounded_out, dist, hit, flags, moved);
+    CLAPGPU_LAUNCH_CHECK("k_ground_apply");
+    return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_bp_index_status(void *stream, clapgpu_bp *bp, uint32_t *status)
+{
+    if (!bp || !status || !bp->indexed) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    *status = 0;
+    if (!bp->indexed_n) return CLAPGPU_OK;
+    uint64_t w = 0;
+    uint32_t epochs[2] = { 0, 0 };
+    hipStream_t s = as_stream(stream);
+    CLAPGPU_HIP(hipMemcpyAsync(&w, bp->k.ctrl + CTRL_INDEX_WORD + 2 * INDEX_OVERSIZE, sizeof(w), hipMemcpyDeviceToHost, s));
+    CLAPGPU_HIP(hipMemcpyAsync(&epochs[0], bp->k.ctrl + CTRL_EPOCH, 4, hipMemcpyDeviceToHost, s));
+    CLAPGPU_HIP(hipMemcpyAsync(&epochs[1], bp->k.ctrl + CTRL_INDEX_EPOCH, 4, hipMemcpyDeviceToHost, s));
+    CLAPGPU_HIP(hipStreamSynchronize(s));
+    *status = (w != ~0ull ? 1u : 0u) | (epochs[0] != epochs[1] ? 2u : 0u);
+    return CLAPGPU_OK;
 }

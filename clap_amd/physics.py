@@ -208,6 +208,62 @@ class PhysWorld:
                                                      _ptr(cd), _ptr(frac), _ptr(normal), _ptr(hit)), "clapgpu_sweep_capsules")
         return frac[:ns], normal[:ns], hit[:ns]
 
+    # ---- ray casts (physics.c:474-540, 695-744) ------------------------------------------
+    def bp_index(self):
+        """The broadphase grid of the bodies' CURRENT boxes (clapgpu_bp_index): what ray_cast(grid=True) looks up."""
+        _lib.check(_lib.lib().clapgpu_bp_index(_stream(), self._bp, self.n, _ptr(self.aabb)), "clapgpu_bp_index")
+
+    def bp_index_status(self):
+        st = C.c_uint32(0)
+        _lib.check(_lib.lib().clapgpu_bp_index_status(_stream(), self._bp, C.byref(st)), "clapgpu_bp_index_status")
+        return st.value
+
+    def ray_cast(self, start, dir, length, skip=None, grid=True):
+        """__phys_ray_cast for a batch: start / dir [n, 3], length [n]; skip [n] (body i, -2 - s, -1).  grid: through the
+        last bp_index().  Returns device tensors (dist [n] (NaN on a miss), hit [n], contact [n, 6], flags [n])."""
+        dev = self.device
+        start, dir = np.asarray(start, np.float64).reshape(-1, 3), np.asarray(dir, np.float64).reshape(-1, 3)
+        nr = start.shape[0]
+        ray = np.zeros((max(nr, 1), 8))
+        ray[:nr, 0:3], ray[:nr, 3:6], ray[:nr, 6] = start, dir, np.broadcast_to(np.asarray(length, np.float64), (nr,))
+        ray_d = torch.from_numpy(ray).to(dev)
+        skip_d = None if skip is None else torch.from_numpy(np.ascontiguousarray(skip, np.int32)).to(dev)
+        dist = torch.full((max(nr, 1),), float("nan"), dtype=torch.float64, device=dev)
+        hit = torch.zeros(max(nr, 1), dtype=torch.int32, device=dev)
+        contact = torch.full((max(nr, 1), 6), float("nan"), dtype=torch.float64, device=dev)
+        flags = torch.zeros(max(nr, 1), dtype=torch.int32, device=dev)
+        g, sg = self.body_geoms(), self.static_geoms()
+        _lib.check(_lib.lib().clapgpu_ray_cast(_stream(), self._bp if grid else None, C.byref(g), C.byref(sg), nr, _ptr(ray_d),
+                                               _ptr(skip_d), _ptr(dist), _ptr(hit), _ptr(contact), _ptr(flags)),
+                   "clapgpu_ray_cast")
+        self._ray_keep = (ray_d, skip_d)
+        return dist[:nr], hit[:nr], contact[:nr], flags[:nr]
+
+    def ground_collide(self, bodies, ray_off, grounded, grid=True):
+        """phys_body_ground_collide for the bodies listed: moves them onto the ground (a body listed twice is flagged
+        CLAPGPU_RAY_INVALID and stays).  Returns device tensors (grounded_out [n] uint8, normal [n, 3] float32, dist [n],
+        hit [n], flags [n])."""
+        dev = self.device
+        nb = len(bodies)
+        up = lambda a, dt, view=None: torch.from_numpy(np.ascontiguousarray(a, dt).view(view or dt)).to(dev)
+        body_d, off_d, gr_d = up(bodies, np.uint32, np.int32), up(ray_off, np.float64), up(np.asarray(grounded) != 0, np.uint8)
+        n1 = max(nb, 1)
+        out = torch.zeros(n1, dtype=torch.uint8, device=dev)
+        normal = torch.zeros((n1, 3), dtype=torch.float32, device=dev)
+        dist = torch.full((n1,), float("nan"), dtype=torch.float64, device=dev)
+        hit = torch.zeros(n1, dtype=torch.int32, device=dev)
+        flags = torch.zeros(n1, dtype=torch.int32, device=dev)
+        scratch = getattr(self, "_ground_scratch", None)
+        if scratch is None:
+            scratch = self._ground_scratch = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dev)
+        sg = self.static_geoms()
+        _lib.check(_lib.lib().clapgpu_bodies_ground_collide(_stream(), self._bp if grid else None, C.byref(self._desc),
+                                                            C.byref(sg), nb, _ptr(body_d), _ptr(off_d), _ptr(gr_d), _ptr(out),
+                                                            _ptr(normal), _ptr(dist), _ptr(hit), _ptr(flags), _ptr(scratch)),
+                   "clapgpu_bodies_ground_collide")
+        self._ground_keep = (body_d, off_d, gr_d)
+        return out[:nb], normal[:nb], dist[:nb], hit[:nb], flags[:nb]
+
     def rotate_from_entities(self, entity_batch, link_body, link_entity, all_dirty=False):
         """phys_body_rotate_xform for the (body, entity) links whose entity default_update is about to
         rebuild (model.c:1680-1687); run before entity_batch.mq_update."""

@@ -912,6 +912,71 @@ int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_g
                            const uint32_t *sweep_body, const float *delta, const uint32_t *cand_first,
                            const uint32_t *cand, float *frac, float *normal, int32_t *hit);
 
+/*
+ * Ray casts against the device scene (__phys_ray_cast / phys_ray_cast2 / phys_ray_cast, physics.c:474-540).
+ *
+ * clapgpu_bp_index: the grid of the CURRENT boxes without the pair search -- the first three launches of
+ * clapgpu_bp_collide and a reduction of the boxes' bounds and of "an edge exceeds `cell`" into control words of the
+ * index's own.  Boxes clapgpu_bodies_step_prebin binned are indexed without the bin launch and binned again after the
+ * scatter, so the prebin stays for the next collide (also one captured in a graph without its bin launch).  `bp` records
+ * the (aabb, n) it indexed; clapgpu_bp_collide, clapgpu_bodies_step_prebin, clapgpu_bp_invalidate, another index and
+ * clapgpu_bodies_ground_collide clear that record.  A collide after an index returns the pairs it returns without one.
+ * Call it after the last step of a frame (clapgpu_frame_issue runs collide -> contacts -> step, so the grid it leaves
+ * describes the boxes from before the step) and again after anything moves bodies.
+ * The host cannot see a replayed graph bin the boxes again: the device counts every bin pass, and a ray through an
+ * index whose count has moved on scans every geom instead (same results, brute-force time) -- index after replays.
+ * clapgpu_bp_index_status: host sync; bit 0: an indexed box's edge exceeds `cell` (this index only, unlike the sticky
+ * bit 0 of clapgpu_bp_status); bit 1: the boxes were binned again since the index (a replayed collide or prebinning
+ * step).  Either way rays through this index scan every geom.  CLAPGPU_ERR_INVALID_ARGUMENTS when not indexed.
+ *
+ * clapgpu_ray_cast: ray k = ray[k][8] (start xyz, direction xyz of any length, normalised as dGeomRaySet does, length,
+ * pad) against every body (a geom of `bodies`) and static (`statics`), as dCreateRay + dGeomRaySetClosestHit +
+ * dSpaceCollide2 over phys->space + the "closest hit that is not self" loop (physics.c:479-520).  skip[k] (or NULL =
+ * none): body i, -2 - s for static s, -1 none.  Out: hit[k] = body i, -2 - s, or -1 (a miss); dist[k] = the hit's depth
+ * (*pdist), unchanged on a miss; contact[k][6] (or NULL) = the dContactGeom's pos and normal, unchanged on a miss;
+ * flags[k] (or NULL) = CLAPGPU_RAY_*.  bp == NULL: every geom is tested (one wavefront per ray: the right call for a
+ * few camera rays); else `bp` must hold an index over bodies->n boxes and have been created with statics->n statics
+ * in the same order (CLAPGPU_ERR_INVALID_ARGUMENTS otherwise), and only the grid cells along the ray are looked up --
+ * same results bit for bit.  The ray scans every geom instead when an indexed box is larger than a cell, when the boxes
+ * were binned again since the index, or when the ray crosses more cells than a scan would test geoms.
+ * Colliders (ODE 0.16 ray.cpp; a hit is at 0 <= depth <= length along the unit direction):
+ *   sphere   dCollideRaySphere: the entry point, outward normal; a start inside: the exit point, normal flipped
+ *            (pointing into the sphere).  The flip follows where the start is (C < 0), not the root taken: a start
+ *            exactly on the surface moving outward hits at depth 0 with the outward normal
+ *   capsule  dCollideRayCapsule: the cylinder between the caps or a cap's sphere, outward normal; a start inside the
+ *            capsule: the exit point, normal flipped
+ *   box      dCollideRayBox on the static's AABB: the entry face, its outward axis normal; an edge or corner takes the
+ *            first axis (x, y, z) whose slab is entered last; a start inside: the exit face, normal flipped
+ *   other    (CLAPGPU_GEOM_OTHER, trimesh): not intersected; see CLAPGPU_RAY_UNRESOLVED
+ * Deviations: the hit kept is the smallest depth, ties to bodies before statics and then to the lower index (ODE keeps
+ * the first in its hash-space order); NaN geometry never hits.
+ */
+#define CLAPGPU_RAY_INVALID      1u   /* zero / NaN / infinite direction, NaN start, negative or NaN length: a miss */
+#define CLAPGPU_RAY_UNRESOLVED   2u   /* the segment enters an OTHER static's AABB before the hit (or there is no hit):
+                                         redo this ray with ODE (the reference's terrain is a trimesh) */
+#define CLAPGPU_RAY_MOVED_TARGET 4u   /* clapgpu_bodies_ground_collide: the hit body was itself moved by this batch */
+int clapgpu_bp_index(void *stream, clapgpu_bp *bp, uint32_t n, const double *aabb);
+int clapgpu_bp_index_status(void *stream, clapgpu_bp *bp, uint32_t *status);
+int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics, uint32_t n_rays,
+                     const double *ray, const int32_t *skip, double *dist, int32_t *hit, double *contact, uint32_t *flags);
+/*
+ * phys_body_ground_collide (physics.c:695-744, called from character_move, character.c:454) for bodies body[k]
+ * (each once; see below), ray_off[k] = phys_body.ray_off, grounded[k] = !ch->airborne.  The ray starts at the body position less
+ * (ray_off - 0.05) in y, through a float vec3, points down, is 2 * ray_len long (ray_len = yoffset - (ray_off - 0.05)
+ * + 1e-3) and skips the body; its bodies are b's geoms.  On a hit normal[k] = the contact normal (float) and the body
+ * moves by (float)(ray_len - dist) or (float)(-(dist - ray_len)) per the reference's three branches
+ * (dBodySetPosition, then pos / axis / aabb / geom record as clapgpu_bodies_aabb writes them).  Out:
+ * grounded_out[k] = the return value, dist[k] (unchanged on a miss), hit[k], flags[k].  Every ray sees the poses from
+ * before the call (the reference moves the characters one at a time): CLAPGPU_RAY_MOVED_TARGET marks a ray whose hit
+ * body moved in this call -- redo those in list order.  INVALID and UNRESOLVED rays move nothing (grounded_out 0).
+ * A body listed more than once: all its rays get CLAPGPU_RAY_INVALID and grounded_out 0, and it does not move.
+ * scratch: [b->n] uint32 of device memory, overwritten.  bp: NULL or an index over (b->n, b->aabb); cleared on return.
+ */
+int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,
+                                  uint32_t n, const uint32_t *body, const double *ray_off, const uint8_t *grounded,
+                                  uint8_t *grounded_out, float *normal, double *dist, int32_t *hit, uint32_t *flags,
+                                  uint32_t *scratch);
+
 /* ======================================================================== */
 /* Characters: the feeder in front of default_update (core/character.c)      */
 /* ======================================================================== */
