@@ -14,13 +14,16 @@ configs[4]'s sizing (2 M entities + 256 k particles per GPU: 16 M + 2 M at 8 GPU
 Started plainly with --gpus N > 1 (no torch.distributed.run environment) it is its own launcher: N fresh child
 processes, one per GPU, before this process makes any GPU call (launch_ranks).
 
-Prints ONE JSON line (rank 0).  `value` = entity updates / s over all GPUs.
-`roofline` = algorithmic bytes of the update kernel / its launch-to-launch time, K launches back to
-back between one HIP event pair on the stream they are launched on (a separate pass after the timed
-region, same process, same data); `step_us` and `expand_launch_us` beside it make the line checkable
-against itself.  `cpu_baseline` = the reference's own default_update + view_entity_in_frustum
-(oracle/_ref, built from the reference sources) on one host core, or the oracle port if that binary
-is absent.
+Prints ONE JSON line (rank 0).  `value` = entity updates / s over all GPUs.  A plain run sets up, warms up, times
+the steps, writes --dump-outputs and prints the line; nothing else.  --full adds the sections that take passes of
+their own, all after the timed steps:
+  `roofline` = algorithmic bytes of the update kernel / its launch-to-launch time, K launches back to back between one
+  HIP event pair on the stream they are launched on (same process, same data); `step_us` and `expand_launch_us` beside
+  it make the line checkable against itself.
+  `c5` = with N > 1 and no explicit sizing, BASELINE configs[4]'s per-rank share as a second timed leg.
+  `extra` = the secondary workloads (bench_extras.py), `summary` / `roofline.secondary` = their digests.
+  `cpu_baseline` = the reference's own default_update + view_entity_in_frustum (oracle/_ref, built from the reference
+  sources) on one host core, or the oracle port if that binary is absent.
 """
 import argparse
 import glob
@@ -41,6 +44,7 @@ if ROOT not in sys.path:
 LINE_ORDER = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "rccl_ranks", "devices", "ms_per_step_per_rank", "summary", "c5", "config", "roofline",
               "cpu_baseline", "extra"]
+FULL_ONLY = ("summary", "c5", "roofline", "cpu_baseline", "extra")    # the sections only a --full run measures
 C5_KEYS = ["workload", "value", "unit", "particle_updates_per_s", "ms_per_step", "ms_per_step_per_rank", "steps", "warmup",
            "entities_per_gpu", "particles_per_gpu", "visible", "global_ids", "scaling"]
 
@@ -54,8 +58,11 @@ def parse():
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--layout", choices=["tiles", "levels"], default="tiles",
                     help="tiles: subtree tiles, one launch for all levels; levels: level-major, one launch per level")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the roofline pass, the "
+                         "configs[4] leg of an N > 1 run, the secondary workloads ('extra') and the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary workloads (pose/skinning, particles, bodies) reported under 'extra'")
+                    help="--full: skip the secondary workloads (pose/skinning, particles, bodies) reported under 'extra'")
     ap.add_argument("--particles", type=int, default=0,
                     help="also update this many particles per GPU (whole 1024-particle systems) inside every step: "
                          "BASELINE configs[4] is --gpus 8 --chains 250000 --particles 262144")
@@ -69,9 +76,9 @@ def parse():
     ap.add_argument("--exchange", choices=["rccl", "c10d"], default="rccl",
                     help="N > 1: call ncclAllGather directly (low host overhead) or through torch.distributed")
     ap.add_argument("--no-testbed", action="store_true",
-                    help="skip the testbed-sized (BASELINE configs[0]) extra: under rocprofv3 its small launches of "
+                    help="--full: skip the testbed-sized (BASELINE configs[0]) extra: under rocprofv3 its small launches of "
                          "the same kernels would be averaged into the full-size per-kernel statistics")
-    ap.add_argument("--cpu-frames", type=int, default=120, help="frames of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-frames", type=int, default=120, help="--full: frames of the CPU baseline sample (0 = skip)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="N > 1: seconds a rank may spend in the collective set-up (process group + ncclCommInitRank) before it "
                          "gives up with exit code 4 -- a rank stuck there would hang the launcher and every other rank")
@@ -209,12 +216,14 @@ def dry_launch():
         raise SystemExit(5)
     if rank == 0:
         args = parse()
-        two_legs = world > 1 and args.chains == 125_000 and args.depth == 8 and args.particles == 0 and not args.c5 and not args.snapshot
+        two_legs = (args.full and world > 1 and args.chains == 125_000 and args.depth == 8 and args.particles == 0 and not args.c5
+                    and not args.snapshot)
         print(json.dumps({"launcher": "dry", "n_gpus": world, "rank_sum": int(t[0]), "local_rank_sum": int(t[1]),
                           "ranks": int(t[2]), "rccl_ranks": proof["rccl_ranks"], "devices": proof["devices"],
                           # the shape of the line the GPU run of the same command prints: headline = configs[1] per GPU
-                          # (weak scaling), and with N > 1 and no explicit sizing the configs[4] share as a second leg
-                          "line_keys": [k for k in LINE_ORDER if k not in ("extra", "cpu_baseline") and (two_legs or k != "c5")],
+                          # (weak scaling), and with --full, N > 1 and no explicit sizing the configs[4] share as a second leg
+                          "line_keys": [k for k in LINE_ORDER if k not in ("extra", "cpu_baseline") and (args.full or k not in FULL_ONLY)
+                                        and (two_legs or k != "c5")],
                           "c5_keys": C5_KEYS if two_legs else None}), flush=True)
     dist.barrier()
     dist.destroy_process_group()
@@ -521,6 +530,51 @@ def dump_outputs(path, batch, visible, pbatch):
     return total
 
 
+def roofline_pass(batch, fr, index_base, steps, ms_per_step, default_workload):
+    """--full, after the timed steps: the `roofline` section, HIP events around the launches of the dominant kernel (same
+    stream, same data)."""
+    import torch
+    if batch.tiled:
+        kernel, launches = "k_entities_tiles<true>", 1
+    else:
+        kernel, launches = "k_entities_level<true>", batch.n_levels
+    # K launches back to back between ONE event pair (events on torch's current stream, the stream the kernels are
+    # launched on): an event pair around every single launch adds its own ~5 us of record latency to a 39 us kernel
+    # and reads LONGER than the whole step.  The expansion launch is timed the same way, so that
+    # mean_launch_us + expand_us ~= ms_per_step * 1000 can be checked from the line itself.
+    K = max(steps, 20)
+
+    def timed(fn, reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        fn()
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / reps                       # ms per call
+
+    if batch.tiled:
+        lvl_ms = np.asarray([timed(lambda: batch.mq_update(fr, all_dirty=True), K)])
+    else:
+        lvl_ms = np.asarray([timed(lambda l=l: batch.update_level(l, fr, all_dirty=True), K) for l in range(launches)])
+    expand_ms = timed(lambda: batch.compact_visible(index_base), K)
+    mean_launch_s = float(lvl_ms.mean()) * 1e-3
+    alg_bytes_step = batch.algorithmic_bytes()                                       # 276 B/child, 212 B/root
+    alg_bytes_launch = alg_bytes_step / launches
+    return dict(roof(alg_bytes_launch, mean_launch_s, *([kernel] if default_workload else [])),
+                kernel=kernel, launches_per_step=launches,
+                per_launch_us=[float(x) for x in (lvl_ms * 1e3)],
+                launches_timed=K, timing="K launches back to back between one HIP event pair",
+                expand_launch_us=float(expand_ms * 1e3),
+                step_us=float(ms_per_step * 1e3),
+                note="mean_launch_us is launch-to-launch in a dependent stream: the kernel plus the few us between "
+                     "two dependent launches (rocprofv3's kernel-only average is in profiles/); expand_launch_us "
+                     "issued alone is bound by the host's launch rate -- inside a step it costs step_us - "
+                     "mean_launch_us")
+
+
 def main():
     args = parse()
     if args.c5:
@@ -611,13 +665,13 @@ def main():
         ids = xch.last()[1] if use_dist else batch.visible
         dumped = dump_outputs(args.dump_outputs, batch, ids[:visible].cpu().numpy().view(np.uint32), pbatch)
 
-    # ---- N > 1, no explicit sizing: BASELINE configs[4]'s per-rank share as a SECOND timed leg of the same run, the same
+    # ---- --full, N > 1, no explicit sizing: BASELINE configs[4]'s per-rank share as a SECOND timed leg of the same run, the same
     #      process group and the same communicator (16 M entities + 2 M particles at 8 GPUs).  The headline above stays
     #      configs[1] per GPU -- comparable with the N = 1 line, which is what a scaling curve needs -- and the first run on
     #      an N-GPU node measures the named 8-GPU configuration too, instead of leaving it to a second lease.
     c5 = None
     default_sizing = (args.chains == 125_000 and args.depth == 8 and args.particles == 0 and not args.c5 and not args.snapshot)
-    if use_dist and default_sizing and os.environ.get("CLAP_BENCH_NO_C5") != "1":
+    if args.full and use_dist and default_sizing and os.environ.get("CLAP_BENCH_NO_C5") != "1":
         rs5 = RankStep(250_000, 8, 262_144, rank, world, device, use_dist=True, route=args.exchange, layout=args.layout, cam=cam,
                        share=xch)
         e5, rank_ms5 = timed_leg(rs5.step)
@@ -635,39 +689,9 @@ def main():
         rs5 = None
         torch.cuda.empty_cache()
 
-    # ---- roofline pass: HIP events around every launch of the dominant kernel (same stream) ----
-    if batch.tiled:
-        kernel, launches = "k_entities_tiles<true>", 1
-    else:
-        kernel, launches = "k_entities_level<true>", batch.n_levels
-    # K launches back to back between ONE event pair (events on torch's current stream, the stream the kernels are
-    # launched on): an event pair around every single launch adds its own ~5 us of record latency to a 39 us kernel
-    # and reads LONGER than the whole step.  The expansion launch is timed the same way, so that
-    # mean_launch_us + expand_us ~= ms_per_step * 1000 can be checked from the line itself.
-    K = max(args.steps, 20)
-
-    def timed(fn, reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fn()
-        torch.cuda.synchronize()
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) / reps                       # ms per call
-
-    if batch.tiled:
-        lvl_ms = np.asarray([timed(lambda: batch.mq_update(fr, all_dirty=True), K)])
-    else:
-        lvl_ms = np.asarray([timed(lambda l=l: batch.update_level(l, fr, all_dirty=True), K) for l in range(launches)])
-    expand_ms = timed(lambda: batch.compact_visible(index_base), K)
-    mean_launch_s = float(lvl_ms.mean()) * 1e-3
-    alg_bytes_step = batch.algorithmic_bytes()                                       # 276 B/child, 212 B/root
-    alg_bytes_launch = alg_bytes_step / launches
-    n_levels = args.depth
     # the committed PMC summary was taken on the default workload: only then is it this launch's traffic
     default_workload = args.chains == 125_000 and args.depth == 8 and not args.snapshot and args.layout == "tiles"
+    roofline = roofline_pass(batch, fr, index_base, args.steps, ms_per_step, default_workload) if args.full else None
 
     if rank == 0:
         out = {
@@ -681,22 +705,14 @@ def main():
                                     else f"BASELINE configs[1]: {n_real} entities/GPU, {args.chains} chains x depth "
                                          f"{args.depth}, ") + f"{args.layout} SoA layout, all dirty, fused frustum cull + ordered visible "
                                    f"list ({visible} visible" + (" in the gathered global set)" if use_dist else ")"),
-                       "entities_per_gpu": n_real, "levels": n_levels,
+                       "entities_per_gpu": n_real, "levels": args.depth,
                        "particles_per_gpu": (pbatch.n_real if pbatch is not None else 0),
                        "exchange": (xch.route
                                     + " of the visibility mask + local expansion to global ids, overlapped with "
                                     "the next frame's update") if use_dist else "none"},
-            "roofline": dict(roof(alg_bytes_launch, mean_launch_s, *([kernel] if default_workload else [])),
-                             kernel=kernel, launches_per_step=launches,
-                             per_launch_us=[float(x) for x in (lvl_ms * 1e3)],
-                             launches_timed=K, timing="K launches back to back between one HIP event pair",
-                             expand_launch_us=float(expand_ms * 1e3),
-                             step_us=float(ms_per_step * 1e3),
-                             note="mean_launch_us is launch-to-launch in a dependent stream: the kernel plus the few us between "
-                                  "two dependent launches (rocprofv3's kernel-only average is in profiles/); expand_launch_us "
-                                  "issued alone is bound by the host's launch rate -- inside a step it costs step_us - "
-                                  "mean_launch_us"),
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if proof is not None:                                # the line proves its own N: RCCL's rank count, one PCI bus id per rank
             out["rccl_ranks"] = proof["rccl_ranks"]
             out["devices"] = proof["devices"]
@@ -705,27 +721,29 @@ def main():
             out["c5"] = c5
         if dumped is not None:
             out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
-        extra = None
         if args.snapshot:
             out["data"] = "snapshot"
-            ex = snapshot_characters(comps, raw, device, args.steps, args.warmup)
-            if ex:
-                extra = {"snapshot_characters": ex}
-        if world == 1 and not args.no_extras and not args.snapshot:
-            if xch is not None:
-                xch.destroy()
-            xch = batch = pbatch = step = rs = None           # the extras want the HBM the headline scene holds
-            torch.cuda.empty_cache()
-            extra = extras(device, testbed=not args.no_testbed)
-        if world == 1 and args.cpu_frames > 0:
-            out["cpu_baseline"] = cpu_baseline(scene, cam, args.cpu_frames)
-        # the secondary numbers a reader of a truncated record needs, as a dozen scalars BEFORE the long sections
-        out["summary"] = summary(out, extra)
-        sec = secondary(out, extra)
-        if sec:
-            out["roofline"]["secondary"] = sec               # the one dict the driver's record keeps whole
-        if extra is not None:
-            out["extra"] = extra
+        if args.full:
+            extra = None
+            if args.snapshot:
+                ex = snapshot_characters(comps, raw, device, args.steps, args.warmup)
+                if ex:
+                    extra = {"snapshot_characters": ex}
+            if world == 1 and not args.no_extras and not args.snapshot:
+                if xch is not None:
+                    xch.destroy()
+                xch = batch = pbatch = step = rs = None       # the extras want the HBM the headline scene holds
+                torch.cuda.empty_cache()
+                extra = extras(device, testbed=not args.no_testbed)
+            if world == 1 and args.cpu_frames > 0:
+                out["cpu_baseline"] = cpu_baseline(scene, cam, args.cpu_frames)
+            # the secondary numbers a reader of a truncated record needs, as a dozen scalars BEFORE the long sections
+            out["summary"] = summary(out, extra)
+            sec = secondary(out, extra)
+            if sec:
+                out["roofline"]["secondary"] = sec           # the one dict a record that drops `summary` and `extra` keeps whole
+            if extra is not None:
+                out["extra"] = extra
         assert c5 is None or list(c5) == C5_KEYS
         out = {k: out[k] for k in LINE_ORDER if k in out} | {k: v for k, v in out.items() if k not in LINE_ORDER}
         print(json.dumps(out), flush=True)

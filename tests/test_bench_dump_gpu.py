@@ -52,3 +52,24 @@ def test_dumped_outputs_are_the_timed_steps_results(tmp_path):
         assert_bits_equal(a["entity_" + k], st[k][rows], k)
     assert a["visible_count"][0] == vis.size > 0
     assert np.array_equal(a["visible"], vis.astype(np.float64))
+
+
+def test_a_plain_run_times_the_headline_alone(tmp_path):
+    """A plain run prints the headline and no section that takes a pass of its own; --full adds them (here the roofline
+    pass and the digest: --no-extras --cpu-frames 0 keep the secondary workloads and the CPU legs out)."""
+    import bench
+
+    def line(*extra):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+                            "--chains", str(CHAINS), "--depth", str(DEPTH), *extra], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        return json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    plain = line()
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["unit"] == "entity updates/s"
+    assert plain["higher_is_better"] is True and plain["dtype"] == "f32"
+    assert plain["config"]["entities_per_gpu"] == CHAINS * DEPTH
+    assert not set(bench.FULL_ONLY) & set(plain)
+    full = line("--full", "--no-extras", "--cpu-frames", "0")
+    assert full["roofline"]["step_us"] == pytest.approx(full["ms_per_step"] * 1e3) and full["roofline"]["mean_launch_us"] > 0
+    assert "summary" in full and not {"c5", "cpu_baseline", "extra"} & set(full)
+    assert [k for k in full if k not in bench.FULL_ONLY] == list(plain)

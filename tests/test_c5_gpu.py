@@ -127,7 +127,7 @@ def test_16m_id_global_expansion_matches_numpy(cuda_device):
 
 
 def test_bench_line_carries_the_configs4_leg_when_distributed(tmp_path):
-    """`bench.py --gpus N` with N > 1 (here: a world of one with the collective path forced, CLAP_BENCH_FORCE_DIST=1 -- the
+    """`bench.py --gpus N --full` with N > 1 (here: a world of one with the collective path forced, CLAP_BENCH_FORCE_DIST=1 -- the
     same code the ranks of an 8-GPU run execute) times TWO legs in one process group over one communicator: the weak-scaling
     headline (configs[1] per GPU) and BASELINE configs[4]'s per-rank share, reported under `c5`; `summary` and `c5` precede
     the long sections of the line."""
@@ -139,7 +139,8 @@ def test_bench_line_carries_the_configs4_leg_when_distributed(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(CLAP_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-extras", "--cpu-frames", "0"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-extras",
+                        "--cpu-frames", "0"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

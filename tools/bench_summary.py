@@ -1,4 +1,4 @@
-"""Print the handful of numbers of a bench.py JSON line that the kernel work is steered by."""
+"""Print the handful of numbers of a `bench.py --full` JSON line that the kernel work is steered by."""
 import json
 import sys
 

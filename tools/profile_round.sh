@@ -9,14 +9,14 @@ tag=${1:-r01_final}
 out=$R/gpurun_out/$tag
 rm -rf "$out"; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-python3 "$R/bench.py" > "$out/bench_unprofiled.json" 2> "$out/bench_unprofiled.err"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 "$R/bench.py" --steps 100 --warmup 10 --cpu-frames 0 --no-testbed > "$out/bench_under_rocprof.log" 2>&1
-timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/fetch" -- python3 "$R/bench.py" --steps 10 --warmup 2 --cpu-frames 0 --no-testbed > "$out/bench_fetch.log" 2>&1
-timeout 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$out/write" -- python3 "$R/bench.py" --steps 10 --warmup 2 --cpu-frames 0 --no-testbed > "$out/bench_write.log" 2>&1
+python3 "$R/bench.py" --full > "$out/bench_unprofiled.json" 2> "$out/bench_unprofiled.err"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 "$R/bench.py" --full --steps 100 --warmup 10 --cpu-frames 0 --no-testbed > "$out/bench_under_rocprof.log" 2>&1
+timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/fetch" -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --cpu-frames 0 --no-testbed > "$out/bench_fetch.log" 2>&1
+timeout 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$out/write" -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --cpu-frames 0 --no-testbed > "$out/bench_write.log" 2>&1
 f=$(find "$out/trace" -name '*kernel_stats.csv' | head -1)
 [ -n "$f" ] && cp "$f" "$out/kernel_stats.csv"
 # the headline kernel alone (no extras, no testbed frame, no drop-in scenes): every k_entities_tiles launch is BASELINE size
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace_h" -- python3 "$R/bench.py" --steps 200 --warmup 20 --cpu-frames 0 --no-testbed --no-extras > "$out/bench_headline_under_rocprof.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace_h" -- python3 "$R/bench.py" --full --steps 200 --warmup 20 --cpu-frames 0 --no-testbed --no-extras > "$out/bench_headline_under_rocprof.log" 2>&1
 f=$(find "$out/trace_h" -name '*kernel_stats.csv' | head -1)
 [ -n "$f" ] && cp "$f" "$out/kernel_stats_headline.csv"
 fc=$(find "$out/fetch" -name '*counter_collection.csv' | head -1)
@@ -35,8 +35,8 @@ fi
 rm -rf "$out"/pose_FETCH_SIZE_* "$out"/pose_WRITE_SIZE_*
 # the headline kernel's traffic from headline-only passes: in the full bench the whole-frame extra launches the same grid
 # with only part of the scene dirty, which would pull the per-launch mean down
-timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/fetch_h" -- python3 "$R/bench.py" --steps 10 --warmup 2 --cpu-frames 0 --no-testbed --no-extras > "$out/bench_fetch_headline.log" 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$out/write_h" -- python3 "$R/bench.py" --steps 10 --warmup 2 --cpu-frames 0 --no-testbed --no-extras > "$out/bench_write_headline.log" 2>&1
+timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/fetch_h" -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --cpu-frames 0 --no-testbed --no-extras > "$out/bench_fetch_headline.log" 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$out/write_h" -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --cpu-frames 0 --no-testbed --no-extras > "$out/bench_write_headline.log" 2>&1
 fch=$(find "$out/fetch_h" -name '*counter_collection.csv' | head -1)
 wch=$(find "$out/write_h" -name '*counter_collection.csv' | head -1)
 [ -n "$fch" ] && [ -n "$wch" ] && python3 "$R/tools/pmc_summary.py" "$fch" "$wch" k_entities_tiles "$out/entities_pmc.json" > /dev/null
