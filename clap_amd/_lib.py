@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 OK = 0
 ERR_NOMEM = -1
@@ -142,6 +142,13 @@ class Geoms(C.Structure):
                 ("material", C.c_void_p), ("records", C.c_void_p)]
 
 
+class TrimeshDesc(C.Structure):
+    """clapgpu_trimesh_desc (include/clapgpu.h): device arrays of the static meshes."""
+    _fields_ = [("n_meshes", C.c_uint32), ("n_statics", C.c_uint32), ("static_index", C.c_void_p), ("vx_first", C.c_void_p),
+                ("tri_first", C.c_void_p), ("vx", C.c_void_p), ("idx", C.c_void_p), ("scale", C.c_void_p),
+                ("pos", C.c_void_p), ("quat", C.c_void_p)]
+
+
 POSE_SKIP_TRS, POSE_SKIP_JOINT_POS, POSE_JOINT_POS_MODEL = 1, 2, 4
 BODY_DISABLED, BODY_AUTO_DISABLE, BODY_NO_GRAVITY, BODY_GYROSCOPIC, BODY_HAS_JOINT = 1, 2, 4, 8, 16
 GEOM_SPHERE, GEOM_CAPSULE, GEOM_BOX, GEOM_OTHER = 0, 1, 2, 3
@@ -268,6 +275,15 @@ SYMBOLS = {
     "clapgpu_bodies_ground_collide": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_uint32,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_trimesh_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(TrimeshDesc)]),
+    "clapgpu_trimesh_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_trimesh_status": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "clapgpu_trimesh_destroy": (None, [C.c_void_p]),
+    "clapgpu_ray_cast_meshes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_void_p, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_bodies_ground_collide_meshes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_void_p,
+                                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_visible_compact_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_characters_update_clock": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),

@@ -25,6 +25,7 @@
 #include "phys_dev.h"
 #include "geoms_dev.h"
 #include "bp_grid.h"
+#include "rays_dev.h"
 
 struct clapgpu_bp;
 int clapgpu_bodies_ground_apply(void *stream, const clapgpu_bodies *b, uint32_t n, const uint32_t *body, const double *ray_off,
@@ -34,9 +35,6 @@ int clapgpu_bodies_ground_apply(void *stream, const clapgpu_bodies *b, uint32_t 
 namespace clapgpu {
 
 constexpr int RB = 256;                                 // 4 rays per workgroup
-constexpr uint32_t KEY_NONE = 0xffffffffu, KEY_STATIC = 0x80000000u;
-
-struct Ray { double s[3], u[3], len; };
 
 // ray_sphere_helper (ray.cpp): mode = the ray starts inside the capsule this cap belongs to
 __device__ __forceinline__ bool ray_sphere(const Ray &r, const double (&c)[3], double radius, bool mode, phd::CGeom &o)
@@ -189,10 +187,13 @@ struct Best {
     double other;                                        // first entry into a CLAPGPU_GEOM_OTHER box
 };
 
-// one geom of a set: the collider of its kind, or, for CLAPGPU_GEOM_OTHER, where the segment enters its AABB
-__device__ __forceinline__ void test_geom(const Ray &r, const GeomsK &g, uint32_t i, uint32_t key, uint32_t skip_key, Best &b)
+// one geom of a set: the collider of its kind, or, for CLAPGPU_GEOM_OTHER, where the segment enters its AABB.  A static
+// with a triangle mesh (meshed[s] >= 0) is left to the mesh pass (trimesh.hip)
+__device__ __forceinline__ void test_geom(const Ray &r, const GeomsK &g, uint32_t i, uint32_t key, uint32_t skip_key, Best &b,
+                                          const int32_t *meshed)
 {
     if (i >= g.n || key == skip_key) return;
+    if (meshed && (key & KEY_STATIC) && meshed[i] >= 0) return;
     phd::Geom ge;
     load_geom(g, i, ge);
     phd::CGeom c;
@@ -235,13 +236,14 @@ struct CastK {
     GeomsK bodies, statics;
     bool grid;
     BpGridView g;
+    const int32_t *meshed;               // NULL, or [statics.n]: the static's mesh in a clapgpu_trimesh set, or -1
 };
 
 __device__ __forceinline__ void scan_all(const CastK &k, const Ray &r, uint32_t skip_key, Best &b)
 {
     const int lane = lane_id();
-    for (uint32_t i = lane; i < k.bodies.n; i += WAVE) test_geom(r, k.bodies, i, i, skip_key, b);
-    for (uint32_t s = lane; s < k.statics.n; s += WAVE) test_geom(r, k.statics, s, KEY_STATIC | s, skip_key, b);
+    for (uint32_t i = lane; i < k.bodies.n; i += WAVE) test_geom(r, k.bodies, i, i, skip_key, b, k.meshed);
+    for (uint32_t s = lane; s < k.statics.n; s += WAVE) test_geom(r, k.statics, s, KEY_STATIC | s, skip_key, b, k.meshed);
 }
 
 __device__ __forceinline__ bool in_box3(const int32_t (&lo)[3], const int32_t (&hi)[3], int32_t x, int32_t y, int32_t z)
@@ -284,7 +286,7 @@ __device__ bool scan_grid(const CastK &k, const Ray &r, uint32_t skip_key, Best 
     const double grow = g.cell * 0.5 * (1.0 + 1e-9);
 
     for (uint32_t j = lane; j < g.n_large; j += WAVE)                       // the large statics: every ray
-        test_geom(r, k.statics, g.s_lrecs[j].idx, KEY_STATIC | g.s_lrecs[j].idx, skip_key, b);
+        test_geom(r, k.statics, g.s_lrecs[j].idx, KEY_STATIC | g.s_lrecs[j].idx, skip_key, b, k.meshed);
 
     int32_t pc_lo[3] = { 1, 1, 1 }, pc_hi[3] = { 0, 0, 0 }, pb_lo[3] = { 1, 1, 1 }, pb_hi[3] = { 0, 0, 0 };   // previous piece: none
     for (uint32_t j = 0; j < np; j++) {
@@ -345,11 +347,11 @@ __device__ bool scan_grid(const CastK &k, const Ray &r, uint32_t skip_key, Best 
                     const uint32_t e = ofirst + (q - oexcl);
                     if (ostat) {
                         const uint32_t s = g.s_recs[e].idx;
-                        test_geom(r, k.statics, s, KEY_STATIC | s, skip_key, b);
+                        test_geom(r, k.statics, s, KEY_STATIC | s, skip_key, b, k.meshed);
                     } else {
                         const int4 t = reinterpret_cast<const int4 *>(g.recs + e)[3];      // idx, cell coordinates
                         if (t.y == ox && t.z == oy && t.w == oz && (uint32_t)t.x < g.n)    // not a hash neighbour
-                            test_geom(r, k.bodies, (uint32_t)t.x, (uint32_t)t.x, skip_key, b);
+                            test_geom(r, k.bodies, (uint32_t)t.x, (uint32_t)t.x, skip_key, b, k.meshed);
                     }
                 }
             }
@@ -357,26 +359,6 @@ __device__ bool scan_grid(const CastK &k, const Ray &r, uint32_t skip_key, Best 
         for (int a = 0; a < 3; a++) { pc_lo[a] = c_lo[a]; pc_hi[a] = c_hi[a]; pb_lo[a] = b_lo[a]; pb_hi[a] = b_hi[a]; }
     }
     return true;
-}
-
-// the ray as dGeomRaySet stores it; false: CLAPGPU_RAY_INVALID
-__device__ __forceinline__ bool make_ray(const double *in, Ray &r)
-{
-    double d[3] = { in[3], in[4], in[5] };
-    r.s[0] = in[0]; r.s[1] = in[1]; r.s[2] = in[2];
-    r.len = in[6];
-    const bool finite_dir = isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]);
-    if (!finite_dir || (d[0] == 0 && d[1] == 0 && d[2] == 0) || r.s[0] != r.s[0] || r.s[1] != r.s[1] || r.s[2] != r.s[2] ||
-        !(r.len >= 0))
-        return false;
-    phd::safe_normalize3(d);                                                 // dNormalize3
-    r.u[0] = d[0]; r.u[1] = d[1]; r.u[2] = d[2];
-    return true;
-}
-
-__device__ __forceinline__ uint32_t skip_key_of(int32_t skip)
-{
-    return skip >= 0 ? (uint32_t)skip : skip <= -2 ? KEY_STATIC | (uint32_t)(-2 - skip) : KEY_NONE;
 }
 
 // one ray on the whole wave: the best hit (every lane) and the ray's flags
@@ -390,18 +372,13 @@ __device__ __forceinline__ uint32_t cast(const CastK &k, const Ray &r, uint32_t 
                       (k.g.n == 0 || k.g.ctrl[CTRL_BIN_EPOCH] == k.g.ctrl[CTRL_INDEX_EPOCH]);
     if (!grid || !scan_grid(k, r, skip_key, b)) scan_all(k, r, skip_key, b);
     reduce_best(b);
-    const bool hit = b.key != KEY_NONE;
-    return (b.other <= r.len && (!hit || b.other <= b.depth)) ? CLAPGPU_RAY_UNRESOLVED : 0u;
+    return unresolved(b.other, r.len, b.key, b.depth);
 }
 
-__device__ __forceinline__ int32_t hit_of(uint32_t key)
-{
-    return key == KEY_NONE ? -1 : (key & KEY_STATIC) ? -2 - (int32_t)(key & ~KEY_STATIC) : (int32_t)key;
-}
-
+// other: NULL, or [n] where a mesh pass follows: the first entry into an OTHER static without a mesh, for its flags
 __global__ __launch_bounds__(RB)
 void k_ray_cast(CastK k, uint32_t n, const double *ray, const int32_t *skip, double *dist, int32_t *hit, double *contact,
-                uint32_t *flags)
+                uint32_t *flags, double *other)
 {
     const uint32_t i = blockIdx.x * (RB / WAVE) + threadIdx.x / WAVE;
     if (i >= n) return;                                                      // whole waves
@@ -421,16 +398,18 @@ void k_ray_cast(CastK k, uint32_t n, const double *ray, const int32_t *skip, dou
                 for (int a = 0; a < 3; a++) { contact[6 * (size_t)i + a] = b.pos[a]; contact[6 * (size_t)i + 3 + a] = b.normal[a]; }
         }
         if (flags) flags[i] = f;
+        if (other) other[i] = b.other;
     }
 }
 
-// phys_body_ground_collide's cast for body[k]: start (float) below the body's position, straight down, 2 * ray_len long,
-// the body skipped; outputs the hit and the decision.  moved[body]: bit 0 = the apply launch will move it (unless it is
-// listed twice), bits 1.. = rays cast for it
+// phys_body_ground_collide's cast for body[k] (ground_ray), the body skipped; outputs the hit and the decision.
+// moved[body]: bit 0 = the apply launch will move it (unless it is listed twice), bits 1.. = rays cast for it.
+// other != NULL: a mesh pass follows and decides; this launch writes the hit so far, its normal (when the flags so far are
+// clear: the mesh pass can only clear them) and `other`
 __global__ __launch_bounds__(RB)
 void k_ground_rays(CastK k, uint32_t n, const double *pos, const double *yoffset, const uint32_t *body, const double *ray_off,
                    const uint8_t *grounded, uint8_t *grounded_out, float *normal, double *dist, int32_t *hit, uint32_t *flags,
-                   uint32_t *moved)
+                   uint32_t *moved, double *other)
 {
     const uint32_t j = blockIdx.x * (RB / WAVE) + threadIdx.x / WAVE;
     if (j >= n) return;
@@ -441,37 +420,29 @@ void k_ground_rays(CastK k, uint32_t n, const double *pos, const double *yoffset
         return;
     }
     if (lane == 0) atomicAdd(&moved[i], 2u);                                 // rays per body (bits 1..): a body listed twice
-    double roff;
-    const double ray_len = phd::ground_ray_len(ray_off[j], yoffset[i], roff);
-    const double *p = pos + 3 * (size_t)i;
-    const float start[3] = { (float)p[0], (float)(p[1] - roff), (float)p[2] };   // through a vec3
     Ray r;
-    r.s[0] = start[0]; r.s[1] = start[1]; r.s[2] = start[2];
-    r.u[0] = 0.0; r.u[1] = -1.0; r.u[2] = 0.0;
-    r.len = ray_len * 2;
+    double ray_len;
     uint32_t f;
     Best b;
-    if (!(r.len >= 0) || r.s[0] != r.s[0] || r.s[1] != r.s[1] || r.s[2] != r.s[2]) {
+    if (!ground_ray(pos, yoffset, i, ray_off[j], r, ray_len)) {
         f = CLAPGPU_RAY_INVALID;
         b.key = KEY_NONE;
     } else {
         f = cast(k, r, i, b);
     }
     if (lane == 0) {
-        bool res = false;
-        hit[j] = hit_of(b.key);
-        if (b.key != KEY_NONE && !f) {
-            normal[3 * (size_t)j] = (float)b.normal[0];
-            normal[3 * (size_t)j + 1] = (float)b.normal[1];
-            normal[3 * (size_t)j + 2] = (float)b.normal[2];
-            float dy;
-            bool mv;
-            res = phd::ground_branch(b.depth, ray_len, grounded[j] != 0, dy, mv);
-            if (mv) atomicOr(&moved[i], 1u);
+        if (other && !(f & CLAPGPU_RAY_INVALID)) {
+            hit[j] = hit_of(b.key);
+            if (b.key != KEY_NONE) {
+                dist[j] = b.depth;
+                if (!f)
+                    for (int a = 0; a < 3; a++) normal[3 * (size_t)j + a] = (float)b.normal[a];
+            }
+            flags[j] = f;
+            other[j] = b.other;
+        } else {
+            ground_decide(j, i, ray_len, b.key, b.depth, b.normal, true, f, grounded, grounded_out, normal, dist, hit, flags, moved);
         }
-        if (b.key != KEY_NONE) dist[j] = b.depth;
-        grounded_out[j] = res ? 1 : 0;
-        flags[j] = f;
     }
 }
 
@@ -479,35 +450,75 @@ void k_ground_rays(CastK k, uint32_t n, const double *pos, const double *yoffset
 
 using namespace clapgpu;
 
-extern "C" int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
-                                uint32_t n_rays, const double *ray, const int32_t *skip, double *dist, int32_t *hit,
-                                double *contact, uint32_t *flags)
+// scratch for `other` between the passes: stream-ordered, freed behind the mesh pass
+static int mesh_scratch(hipStream_t s, const clapgpu_trimesh *meshes, uint32_t n, double **other)
+{
+    *other = nullptr;
+    if (!meshes || n == 0) return CLAPGPU_OK;
+    CLAPGPU_HIP(hipMallocAsync(reinterpret_cast<void **>(other), (size_t)n * sizeof(double), s));
+    return CLAPGPU_OK;
+}
+
+// ... freed behind whatever the stream holds, on the error paths too; rc: the call's result so far
+static int free_scratch(hipStream_t s, double *other, int rc)
+{
+    if (!other) return rc;
+    const hipError_t e = hipFreeAsync(other, s);
+    if (!rc && e != hipSuccess) return hip_fail(e, "hipFreeAsync");
+    return rc;
+}
+
+extern "C" int clapgpu_ray_cast_meshes(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
+                                       const clapgpu_trimesh *meshes, uint32_t n_rays, const double *ray, const int32_t *skip,
+                                       double *dist, int32_t *hit, double *contact, uint32_t *flags)
 {
     if (!bodies || !statics || (n_rays && (!ray || !dist || !hit))) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (meshes && trimesh_n_statics(meshes) != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;   // built for other statics
     CastK k;
     memset(&k, 0, sizeof(k));
     k.bodies = geoms_k(bodies); k.statics = geoms_k(statics);
+    k.meshed = meshes ? trimesh_static_mesh(meshes) : nullptr;
     if (bp) {
         if (!clapgpu_bp_grid_view(bp, bodies->n, nullptr, &k.g) || k.g.n_static != statics->n)
             return CLAPGPU_ERR_INVALID_ARGUMENTS;                           // not indexed over these bodies and statics
         k.grid = true;
     }
     if (n_rays == 0) return CLAPGPU_OK;
-    hipLaunchKernelGGL(k_ray_cast, dim3((n_rays + RB / WAVE - 1) / (RB / WAVE)), dim3(RB), 0, as_stream(stream), k, n_rays,
-                       ray, skip, dist, hit, contact, flags);
-    CLAPGPU_LAUNCH_CHECK("k_ray_cast");
-    return CLAPGPU_OK;
+    hipStream_t s = as_stream(stream);
+    double *other;
+    int rc = mesh_scratch(s, flags ? meshes : nullptr, n_rays, &other);     // no flags asked for: `other` is not needed
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ray_cast, dim3((n_rays + RB / WAVE - 1) / (RB / WAVE)), dim3(RB), 0, s, k, n_rays, ray, skip, dist, hit,
+                       contact, flags, other);
+    const hipError_t le = launch_error();
+    if (le != hipSuccess) rc = hip_fail(le, "k_ray_cast");
+    if (!rc && meshes) {
+        MeshPass p;
+        memset(&p, 0, sizeof(p));
+        p.n = n_rays; p.ray = ray; p.skip = skip; p.dist = dist; p.contact = contact; p.hit = hit; p.flags = flags; p.other = other;
+        rc = trimesh_pass(s, meshes, p);
+    }
+    return free_scratch(s, other, rc);
 }
 
-extern "C" int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,
-                                             uint32_t n, const uint32_t *body, const double *ray_off, const uint8_t *grounded,
-                                             uint8_t *grounded_out, float *normal, double *dist, int32_t *hit, uint32_t *flags,
-                                             uint32_t *scratch)
+extern "C" int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
+                                uint32_t n_rays, const double *ray, const int32_t *skip, double *dist, int32_t *hit,
+                                double *contact, uint32_t *flags)
+{
+    return clapgpu_ray_cast_meshes(stream, bp, bodies, statics, nullptr, n_rays, ray, skip, dist, hit, contact, flags);
+}
+
+extern "C" int clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b,
+                                                    const clapgpu_geoms *statics, const clapgpu_trimesh *meshes, uint32_t n,
+                                                    const uint32_t *body, const double *ray_off, const uint8_t *grounded,
+                                                    uint8_t *grounded_out, float *normal, double *dist, int32_t *hit,
+                                                    uint32_t *flags, uint32_t *scratch)
 {
     if (!b || !statics || !b->pos || !b->quat || !b->radius || !b->yoffset)
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (n && (!body || !ray_off || !grounded || !grounded_out || !normal || !dist || !hit || !flags || !scratch))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (meshes && trimesh_n_statics(meshes) != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     clapgpu_geoms g;                                                         // the bodies' geoms, as PhysWorld.body_geoms
     memset(&g, 0, sizeof(g));
     g.n = b->n; g.pos = b->pos; g.axis = b->axis; g.radius = b->radius; g.length = b->length; g.records = b->geom_records;
@@ -515,6 +526,7 @@ extern "C" int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const
     CastK k;
     memset(&k, 0, sizeof(k));
     k.bodies = geoms_k(&g); k.statics = geoms_k(statics);
+    k.meshed = meshes ? trimesh_static_mesh(meshes) : nullptr;
     if (bp) {
         if (!clapgpu_bp_grid_view(bp, b->n, b->aabb, &k.g) || k.g.n_static != statics->n)
             return CLAPGPU_ERR_INVALID_ARGUMENTS;
@@ -523,11 +535,34 @@ extern "C" int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const
     if (n == 0) return CLAPGPU_OK;
     hipStream_t s = as_stream(stream);
     CLAPGPU_HIP(hipMemsetAsync(scratch, 0, (size_t)(b->n ? b->n : 1) * sizeof(uint32_t), s));
+    double *other;
+    int rc = mesh_scratch(s, meshes, n, &other);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_ground_rays, dim3((n + RB / WAVE - 1) / (RB / WAVE)), dim3(RB), 0, s, k, n, b->pos, b->yoffset, body,
-                       ray_off, grounded, grounded_out, normal, dist, hit, flags, scratch);
-    CLAPGPU_LAUNCH_CHECK("k_ground_rays");
-    int rc = clapgpu_bodies_ground_apply(stream, b, n, body, ray_off, grounded, grounded_out, dist, hit, flags, scratch);
+                       ray_off, grounded, grounded_out, normal, dist, hit, flags, scratch, other);
+    const hipError_t le = launch_error();
+    if (le != hipSuccess) rc = hip_fail(le, "k_ground_rays");
+    if (!rc && meshes) {                                                     // the decision on the merged hit
+        MeshPass p;
+        memset(&p, 0, sizeof(p));
+        p.n = n; p.dist = dist; p.hit = hit; p.flags = flags; p.other = other;
+        p.n_bodies = b->n; p.pos = b->pos; p.yoffset = b->yoffset; p.ray_off = ray_off; p.body = body; p.grounded = grounded;
+        p.grounded_out = grounded_out; p.normal = normal; p.moved = scratch;
+        rc = trimesh_pass(s, meshes, p);
+    }
+    rc = free_scratch(s, other, rc);
+    if (rc) return rc;
+    rc = clapgpu_bodies_ground_apply(stream, b, n, body, ray_off, grounded, grounded_out, dist, hit, flags, scratch);
     if (rc) return rc;
     if (bp) return clapgpu_bp_invalidate(stream, bp);                        // the moved boxes: the index is stale
     return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,
+                                             uint32_t n, const uint32_t *body, const double *ray_off, const uint8_t *grounded,
+                                             uint8_t *grounded_out, float *normal, double *dist, int32_t *hit, uint32_t *flags,
+                                             uint32_t *scratch)
+{
+    return clapgpu_bodies_ground_collide_meshes(stream, bp, b, statics, nullptr, n, body, ray_off, grounded, grounded_out, normal,
+                                                dist, hit, flags, scratch);
 }

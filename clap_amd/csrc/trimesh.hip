@@ -1,0 +1,634 @@
+// trimesh.hip -- the triangle meshes of static trimesh geoms on the device, and ray casts against them, for gfx950:
+//
+//   k_tm_check      the index check of clapgpu_trimesh_create: every vertex index below its mesh's vertex count, every
+//                   static at most once and in range; fills static -> mesh and triangle -> mesh
+//   k_tm_bake       phys_geom_trimesh_new (physics.c:882-930) + the geom's pose: world-space fp64 triangles (72 B each)
+//   k_tm_morton     30-bit Morton code of each centroid in the centroids' bounds, the triangle index below it (64-bit key)
+//   (rocPRIM)       radix sort of the keys
+//   k_tm_gather     the triangles and their (static, triangle of its mesh) in leaf order
+//   k_tm_hierarchy  Karras 2012: the binary radix tree over the sorted keys (all distinct: the index breaks ties)
+//   k_tm_boxes      bottom-up: each node's two child boxes (float, rounded outward) and its subtree height
+//   k_ray_trimesh   one lane per ray: the BVH walk and the watertight ray-triangle test, merged with the best hit the
+//                   pass over bodies and statics (rays.hip) found
+//
+// The mesh: model3d.collision_vx scaled by the entity's scale in float the way mat4x4_scale_aniso + mat4x4_mul_vec4
+// compute it (each row starts from 0.f and adds the products, so -0 becomes +0; w == 1), widened to double, then
+// R * v + pos in fp64 with R = dQtoR(w, x, y, z) of the entity quaternion and pos the entity position (yoffset is 0 for a
+// trimesh).  Triangles are the u16 index triples in order, winding kept (physics.c:898-903).
+//
+// The test: ODE's dCollideRTL runs OPCODE's float ray-triangle test with ClosestHit = 1, BackfaceCull = 1 (physics.c:485-487).
+// Here the triangles are tested in fp64 with the watertight test of Woop, Benthin and Wald (JCGT 2013): the ray's dominant
+// axis is z, the other two are sheared onto it once per ray, and the three edge functions U, V, W of the projected
+// triangle decide.  A shared edge gets the same edge function with opposite sign in both triangles (the products
+// commute and the difference is negated exactly; no FMA contraction), so a ray through an edge or a vertex of front faces
+// hits at least one of them: no ray falls through the terrain.  Front face: U, V, W >= 0 and det = U + V + W > 0, which is
+// u . n < 0 for n = (v1 - v0) x (v2 - v0).  n == 0 never hits (ODE's dSafeNormalize3 fails there); a hit needs
+// 0 <= depth <= length.  Contact: pos = start + depth * u, normal = n / |n| (dSafeNormalize3), pointing back towards the
+// start.  Our reading is that dCollideRTL forms the reversed cross product and dCollide flips it again when it swaps
+// (trimesh, ray) into (ray, trimesh); ODE is an absent submodule of the reference, so this is PARITY UNPINNED.
+//
+// Ties: the smallest depth, then bodies before statics, then the lower static index, then the lower triangle index of
+// the mesh.  The walk prunes with the best depth so far inclusively (the ray's length while there is none) and takes
+// the minimum of (depth, key, triangle), which does not depend on the order the leaves are reached in.
+//
+// Tree: one BVH2 over every triangle of every mesh.  A node is 64 B: both children's boxes (float, min xyz / max xyz,
+// rounded outward from the fp64 triangles so that a box never excludes a point of a triangle it holds) and both links
+// (bit 31: a leaf = one triangle in leaf order).  The keys are distinct and the Morton part leaves the top two bits
+// clear, so the prefix length grows by at least one per level: the height is at most 62 (see clapgpu_trimesh_status).
+// The walk's stack is in LDS, [64 entries][64 lanes] of u32 (16 KiB per one-wave workgroup): a register array indexed by
+// a per-lane stack pointer would live in scratch memory, and the deep trees of degenerate meshes need all 64.
+#include <string.h>
+#include <stdlib.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include "common.h"
+#include "phys_dev.h"
+#include "bp_grid.h"
+#include "rays_dev.h"
+
+namespace clapgpu {
+
+constexpr int TB = 256;                                 // set-up kernels
+constexpr int RT = 64;                                  // k_ray_trimesh: one wave per workgroup
+constexpr int STACK = 64;
+constexpr uint32_t LEAF = 0x80000000u, NO_SLOT = 0xffffffffu;
+
+struct alignas(16) Node {
+    float box[12];                                      // child 0: min xyz, max xyz; child 1: the same
+    uint32_t child[2];
+    uint32_t pad[2];
+};
+static_assert(sizeof(Node) == 64, "one node, one 64-byte sector");
+
+struct MeshK {
+    const Node *nodes;
+    const double *tri;                                  // [T][9] in leaf order
+    const uint2 *key;                                   // [T]: (static, triangle of its mesh) in leaf order
+    uint32_t n_tris;
+};
+
+} // namespace clapgpu
+
+struct clapgpu_trimesh {
+    uint32_t n_meshes, n_statics, n_vx, n_tris;
+    uint32_t *static_index, *vx_first, *tri_first, *tri_mesh;
+    float *vx, *scale, *quat;
+    uint16_t *idx;
+    double *pos;
+    int32_t *static_mesh;                               // [n_statics]: the static's mesh or -1
+    double *tri, *stri;                                 // [T][9]: input order, leaf order
+    uint2 *skey;
+    uint64_t *keys[2];
+    clapgpu::Node *nodes;                               // [max(T - 1, 1)]
+    uint32_t *parent;                                   // [T - 1 + T]: of the internal nodes, then of the leaves
+    uint32_t *counter, *height;                         // [T - 1] each
+    uint64_t *bounds;                                   // [6]: centroid min xyz, max xyz as order keys
+    uint32_t *ctl;                                      // [0] check error, [1] tree height
+    void *sort_tmp;
+    size_t sort_bytes;
+};
+
+namespace clapgpu {
+
+// ------------------------------------------------------------------------------------------------- set-up kernels
+__global__ __launch_bounds__(TB)
+void k_tm_check(uint32_t M, uint32_t T, uint32_t n_statics, const uint32_t *static_index, const uint32_t *vx_first,
+                const uint32_t *tri_first, const uint16_t *idx, uint32_t *tri_mesh, int32_t *static_mesh, uint32_t *ctl)
+{
+    const uint32_t t = blockIdx.x * TB + threadIdx.x;
+    if (t < T) {
+        uint32_t lo = 0, hi = M;                        // the last mesh whose first triangle is <= t (tri_first ascending)
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) / 2;
+            if (tri_first[mid] <= t) lo = mid; else hi = mid;
+        }
+        tri_mesh[t] = lo;
+        const uint32_t nv = vx_first[lo + 1] - vx_first[lo];
+        for (int c = 0; c < 3; c++)
+            if (idx[3 * (size_t)t + c] >= nv) atomicOr(&ctl[0], 1u);
+    }
+    if (t < M) {
+        const uint32_t s = static_index[t];
+        if (s >= n_statics) atomicOr(&ctl[0], 2u);
+        else if (atomicCAS(&static_mesh[s], -1, (int32_t)t) != -1) atomicOr(&ctl[0], 4u);
+    }
+}
+
+// mat4x4_scale_aniso(identity, s, s, s) then mat4x4_mul_vec4 on (x, y, z, 1): each row from 0.f plus the four
+// products in order, then vec3_scale by 1 / w
+__device__ __forceinline__ void scaled(float s, const float *v, double (&o)[3])
+{
+    const float v4[4] = { v[0], v[1], v[2], 1.0f };
+    float r[4];
+    for (int j = 0; j < 4; j++) {
+        r[j] = 0.f;
+        for (int i = 0; i < 4; i++) r[j] += (i == j ? (j < 3 ? s : 1.0f) : 0.0f) * v4[i];
+    }
+    const float w = 1.0f / r[3];
+    for (int j = 0; j < 3; j++) o[j] = r[j] * w;
+}
+
+__global__ __launch_bounds__(TB)
+void k_tm_bake(uint32_t T, const uint32_t *tri_mesh, const uint32_t *vx_first, const float *vx, const uint16_t *idx,
+               const float *scale, const double *pos, const float *quat, double *tri, uint64_t *bounds)
+{
+    const uint32_t t = blockIdx.x * TB + threadIdx.x;
+    double c[3] = { NAN, NAN, NAN };
+    if (t < T) {
+        const uint32_t m = tri_mesh[t];
+        const double q[4] = { quat[4 * (size_t)m + 3], quat[4 * (size_t)m], quat[4 * (size_t)m + 1], quat[4 * (size_t)m + 2] };
+        double R[12];
+        phd::q_to_R(q, R);
+        const double p[3] = { pos[3 * (size_t)m], pos[3 * (size_t)m + 1], pos[3 * (size_t)m + 2] };
+        const float s = scale[m];
+        double w[9];
+        for (int k = 0; k < 3; k++) {
+            const float *v = vx + 3 * ((size_t)vx_first[m] + idx[3 * (size_t)t + k]);
+            double ms[3];
+            scaled(s, v, ms);
+            for (int a = 0; a < 3; a++)
+                w[3 * k + a] = R[4 * a] * ms[0] + R[4 * a + 1] * ms[1] + R[4 * a + 2] * ms[2] + p[a];
+        }
+        for (int a = 0; a < 9; a++) tri[9 * (size_t)t + a] = w[a];
+        for (int a = 0; a < 3; a++) c[a] = (w[a] + w[3 + a] + w[6 + a]) / 3.0;
+    }
+    // the centroids' bounds: the wave's, then the workgroup's in LDS, then one atomic per workgroup and side (NaN
+    // centroids left out)
+    __shared__ double red[TB / WAVE][6];
+    const int wv = threadIdx.x / WAVE;
+    for (int a = 0; a < 3; a++) {
+        double lo = c[a] == c[a] ? c[a] : INFINITY, hi = c[a] == c[a] ? c[a] : -INFINITY;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo = fmin(lo, __shfl_xor(lo, o));
+            hi = fmax(hi, __shfl_xor(hi, o));
+        }
+        if (lane_id() == 0) { red[wv][a] = lo; red[wv][3 + a] = hi; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        double lo = red[0][a], hi = red[0][3 + a];
+        for (int k = 1; k < TB / WAVE; k++) { lo = fmin(lo, red[k][a]); hi = fmax(hi, red[k][3 + a]); }
+        if (lo <= hi) {
+            atomicMin((unsigned long long *)&bounds[a], (unsigned long long)order_key(lo));
+            atomicMax((unsigned long long *)&bounds[3 + a], (unsigned long long)order_key(hi));
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t spread10(uint32_t x)                // 10 bits -> every third bit
+{
+    x &= 0x3ffu;
+    x = (x | (x << 16)) & 0x030000ffu;
+    x = (x | (x << 8)) & 0x0300f00fu;
+    x = (x | (x << 4)) & 0x030c30c3u;
+    x = (x | (x << 2)) & 0x09249249u;
+    return x;
+}
+
+__global__ __launch_bounds__(TB)
+void k_tm_morton(uint32_t T, const double *tri, const uint64_t *bounds, uint64_t *keys)
+{
+    const uint32_t t = blockIdx.x * TB + threadIdx.x;
+    if (t >= T) return;
+    uint32_t code = 0;
+    if (bounds[0] != ~0ull) {                           // else every centroid is NaN: code 0
+        for (int a = 0; a < 3; a++) {
+            const double lo = order_value(bounds[a]), hi = order_value(bounds[3 + a]);
+            const double c = (tri[9 * (size_t)t + a] + tri[9 * (size_t)t + 3 + a] + tri[9 * (size_t)t + 6 + a]) / 3.0;
+            double f = hi > lo ? (c - lo) / (hi - lo) : 0.0;
+            f = f >= 0.0 ? (f <= 1.0 ? f : 1.0) : 0.0;  // NaN: 0
+            const uint32_t q = (uint32_t)fmin(f * 1024.0, 1023.0);
+            code |= spread10(q) << (2 - a);
+        }
+    }
+    keys[t] = ((uint64_t)code << 32) | t;
+}
+
+__global__ __launch_bounds__(TB)
+void k_tm_gather(uint32_t T, const uint64_t *keys, const double *tri, const uint32_t *tri_mesh, const uint32_t *tri_first,
+                 const uint32_t *static_index, double *stri, uint2 *skey)
+{
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i >= T) return;
+    const uint32_t t = (uint32_t)keys[i], m = tri_mesh[t];
+    for (int a = 0; a < 9; a++) stri[9 * (size_t)i + a] = tri[9 * (size_t)t + a];
+    skey[i] = make_uint2(static_index[m], t - tri_first[m]);
+}
+
+__device__ __forceinline__ int delta(const uint64_t *k, int64_t T, int64_t i, int64_t j)
+{
+    return (j < 0 || j >= T) ? -1 : __clzll((long long)(k[i] ^ k[j]));
+}
+
+// Karras 2012, "Maximizing parallelism in the construction of BVHs, octrees, and k-d trees", internal node i of T - 1
+__global__ __launch_bounds__(TB)
+void k_tm_hierarchy(uint32_t T, const uint64_t *k, Node *nodes, uint32_t *parent)
+{
+    const int64_t i = blockIdx.x * (int64_t)TB + threadIdx.x, n = T;
+    if (i >= n - 1) return;
+    const int d = delta(k, n, i, i + 1) - delta(k, n, i, i - 1) >= 0 ? 1 : -1;
+    const int dmin = delta(k, n, i, i - d);
+    int64_t lmax = 2;
+    while (delta(k, n, i, i + lmax * d) > dmin) lmax <<= 1;
+    int64_t l = 0;
+    for (int64_t t = lmax >> 1; t >= 1; t >>= 1)
+        if (delta(k, n, i, i + (l + t) * d) > dmin) l += t;
+    const int64_t j = i + l * d;
+    const int dnode = delta(k, n, i, j);
+    int64_t s = 0, t = l;
+    do {
+        t = (t + 1) >> 1;
+        if (delta(k, n, i, i + (s + t) * d) > dnode) s += t;
+    } while (t > 1);
+    const int64_t g = i + s * d + (d < 0 ? -1 : 0);
+    const int64_t lo = i < j ? i : j, hi = i < j ? j : i;
+    const uint32_t c0 = lo == g ? LEAF | (uint32_t)g : (uint32_t)g;
+    const uint32_t c1 = hi == g + 1 ? LEAF | (uint32_t)(g + 1) : (uint32_t)(g + 1);
+    nodes[i].child[0] = c0;
+    nodes[i].child[1] = c1;
+    nodes[i].pad[0] = nodes[i].pad[1] = 0;
+    parent[(c0 & LEAF) ? (n - 1) + (c0 & ~LEAF) : c0] = (uint32_t)i;
+    parent[(c1 & LEAF) ? (n - 1) + (c1 & ~LEAF) : c1] = (uint32_t)i;
+}
+
+__device__ __forceinline__ float round_down(double d)
+{
+    float f = (float)d;
+    if ((double)f > d) f = nextafterf(f, -INFINITY);
+    return f;
+}
+
+__device__ __forceinline__ float round_up(double d)
+{
+    float f = (float)d;
+    if ((double)f < d) f = nextafterf(f, INFINITY);
+    return f;
+}
+
+__device__ __forceinline__ float load_agent(const float *p)
+{
+    return __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+// one thread per leaf climbs while it is the second child to arrive at a node
+__global__ __launch_bounds__(TB)
+void k_tm_boxes(uint32_t T, const double *stri, Node *nodes, const uint32_t *parent, uint32_t *counter, uint32_t *height,
+                uint32_t *ctl)
+{
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i >= T) return;
+    float b[6];
+    const double *v = stri + 9 * (size_t)i;
+    for (int a = 0; a < 3; a++) {
+        b[a] = round_down(fmin(fmin(v[a], v[3 + a]), v[6 + a]));
+        b[3 + a] = round_up(fmax(fmax(v[a], v[3 + a]), v[6 + a]));
+    }
+    if (T == 1) {                                       // a root holding the one leaf twice
+        for (int a = 0; a < 6; a++) { nodes[0].box[a] = b[a]; nodes[0].box[6 + a] = b[a]; }
+        nodes[0].child[0] = nodes[0].child[1] = LEAF;
+        nodes[0].pad[0] = nodes[0].pad[1] = 0;
+        ctl[1] = 1;
+        return;
+    }
+    uint32_t x = LEAF | i, h = 0, p = parent[(T - 1) + i];
+    for (;;) {
+        Node &n = nodes[p];
+        const int side = n.child[0] == x ? 0 : 1;
+        for (int a = 0; a < 6; a++) n.box[6 * side + a] = b[a];
+        const uint32_t old = __hip_atomic_fetch_add(&counter[p], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == 0) return;                           // the sibling finishes this node
+        const uint32_t sib = n.child[1 - side];
+        for (int a = 0; a < 3; a++) {
+            b[a] = fminf(b[a], load_agent(&n.box[6 * (1 - side) + a]));
+            b[3 + a] = fmaxf(b[3 + a], load_agent(&n.box[6 * (1 - side) + 3 + a]));
+        }
+        const uint32_t hs = (sib & LEAF) ? 0u : __hip_atomic_load(&height[sib], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        h = 1 + (h > hs ? h : hs);
+        __hip_atomic_store(&height[p], h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (p == 0) { ctl[1] = h; return; }
+        x = p;
+        p = parent[p];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------- ray pass
+struct Shear {
+    int kx, ky, kz;
+    double Sx, Sy, Sz;
+    double inv[3];
+};
+
+__device__ __forceinline__ double pick(const double (&v)[3], int k) { return k == 0 ? v[0] : k == 1 ? v[1] : v[2]; }
+
+__device__ __forceinline__ void shear_of(const Ray &r, Shear &q)
+{
+    const double ax = fabs(r.u[0]), ay = fabs(r.u[1]), az = fabs(r.u[2]);
+    q.kz = ax >= ay ? (ax >= az ? 0 : 2) : (ay >= az ? 1 : 2);
+    q.kx = q.kz == 2 ? 0 : q.kz + 1;
+    q.ky = q.kx == 2 ? 0 : q.kx + 1;
+    const double uz = pick(r.u, q.kz);
+    if (uz < 0) { const int t = q.kx; q.kx = q.ky; q.ky = t; }                 // keeps the winding
+    q.Sx = pick(r.u, q.kx) / uz;
+    q.Sy = pick(r.u, q.ky) / uz;
+    q.Sz = 1.0 / uz;
+    for (int a = 0; a < 3; a++) q.inv[a] = r.u[a] == 0 ? 0.0 : 1.0 / r.u[a];             // 0: see box_hit
+}
+
+// where the segment [0, tmax] enters a float box, conservatively: a box holding a hit point at t <= tmax passes.  An axis
+// the ray does not move along is a containment test (a start on the slab's face is inside it)
+__device__ __forceinline__ bool box_hit(const Ray &r, const Shear &q, const float *b, double tmax, double &tn)
+{
+    double lo = 0.0, hi = INFINITY;
+    for (int a = 0; a < 3; a++) {
+        const double ta = ((double)b[a] - r.s[a]) * q.inv[a], tb = ((double)b[3 + a] - r.s[a]) * q.inv[a];
+        const bool in = (double)b[a] <= r.s[a] && r.s[a] <= (double)b[3 + a];
+        const bool flat = r.u[a] == 0;
+        lo = fmax(lo, flat ? (in ? -INFINITY : INFINITY) : fmin(ta, tb));
+        hi = fmin(hi, flat ? (in ? INFINITY : -INFINITY) : fmax(ta, tb));
+    }
+    tn = lo;
+    return lo * (1.0 - 0x1p-48) <= fmin(hi * (1.0 + 0x1p-48), tmax);
+}
+
+struct MeshBest { double t; uint32_t key, tri, slot; };
+
+__device__ __forceinline__ void test_tri(const MeshK &m, const Ray &r, const Shear &q, uint32_t slot, uint32_t skip_key,
+                                         MeshBest &b)
+{
+    const uint2 kt = m.key[slot];
+    const uint32_t key = KEY_STATIC | kt.x;
+    if (key == skip_key) return;
+    const double *v = m.tri + 9 * (size_t)slot;
+    const double A[3] = { v[0] - r.s[0], v[1] - r.s[1], v[2] - r.s[2] };
+    const double B[3] = { v[3] - r.s[0], v[4] - r.s[1], v[5] - r.s[2] };
+    const double C[3] = { v[6] - r.s[0], v[7] - r.s[1], v[8] - r.s[2] };
+    const double Az = pick(A, q.kz), Bz = pick(B, q.kz), Cz = pick(C, q.kz);
+    const double Ax = pick(A, q.kx) - q.Sx * Az, Ay = pick(A, q.ky) - q.Sy * Az;
+    const double Bx = pick(B, q.kx) - q.Sx * Bz, By = pick(B, q.ky) - q.Sy * Bz;
+    const double Cx = pick(C, q.kx) - q.Sx * Cz, Cy = pick(C, q.ky) - q.Sy * Cz;
+    const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    if (!(U >= 0 && V >= 0 && W >= 0)) return;                              // outside, or a back face
+    const double det = U + V + W;
+    if (!(det > 0)) return;                                                   // edge-on or parallel
+    const double T = U * (q.Sz * Az) + V * (q.Sz * Bz) + W * (q.Sz * Cz);
+    const double t = T / det;
+    if (!(t >= 0 && t <= r.len)) return;
+    if (!(t < b.t || (t == b.t && (key < b.key || (key == b.key && kt.y < b.tri))))) return;
+    const double e1[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, e2[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
+    const double n[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
+    if (n[0] == 0 && n[1] == 0 && n[2] == 0) return;                          // zero area: never a hit
+    b.t = t; b.key = key; b.tri = kt.y; b.slot = slot;
+}
+
+__device__ void trace(const MeshK &m, const Ray &r, uint32_t skip_key, MeshBest &b, uint32_t *stk)
+{
+    if (m.n_tris == 0) return;
+    Shear q;
+    shear_of(r, q);
+    uint32_t node = 0;
+    int sp = 0;
+    for (;;) {
+        const float4 *np = reinterpret_cast<const float4 *>(m.nodes + node);
+        const float4 f0 = np[0], f1 = np[1], f2 = np[2];
+        const uint4 c = reinterpret_cast<const uint4 *>(np)[3];
+        const float bl[6] = { f0.x, f0.y, f0.z, f0.w, f1.x, f1.y }, br[6] = { f1.z, f1.w, f2.x, f2.y, f2.z, f2.w };
+        double tl, tr;
+        bool hl = box_hit(r, q, bl, b.t, tl), hr = box_hit(r, q, br, b.t, tr);
+        if (hl && (c.x & LEAF)) { test_tri(m, r, q, c.x & ~LEAF, skip_key, b); hl = false; }
+        if (hr && (c.y & LEAF)) { test_tri(m, r, q, c.y & ~LEAF, skip_key, b); hr = false; }
+        if (hl && hr) {
+            const bool lfirst = tl <= tr;
+            if (sp < STACK) stk[sp++ * RT] = lfirst ? c.y : c.x;
+            node = lfirst ? c.x : c.y;
+        } else if (hl) {
+            node = c.x;
+        } else if (hr) {
+            node = c.y;
+        } else {
+            if (sp == 0) break;
+            node = stk[--sp * RT];
+        }
+    }
+}
+
+template <bool GROUND>
+__global__ __launch_bounds__(RT)
+void k_ray_trimesh(MeshK m, MeshPass p)
+{
+    __shared__ uint32_t stk[STACK * RT];
+    const uint32_t j = blockIdx.x * RT + threadIdx.x;
+    if (j >= p.n) return;
+    Ray r;
+    double ray_len = 0;
+    uint32_t i = 0, skip_key;
+    if (GROUND) {
+        i = p.body[j];
+        if (i >= p.n_bodies || (p.flags[j] & CLAPGPU_RAY_INVALID)) return;   // decided by rays.hip
+        ground_ray(p.pos, p.yoffset, i, p.ray_off[j], r, ray_len);
+        skip_key = i;
+    } else {
+        if (!make_ray(p.ray + 8 * (size_t)j, r)) return;
+        skip_key = skip_key_of(p.skip ? p.skip[j] : -1);
+    }
+    MeshBest b;
+    b.key = key_of(p.hit[j]);
+    b.t = b.key == KEY_NONE ? r.len : p.dist[j];        // the walk stays within the segment (KEY_NONE: t == len still wins)
+    b.tri = 0;
+    b.slot = NO_SLOT;
+    trace(m, r, skip_key, b, stk + threadIdx.x);
+    const bool won = b.slot != NO_SLOT;
+    double nrm[3] = { 0, 0, 0 };
+    if (won) {
+        const double *v = m.tri + 9 * (size_t)b.slot;
+        const double e1[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, e2[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
+        nrm[0] = e1[1] * e2[2] - e1[2] * e2[1];
+        nrm[1] = e1[2] * e2[0] - e1[0] * e2[2];
+        nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
+        phd::safe_normalize3(nrm);
+    }
+    const uint32_t f = p.other ? unresolved(p.other[j], r.len, b.key, b.t) : 0u;
+    if (GROUND) {
+        ground_decide(j, i, ray_len, b.key, b.t, nrm, won, f, p.grounded, p.grounded_out, p.normal, p.dist, p.hit,
+                      p.flags, p.moved);
+    } else {
+        if (won) {
+            p.hit[j] = hit_of(b.key);
+            p.dist[j] = b.t;
+            if (p.contact)
+                for (int a = 0; a < 3; a++) {
+                    p.contact[6 * (size_t)j + a] = r.s[a] + b.t * r.u[a];
+                    p.contact[6 * (size_t)j + 3 + a] = nrm[a];
+                }
+        }
+        if (p.flags) p.flags[j] = f;
+    }
+}
+
+const int32_t *trimesh_static_mesh(const clapgpu_trimesh *m) { return m->static_mesh; }
+uint32_t trimesh_n_statics(const clapgpu_trimesh *m) { return m->n_statics; }
+
+int trimesh_pass(hipStream_t s, const clapgpu_trimesh *tm, const MeshPass &p)
+{
+    if (p.n == 0) return CLAPGPU_OK;
+    MeshK m;
+    m.nodes = tm->nodes; m.tri = tm->stri; m.key = tm->skey; m.n_tris = tm->n_tris;
+    if (p.ray) hipLaunchKernelGGL(k_ray_trimesh<false>, dim3((p.n + RT - 1) / RT), dim3(RT), 0, s, m, p);
+    else hipLaunchKernelGGL(k_ray_trimesh<true>, dim3((p.n + RT - 1) / RT), dim3(RT), 0, s, m, p);
+    CLAPGPU_LAUNCH_CHECK("k_ray_trimesh");
+    return CLAPGPU_OK;
+}
+
+// bake + tree from the current poses: the one rebuild path of create and pose
+static int build(hipStream_t s, clapgpu_trimesh *m)
+{
+    const uint32_t T = m->n_tris;
+    if (T == 0) return CLAPGPU_OK;
+    const dim3 g((T + TB - 1) / TB);
+    CLAPGPU_HIP(hipMemsetAsync(m->bounds, 0xff, 3 * sizeof(uint64_t), s));
+    CLAPGPU_HIP(hipMemsetAsync(m->bounds + 3, 0, 3 * sizeof(uint64_t), s));
+    hipLaunchKernelGGL(k_tm_bake, g, dim3(TB), 0, s, T, m->tri_mesh, m->vx_first, m->vx, m->idx, m->scale, m->pos, m->quat, m->tri,
+                       m->bounds);
+    CLAPGPU_LAUNCH_CHECK("k_tm_bake");
+    hipLaunchKernelGGL(k_tm_morton, g, dim3(TB), 0, s, T, m->tri, m->bounds, m->keys[0]);
+    CLAPGPU_LAUNCH_CHECK("k_tm_morton");
+    size_t bytes = m->sort_bytes;
+    CLAPGPU_HIP(rocprim::radix_sort_keys(m->sort_tmp, bytes, m->keys[0], m->keys[1], T, 0, 62, s));
+    hipLaunchKernelGGL(k_tm_gather, g, dim3(TB), 0, s, T, m->keys[1], m->tri, m->tri_mesh, m->tri_first, m->static_index, m->stri,
+                       m->skey);
+    CLAPGPU_LAUNCH_CHECK("k_tm_gather");
+    if (T > 1) {
+        CLAPGPU_HIP(hipMemsetAsync(m->counter, 0, (size_t)(T - 1) * sizeof(uint32_t), s));
+        hipLaunchKernelGGL(k_tm_hierarchy, dim3((T - 1 + TB - 1) / TB), dim3(TB), 0, s, T, m->keys[1], m->nodes, m->parent);
+        CLAPGPU_LAUNCH_CHECK("k_tm_hierarchy");
+    }
+    hipLaunchKernelGGL(k_tm_boxes, g, dim3(TB), 0, s, T, m->stri, m->nodes, m->parent, m->counter, m->height, m->ctl);
+    CLAPGPU_LAUNCH_CHECK("k_tm_boxes");
+    return CLAPGPU_OK;
+}
+
+} // namespace clapgpu
+
+using namespace clapgpu;
+
+extern "C" void clapgpu_trimesh_destroy(clapgpu_trimesh *m)
+{
+    if (!m) return;
+    void *p[] = { m->static_index, m->vx_first, m->tri_first, m->tri_mesh, m->vx, m->scale, m->quat, m->idx, m->pos,
+                  m->static_mesh, m->tri, m->stri, m->skey, m->keys[0], m->keys[1], m->nodes, m->parent, m->counter,
+                  m->height, m->bounds, m->ctl, m->sort_tmp };
+    for (void *q : p)
+        if (q) (void)hipFree(q);
+    free(m);
+}
+
+template <typename T> static int dev_alloc(T *&p, size_t n)
+{
+    CLAPGPU_HIP(hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T)));
+    return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_trimesh_create(void *stream, clapgpu_trimesh **out, const clapgpu_trimesh_desc *d)
+{
+    if (!out || !d) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    *out = nullptr;
+    const uint32_t M = d->n_meshes;
+    const bool any = d->static_index || d->vx_first || d->tri_first || d->vx || d->idx || d->scale || d->pos || d->quat;
+    const bool all = d->static_index && d->vx_first && d->tri_first && d->vx && d->idx && d->scale && d->pos && d->quat;
+    if (M == 0 ? any : !all) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (M > 0 && d->n_statics == 0) return CLAPGPU_ERR_INVALID_ARGUMENTS;     // every static_index would be out of range
+    hipStream_t s = as_stream(stream);
+    clapgpu_trimesh *m = static_cast<clapgpu_trimesh *>(calloc(1, sizeof(clapgpu_trimesh)));
+    if (!m) return CLAPGPU_ERR_NOMEM;
+    m->n_meshes = M;
+    m->n_statics = d->n_statics;
+    int rc = CLAPGPU_OK;
+#define TRY(x) do { rc = (x); if (rc) { clapgpu_trimesh_destroy(m); return rc; } } while (0)
+    uint32_t *hf = static_cast<uint32_t *>(malloc(2 * ((size_t)M + 1) * sizeof(uint32_t)));
+    if (!hf) { clapgpu_trimesh_destroy(m); return CLAPGPU_ERR_NOMEM; }
+    hf[0] = hf[M + 1] = 0;
+    if (M) {                                                                   // the ranges, on the host: they size everything
+        hipError_t e = hipMemcpyAsync(hf, d->vx_first, ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(hf + M + 1, d->tri_first, ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { free(hf); clapgpu_trimesh_destroy(m); return hip_fail(e, "clapgpu_trimesh_create: ranges"); }
+    }
+    bool ok = hf[0] == 0 && hf[M + 1] == 0;
+    for (uint32_t k = 0; k < M && ok; k++) ok = hf[k + 1] >= hf[k] && hf[M + 2 + k] >= hf[M + 1 + k];
+    m->n_vx = hf[M];
+    m->n_tris = hf[2 * M + 1];
+    free(hf);
+    if (!ok || m->n_tris >= LEAF) { clapgpu_trimesh_destroy(m); return CLAPGPU_ERR_INVALID_ARGUMENTS; }
+    const size_t V = m->n_vx, T = m->n_tris;
+    TRY(dev_alloc(m->static_index, M)); TRY(dev_alloc(m->vx_first, M + 1)); TRY(dev_alloc(m->tri_first, M + 1));
+    TRY(dev_alloc(m->tri_mesh, T)); TRY(dev_alloc(m->vx, 3 * V)); TRY(dev_alloc(m->scale, M)); TRY(dev_alloc(m->quat, 4 * M));
+    TRY(dev_alloc(m->idx, 3 * T)); TRY(dev_alloc(m->pos, 3 * M)); TRY(dev_alloc(m->static_mesh, m->n_statics));
+    TRY(dev_alloc(m->tri, 9 * T)); TRY(dev_alloc(m->stri, 9 * T)); TRY(dev_alloc(m->skey, T));
+    TRY(dev_alloc(m->keys[0], T)); TRY(dev_alloc(m->keys[1], T)); TRY(dev_alloc(m->nodes, T > 1 ? T - 1 : 1));
+    TRY(dev_alloc(m->parent, 2 * T)); TRY(dev_alloc(m->counter, T)); TRY(dev_alloc(m->height, T));
+    TRY(dev_alloc(m->bounds, 6)); TRY(dev_alloc(m->ctl, 4));
+    if (T) {
+        size_t bytes = 0;
+        if (rocprim::radix_sort_keys(nullptr, bytes, m->keys[0], m->keys[1], (size_t)T, 0, 62, s) != hipSuccess)
+            TRY(CLAPGPU_ERR_UNKNOWN);
+        m->sort_bytes = bytes;
+        TRY(dev_alloc(reinterpret_cast<uint8_t *&>(m->sort_tmp), bytes));
+    }
+    auto cp = [&](void *dst, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+    };
+    hipError_t e = hipSuccess;
+    if (M) {
+        const hipError_t es[] = { cp(m->static_index, d->static_index, M * 4), cp(m->vx_first, d->vx_first, (M + 1) * 4),
+                                  cp(m->tri_first, d->tri_first, (M + 1) * 4), cp(m->vx, d->vx, 12 * V), cp(m->idx, d->idx, 6 * T),
+                                  cp(m->scale, d->scale, 4 * (size_t)M), cp(m->pos, d->pos, 24 * (size_t)M),
+                                  cp(m->quat, d->quat, 16 * (size_t)M) };
+        for (hipError_t x : es) if (x != hipSuccess) e = x;
+    }
+    if (e == hipSuccess && m->n_statics) e = hipMemsetAsync(m->static_mesh, 0xff, (size_t)m->n_statics * 4, s);
+    if (e == hipSuccess) e = hipMemsetAsync(m->ctl, 0, 4 * sizeof(uint32_t), s);
+    if (e != hipSuccess) { clapgpu_trimesh_destroy(m); return hip_fail(e, "clapgpu_trimesh_create: copies"); }
+    const size_t nt = T > M ? T : M;
+    if (nt) {
+        hipLaunchKernelGGL(k_tm_check, dim3((unsigned)((nt + TB - 1) / TB)), dim3(TB), 0, s, M, (uint32_t)T, m->n_statics,
+                           m->static_index, m->vx_first, m->tri_first, m->idx, m->tri_mesh, m->static_mesh, m->ctl);
+        e = launch_error();
+        uint32_t err = 0;
+        if (e == hipSuccess) e = hipMemcpyAsync(&err, m->ctl, sizeof(err), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { clapgpu_trimesh_destroy(m); return hip_fail(e, "k_tm_check"); }
+        if (err) {
+            set_last_error(err & 1 ? "clapgpu_trimesh_create: a vertex index at or beyond its mesh's vertex count"
+                                   : err & 2 ? "clapgpu_trimesh_create: a static_index out of range"
+                                             : "clapgpu_trimesh_create: a static listed twice");
+            clapgpu_trimesh_destroy(m);
+            return CLAPGPU_ERR_INVALID_ARGUMENTS;
+        }
+    }
+    TRY(build(s, m));
+#undef TRY
+    *out = m;
+    return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_trimesh_pose(void *stream, clapgpu_trimesh *m, const double *pos, const float *quat)
+{
+    if (!m || (m->n_meshes && (!pos || !quat))) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (m->n_meshes == 0) return CLAPGPU_OK;
+    hipStream_t s = as_stream(stream);
+    CLAPGPU_HIP(hipMemcpyAsync(m->pos, pos, 24 * (size_t)m->n_meshes, hipMemcpyDeviceToDevice, s));
+    CLAPGPU_HIP(hipMemcpyAsync(m->quat, quat, 16 * (size_t)m->n_meshes, hipMemcpyDeviceToDevice, s));
+    return build(s, m);
+}
+
+extern "C" int clapgpu_trimesh_status(void *stream, const clapgpu_trimesh *m, uint32_t *depth, uint32_t *n_tris)
+{
+    if (!m || !depth || !n_tris) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    *n_tris = m->n_tris;
+    *depth = 0;
+    if (m->n_tris == 0) return CLAPGPU_OK;
+    hipStream_t s = as_stream(stream);
+    CLAPGPU_HIP(hipMemcpyAsync(depth, m->ctl + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    CLAPGPU_HIP(hipStreamSynchronize(s));
+    return CLAPGPU_OK;
+}

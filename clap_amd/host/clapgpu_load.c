@@ -688,12 +688,14 @@ struct ld_model {
     uint8_t *joints;
     struct ld_anim *anims; uint32_t n_anims;
     char **anim_name;
+    uint16_t *cidx; uint32_t n_ctri;     /* "geom": "trimesh": model3d.collision_idx (the vertices are `position`) */
+    int has_collision;
 };
 
 static void model_free(struct ld_model *m)
 {
     free(m->name); free(m->joint_parent); free(m->invmx); free(m->bind); free(m->position); free(m->normal);
-    free(m->weights); free(m->joints);
+    free(m->weights); free(m->joints); free(m->cidx);
     for (uint32_t j = 0; m->joint_name && j < m->nr_joints; j++) free(m->joint_name[j]);
     free(m->joint_name);
     for (uint32_t a = 0; a < m->n_anims; a++) {
@@ -849,6 +851,33 @@ static int model_from_gltf(struct ld_model *m, const struct gltf *g, int mesh, i
         m->anim_name[m->n_anims] = ga->name ? strdup(ga->name) : NULL;
         m->anims[m->n_anims++] = an;
     }
+    return LD_OK;
+}
+
+/* model3d_make keeps the instantiated mesh's vertices (after fix_origin) and u16 indices as the collision mesh
+ * (model.c:99-102); phys_geom_trimesh_new reads them (physics.c:882-930).  Indices of another width are narrowed when
+ * they fit in u16; a trailing partial triple is dropped (ODE takes whole triangles). */
+static int collision_from_gltf(struct ld_model *m, const struct gltf *g, int mesh, struct ld_err *e)
+{
+    const struct g_mesh *gm = &g->meshes[mesh];
+    const int ia = gm->indices;
+    size_t es; unsigned cnt;
+    const uint8_t *ib = accr_buf(g, ia, &es, &cnt);
+    if (!ib || g->accrs[ia].comps != 1) return fail(e, LD_PARSE, "mesh '%s': indices are not a readable scalar accessor", gm->name);
+    const unsigned ct = g->accrs[ia].comptype;
+    if (ct != 0x1401 && ct != 0x1403 && ct != 0x1405) return fail(e, LD_PARSE, "mesh '%s': indices are not u8 / u16 / u32", gm->name);
+    m->n_ctri = cnt / 3;
+    m->cidx = malloc((size_t)(m->n_ctri ? m->n_ctri : 1) * 6);
+    if (!m->cidx) return LD_NOMEM;
+    for (size_t i = 0; i < (size_t)m->n_ctri * 3; i++) {
+        uint32_t v;
+        if (ct == 0x1401) v = ib[i];
+        else if (ct == 0x1403) { uint16_t h; memcpy(&h, ib + 2 * i, 2); v = h; }
+        else memcpy(&v, ib + 4 * i, 4);
+        if (v >= m->n_verts || v > 0xffffu) return fail(e, LD_PARSE, "mesh '%s': index %u outside the mesh's %u vertices", gm->name, v, m->n_verts);
+        m->cidx[i] = (uint16_t)v;
+    }
+    m->has_collision = 1;
     return LD_OK;
 }
 
@@ -1057,6 +1086,10 @@ static int model_from_json(struct ld_scene *s, const struct jnode *node, struct 
                 else if (!strcmp(p->str, "geom")) ptype = 1;
             }
         }
+    if (phys && geom_class == 2) {                                       /* a trimesh body: its collision mesh */
+        rc = collision_from_gltf(m, &g, mesh, e);
+        if (rc) { gltf_free(&g); return rc; }
+    }
     /* "armature": semantic joint roles by joint name (scene.c:1476-1492) */
     const struct jnode *arm = jfind(node, "armature");
     if (arm && arm->tag == J_OBJECT) {
@@ -1254,6 +1287,30 @@ static int write_scene(const struct ld_scene *s, const char *snapshot_path)
     A("entities", "model_aabb", CLAPGPU_DT_F32, 2, nm, 6, maabb);
     A("entities", "model_skip", CLAPGPU_DT_U8, 1, nm, 0, mskip);
     if (!rc) rc = add_i64(w, "scene", "n_models", (int64_t)nm);
+    {   /* collision meshes of the trimesh bodies' models: model k's are vx[vx_first[k] ..), idx[tri_first[k] ..) */
+        uint32_t *vf = calloc(nm + 1, 4), *tf = calloc(nm + 1, 4);
+        if (!vf || !tf) rc = rc ? rc : LD_NOMEM;
+        for (size_t k = 0; vf && tf && k < nm; k++) {
+            vf[k + 1] = vf[k] + (md[k].has_collision ? md[k].n_verts : 0);
+            tf[k + 1] = tf[k] + (md[k].has_collision ? md[k].n_ctri : 0);
+        }
+        float *cv = vf ? malloc((size_t)(vf[nm] ? vf[nm] : 1) * 12) : NULL;
+        uint32_t *ci = tf ? malloc((size_t)(tf[nm] ? tf[nm] : 1) * 12) : NULL;     /* u16 values: the snapshot has no u16 */
+        if (!cv || !ci) rc = rc ? rc : LD_NOMEM;
+        else
+            for (size_t k = 0; k < nm; k++) {
+                if (!md[k].has_collision) continue;
+                memcpy(cv + 3 * (size_t)vf[k], md[k].position, (size_t)md[k].n_verts * 12);
+                for (size_t i = 0; i < (size_t)md[k].n_ctri * 3; i++) ci[3 * (size_t)tf[k] + i] = md[k].cidx[i];
+            }
+        A("collision", "vx_first", CLAPGPU_DT_U32, 1, nm + 1, 0, vf);
+        A("collision", "tri_first", CLAPGPU_DT_U32, 1, nm + 1, 0, tf);
+        if (cv && ci) {
+            A("collision", "vx", CLAPGPU_DT_F32, 2, vf[nm], 3, cv);
+            A("collision", "idx", CLAPGPU_DT_U32, 2, tf[nm], 3, ci);
+        }
+        free(vf); free(tf); free(cv); free(ci);
+    }
     for (size_t k = 0; k < nm && !rc; k++) rc = write_model(w, (unsigned)k, &md[k]);
     {   /* lights */
         const struct ld_lights *L = &s->lights;

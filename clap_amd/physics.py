@@ -79,6 +79,10 @@ class PhysWorld:
         self.bodies_aabb()
 
     def __del__(self):
+        try:
+            self._free_meshes()
+        except Exception:
+            pass
         bp, self._bp = getattr(self, "_bp", None), None
         if bp:
             try:
@@ -218,9 +222,57 @@ class PhysWorld:
         _lib.check(_lib.lib().clapgpu_bp_index_status(_stream(), self._bp, C.byref(st)), "clapgpu_bp_index_status")
         return st.value
 
-    def ray_cast(self, start, dir, length, skip=None, grid=True):
+    _meshes = None
+
+    def set_static_meshes(self, static_index, vertices, indices, scale, pos, quat):
+        """The triangle meshes of trimesh statics (phys_geom_trimesh_new, physics.c:882-930): mesh m belongs to static
+        static_index[m]; vertices[m] float [V, 3] in model space, indices[m] u16 [T, 3], scale[m] (entity->scale),
+        pos[m] (entity position), quat[m] (entity rotation x, y, z, w).  From then on ray_cast and ground_collide
+        intersect those statics through their triangles (clapgpu_trimesh_create)."""
+        dev = self.device
+        m = len(static_index)
+        vx = [np.asarray(v, np.float32).reshape(-1, 3) for v in vertices]
+        ix = [np.asarray(i, np.uint16).reshape(-1, 3) for i in indices]
+        vx_first = np.concatenate([[0], np.cumsum([len(v) for v in vx])]).astype(np.uint32)
+        tri_first = np.concatenate([[0], np.cumsum([len(i) for i in ix])]).astype(np.uint32)
+        up = lambda a, dt, view=None: torch.from_numpy(np.ascontiguousarray(a, dt).view(view or dt)).to(dev)
+        keep = dict(static_index=up(np.asarray(static_index, np.uint32), np.uint32, np.int32),
+                    vx_first=up(vx_first, np.uint32, np.int32), tri_first=up(tri_first, np.uint32, np.int32),
+                    vx=up(np.concatenate(vx) if m else np.zeros((1, 3)), np.float32),
+                    idx=up(np.concatenate(ix) if m else np.zeros((1, 3)), np.uint16, np.int16),
+                    scale=up(np.asarray(scale, np.float32).reshape(-1), np.float32),
+                    pos=up(np.asarray(pos, np.float64).reshape(-1, 3), np.float64),
+                    quat=up(np.asarray(quat, np.float32).reshape(-1, 4), np.float32))
+        d = _lib.TrimeshDesc(m, self.n_static, *[(_ptr(keep[k]) if m else None) for k in
+                                                  ("static_index", "vx_first", "tri_first", "vx", "idx", "scale", "pos", "quat")])
+        out = C.c_void_p()
+        _lib.check(_lib.lib().clapgpu_trimesh_create(_stream(), C.byref(out), C.byref(d)), "clapgpu_trimesh_create")
+        self._free_meshes()
+        self._meshes, self._meshes_keep = out, keep
+
+    def pose_static_meshes(self, pos, quat):
+        """New poses of every mesh (entity position, rotation x, y, z, w): re-bake and rebuild (clapgpu_trimesh_pose)."""
+        dev = self.device
+        p = torch.from_numpy(np.ascontiguousarray(pos, np.float64).reshape(-1, 3)).to(dev)
+        q = torch.from_numpy(np.ascontiguousarray(quat, np.float32).reshape(-1, 4)).to(dev)
+        _lib.check(_lib.lib().clapgpu_trimesh_pose(_stream(), self._meshes, _ptr(p), _ptr(q)), "clapgpu_trimesh_pose")
+        torch.cuda.current_stream().synchronize()
+
+    def static_meshes_status(self):
+        """(tree height, triangles) of the mesh set."""
+        depth, ntri = C.c_uint32(0), C.c_uint32(0)
+        _lib.check(_lib.lib().clapgpu_trimesh_status(_stream(), self._meshes, C.byref(depth), C.byref(ntri)),
+                   "clapgpu_trimesh_status")
+        return depth.value, ntri.value
+
+    def _free_meshes(self):
+        m, self._meshes = self._meshes, None
+        if m:
+            _lib.lib().clapgpu_trimesh_destroy(m)
+
+    def ray_cast(self, start, dir, length, skip=None, grid=True, meshes=True):
         """__phys_ray_cast for a batch: start / dir [n, 3], length [n]; skip [n] (body i, -2 - s, -1).  grid: through the
-        last bp_index().  Returns device tensors (dist [n] (NaN on a miss), hit [n], contact [n, 6], flags [n])."""
+        last bp_index().  meshes: through the static meshes once set_static_meshes ran.  Returns device tensors (dist [n] (NaN on a miss), hit [n], contact [n, 6], flags [n])."""
         dev = self.device
         start, dir = np.asarray(start, np.float64).reshape(-1, 3), np.asarray(dir, np.float64).reshape(-1, 3)
         nr = start.shape[0]
@@ -233,13 +285,15 @@ class PhysWorld:
         contact = torch.full((max(nr, 1), 6), float("nan"), dtype=torch.float64, device=dev)
         flags = torch.zeros(max(nr, 1), dtype=torch.int32, device=dev)
         g, sg = self.body_geoms(), self.static_geoms()
-        _lib.check(_lib.lib().clapgpu_ray_cast(_stream(), self._bp if grid else None, C.byref(g), C.byref(sg), nr, _ptr(ray_d),
-                                               _ptr(skip_d), _ptr(dist), _ptr(hit), _ptr(contact), _ptr(flags)),
-                   "clapgpu_ray_cast")
+        _lib.check(_lib.lib().clapgpu_ray_cast_meshes(_stream(), self._bp if grid else None, C.byref(g), C.byref(sg),
+                                                      self._meshes if meshes else None, nr, _ptr(ray_d), _ptr(skip_d),
+                                                      _ptr(dist), _ptr(hit),
+                                                      _ptr(contact), _ptr(flags)),
+                   "clapgpu_ray_cast_meshes")
         self._ray_keep = (ray_d, skip_d)
         return dist[:nr], hit[:nr], contact[:nr], flags[:nr]
 
-    def ground_collide(self, bodies, ray_off, grounded, grid=True):
+    def ground_collide(self, bodies, ray_off, grounded, grid=True, meshes=True):
         """phys_body_ground_collide for the bodies listed: moves them onto the ground (a body listed twice is flagged
         CLAPGPU_RAY_INVALID and stays).  Returns device tensors (grounded_out [n] uint8, normal [n, 3] float32, dist [n],
         hit [n], flags [n])."""
@@ -257,10 +311,12 @@ class PhysWorld:
         if scratch is None:
             scratch = self._ground_scratch = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dev)
         sg = self.static_geoms()
-        _lib.check(_lib.lib().clapgpu_bodies_ground_collide(_stream(), self._bp if grid else None, C.byref(self._desc),
-                                                            C.byref(sg), nb, _ptr(body_d), _ptr(off_d), _ptr(gr_d), _ptr(out),
-                                                            _ptr(normal), _ptr(dist), _ptr(hit), _ptr(flags), _ptr(scratch)),
-                   "clapgpu_bodies_ground_collide")
+        _lib.check(_lib.lib().clapgpu_bodies_ground_collide_meshes(_stream(), self._bp if grid else None, C.byref(self._desc),
+                                                                   C.byref(sg), self._meshes if meshes else None, nb,
+                                                                   _ptr(body_d), _ptr(off_d),
+                                                                   _ptr(gr_d), _ptr(out), _ptr(normal), _ptr(dist), _ptr(hit),
+                                                                   _ptr(flags), _ptr(scratch)),
+                   "clapgpu_bodies_ground_collide_meshes")
         self._ground_keep = (body_d, off_d, gr_d)
         return out[:nb], normal[:nb], dist[:nb], hit[:nb], flags[:nb]
 

@@ -947,7 +947,8 @@ int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_g
  *            capsule: the exit point, normal flipped
  *   box      dCollideRayBox on the static's AABB: the entry face, its outward axis normal; an edge or corner takes the
  *            first axis (x, y, z) whose slab is entered last; a start inside: the exit face, normal flipped
- *   other    (CLAPGPU_GEOM_OTHER, trimesh): not intersected; see CLAPGPU_RAY_UNRESOLVED
+ *   other    (CLAPGPU_GEOM_OTHER, trimesh): not intersected; see CLAPGPU_RAY_UNRESOLVED.  With a mesh set
+ *            (clapgpu_ray_cast_meshes) a static that owns a mesh is intersected through its triangles instead
  * Deviations: the hit kept is the smallest depth, ties to bodies before statics and then to the lower index (ODE keeps
  * the first in its hash-space order); NaN geometry never hits.
  */
@@ -976,6 +977,66 @@ int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bo
                                   uint32_t n, const uint32_t *body, const double *ray_off, const uint8_t *grounded,
                                   uint8_t *grounded_out, float *normal, double *dist, int32_t *hit, uint32_t *flags,
                                   uint32_t *scratch);
+
+/*
+ * The triangle meshes of static trimesh geoms (phys_geom_trimesh_new, physics.c:882-930), for the ray casts above.
+ * clapgpu_trimesh_desc holds DEVICE arrays for mesh m of n_meshes:
+ *   static_index[m]       the static (of a statics set of n_statics) the mesh belongs to, meant to be a
+ *                         CLAPGPU_GEOM_OTHER static.  The kind is not checked: a sphere, capsule or box static that owns
+ *                         a mesh is intersected through its mesh alone (the mesh replaces its collider in the ray casts)
+ *   vx_first[m + 1]       ascending from 0: mesh m's vertices are vx[vx_first[m] .. vx_first[m + 1])
+ *   tri_first[m + 1]      ascending from 0: its triangles are idx[tri_first[m] .. tri_first[m + 1])
+ *   vx[V][3]              model3d.collision_vx: float xyz in model space
+ *   idx[T][3]             model3d.collision_idx: u16 vertex indices into the mesh's own vertices, winding as given
+ *   scale[m]              entity->scale (float)
+ *   pos[m][3]             the geom position: the entity position (dGeomSetPosition; yoffset is 0 for a trimesh)
+ *   quat[m][4]            the entity rotation x, y, z, w (dGeomSetQuaternion(w, x, y, z) via phys_body_rotate_xform;
+ *                         a geom just created has the identity, 0, 0, 0, 1)
+ * The world-space triangle vertex is R * (double)(float)(scale * v) + pos in fp64, R = dQtoR(w, x, y, z).
+ * clapgpu_trimesh_create copies the arrays, checks them (may synchronise: a set-up call) and builds one BVH over every
+ * triangle of every mesh.  CLAPGPU_ERR_INVALID_ARGUMENTS: a NULL desc or out; n_meshes == 0 with any array given, or
+ * n_meshes > 0 with any array missing or n_statics == 0 (all before any HIP call); ranges that do not ascend from 0; a
+ * vertex index at or beyond its mesh's vertex count; a static_index >= n_statics or listed twice.
+ * clapgpu_trimesh_pose: new pos / quat (device arrays as above) for every mesh, then the same bake and rebuild as create.
+ * clapgpu_trimesh_status: host sync; *depth = the tree's height (edges from the root to the deepest leaf; at most 62,
+ * 0 without triangles), *n_tris = the triangles of all meshes.
+ *
+ * clapgpu_ray_cast_meshes / clapgpu_bodies_ground_collide_meshes: clapgpu_ray_cast / clapgpu_bodies_ground_collide with
+ * the statics that own a mesh of `meshes` intersected through their triangles (one more launch, one lane per ray; the
+ * ground-collide decision and move see the merged hit).  Such statics raise no CLAPGPU_RAY_UNRESOLVED; OTHER statics
+ * without a mesh still do.  meshes == NULL: exactly clapgpu_ray_cast / clapgpu_bodies_ground_collide, which are these
+ * calls with NULL.  meshes must have been created with n_statics == statics->n (CLAPGPU_ERR_INVALID_ARGUMENTS otherwise).
+ * With meshes the call takes 8 bytes per ray of stream-ordered scratch (hipMallocAsync) when flags are written.
+ * The triangle test (BackfaceCull, ClosestHit: physics.c:485-487): a triangle is hit from its front only,
+ * u . n < 0 for the unit direction u and n = (v1 - v0) x (v2 - v0); n == 0 and a ray parallel to the plane never hit;
+ * a start inside a closed mesh sees back faces only and misses it.  Contact pos = start + depth * u, normal = n / |n|
+ * (towards the start); hit = -2 - s for the mesh's static s; skip = -2 - s skips the whole mesh.
+ * Deviation: ODE tests the triangles in float (OPCODE); here in fp64 with the watertight test of Woop, Benthin and Wald
+ * (2013), so a ray through a shared edge or vertex of front faces always hits one of them.  Ties extend the rule above:
+ * the smallest depth, bodies before statics, the lower static index, the lower triangle index of the mesh.
+ */
+typedef struct clapgpu_trimesh clapgpu_trimesh;
+typedef struct clapgpu_trimesh_desc {
+    uint32_t        n_meshes, n_statics;
+    const uint32_t *static_index;
+    const uint32_t *vx_first, *tri_first;
+    const float    *vx;
+    const uint16_t *idx;
+    const float    *scale;
+    const double   *pos;
+    const float    *quat;
+} clapgpu_trimesh_desc;
+int  clapgpu_trimesh_create(void *stream, clapgpu_trimesh **out, const clapgpu_trimesh_desc *d);
+int  clapgpu_trimesh_pose(void *stream, clapgpu_trimesh *mesh, const double *pos, const float *quat);
+int  clapgpu_trimesh_status(void *stream, const clapgpu_trimesh *mesh, uint32_t *depth, uint32_t *n_tris);
+void clapgpu_trimesh_destroy(clapgpu_trimesh *mesh);
+int  clapgpu_ray_cast_meshes(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
+                             const clapgpu_trimesh *meshes, uint32_t n_rays, const double *ray, const int32_t *skip,
+                             double *dist, int32_t *hit, double *contact, uint32_t *flags);
+int  clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,
+                                          const clapgpu_trimesh *meshes, uint32_t n, const uint32_t *body,
+                                          const double *ray_off, const uint8_t *grounded, uint8_t *grounded_out, float *normal,
+                                          double *dist, int32_t *hit, uint32_t *flags, uint32_t *scratch);
 
 /* ======================================================================== */
 /* Characters: the feeder in front of default_update (core/character.c)      */

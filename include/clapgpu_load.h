@@ -27,6 +27,14 @@
  *   attach.*      entity[], parent[], joint[]                              ("attach" / "attach_joint", scene.c:1529-1541)
  *   bodies.*      entity[], geom_class[], phys_type[], mass[], radius[], length[], yoffset[], bounce[], bounce_vel[]
  *                                                                          ("physics", scene.c:1436-1466, 1653-1661)
+ *   collision.*   the collision mesh of every model with a "geom": "trimesh" body, as model3d_make keeps it
+ *                 (model.c:99-102) and phys_geom_trimesh_new reads it (physics.c:882-930): the instantiated mesh's
+ *                 positions after fix_origin and its u16 index triples.  vx_first[m + 1] / tri_first[m + 1] (u32, per
+ *                 model in model order; empty ranges for models without a trimesh body), vx[V][3] (f32, model space),
+ *                 idx[T][3] (u32 holding the u16 indices, relative to the model's own vertices).  scene.c:1395-1414
+ *                 also looks up a mesh named "collision", but nothing reads that choice: the engine's collision mesh
+ *                 is the mesh it instantiates.  A trimesh body's entity gives the static's scale (pos_scale[3]), position
+ *                 and rotation (clapgpu_trimesh_desc, include/clapgpu.h)
  *
  * Channels are kept as listed.  Should two channels of one animation drive the same (joint, path), the engine shares one
  * keyframe cursor between them (joint->off[path], model.c:1305-1311) and its result depends on that cursor's history;

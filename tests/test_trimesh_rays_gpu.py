@@ -1,0 +1,643 @@
+"""GPU: ray casts against static triangle meshes (clapgpu_trimesh_* / clapgpu_ray_cast_meshes /
+clapgpu_bodies_ground_collide_meshes) against the exact truth of tests/trimeshref.py: a heightfield terrain under the
+ray-time body scene, watertightness on shared edges and vertices, culling and degenerate cases, tie order, flags, poses,
+ground collide, degenerate trees and a loaded scene."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+from clap_amd import _lib, synth
+import trimeshref as tr
+
+pytestmark = pytest.mark.gpu
+
+SPHERE, CAPSULE, BOX, OTHER = _lib.GEOM_SPHERE, _lib.GEOM_CAPSULE, _lib.GEOM_BOX, _lib.GEOM_OTHER
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+IDENT = [0.0, 0.0, 0.0, 1.0]
+WORST = {}
+
+
+def rng(seed):
+    return np.random.Generator(np.random.PCG64(seed))
+
+
+def fetch(res):
+    return [t.cpu().numpy() for t in res]
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def unit(v):
+    v = np.asarray(v, float)
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+# ------------------------------------------------------------------------------------------- meshes
+def heightfield(nv, side, y0=0.0, amp=1.0, integer=False):
+    """nv x nv vertices over [0, side]^2 in x / z, front faces up"""
+    g = np.linspace(0.0, side, nv)
+    x, z = np.meshgrid(g, g, indexing="ij")
+    y = ((x * 3 + z * 5) % 4) if integer else y0 + amp * np.sin(x * 0.37) * np.cos(z * 0.29)
+    vx = np.stack([x, y, z], -1).reshape(-1, 3).astype(np.float32)
+    i, j = np.meshgrid(np.arange(nv - 1), np.arange(nv - 1), indexing="ij")
+    v00, v10, v01, v11 = i * nv + j, (i + 1) * nv + j, i * nv + j + 1, (i + 1) * nv + j + 1
+    idx = np.stack([np.stack([v00, v01, v10], -1), np.stack([v10, v01, v11], -1)], 2).reshape(-1, 3)
+    return vx, idx.astype(np.uint16)
+
+
+def box_mesh(h=0.5):
+    """a closed cube, outward front faces"""
+    v = np.array([[x, y, z] for x in (-h, h) for y in (-h, h) for z in (-h, h)], np.float32)
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    tris = []
+    for a, b, c, d in quads:
+        tris += [(a, b, c), (a, c, d)]
+    idx = np.array(tris, np.uint16)
+    c = v[idx].mean(1)
+    n = np.cross(v[idx[:, 1]] - v[idx[:, 0]], v[idx[:, 2]] - v[idx[:, 0]])
+    flip = (n * c).sum(1) < 0
+    idx[flip] = idx[flip][:, [0, 2, 1]]
+    return v, idx
+
+
+def icosphere(r=0.7, sub=1):
+    t = (1 + 5 ** 0.5) / 2
+    v = [[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t], [t, 0, -1], [t, 0, 1],
+         [-t, 0, -1], [-t, 0, 1]]
+    f = [[0, 11, 5], [0, 5, 1], [0, 1, 7], [0, 7, 10], [0, 10, 11], [1, 5, 9], [5, 11, 4], [11, 10, 2], [10, 7, 6], [7, 1, 8],
+         [3, 9, 4], [3, 4, 2], [3, 2, 6], [3, 6, 8], [3, 8, 9], [4, 9, 5], [2, 4, 11], [6, 2, 10], [8, 6, 7], [9, 8, 1]]
+    v = [list(unit(p)) for p in v]
+    for _ in range(sub):
+        nf, cache = [], {}
+
+        def mid(a, b):
+            k = (min(a, b), max(a, b))
+            if k not in cache:
+                v.append(list(unit((np.array(v[a]) + np.array(v[b])) / 2)))
+                cache[k] = len(v) - 1
+            return cache[k]
+        for a, b, c in f:
+            ab, bc, ca = mid(a, b), mid(b, c), mid(c, a)
+            nf += [[a, ab, ca], [b, bc, ab], [c, ca, bc], [ab, bc, ca]]
+        f = nf
+    v = np.array(v) * r
+    idx = np.array(f, np.uint16)
+    n = np.cross(v[idx[:, 1]] - v[idx[:, 0]], v[idx[:, 2]] - v[idx[:, 0]])
+    flip = (n * v[idx].mean(1)).sum(1) < 0
+    idx[flip] = idx[flip][:, [0, 2, 1]]
+    return v.astype(np.float32), idx
+
+
+def rand_quat(R):
+    q = unit(R.normal(size=4))
+    return q.astype(np.float32)                             # x, y, z, w
+
+
+class Scene:
+    """A PhysWorld whose statics are `bb` / kinds plus one OTHER static per mesh (its baked AABB), with the meshes set."""
+
+    def __init__(self, cuda_device, bodies, meshes, bb=None, kind=None, geo=None, unmeshed=(), tail_boxes=()):
+        from clap_amd import physics
+        bb = np.zeros((0, 6)) if bb is None else np.asarray(bb, float)
+        kind = np.zeros(0, np.uint8) if kind is None else np.asarray(kind, np.uint8)
+        self.base = len(bb)
+        self.meshes = meshes                                # [(vx, idx, scale, pos, quat)]
+        tris = [tr.bake(*m) for m in meshes]
+        mbb = np.zeros((len(tris), 6))
+        for k, t in enumerate(tris):
+            lo, hi = t.reshape(-1, 3).min(0), t.reshape(-1, 3).max(0)
+            mbb[k, 0::2], mbb[k, 1::2] = lo, hi
+        ub = np.asarray(list(unmeshed), float).reshape(-1, 6)
+        tb = np.asarray(list(tail_boxes), float).reshape(-1, 6)            # boxes after the meshes (higher indices)
+        allbb = np.concatenate([bb, mbb, ub, tb])
+        allkind = np.concatenate([kind, np.full(len(tris) + len(ub), OTHER, np.uint8), np.full(len(tb), BOX, np.uint8)])
+        ns = len(allbb)
+        g = geo or {}
+        pad = lambda a, shape: np.concatenate([np.asarray(a, float).reshape((-1,) + shape), np.zeros((ns - self.base,) + shape)])
+        c = (allbb[:, 0::2] + allbb[:, 1::2]) / 2
+        self.w = physics.PhysWorld(bodies, allbb, pair_capacity=4_000_000, static_pair_capacity=8_000_000, device=cuda_device)
+        self.w.set_static_geoms(allkind, pad(g["pos"], (3,)) if "pos" in g else c,
+                                pad(g["axis"], (3,)) if "axis" in g else np.tile([0, 0, 1.0], (ns, 1)),
+                                pad(g["radius"], ()) if "radius" in g else np.zeros(ns),
+                                pad(g["length"], ()) if "length" in g else np.zeros(ns))
+        self.mesh_static = self.base + np.arange(len(tris))
+        self.ref = tr.Meshes.from_list([(self.base + k, t) for k, t in enumerate(tris)])
+        if meshes:
+            self.w.set_static_meshes(self.mesh_static, [m[0] for m in meshes], [m[1] for m in meshes], [m[2] for m in meshes],
+                                     [m[3] for m in meshes], [m[4] for m in meshes])
+
+
+def _cast(self, *a, **k):
+    """brute force: these scenes have no broadphase index"""
+    k.setdefault("grid", False)
+    return self.w.ray_cast(*a, **k)
+
+
+Scene.cast = _cast
+
+
+def far_body(n=1):
+    b = synth.sphere_bodies(n, box=1.0, seed=1)
+    b["pos"][:] = [-500.0, -500.0, -500.0]
+    b["lvel"][:] = 0
+    return b
+
+
+def check_against_truth(sc, s, d, L, skip, got, base, name):
+    """got = the meshed cast; base = the same rays without the mesh set (bodies and other statics only).  Where the truth's
+    mesh hit and the base hit are apart by more than the bounds, the merged hit's identity must match, depth and normal
+    within their bounds."""
+    dist, hit, contact, _flags = got
+    bdist, bhit = base[0], base[1]
+    worst_d = worst_n = 0.0
+    compared = 0
+    for k in range(len(L)):
+        sk = skip[k] if skip is not None else -1
+        u = tr.unit_dir(d[k])
+        t = sc.ref.cast(s[k], u, L[k], skip_static=(-2 - sk) if sk <= -2 else None)
+        bd = bdist[k] if bhit[k] != -1 else np.inf
+        if t is None:
+            assert hit[k] == bhit[k] and (bhit[k] == -1 or same_bits(dist[k], bdist[k])), (name, k)
+            continue
+        st, _lo, td, tn, margin, bound = t
+        if not margin or abs(td - bd) <= 2 * bound:
+            continue
+        compared += 1
+        if td < bd:
+            assert hit[k] == -2 - st, (name, k, hit[k], st, td, bd)
+            err = abs(dist[k] - td)
+            assert err <= bound, (name, k, err, bound)
+            worst_d = max(worst_d, err / bound)
+            nb = 64 * tr.EPS * (1 + 1 / max(abs(float(tn @ u)), 1e-3))
+            nerr = np.abs(contact[k, 3:] - tn).max()
+            assert nerr <= nb, (name, k, nerr, nb)
+            worst_n = max(worst_n, nerr / nb)
+        else:
+            assert hit[k] == bhit[k] and same_bits(dist[k], bdist[k]), (name, k)
+    WORST[name] = (worst_d, worst_n, compared)
+    print(f"{name}: {compared} rays compared; worst depth error {worst_d:.3g} of its bound, normal {worst_n:.3g}")
+    return compared
+
+
+# ------------------------------------------------------------------------------------------- 1. the big scene
+def big_scene(cuda_device):
+    b = synth.capsule_bodies(262_144, box=60.0, seed=4)
+    b["lvel"][:] = 0
+    R = rng(5)
+    ns = 5000
+    lo = R.uniform(-5, 65, (ns, 3))
+    bb = np.empty((ns, 6))
+    bb[:, 0::2], bb[:, 1::2] = lo, lo + R.uniform(0.1, 3.0, (ns, 3))
+    bb[0] = [-1e3, 1e3, -10.0, -3.0, -1e3, 1e3]
+    kind = R.choice([SPHERE, CAPSULE, BOX, OTHER], ns, p=[0.3, 0.3, 0.3, 0.1]).astype(np.uint8)
+    kind[0] = BOX
+    c, h = (bb[:, 0::2] + bb[:, 1::2]) / 2, (bb[:, 1::2] - bb[:, 0::2]) / 2
+    big = np.argmax(h, 1)
+    r = h.min(1)
+    axis = np.zeros((ns, 3))
+    axis[np.arange(ns), big] = 1.0
+    length = np.where(kind == CAPSULE, 2 * (h[np.arange(ns), big] - r), 0.0)
+    vx, idx = heightfield(256, 64.0, y0=-1.0, amp=1.0)
+    meshes = [(vx, idx, 1.0, [-2.0, 0.0, -2.0], IDENT)]
+    bv, bi = box_mesh()
+    iv, ii = icosphere()
+    for k in range(64):
+        m = (bv, bi) if k % 2 == 0 else (iv, ii)
+        meshes.append((m[0], m[1], float(R.uniform(0.5, 3.0)), R.uniform(0, 60, 3), rand_quat(R)))
+    return Scene(cuda_device, b, meshes, bb, kind, dict(pos=c, axis=axis, radius=r, length=length)), b
+
+
+def test_big_scene_against_truth_and_grid_equals_brute(cuda_device):
+    sc, b = big_scene(cuda_device)
+    w = sc.w
+    depth, ntri = w.static_meshes_status()
+    assert ntri == 130050 + 32 * 12 + 32 * 80 and 0 < depth <= 64
+    w.bp_index()
+    R = rng(9)
+    n = 65536
+    s = R.uniform(-5, 65, (n, 3))
+    d = R.normal(size=(n, 3))
+    d[: n // 4, 1] = -np.abs(d[: n // 4, 1]) - 1.0                          # a quarter aimed down at the terrain
+    L = R.choice([2.0, 20.0, 1e6], n)
+    skip = np.where(np.arange(n) % 7 == 0, -2 - sc.mesh_static[np.arange(n) % 65], -1).astype(np.int32)
+    sel = R.choice(w.n, n, replace=False).astype(np.uint32)
+    ray_off = b["yoffset"][sel] * 0.9
+    rl = b["yoffset"][sel] - (ray_off - 0.05) + 1e-3
+    gs = (b["pos"][sel] - np.stack([np.zeros(n), ray_off - 0.05, np.zeros(n)], 1)).astype(np.float32).astype(np.float64)
+    gd, gl, gskip = np.tile([0, -1.0, 0], (n, 1)), 2 * rl + 5.0, sel.astype(np.int32)
+    for name, (ss, dd, ll, sk) in (("random", (s, d, L, skip)), ("ground", (gs, gd, gl, gskip))):
+        g = fetch(w.ray_cast(ss, dd, ll, skip=sk, grid=True))
+        f = fetch(w.ray_cast(ss, dd, ll, skip=sk, grid=False))
+        for a, c in zip(g, f):
+            assert same_bits(a, c), name
+        base = fetch(w.ray_cast(ss, dd, ll, skip=sk, grid=True, meshes=False))
+        mesh_hits = np.isin(g[1], -2 - sc.mesh_static).sum()
+        print(f"{name}: {mesh_hits} of {n} rays hit a mesh")
+        assert mesh_hits > 100, (name, mesh_hits)
+        sub = np.arange(0, n, 32)                                           # 2 048 rays against the exact truth
+        got = [a[sub] for a in g]
+        compared = check_against_truth(sc, ss[sub], dd[sub], ll[sub], sk[sub], got, [a[sub] for a in base], name)
+        assert compared > 30, compared
+
+
+# ------------------------------------------------------------------------------------------- 2. watertightness
+def nrm_of(v, idx, t):
+    n = np.cross(v[idx[t, 1]] - v[idx[t, 0]], v[idx[t, 2]] - v[idx[t, 0]])
+    return n / np.linalg.norm(n, axis=1, keepdims=True)
+
+
+def test_watertight_on_shared_vertices_and_edges(cuda_device):
+    nv = 64
+    vx, idx = heightfield(nv, float(nv - 1), integer=True)
+    sc = Scene(cuda_device, far_body(), [(vx, idx, 1.0, [0.0, 0.0, 0.0], IDENT)])
+    v = vx.astype(np.float64)
+    # straight down through every vertex and every edge midpoint
+    pts, owners = [], []
+    for p in range(len(v)):
+        pts.append(v[p])
+        owners.append(np.nonzero((idx == p).any(1))[0])
+    edges = {}
+    for t, (a, b_, c) in enumerate(idx):
+        for e in ((a, b_), (b_, c), (c, a)):
+            edges.setdefault((min(e), max(e)), []).append(t)
+    for (a, b_), ts in edges.items():
+        pts.append((v[a] + v[b_]) / 2)
+        owners.append(np.array(ts))
+    pts = np.array(pts)
+    start = pts + [0, 10.0, 0]
+    dist, hit, _c, flags = fetch(sc.cast(start, np.tile([0, -1.0, 0], (len(pts), 1)), 20.0))
+    assert (hit == -2).all(), np.nonzero(hit != -2)[0][:10]
+    assert (dist == 10.0).all()
+    # which triangle: the contact normal of the lowest-indexed owner (owners share the depth exactly)
+    _d, _h, contact, _f = fetch(sc.cast(start, np.tile([0, -1.0, 0], (len(pts), 1)), 20.0))
+    nrm = np.cross(v[idx[:, 1]] - v[idx[:, 0]], v[idx[:, 2]] - v[idx[:, 0]])
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    for k in range(len(pts)):
+        want = nrm[owners[k].min()]
+        ok = [np.allclose(contact[k, 3:], nrm[t], atol=1e-12) for t in owners[k]]
+        assert any(ok), k
+        assert np.allclose(contact[k, 3:], want, atol=1e-12), (k, owners[k])
+    # random non-axis directions aimed at shared edges: every ray hits
+    R = rng(3)
+    inner = [(e, ts) for e, ts in edges.items() if len(ts) == 2]
+    pick = R.choice(len(inner), 20000)
+    tgt = np.array([(v[inner[i][0][0]] + v[inner[i][0][1]]) * 0.5 for i in pick])
+    frac = R.uniform(0.05, 0.95, len(pick))
+    tgt = np.array([v[inner[i][0][0]] * (1 - f) + v[inner[i][0][1]] * f for i, f in zip(pick, frac)])
+    dd = unit(np.stack([R.normal(size=len(pick)), -R.uniform(0.5, 2.0, len(pick)), R.normal(size=len(pick))], 1))
+    back = (4.0 - tgt[:, 1]) / -dd[:, 1]                                     # starts above the highest vertex (y = 3) ...
+    st = tgt - dd * back[:, None]
+    keep = np.all((st[:, 0::2] > 0.5) & (st[:, 0::2] < nv - 1.5), 1)       # ... over the terrain: above it all the way
+    # both triangles of the edge face the ray: the watertight case (over a ridge, one is a back face and a ray grazing
+    # the ridge exactly may round to that side)
+    ta, tb = np.array([inner[i][1][0] for i in pick]), np.array([inner[i][1][1] for i in pick])
+    keep &= ((nrm_of(v, idx, ta) * dd).sum(1) < -1e-3) & ((nrm_of(v, idx, tb) * dd).sum(1) < -1e-3)
+    assert keep.sum() > 3000, keep.sum()
+    dist, hit, _c, _f = fetch(sc.cast(st[keep], dd[keep], back[keep] + 1.0))
+    assert (hit == -2).all(), (hit != -2).sum()
+
+
+# ------------------------------------------------------------------------------------------- 3. culling, degenerate
+def test_culling_and_degenerate_cases(cuda_device):
+    vx, idx = heightfield(9, 8.0, y0=0.0, amp=0.0)                           # flat, y = 0
+    bv, bi = box_mesh(1.0)
+    tri = np.array([[0, 0, 0], [0, 0, 1], [1, 0, 0]], np.float32)           # y = 0, front face up
+    degen = np.array([[0, 0, 0], [0, 0, 0], [1, 0, 0]], np.float32)         # v0 == v1
+    meshes = [(vx, idx, 1.0, [0.0, 0.0, 0.0], IDENT),                       # static 0: terrain
+              (bv, bi, 1.0, [20.0, 0.0, 0.0], IDENT),                        # 1: closed box around x = 20
+              (bv, bi, 1.0, [26.0, 0.0, 0.0], IDENT),                        # 2: another one beyond it
+              (tri, np.array([[0, 1, 2]], np.uint16), 1.0, [40.0, 0.0, 0.0], IDENT),    # 3: one triangle
+              (degen, np.array([[0, 1, 2]], np.uint16), 1.0, [50.0, 0.0, 0.0], IDENT)]  # 4: zero area
+    sc = Scene(cuda_device, far_body(), meshes)
+    s = np.array([[4.0, -3.0, 4.0],                 # under the terrain going up: back faces only
+                  [20.0, 0.2, 0.1],                  # inside box 1, towards +x: misses its faces, hits box 2
+                  [38.0, 0.0, 0.3],                  # in the plane of the triangle, through it
+                  [50.5, 3.0, 0.0],                  # down through the zero-area triangle
+                  [40.3, 0.0, 0.3]])                 # on the triangle's front face, going down into it
+    d = np.array([[0, 1.0, 0], [1.0, 0, 0], [1.0, 0, 0], [0, -1.0, 0], [0, -1.0, 0]])
+    dist, hit, contact, flags = fetch(sc.cast(s, d, 30.0))
+    assert hit[0] == -1 and flags[0] == 0
+    assert hit[1] == -2 - 2 and abs(dist[1] - 5.0) < 1e-12 and list(contact[1, 3:]) == [-1.0, 0.0, 0.0]
+    assert hit[2] == -1
+    assert hit[3] == -1
+    assert hit[4] == -2 - 3 and dist[4] == 0.0 and list(contact[4, 3:]) == [0.0, 1.0, 0.0]
+
+
+# ------------------------------------------------------------------------------------------- 4. tie order
+def test_tie_order(cuda_device):
+    tri = np.array([[-2, 0, -2], [-2, 0, 2], [2, 0, -2]], np.float32)        # y = 0 plane piece, front up
+    one = np.array([[0, 1, 2]], np.uint16)
+    b = far_body(2)
+    b["radius"][:] = 1.0
+    b["pos"][0] = [0.0, 5.0, 0.0]                                            # top at y = 6
+    # statics: 0 a box whose top is y = 6 at x = 10; meshes: static 1 at y = 6 (x = 0), 2 at y = 6 (x = 10),
+    # 3 and 4 coplanar at y = 6 (x = 20), 5 below 3/4 at x = 20 (y = 2)
+    bb = [[9.0, 11.0, 4.0, 6.0, -1.0, 1.0]]
+    meshes = [(tri, one, 1.0, [0.0, 6.0, 0.0], IDENT), (tri, one, 1.0, [10.0, 6.0, 0.0], IDENT),
+              (tri, one, 1.0, [20.0, 6.0, 0.0], IDENT), (tri, one, 1.0, [20.0, 6.0, 0.0], IDENT),
+              (tri, one, 1.0, [20.0, 2.0, 0.0], IDENT)]
+    sc = Scene(cuda_device, b, meshes, bb, [BOX])
+    s = np.array([[0.0, 10.0, 0.0], [10.0, 10.0, 0.0], [20.3, 10.0, -0.4], [20.3, 10.0, -0.4], [20.3, 10.0, -0.4]])
+    d = np.tile([0, -1.0, 0], (5, 1))
+    skip = np.array([-1, -1, -1, -2 - 3, -2 - 3], np.int32)
+    skip2 = skip.copy()
+    skip2[4] = -2 - 4
+    dist, hit, _c, _f = fetch(sc.cast(s, d, 30.0, skip=skip))
+    assert hit[0] == 0 and dist[0] == 4.0                                     # a body before a static at the same depth
+    assert hit[1] == -2 and dist[1] == 4.0                                    # box static 0 before mesh static 2
+    assert hit[2] == -2 - 3                                                   # coplanar: the lower static
+    assert hit[3] == -2 - 4                                                   # skip = -2 - s skips its whole mesh
+    _d2, hit2, _c2, _f2 = fetch(sc.cast(s[4:], d[4:], 30.0, skip=np.array([-2 - 4], np.int32)))
+    assert hit2[0] == -2 - 3
+    # the converse: mesh static 0 before box static 1, both with their top at y = 6 under the ray
+    sc2 = Scene(cuda_device, far_body(), [(tri, one, 1.0, [10.0, 6.0, 0.0], IDENT)], tail_boxes=bb)
+    dist3, hit3, _c3, _f3 = fetch(sc2.cast(s[1:2], d[1:2], 30.0))
+    assert hit3[0] == -2 and dist3[0] == 4.0                                 # the mesh, the lower static index
+    dist4, hit4, _c4, _f4 = fetch(sc2.cast(s[1:2], d[1:2], 30.0, meshes=False))
+    assert hit4[0] == -3 and dist4[0] == 4.0                                 # without the mesh set: the box
+
+
+# ------------------------------------------------------------------------------------------- create: the device checks
+def _create(static_index, vx_first, tri_first, vx, idx, n_statics):
+    import torch
+    from clap_amd import physics
+    up = lambda a, dt, view=None: torch.from_numpy(np.ascontiguousarray(a, dt).view(view or dt)).cuda()
+    m = len(static_index)
+    keep = [up(static_index, np.uint32, np.int32), up(vx_first, np.uint32, np.int32), up(tri_first, np.uint32, np.int32),
+            up(vx, np.float32), up(idx, np.uint16, np.int16), up(np.ones(m), np.float32), up(np.zeros((m, 3)), np.float64),
+            up(np.tile(IDENT, (m, 1)), np.float32)]
+    d = _lib.TrimeshDesc(m, n_statics, *[t.data_ptr() for t in keep])
+    out = C.c_void_p(0)
+    rc = _lib.lib().clapgpu_trimesh_create(physics._stream(), C.byref(out), C.byref(d))
+    if out.value:
+        _lib.lib().clapgpu_trimesh_destroy(out)
+    return rc, out.value
+
+
+def test_create_refuses_what_the_device_checks(cuda_device):
+    vx = np.array([[0, 0, 0], [0, 0, 1], [1, 0, 0], [0, 1, 0], [0, 1, 1], [1, 1, 0]], np.float32)
+    good = dict(static_index=[0, 1], vx_first=[0, 3, 6], tri_first=[0, 1, 2], vx=vx, idx=[[0, 1, 2], [0, 1, 2]], n_statics=2)
+    rc, out = _create(**good)
+    assert rc == _lib.OK and out
+    bad = [dict(idx=[[0, 1, 3], [0, 1, 2]]),                                 # index 3 of a 3-vertex mesh
+           dict(idx=[[0, 1, 2], [2, 1, 65535]]),                             # far beyond
+           dict(static_index=[1, 1]),                                        # a static listed twice
+           dict(static_index=[0, 2]),                                        # static_index >= n_statics
+           dict(static_index=[0, 7], n_statics=8, vx_first=[0, 4, 3]),       # vertex ranges descending
+           dict(tri_first=[0, 2, 1]),                                        # triangle ranges descending
+           dict(tri_first=[1, 1, 2])]                                        # not from 0
+    for k, b in enumerate(bad):
+        a = dict(good)
+        a.update(b)
+        rc, out = _create(**a)
+        assert rc == _lib.ERR_INVALID_ARGUMENTS and not out, (k, rc)
+
+
+# ------------------------------------------------------------------------------------------- 5. flags
+def test_flags_with_and_without_mesh_set(cuda_device):
+    bv, bi = box_mesh(1.0)
+    sc = Scene(cuda_device, far_body(), [(bv, bi, 1.0, [0.0, 0.0, 0.0], IDENT)],
+               unmeshed=[[9.0, 11.0, -1.0, 1.0, -1.0, 1.0]])                 # static 1: OTHER without a mesh
+    s = np.array([[0.0, 5.0, 0.0], [10.0, 5.0, 0.0], [5.0, 5.0, 0.0]])
+    d = np.tile([0, -1.0, 0], (3, 1))
+    _dist, hit, _c, flags = fetch(sc.cast(s, d, 20.0))
+    assert hit[0] == -2 and flags[0] == 0
+    assert hit[1] == -1 and flags[1] == _lib.RAY_UNRESOLVED
+    assert hit[2] == -1 and flags[2] == 0
+    _d0, h0, _c0, f0 = fetch(sc.cast(s, d, 20.0, meshes=False))
+    assert list(f0) == [_lib.RAY_UNRESOLVED] * 2 + [0] and (h0 == -1).all()
+
+
+def test_every_other_meshed_leaves_nothing_unresolved(cuda_device):
+    sc, _b = big_scene_small(cuda_device)
+    R = rng(12)
+    s = R.uniform(-5, 65, (20000, 3))
+    d = R.normal(size=(20000, 3))
+    _dist, hit, _c, flags = fetch(sc.cast(s, d, R.choice([2.0, 20.0, 1e6], 20000)))
+    assert not (flags & _lib.RAY_UNRESOLVED).any()
+    assert np.isin(hit, -2 - sc.mesh_static).sum() > 100
+
+
+def big_scene_small(cuda_device):
+    """every OTHER static meshed: 200 statics of mixed kinds, the OTHER ones boxes or icospheres"""
+    b = synth.capsule_bodies(4096, box=60.0, seed=7)
+    b["lvel"][:] = 0
+    R = rng(6)
+    bv, bi = box_mesh()
+    iv, ii = icosphere()
+    ns = 200
+    lo = R.uniform(-5, 65, (ns, 3))
+    bb = np.empty((ns, 6))
+    bb[:, 0::2], bb[:, 1::2] = lo, lo + R.uniform(0.1, 3.0, (ns, 3))
+    kind = R.choice([SPHERE, CAPSULE, BOX], ns).astype(np.uint8)
+    c, h = (bb[:, 0::2] + bb[:, 1::2]) / 2, (bb[:, 1::2] - bb[:, 0::2]) / 2
+    big = np.argmax(h, 1)
+    r = h.min(1)
+    axis = np.zeros((ns, 3))
+    axis[np.arange(ns), big] = 1.0
+    length = np.where(kind == CAPSULE, 2 * (h[np.arange(ns), big] - r), 0.0)
+    meshes = [((bv, bi) if k % 2 else (iv, ii)) + (float(R.uniform(1, 4)), R.uniform(0, 60, 3), rand_quat(R)) for k in range(60)]
+    return Scene(cuda_device, b, meshes, bb, kind, dict(pos=c, axis=axis, radius=r, length=length)), b
+
+
+def test_null_mesh_set_equals_ray_cast_bit_for_bit(cuda_device):
+    import torch
+    from clap_amd import physics
+    sc, _b = big_scene_small(cuda_device)
+    w = sc.w
+    R = rng(13)
+    n = 8192
+    ray = np.zeros((n, 8))
+    ray[:, 0:3], ray[:, 3:6], ray[:, 6] = R.uniform(-5, 65, (n, 3)), R.normal(size=(n, 3)), R.choice([2.0, 20.0, 1e6], n)
+    rd = torch.from_numpy(ray).cuda()
+    outs = []
+    for fn in ("clapgpu_ray_cast", "clapgpu_ray_cast_meshes"):
+        o = [torch.full((n,), float("nan"), dtype=torch.float64, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda"),
+             torch.full((n, 6), float("nan"), dtype=torch.float64, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda")]
+        g, sg = w.body_geoms(), w.static_geoms()
+        args = [physics._stream(), None, C.byref(g), C.byref(sg)] + ([None] if fn.endswith("meshes") else []) + \
+               [n, rd.data_ptr(), None] + [t.data_ptr() for t in o]
+        _lib.check(getattr(_lib.lib(), fn)(*args), fn)
+        outs.append([t.cpu().numpy() for t in o])
+    for a, c in zip(*outs):
+        assert same_bits(a, c)
+    assert (outs[0][3] & _lib.RAY_UNRESOLVED).any()
+
+
+# ------------------------------------------------------------------------------------------- 6. pose
+def test_pose_rebuild_matches_truth(cuda_device):
+    R = rng(21)
+    bv, bi = box_mesh()
+    iv, ii = icosphere()
+    vx, idx = heightfield(64, 32.0)
+    meshes = [(vx, idx, 1.0, [0.0, 0.0, 0.0], IDENT)] + \
+             [((bv, bi) if k % 2 else (iv, ii)) + (float(R.uniform(1, 3)), R.uniform(0, 30, 3), rand_quat(R)) for k in range(16)]
+    sc = Scene(cuda_device, far_body(), meshes)
+    st0 = sc.w.static_meshes_status()
+    pos = np.array([m[3] for m in meshes]) + R.uniform(-2, 2, (len(meshes), 3))
+    quat = np.array([rand_quat(R) for _ in meshes])
+    sc.w.pose_static_meshes(pos, quat)
+    assert sc.w.static_meshes_status()[1] == st0[1] and 0 < sc.w.static_meshes_status()[0] <= 64
+    posed = [(m[0], m[1], m[2], pos[k], quat[k]) for k, m in enumerate(meshes)]
+    ref = tr.Meshes.from_list([(k, tr.bake(*m)) for k, m in enumerate(posed)])
+    sc.ref = ref
+    n = 2048
+    s = np.concatenate([R.uniform(-5, 35, (n // 2, 3)), np.stack([R.uniform(0, 32, n // 2), np.full(n // 2, 20.0),
+                                                                   R.uniform(0, 32, n // 2)], 1)])
+    d = np.concatenate([R.normal(size=(n // 2, 3)), np.tile([0, -1.0, 0], (n // 2, 1))])
+    L = np.full(n, 50.0)
+    got = fetch(sc.cast(s, d, L))
+    base = [np.full(n, np.nan), np.full(n, -1, np.int32)]
+    assert check_against_truth(sc, s, d, L, None, got, base, "pose") > 200
+
+
+# ------------------------------------------------------------------------------------------- 7. ground collide
+def test_ground_collide_on_the_terrain(cuda_device):
+    R = rng(31)
+    n = 2048
+    b = synth.capsule_bodies(n, box=60.0, seed=14)
+    b["lvel"][:] = 0
+    vx, idx = heightfield(128, 64.0, y0=0.0, amp=1.0)
+    terrain = tr.bake(vx, idx, 1.0, [0.0, 0.0, 0.0], IDENT)
+    xz = R.uniform(1, 63, (n, 2))
+    b["pos"][:, 0], b["pos"][:, 2] = xz[:, 0], xz[:, 1]
+    ray_off = np.asarray(b["yoffset"], float) * R.uniform(0.7, 1.0, n)
+    rl = b["yoffset"] - (ray_off - 0.05) + 1e-3
+    ground = 1.0 * np.sin(xz[:, 0] * 0.37) * np.cos(xz[:, 1] * 0.29)
+    b["pos"][:, 1] = ground + b["yoffset"] + 1e-3 + rl * R.uniform(-0.9, 0.9, n) + 0.02
+    b["pos"][np.arange(n) % 9 == 4, 1] += 10.0                                # out of reach
+    # body 1 stacked on body 0, both spheres: body 1's ray starts 0.01 above body 0's top, straight over its centre
+    b["length"][:2] = 0.0
+    b["pos"][1, :] = b["pos"][0, :] + [0.0, b["radius"][0] + (ray_off[1] - 0.05) + 0.01, 0.0]
+    sc = Scene(cuda_device, b, [(vx, idx, 1.0, [0.0, 0.0, 0.0], IDENT)])
+    w = sc.w
+    grounded = R.uniform(0, 1, n) < 0.5
+    grounded[0] = True                                                        # body 0 moves whichever way it is off
+    sel = np.arange(n, dtype=np.uint32)
+    pos0 = w.pos.cpu().numpy().copy()
+    w.bp_index()
+    out, normal, dist, hit, flags = fetch(w.ground_collide(sel, ray_off, grounded, grid=True))
+    roff = ray_off - 0.05
+    rlen = b["yoffset"] - roff + 1e-3
+    start = np.stack([pos0[:, 0].astype(np.float32), (pos0[:, 1] - roff).astype(np.float32), pos0[:, 2].astype(np.float32)],
+                     1).astype(np.float64)
+    exp_move = np.zeros(n, np.float32)
+    branches = np.zeros(4, int)
+    for k in range(n):
+        if hit[k] != -2:
+            continue
+        t = sc.ref.cast(start[k], np.array([0, -1.0, 0]), 2 * rlen[k])
+        assert t is not None, k
+        _st, _lo, td, tn, margin, bound = t
+        assert abs(dist[k] - td) <= bound, (k, dist[k], td)
+        assert np.allclose(normal[k], tn.astype(np.float32), atol=1e-6)
+        # the reference's branches.  The move the device applies is (float)(ray_len - depth) of ITS depth, so the bits
+        # are restated on the device depth; the truth's depth, within `bound` of it, must pick the same branch wherever
+        # it is farther than `bound` from ray_len (closer, the two may fall on either side)
+        dk = dist[k]
+        if grounded[k] and dk > rlen[k]:
+            exp_move[k], br = np.float32(-(dk - rlen[k])), 0
+        elif dk < rlen[k]:
+            exp_move[k], br = np.float32(rlen[k] - dk), 1
+        elif dk > rlen[k]:
+            br = 2
+        else:
+            br = 3
+        if abs(td - rlen[k]) > bound:
+            bt = 0 if grounded[k] and td > rlen[k] else 1 if td < rlen[k] else 2
+            assert bt == br, (k, td, dk, rlen[k])
+        branches[br] += 1
+        assert bool(out[k]) == (br != 2), k
+    assert (hit == -2).sum() > n // 2 and branches[0] > 50 and branches[1] > 50 and branches[2] > 50, branches
+    pos1 = w.pos.cpu().numpy()
+    mv = (hit == -2) & (flags == 0)
+    assert same_bits(pos1[mv, 1], pos0[mv, 1] + exp_move[mv].astype(np.float64))
+    assert hit[0] == -2 and flags[0] == 0 and exp_move[0] != 0              # body 0 grounded on the terrain, moved
+    assert hit[1] == 0 and flags[1] & _lib.RAY_MOVED_TARGET                   # body 1's ray saw body 0 where it was
+    # a body listed twice: flagged invalid, does not move
+    pos0 = w.pos.cpu().numpy().copy()
+    out2, _n2, _d2, _h2, flags2 = fetch(w.ground_collide(np.array([3, 4, 3], np.uint32), ray_off[[3, 4, 3]],
+                                                         np.ones(3, bool), grid=False))
+    assert (flags2[[0, 2]] & _lib.RAY_INVALID).all() and not out2[[0, 2]].any()
+    assert same_bits(w.pos.cpu().numpy()[3], pos0[3])
+
+
+# ------------------------------------------------------------------------------------------- 8. degenerate trees
+def test_degenerate_trees_stay_shallow_and_exact(cuda_device):
+    R = rng(41)
+    n = 100_000
+    ang = R.uniform(0, 2 * np.pi, n)
+    c = np.array([5.0, 1.0, 5.0])                                           # identical centroids: the triangle spun about it
+    a = np.stack([np.cos(ang), np.zeros(n), np.sin(ang)], 1)
+    b = np.stack([np.cos(ang + 2.1), np.zeros(n), np.sin(ang + 2.1)], 1)
+    v = np.stack([a, b, -(a + b)], 1)
+    if np.cross(v[0, 1] - v[0, 0], v[0, 2] - v[0, 0])[1] < 0:
+        v = v[:, [0, 2, 1]]                                                  # front faces up
+    same = (v + c).astype(np.float32)
+    t = R.uniform(0, 100, n)                                                 # along a line
+    line = (np.stack([np.stack([t, np.zeros(n), t * 0], 1), np.stack([t, np.zeros(n), t * 0 + 0.5], 1),
+                      np.stack([t + 0.5, np.zeros(n), t * 0], 1)], 1) + [0.0, 3.0, 20.0]).astype(np.float32)
+    for tri in (same, line):
+        vx = tri.reshape(-1, 3)
+        meshes, k = [], 0
+        while k < n:                                                         # u16 indices: meshes of at most 21 845 triangles
+            m = min(21845, n - k)
+            meshes.append((vx[3 * k:3 * (k + m)], np.arange(3 * m, dtype=np.uint16).reshape(-1, 3), 1.0, [0.0, 0.0, 0.0],
+                           IDENT))
+            k += m
+        sc = Scene(cuda_device, far_body(), meshes)
+        depth, ntri = sc.w.static_meshes_status()
+        assert ntri == n and 0 < depth <= 64, depth
+        s = np.stack([R.uniform(-1, 101, 256), np.full(256, 10.0), R.uniform(19.9, 20.6, 256)], 1)
+        if tri is same:
+            s[:, 0], s[:, 2] = R.uniform(4, 6, 256), R.uniform(4, 6, 256)
+        d = np.tile([0, -1.0, 0], (256, 1))
+        dist, hit, _c, _f = fetch(sc.cast(s, d, 20.0))
+        for k in range(256):
+            tt = sc.ref.cast(s[k], d[k], 20.0)
+            if tt is None:
+                assert hit[k] == -1, k
+            else:
+                assert hit[k] <= -2 and abs(dist[k] - tt[2]) <= tt[5], (k, hit[k], tt)
+
+
+# ------------------------------------------------------------------------------------------- 9. a loaded scene
+def test_loaded_scene_rays_onto_the_crate(cuda_device, tmp_path):
+    from clap_amd import snapshot
+    fix = os.path.join(ROOT, "tests", "golden", "scene_fixture")
+    out = str(tmp_path / "scene.clps")
+    snapshot.load_scene_json(os.path.join(fix, "scene.json"), out)
+    comps = snapshot.load_scene(out)
+    ent, col, bod = comps["entities"], comps["collision"], comps["bodies"]
+    trim = np.nonzero(bod["geom_class"] == 2)[0]
+    assert len(trim) >= 1
+    meshes = []
+    for bi in trim:
+        e = bod["entity"][bi]
+        m = ent["model"][e]
+        vf, tf = col["vx_first"], col["tri_first"]
+        meshes.append((col["vx"][vf[m]:vf[m + 1]], col["idx"][tf[m]:tf[m + 1]].astype(np.uint16), float(ent["pos_scale"][e, 3]),
+                       ent["pos_scale"][e, :3].astype(np.float64), ent["rot"][e]))
+    sc = Scene(cuda_device, far_body(), meshes)
+    R = rng(51)
+    hits = 0
+    for k, m in enumerate(meshes):
+        tris = tr.bake(*m).reshape(-1, 3)
+        lo, hi = tris.min(0), tris.max(0)
+        s = np.stack([R.uniform(lo[0], hi[0], 64), np.full(64, hi[1] + 5.0), R.uniform(lo[2], hi[2], 64)], 1)
+        d = np.tile([0, -1.0, 0], (64, 1))
+        dist, hit, contact, _f = fetch(sc.cast(s, d, 50.0))
+        for j in range(64):
+            t = sc.ref.cast(s[j], d[j], 50.0)
+            if t is None:
+                assert hit[j] == -1, (k, j)
+                continue
+            assert hit[j] == -2 - t[0] and abs(dist[j] - t[2]) <= t[5], (k, j, hit[j], dist[j], t)
+            assert abs(contact[j, 1] - (s[j, 1] - t[2])) <= t[5]
+            hits += 1
+    assert hits > 20, hits
