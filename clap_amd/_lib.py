@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 OK = 0
 ERR_NOMEM = -1
@@ -155,6 +155,11 @@ GEOM_SPHERE, GEOM_CAPSULE, GEOM_BOX, GEOM_OTHER = 0, 1, 2, 3
 CONTACT_DEEP = 0x80000000
 
 
+def mesh_contact_scratch(static_capacity):
+    """CLAPGPU_MESH_CONTACT_SCRATCH: uint32 words of scratch clapgpu_contacts_meshes takes."""
+    return (int(static_capacity) + 63) // 64 + 1
+
+
 class Characters(C.Structure):
     """clapgpu_characters (include/clapgpu.h)."""
     _fields_ = [("n", C.c_uint32), ("limbo_height", C.c_float), ("entity", C.c_void_p), ("body", C.c_void_p),
@@ -191,7 +196,10 @@ class Frame(C.Structure):
                 ("particles", C.POINTER(Particles)),
                 ("index_base", C.c_uint32), ("visible", C.c_void_p), ("visible_count", C.c_void_p), ("visible_scratch", C.c_void_p),
                 ("cam_pos", C.c_float * 3), ("force_lod", C.c_void_p), ("cur_lod", C.c_void_p), ("draw_lod", C.c_void_p),
-                ("flags", C.c_uint32)]
+                ("flags", C.c_uint32),
+                ("meshes", C.c_void_p), ("mesh_contacts", C.c_void_p), ("mesh_ref", C.c_void_p),
+                ("mesh_contact_capacity", C.c_uint32), ("mesh_contact_total", C.c_void_p), ("mesh_capped", C.c_void_p),
+                ("mesh_scratch", C.c_void_p)]
 
 
 LIGHTS_MAX = 128
@@ -284,6 +292,11 @@ SYMBOLS = {
     "clapgpu_bodies_ground_collide_meshes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_void_p,
                                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_contacts_meshes": (C.c_int, [C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "clapgpu_sweep_capsules_meshes": (C.c_int, [C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_void_p, C.c_uint32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_visible_compact_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_characters_update_clock": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),

@@ -2,7 +2,10 @@
 // translation unit alone is built with -mllvm -simplifycfg-sink-common=false, see the Makefile).
 //
 //   k_contacts_geoms[_both]  near_callback's dCollide + phys_contact_surface (physics.c:399-449, 291-330)
-//   k_sweep_capsules         phys_body_sweep_capsule (physics.c:559-670), one wavefront per sweep
+//   k_sweep_capsules         phys_body_sweep_capsule (physics.c:559-670), one wavefront per sweep; <true>: candidates
+//                            that own a mesh of the mesh set collide through its triangles (tricontact_dev.h)
+//   k_mesh_contacts_count / _scan / _write   near_callback for (body, static) pairs whose static owns a mesh: the
+//                            triangles under the body's box, the rule of tricontact_dev.h, MAX_CONTACTS, canonical order
 //
 // Why the flag: phd::collide() writes its (up to two) contacts through CGeom references.  After inlining, LLVM's
 // SimplifyCFG sinks the "same" stores of different call sites into one block that stores through a SELECTED pointer
@@ -14,6 +17,8 @@
 #include "common.h"
 #include "phys_dev.h"
 #include "geoms_dev.h"
+#include "trimesh_dev.h"
+#include "tricontact_dev.h"
 
 struct clapgpu_bp;
 unsigned long long *clapgpu_bp_contact_ticket(clapgpu_bp *bp);       // physics2.hip
@@ -267,13 +272,37 @@ void k_contacts_geoms_both(GeomsK A, GeomsK B, const uint2 *pairs, const uint32_
     }
 }
 
-// phys_body_sweep_capsule: one wavefront per sweep, the candidates of a step spread over the lanes
+// the probe's box for a BVH query: the segment's box grown by the radius, and by a relative margin so that a triangle
+// touching the geom (depth 0) is never left out by the rounding of the box
+__device__ __forceinline__ void segment_box(const double (&a)[3], const double (&b)[3], double r, double (&lo)[3], double (&hi)[3])
+{
+    for (int i = 0; i < 3; i++) {
+        const double l = fmin(a[i], b[i]) - r, h = fmax(a[i], b[i]) + r;
+        const double pad = (fabs(l) + fabs(h) + r) * 0x1p-40;
+        lo[i] = l - pad;
+        hi[i] = h + pad;
+    }
+}
+
+// the mesh of static `id`, or -1
+__device__ __forceinline__ int32_t mesh_of(const MeshSet &M, uint32_t id)
+{
+    return (M.static_mesh && id < M.n_statics) ? M.static_mesh[id] : -1;
+}
+
+// phys_body_sweep_capsule: one wavefront per sweep, the candidates of a step spread over the lanes.  MESH: a candidate
+// static that owns a mesh collides with that mesh's triangles under the probe's box instead of its own collider, its
+// contacts in ascending triangle index (the 16 lowest touching triangles kept in LDS: no more can be taken); one
+// wavefront per workgroup for the LDS stack
+template <bool MESH>
 __global__ __launch_bounds__(PB)
-void k_sweep_capsules(GeomsK A, GeomsK B, uint32_t n_sweeps, const uint32_t *sweep_body, const float *delta_in,
+void k_sweep_capsules(GeomsK A, GeomsK B, MeshSet M, uint32_t n_sweeps, const uint32_t *sweep_body, const float *delta_in,
                       const uint32_t *cand_first, const uint32_t *cand, float *frac_out, float *normal_out, int32_t *hit_out)
 {
+    constexpr uint32_t SW = MESH ? 1 : PB / WAVE;                         // sweeps per workgroup
+    __shared__ uint32_t stk[MESH ? TM_STACK * WAVE : 1], ltri[MESH ? 16 * WAVE : 1], lslot[MESH ? 16 * WAVE : 1];
     const int lane = lane_id();
-    const uint32_t sw = blockIdx.x * (PB / WAVE) + threadIdx.x / WAVE;
+    const uint32_t sw = blockIdx.x * SW + threadIdx.x / WAVE;
     if (sw >= n_sweeps) return;
     const uint32_t self = sweep_body[sw];
     const float delta[3] = { delta_in[3 * (size_t)sw], delta_in[3 * (size_t)sw + 1], delta_in[3 * (size_t)sw + 2] };
@@ -308,11 +337,38 @@ void k_sweep_capsules(GeomsK A, GeomsK B, uint32_t n_sweeps, const uint32_t *swe
                 memset(&cg1, 0, sizeof(cg1));
                 bool is_body = false;
                 uint32_t id = 0;
+                uint32_t n_mesh = 0;                                          // MESH: touching triangles listed
+                double sa[3], sb[3];                                          // MESH: the probe's segment
                 if (kk < c1) {
                     const uint32_t cv = cand[kk];
                     is_body = (cv >> 31) != 0;
                     id = cv & 0x7fffffffu;
-                    if (!(is_body && id == self) && id < (is_body ? A.n : B.n)) {
+                    if (MESH && !is_body && id < B.n && mesh_of(M, id) >= 0) {
+                        if (phd::geom_segment(probe, sa, sb)) {
+                            double lo[3], hi[3];
+                            segment_box(sa, sb, probe.radius, lo, hi);
+                            uint32_t total = 0;
+                            box_walk(M, lo, hi, stk + lane, [&](uint32_t slot) {
+                                const uint2 kt = M.key[slot];
+                                if (kt.x != id) return;
+                                phd::CGeom t0, t1;
+                                const int n = phd::collide_segment_triangle(sa, sb, probe.radius, M.tri + 9 * (size_t)slot, t0, t1);
+                                if (n <= 0) return;
+                                total += (uint32_t)n;
+                                // the 16 lowest triangle indices, ascending
+                                if (n_mesh == 16 && ltri[15 * WAVE + lane] < kt.y) return;
+                                int k = n_mesh < 16 ? (int)n_mesh : 16;
+                                while (k > 0 && ltri[(k - 1) * WAVE + lane] > kt.y) {
+                                    if (k < 16) { ltri[k * WAVE + lane] = ltri[(k - 1) * WAVE + lane]; lslot[k * WAVE + lane] = lslot[(k - 1) * WAVE + lane]; }
+                                    k--;
+                                }
+                                ltri[k * WAVE + lane] = kt.y;
+                                lslot[k * WAVE + lane] = slot | ((uint32_t)(n - 1) << 31);
+                                if (n_mesh < 16) n_mesh++;
+                            });
+                            nc = (int)total;
+                        }
+                    } else if (!(is_body && id == self) && id < (is_body ? A.n : B.n)) {
                         phd::Geom other;
                         load_geom(is_body ? A : B, id, other);
                         nc = phd::collide(probe, other, cg0, cg1);
@@ -344,8 +400,20 @@ void k_sweep_capsules(GeomsK A, GeomsK B, uint32_t n_sweeps, const uint32_t *swe
                         step_hit = is_body ? (int32_t)id : -2 - (int32_t)id;
                     }
                 };
-                if (nc > 0) take(cg0, 0);
-                if (nc > 1) take(cg1, 1);
+                if (MESH && n_mesh) {                                         // the mesh's contacts in triangle order
+                    uint32_t i = 0;
+                    for (uint32_t k = 0; k < n_mesh && first + i < 16; k++) {
+                        const uint32_t slot = lslot[k * WAVE + lane] & 0x7fffffffu;
+                        phd::CGeom t0, t1;
+                        const int n = phd::collide_segment_triangle(sa, sb, probe.radius, M.tri + 9 * (size_t)slot, t0, t1);
+                        if (n > 0) take(t0, i);
+                        if (n > 1) take(t1, i + 1);
+                        i += (uint32_t)(n > 0 ? n : 0);
+                    }
+                } else {
+                    if (nc > 0) take(cg0, 0);
+                    if (nc > 1) take(cg1, 1);
+                }
                 taken += __shfl(incl, WAVE - 1);
             }
             // the sequential loop keeps the FIRST contact (in order) among those with the smallest frac below best_frac
@@ -374,6 +442,177 @@ void k_sweep_capsules(GeomsK A, GeomsK B, uint32_t n_sweeps, const uint32_t *swe
         normal_out[3 * (size_t)sw + 2] = best_normal[2];
         hit_out[sw] = best_hit;
     }
+}
+
+
+// ================================================================================== contacts against meshes
+// One lane per (body, static) pair, one wavefront per workgroup (the LDS below is per lane: [entry][lane] columns).  A
+// pair's records are kept in LDS as the 16 best by (deeper first, then lower triangle index) -- a pair keeps at most 16
+// contacts, so no record beyond those can be kept -- and the kept ones are that order's longest prefix whose contacts
+// fit in 16.  Both passes compute the same selection; the first counts, the scan places, the second writes.
+constexpr int MC = WAVE;
+constexpr int MC_KEEP = 16;                                              // MAX_CONTACTS, physics.c:150
+
+struct MeshLds {
+    uint32_t stk[TM_STACK * MC];
+    double dep[MC_KEEP * MC];                                            // a record's depth: the deeper of its contacts
+    uint32_t tri[MC_KEEP * MC];                                          // triangle of the mesh
+    uint32_t slot[MC_KEEP * MC];                                         // leaf slot | (nc - 1) << 31
+};
+
+struct PairSel { uint32_t body, stat, kept, found; double a[3], b[3], r; };
+
+// pair p's selection into the lane's LDS columns; false: the pair has no mesh contacts to look for
+__device__ __forceinline__ bool select_mesh_records(const GeomsK &A, const GeomsK &B, const MeshSet &M, const uint2 *pairs,
+                                                    uint32_t p, uint32_t np, MeshLds &L, int lane, PairSel &s)
+{
+    s.kept = s.found = 0;
+    if (p >= np) return false;
+    const uint2 pr = pairs[p];
+    s.body = pr.x; s.stat = pr.y;
+    if (pr.x >= A.n || pr.y >= B.n || mesh_of(M, pr.y) < 0) return false;
+    phd::Geom g;
+    load_geom(A, pr.x, g);
+    if (!phd::geom_segment(g, s.a, s.b)) return false;                   // boxes: no triangle collider here
+    s.r = g.radius;
+    double lo[3], hi[3];
+    segment_box(s.a, s.b, s.r, lo, hi);
+    uint32_t n = 0, found = 0;
+    box_walk(M, lo, hi, L.stk + lane, [&](uint32_t slot) {
+        const uint2 kt = M.key[slot];
+        if (kt.x != pr.y) return;                                        // another mesh's leaf
+        phd::CGeom c0, c1;
+        const int nc = phd::collide_segment_triangle(s.a, s.b, s.r, M.tri + 9 * (size_t)slot, c0, c1);
+        if (nc <= 0) return;
+        found++;
+        const double d = nc > 1 && c1.depth > c0.depth ? c1.depth : c0.depth;
+        auto before = [&](int k) {                                       // the new record goes before entry k
+            const double dk = L.dep[k * MC + lane];
+            return d > dk || (d == dk && kt.y < L.tri[k * MC + lane]);
+        };
+        if (n == MC_KEEP && !before(MC_KEEP - 1)) return;
+        int k = n < MC_KEEP ? (int)n : MC_KEEP;
+        while (k > 0 && before(k - 1)) {
+            if (k < MC_KEEP) {
+                L.dep[k * MC + lane] = L.dep[(k - 1) * MC + lane];
+                L.tri[k * MC + lane] = L.tri[(k - 1) * MC + lane];
+                L.slot[k * MC + lane] = L.slot[(k - 1) * MC + lane];
+            }
+            k--;
+        }
+        L.dep[k * MC + lane] = d;
+        L.tri[k * MC + lane] = kt.y;
+        L.slot[k * MC + lane] = slot | ((uint32_t)(nc - 1) << 31);
+        if (n < MC_KEEP) n++;
+    });
+    uint32_t used = 0, kept = 0;
+    for (; kept < n; kept++) {
+        const uint32_t nc = (L.slot[kept * MC + lane] >> 31) + 1;
+        if (used + nc > (uint32_t)MC_KEEP) break;
+        used += nc;
+    }
+    s.kept = kept;
+    s.found = found;
+    return true;
+}
+
+__global__ __launch_bounds__(MC)
+void k_mesh_contacts_count(GeomsK A, GeomsK B, MeshSet M, const uint2 *pairs, const uint32_t *pair_total, uint32_t capacity,
+                           uint32_t *wsum, uint32_t *capped)
+{
+    __shared__ MeshLds L;
+    const int lane = lane_id();
+    uint32_t np = *pair_total;
+    if (np > capacity) np = capacity;
+    PairSel s;
+    select_mesh_records(A, B, M, pairs, blockIdx.x * MC + lane, np, L, lane, s);
+    uint32_t kept = s.kept, cap = s.found > s.kept ? 1u : 0u;
+    for (int o = 32; o > 0; o >>= 1) { kept += __shfl_xor(kept, o); cap += __shfl_xor(cap, o); }
+    if (lane == 0) {
+        wsum[blockIdx.x] = kept;
+        if (cap && capped) atomicAdd(capped, cap);
+    }
+}
+
+// one workgroup: the exclusive scan of the wavefronts' record counts in place, and the total
+constexpr int MS = 1024;
+__global__ __launch_bounds__(MS)
+void k_mesh_contacts_scan(const uint32_t *pair_total, uint32_t capacity, uint32_t *wsum, uint32_t *total)
+{
+    __shared__ uint32_t part[MS / WAVE];
+    uint32_t np = *pair_total;
+    if (np > capacity) np = capacity;
+    const uint32_t nw = (np + MC - 1) / MC, per = (nw + MS - 1) / MS;
+    const uint32_t b0 = threadIdx.x * per, b1 = b0 + per < nw ? b0 + per : nw;
+    uint32_t sum = 0;
+    for (uint32_t i = b0; i < b1; i++) sum += wsum[i];
+    const int lane = lane_id(), wv = threadIdx.x / WAVE;
+    uint32_t incl = sum;
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const uint32_t u = __shfl_up(incl, o);
+        if (lane >= o) incl += u;
+    }
+    if (lane == WAVE - 1) part[wv] = incl;
+    __syncthreads();
+    uint32_t off = incl - sum;
+    for (int k = 0; k < wv; k++) off += part[k];
+    for (uint32_t i = b0; i < b1; i++) { const uint32_t c = wsum[i]; wsum[i] = off; off += c; }
+    if (threadIdx.x == MS - 1) {
+        uint32_t t = 0;
+        for (int k = 0; k < MS / WAVE; k++) t += part[k];
+        if (total) *total = t;
+    }
+}
+
+__global__ __launch_bounds__(MC)
+void k_mesh_contacts_write(GeomsK A, GeomsK B, MeshSet M, const uint2 *pairs, const uint32_t *pair_total, uint32_t capacity,
+                           const uint32_t *wsum, uint32_t out_capacity, clapgpu_contact2 *out, uint32_t *mesh_ref,
+                           uint32_t *body_flags)
+{
+    __shared__ MeshLds L;
+    const int lane = lane_id();
+    uint32_t np = *pair_total;
+    if (np > capacity) np = capacity;
+    if (blockIdx.x * MC >= np) return;                                   // wave-uniform
+    const uint32_t p = blockIdx.x * MC + lane;
+    PairSel s;
+    select_mesh_records(A, B, M, pairs, p, np, L, lane, s);
+    uint32_t incl = s.kept;
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const uint32_t u = __shfl_up(incl, o);
+        if (lane >= o) incl += u;
+    }
+    const uint32_t base = wsum[blockIdx.x] + incl - s.kept;
+    if (s.kept == 0) return;
+    const double *m1 = (A.material && B.material) ? A.material + 5 * (size_t)s.body : nullptr;
+    const double *m2 = (A.material && B.material) ? B.material + 5 * (size_t)s.stat : nullptr;
+    for (uint32_t k = 0; k < s.kept; k++) {
+        const uint32_t t = L.tri[k * MC + lane];
+        uint32_t rank = 0;                                               // ascending triangle index within the pair
+        for (uint32_t j = 0; j < s.kept; j++) rank += L.tri[j * MC + lane] < t ? 1u : 0u;
+        const uint32_t o = base + rank;
+        if (o >= out_capacity) continue;
+        const uint32_t slot = L.slot[k * MC + lane] & 0x7fffffffu;
+        phd::CGeom c0, c1;
+        memset(&c0, 0, sizeof(c0));
+        memset(&c1, 0, sizeof(c1));
+        const int nc = phd::collide_segment_triangle(s.a, s.b, s.r, M.tri + 9 * (size_t)slot, c0, c1);
+        clapgpu_contact2 c;
+        memset(&c, 0, sizeof(c));
+        for (int i = 0; i < 3; i++) { c.pos[i] = c0.pos[i]; c.normal[i] = c0.normal[i]; }
+        c.depth = c0.depth;
+        if (nc > 1) {
+            for (int i = 0; i < 3; i++) { c.pos2[i] = c1.pos[i]; c.normal2[i] = c1.normal[i]; }
+            c.depth2 = c1.depth;
+        }
+        contact_surface2(c, m1, m2);
+        c.nc = (uint32_t)nc;
+        out[o] = c;
+        mesh_ref[2 * (size_t)o] = p;
+        mesh_ref[2 * (size_t)o + 1] = t;
+    }
+    // plain read-modify-write: every writer of this launch sets the same bit and nothing else changes the word
+    if (body_flags && !(body_flags[s.body] & CLAPGPU_BODY_HAS_JOINT)) body_flags[s.body] |= CLAPGPU_BODY_HAS_JOINT;
 }
 
 
@@ -457,15 +696,61 @@ extern "C" int clapgpu_contacts_geoms_both(void *stream, clapgpu_bp *bp, const c
     return CLAPGPU_OK;
 }
 
+extern "C" int clapgpu_sweep_capsules_meshes(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B,
+                                             const clapgpu_trimesh *meshes, uint32_t n_sweeps, const uint32_t *sweep_body,
+                                             const float *delta, const uint32_t *cand_first, const uint32_t *cand, float *frac,
+                                             float *normal, int32_t *hit)
+{
+    if (!A || !B || (n_sweeps && (!sweep_body || !delta || !cand_first || !frac || !normal || !hit)))
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (meshes && trimesh_n_statics(meshes) != B->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (n_sweeps == 0) return CLAPGPU_OK;
+    MeshSet M;
+    memset(&M, 0, sizeof(M));
+    if (meshes) {
+        M = trimesh_set(meshes);
+        hipLaunchKernelGGL(k_sweep_capsules<true>, dim3(n_sweeps), dim3(WAVE), 0, as_stream(stream), geoms_k(A), geoms_k(B), M,
+                           n_sweeps, sweep_body, delta, cand_first, cand, frac, normal, hit);
+    } else {
+        hipLaunchKernelGGL(k_sweep_capsules<false>, dim3((n_sweeps + PB / WAVE - 1) / (PB / WAVE)), dim3(PB), 0, as_stream(stream),
+                           geoms_k(A), geoms_k(B), M, n_sweeps, sweep_body, delta, cand_first, cand, frac, normal, hit);
+    }
+    CLAPGPU_LAUNCH_CHECK("k_sweep_capsules");
+    return CLAPGPU_OK;
+}
+
 extern "C" int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B, uint32_t n_sweeps,
                                       const uint32_t *sweep_body, const float *delta, const uint32_t *cand_first,
                                       const uint32_t *cand, float *frac, float *normal, int32_t *hit)
 {
-    if (!A || !B || (n_sweeps && (!sweep_body || !delta || !cand_first || !frac || !normal || !hit)))
+    return clapgpu_sweep_capsules_meshes(stream, A, B, nullptr, n_sweeps, sweep_body, delta, cand_first, cand, frac, normal, hit);
+}
+
+extern "C" int clapgpu_contacts_meshes(void *stream, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
+                                       const clapgpu_trimesh *meshes, const uint32_t *static_pairs,
+                                       const uint32_t *static_pair_total, uint32_t static_capacity, uint32_t *scratch,
+                                       uint32_t capacity, clapgpu_contact2 *contacts, uint32_t *mesh_ref,
+                                       uint32_t *contact_total, uint32_t *capped_pairs, uint32_t *body_flags)
+{
+    if (!bodies || !statics || !meshes || !static_pair_total || (static_capacity && (!static_pairs || !scratch)) ||
+        (capacity && (!contacts || !mesh_ref)))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (n_sweeps == 0) return CLAPGPU_OK;
-    hipLaunchKernelGGL(k_sweep_capsules, dim3((n_sweeps + PB / WAVE - 1) / (PB / WAVE)), dim3(PB), 0, as_stream(stream),
-                       geoms_k(A), geoms_k(B), n_sweeps, sweep_body, delta, cand_first, cand, frac, normal, hit);
-    CLAPGPU_LAUNCH_CHECK("k_sweep_capsules");
+    if (reinterpret_cast<uintptr_t>(contacts) & 15u) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (trimesh_n_statics(meshes) != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    hipStream_t s = as_stream(stream);
+    if (contact_total) CLAPGPU_HIP(hipMemsetAsync(contact_total, 0, sizeof(uint32_t), s));
+    if (capped_pairs) CLAPGPU_HIP(hipMemsetAsync(capped_pairs, 0, sizeof(uint32_t), s));
+    if (static_capacity == 0 || bodies->n == 0 || statics->n == 0) return CLAPGPU_OK;
+    const MeshSet M = trimesh_set(meshes);
+    const uint32_t waves = (static_capacity + MC - 1) / MC;
+    const uint2 *pairs = reinterpret_cast<const uint2 *>(static_pairs);
+    hipLaunchKernelGGL(k_mesh_contacts_count, dim3(waves), dim3(MC), 0, s, geoms_k(bodies), geoms_k(statics), M, pairs,
+                       static_pair_total, static_capacity, scratch, capped_pairs);
+    CLAPGPU_LAUNCH_CHECK("k_mesh_contacts_count");
+    hipLaunchKernelGGL(k_mesh_contacts_scan, dim3(1), dim3(MS), 0, s, static_pair_total, static_capacity, scratch, contact_total);
+    CLAPGPU_LAUNCH_CHECK("k_mesh_contacts_scan");
+    hipLaunchKernelGGL(k_mesh_contacts_write, dim3(waves), dim3(MC), 0, s, geoms_k(bodies), geoms_k(statics), M, pairs,
+                       static_pair_total, static_capacity, scratch, capacity, contacts, mesh_ref, body_flags);
+    CLAPGPU_LAUNCH_CHECK("k_mesh_contacts_write");
     return CLAPGPU_OK;
 }

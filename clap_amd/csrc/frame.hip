@@ -166,6 +166,11 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
                                                   f->static_pair_capacity, f->static_contacts, f->static_contact_total,
                                                   f->bodies->bflags, nullptr));
                 }
+                if (f->meshes && f->body_geoms && f->static_geoms && f->static_pair_total)
+                    FR(clapgpu_contacts_meshes(stream, f->body_geoms, f->static_geoms, f->meshes, f->static_pairs,
+                                               f->static_pair_total, f->static_pair_capacity, f->mesh_scratch,
+                                               f->mesh_contact_capacity, f->mesh_contacts, f->mesh_ref,
+                                               f->mesh_contact_total, f->mesh_capped, f->bodies->bflags));
             }
             if ((f->flags & CLAPGPU_FRAME_PREBIN) && f->bp && f->bodies->aabb)
                 FR(clapgpu_bodies_step_prebin(stream, f->bodies, f->world, 1.0 / 120.0, f->bp));

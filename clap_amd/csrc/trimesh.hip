@@ -44,6 +44,7 @@
 #include "phys_dev.h"
 #include "bp_grid.h"
 #include "rays_dev.h"
+#include "trimesh_dev.h"
 
 namespace clapgpu {
 
@@ -51,13 +52,6 @@ constexpr int TB = 256;                                 // set-up kernels
 constexpr int RT = 64;                                  // k_ray_trimesh: one wave per workgroup
 constexpr int STACK = 64;
 constexpr uint32_t LEAF = 0x80000000u, NO_SLOT = 0xffffffffu;
-
-struct alignas(16) Node {
-    float box[12];                                      // child 0: min xyz, max xyz; child 1: the same
-    uint32_t child[2];
-    uint32_t pad[2];
-};
-static_assert(sizeof(Node) == 64, "one node, one 64-byte sector");
 
 struct MeshK {
     const Node *nodes;
@@ -467,6 +461,14 @@ void k_ray_trimesh(MeshK m, MeshPass p)
 
 const int32_t *trimesh_static_mesh(const clapgpu_trimesh *m) { return m->static_mesh; }
 uint32_t trimesh_n_statics(const clapgpu_trimesh *m) { return m->n_statics; }
+
+MeshSet trimesh_set(const clapgpu_trimesh *m)
+{
+    MeshSet s;
+    s.nodes = m->nodes; s.tri = m->stri; s.key = m->skey; s.static_mesh = m->static_mesh;
+    s.n_tris = m->n_tris; s.n_statics = m->n_statics;
+    return s;
+}
 
 int trimesh_pass(hipStream_t s, const clapgpu_trimesh *tm, const MeshPass &p)
 {

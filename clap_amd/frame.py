@@ -76,6 +76,13 @@ class FrameLoop:
                     f.static_geoms = C.pointer(sg)
                     f.static_contacts = w.static_contact2_buf.data_ptr()
                     f.static_contact_total = w.static_contact2_total.data_ptr()
+                    if w._meshes is not None:                   # contacts against the static meshes (clapgpu_contacts_meshes)
+                        w.alloc_mesh_contacts()
+                        f.meshes = w._meshes
+                        f.mesh_contacts, f.mesh_ref = w.mesh_contact_buf.data_ptr(), w.mesh_ref.data_ptr()
+                        f.mesh_contact_capacity = w.mesh_contact_capacity
+                        f.mesh_contact_total, f.mesh_capped = w.mesh_contact_total.data_ptr(), w.mesh_capped.data_ptr()
+                        f.mesh_scratch = w.mesh_scratch.data_ptr()
             if self.body_links is not None:
                 lb, le = w.upload_links(*self.body_links)
                 f.n_body_links, f.link_body, f.link_entity = len(self.body_links[0]), lb.data_ptr(), le.data_ptr()

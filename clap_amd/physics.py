@@ -198,8 +198,9 @@ class PhysWorld:
                              int(self.static_contact2_total.item()))
         return out
 
-    def sweep_capsules(self, sweep_body, delta, cand_first, cand):
-        """phys_body_sweep_capsule for a batch (physics.c:559-670): returns (frac, normal[n,3], hit) device tensors."""
+    def sweep_capsules(self, sweep_body, delta, cand_first, cand, meshes=True):
+        """phys_body_sweep_capsule for a batch (physics.c:559-670): returns (frac, normal[n,3], hit) device tensors.
+        meshes: candidate statics that own a mesh collide through its triangles once set_static_meshes ran."""
         dev = self.device
         ns = len(sweep_body)
         up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt).view(np.int32 if dt == np.uint32 else dt)).to(dev)
@@ -208,9 +209,48 @@ class PhysWorld:
         normal = torch.zeros((max(ns, 1), 3), dtype=torch.float32, device=dev)
         hit = torch.zeros(max(ns, 1), dtype=torch.int32, device=dev)
         g, sg = self.body_geoms(), self.static_geoms()
-        _lib.check(_lib.lib().clapgpu_sweep_capsules(_stream(), C.byref(g), C.byref(sg), ns, _ptr(sb), _ptr(dl), _ptr(cf),
-                                                     _ptr(cd), _ptr(frac), _ptr(normal), _ptr(hit)), "clapgpu_sweep_capsules")
+        _lib.check(_lib.lib().clapgpu_sweep_capsules_meshes(_stream(), C.byref(g), C.byref(sg), self._meshes if meshes else None,
+                                                            ns, _ptr(sb), _ptr(dl), _ptr(cf), _ptr(cd), _ptr(frac), _ptr(normal),
+                                                            _ptr(hit)), "clapgpu_sweep_capsules_meshes")
+        self._sweep_keep = (sb, dl, cf, cd)
         return frac[:ns], normal[:ns], hit[:ns]
+
+    def alloc_mesh_contacts(self, capacity=None):
+        """The mesh contact list (clapgpu_contact2 records, mesh_ref [k][2]), its totals and scratch."""
+        cap = int(capacity if capacity is not None else getattr(self, "mesh_contact_capacity", None) or
+                  max(min(self.static_capacity, 16 * self.n), 1024))
+        if getattr(self, "mesh_contact_buf", None) is None or self.mesh_contact_capacity != cap:
+            dev = self.device
+            self.mesh_contact_capacity = cap
+            self.mesh_contact_buf = torch.zeros((max(cap, 1), 160), dtype=torch.uint8, device=dev)
+            self.mesh_ref = torch.zeros((max(cap, 1), 2), dtype=torch.int32, device=dev)
+            self.mesh_contact_total = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.mesh_capped = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.mesh_scratch = torch.zeros(_lib.mesh_contact_scratch(self.static_capacity), dtype=torch.int32, device=dev)
+
+    def contacts_meshes(self, set_joint_flags=True, capacity=None):
+        """near_callback for the (body, static) pairs of the last broadphase() whose static owns a mesh of
+        set_static_meshes (clapgpu_contacts_meshes): one record per touching (pair, triangle)."""
+        if self._meshes is None:
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "contacts_meshes", "no mesh set: call set_static_meshes")
+        self.alloc_mesh_contacts(capacity)
+        g, sg = self.body_geoms(), self.static_geoms()
+        _lib.check(_lib.lib().clapgpu_contacts_meshes(_stream(), C.byref(g), C.byref(sg), self._meshes, _ptr(self.static_pairs),
+                                                      _ptr(self.static_pair_total), self.static_capacity,
+                                                      _ptr(self.mesh_scratch), self.mesh_contact_capacity,
+                                                      _ptr(self.mesh_contact_buf), _ptr(self.mesh_ref),
+                                                      _ptr(self.mesh_contact_total), _ptr(self.mesh_capped),
+                                                      _ptr(self.bflags) if set_joint_flags else None),
+                   "clapgpu_contacts_meshes")
+
+    def download_mesh_contacts(self, dtype):
+        """(records [k] of dtype, mesh_ref [k, 2] (static pair index, triangle of the mesh), total, capped pairs); k is
+        the written prefix: min(total, capacity)."""
+        torch.cuda.synchronize(self.device)
+        total = int(self.mesh_contact_total.item())
+        k = min(total, self.mesh_contact_capacity)
+        return (self.mesh_contact_buf[:k].cpu().numpy().view(dtype).reshape(-1),
+                self.mesh_ref[:k].cpu().numpy().view(np.uint32), total, int(self.mesh_capped.item()))
 
     # ---- ray casts (physics.c:474-540, 695-744) ------------------------------------------
     def bp_index(self):

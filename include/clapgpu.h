@@ -695,7 +695,8 @@ typedef struct clapgpu_world {
 #define CLAPGPU_GEOM_SPHERE  0
 #define CLAPGPU_GEOM_CAPSULE 1
 #define CLAPGPU_GEOM_BOX     2                 /* an axis-aligned box given by its AABB (stand-in for any static geom) */
-#define CLAPGPU_GEOM_OTHER   3                 /* trimesh etc.: broadphase only, no narrowphase here */
+#define CLAPGPU_GEOM_OTHER   3                 /* trimesh etc.: broadphase only, no narrowphase here (with a mesh set:
+                                                  clapgpu_contacts_meshes / clapgpu_sweep_capsules_meshes) */
 
 /*
  * Bodies of the character_space, fp64 like the reference's dDOUBLE ODE (physics.h:5-9): capsules
@@ -906,7 +907,7 @@ int clapgpu_contacts_geoms_both(void *stream, clapgpu_bp *bp, const clapgpu_geom
  * every step with its candidate geoms cand[cand_first[k] .. cand_first[k + 1]): an index into B (statics) or,
  * with bit 31 set, into A (other bodies; the body itself is skipped).  Out per sweep: frac (best_frac),
  * normal[3], hit (body index, -2 - static index, or -1).  Contacts are taken in candidate order, 16 per
- * step at most (MAX_CONTACTS).  One wavefront per sweep.
+ * step at most (MAX_CONTACTS).  One wavefront per sweep.  Against static meshes: clapgpu_sweep_capsules_meshes.
  */
 int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B, uint32_t n_sweeps,
                            const uint32_t *sweep_body, const float *delta, const uint32_t *cand_first,
@@ -1000,6 +1001,8 @@ int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bo
  * clapgpu_trimesh_pose: new pos / quat (device arrays as above) for every mesh, then the same bake and rebuild as create.
  * clapgpu_trimesh_status: host sync; *depth = the tree's height (edges from the root to the deepest leaf; at most 62,
  * 0 without triangles), *n_tris = the triangles of all meshes.
+ * A static's broadphase AABB (clapgpu_bp_create) must hold its posed mesh: the mesh contacts below only see pairs the
+ * broadphase found.
  *
  * clapgpu_ray_cast_meshes / clapgpu_bodies_ground_collide_meshes: clapgpu_ray_cast / clapgpu_bodies_ground_collide with
  * the statics that own a mesh of `meshes` intersected through their triangles (one more launch, one lane per ray; the
@@ -1037,6 +1040,64 @@ int  clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp, const cl
                                           const clapgpu_trimesh *meshes, uint32_t n, const uint32_t *body,
                                           const double *ray_off, const uint8_t *grounded, uint8_t *grounded_out, float *normal,
                                           double *dist, int32_t *hit, uint32_t *flags, uint32_t *scratch);
+
+/*
+ * Contacts against the mesh set: near_callback's dCollide for (body, static) pairs whose static owns a mesh, and the
+ * capsule sweep against meshes.  ODE's trimesh colliders (dCollideSTL, dCollideCCTL, OPCODE) are an absent submodule of
+ * the reference: the rule below is this project's own, PARITY UNPINNED.
+ *
+ * Sphere / capsule against one triangle (tricontact_dev.h).  The body geom is a segment a, b with radius r: a capsule's
+ * ends pos + axis * length / 2 and pos - axis * length / 2, a sphere's centre twice (a capsule of length 0).  The
+ * triangle (v0, v1, v2) is the mesh set's fp64 bake.  fp64, no FMA contraction.  Normals point from the static towards
+ * the body (as in sphere-box); depth >= 0 is a contact.
+ *   1. n = (v1 - v0) x (v2 - v0).  n == 0: no contact.  Otherwise n^ = n / |n|.
+ *   2. sa, sb = the signed distances (p - v0) . n^ of a and b; m = min(sa, sb); e = the endpoint attaining m, a on a tie.
+ *   3. Face: the segment meets the closed triangle, or -r < m <= 0 and e projects into the closed triangle.  One
+ *      contact: normal n^, depth r - m, pos e - m n^ (a half-sunk sphere, or a capsule whose foot went through the
+ *      ground, is pushed back out along the face).
+ *   4. Parallel: a != b, m > 0, |sa - sb| <= 1e-5 |b - a|, both endpoints project into the triangle and
+ *      max(sa, sb) <= r.  Two contacts (the record's second slot, as dCollideCapsuleCapsule's parallel case), at a's and
+ *      then b's projection: normal n^, depths r - sa and r - sb.  A sphere never takes this case.
+ *   5. Otherwise the closest points p on the segment and q on the triangle, at distance d: a contact when 0 < d <= r and
+ *      (p - q) . n > 0: normal (p - q) / d, depth r - d, pos q.  A closest point behind the face is no contact (that
+ *      is a neighbouring face's contact, or nothing).
+ * Depth and normal are unique under the rule; pos may lie anywhere on a tied closest set.  Box bodies and OTHER bodies
+ * have no triangle collider here: no mesh contacts.
+ *
+ * clapgpu_contacts_meshes: for the (body, static) candidate pairs of clapgpu_bp_collide (static_pairs /
+ * static_pair_total / static_capacity as clapgpu_contacts_geoms takes them) whose static owns a mesh of `meshes`: the
+ * mesh's triangles whose boxes meet the body geom's box (through the BVH), each collided by the rule.  One
+ * clapgpu_contact2 per touching (pair, triangle), nc 1 or 2, with mesh_ref[k][2] = (static pair index, triangle index
+ * within the mesh).  Canonical order: ascending pair index, then ascending triangle index; the same bits whatever the
+ * launch shape.  Surface parameters: phys_contact_surface of the body's and the static's material (as the other lists);
+ * touching bodies get CLAPGPU_BODY_HAS_JOINT in body_flags (may be NULL).
+ * MAX_CONTACTS (physics.c:150, 413): a pair keeps at most 16 contacts, a two-contact record counting two.  Its records
+ * are ordered deeper first (a record's depth: the deeper of its contacts), then lower triangle index, and taken in that
+ * order while they fit (the first that does not fit ends the pair's list); the kept ones are written in triangle
+ * order.  *capped_pairs (may be NULL) = the pairs that dropped records.  *contact_total (may be NULL) = the records
+ * kept, at most `capacity` of them written (16-byte aligned).  scratch: CLAPGPU_MESH_CONTACT_SCRATCH(static_capacity)
+ * uint32 of device memory (static_capacity + 1 always suffices), overwritten.  No host synchronisation and no
+ * allocation: a captured graph can hold the call.  meshes must have been created with n_statics == statics->n
+ * (CLAPGPU_ERR_INVALID_ARGUMENTS otherwise).
+ * Precondition: a pair is only found if the static's broadphase AABB holds its posed mesh.
+ * The list is additive: clapgpu_contacts_geoms[_both] are unchanged, and a meshed OTHER static still gets nc = 0
+ * there.  A mesh given to a sphere, capsule or box static adds mesh contacts on top of that static's own record (the
+ * loader meshes only trimesh statics).
+ *
+ * clapgpu_sweep_capsules_meshes: clapgpu_sweep_capsules with a candidate static that owns a mesh collided through that
+ * mesh's triangles alone (the mesh replaces its collider, as in the ray casts), queried with the probe's box at every
+ * step.  Contacts are taken in candidate order, and within a mesh candidate in ascending triangle index; the cap of 16
+ * per step applies.  hit = -2 - s for the mesh's static s.  meshes == NULL: exactly clapgpu_sweep_capsules, which is this
+ * call with NULL.  meshes must have been created with n_statics == B->n.
+ */
+#define CLAPGPU_MESH_CONTACT_SCRATCH(static_capacity) (((static_capacity) + 63u) / 64u + 1u)
+int  clapgpu_contacts_meshes(void *stream, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
+                             const clapgpu_trimesh *meshes, const uint32_t *static_pairs, const uint32_t *static_pair_total,
+                             uint32_t static_capacity, uint32_t *scratch, uint32_t capacity, clapgpu_contact2 *contacts,
+                             uint32_t *mesh_ref, uint32_t *contact_total, uint32_t *capped_pairs, uint32_t *body_flags);
+int  clapgpu_sweep_capsules_meshes(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B, const clapgpu_trimesh *meshes,
+                                   uint32_t n_sweeps, const uint32_t *sweep_body, const float *delta, const uint32_t *cand_first,
+                                   const uint32_t *cand, float *frac, float *normal, int32_t *hit);
 
 /* ======================================================================== */
 /* Characters: the feeder in front of default_update (core/character.c)      */
@@ -1176,6 +1237,12 @@ typedef struct clapgpu_frame {
     uint32_t index_base; uint32_t *visible, *visible_count; void *visible_scratch;
     float cam_pos[3]; const int32_t *force_lod; int32_t *cur_lod, *draw_lod;
     uint32_t flags;                            /* CLAPGPU_FRAME_* */
+    /* contacts against static meshes (clapgpu_contacts_meshes) after each substep's static contacts; meshes NULL: none.
+     * Needs body_geoms, static_geoms, static_pairs and static_pair_total */
+    const clapgpu_trimesh    *meshes;
+    clapgpu_contact2 *mesh_contacts; uint32_t *mesh_ref; uint32_t mesh_contact_capacity;
+    uint32_t *mesh_contact_total, *mesh_capped;
+    uint32_t *mesh_scratch;                    /* CLAPGPU_MESH_CONTACT_SCRATCH(static_pair_capacity) uint32 */
 } clapgpu_frame;
 
 /* Default (0): everything on the caller's stream in the reference's order.  CLAPGPU_FRAME_OVERLAP: the frame's three
