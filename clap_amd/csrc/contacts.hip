@@ -703,7 +703,7 @@ extern "C" int clapgpu_sweep_capsules_meshes(void *stream, const clapgpu_geoms *
 {
     if (!A || !B || (n_sweeps && (!sweep_body || !delta || !cand_first || !frac || !normal || !hit)))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (meshes && trimesh_n_statics(meshes) != B->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (meshes && trimesh_set(meshes).n_statics != B->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (n_sweeps == 0) return CLAPGPU_OK;
     MeshSet M;
     memset(&M, 0, sizeof(M));
@@ -736,7 +736,7 @@ extern "C" int clapgpu_contacts_meshes(void *stream, const clapgpu_geoms *bodies
         (capacity && (!contacts || !mesh_ref)))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (reinterpret_cast<uintptr_t>(contacts) & 15u) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (trimesh_n_statics(meshes) != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (trimesh_set(meshes).n_statics != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     hipStream_t s = as_stream(stream);
     if (contact_total) CLAPGPU_HIP(hipMemsetAsync(contact_total, 0, sizeof(uint32_t), s));
     if (capped_pairs) CLAPGPU_HIP(hipMemsetAsync(capped_pairs, 0, sizeof(uint32_t), s));

@@ -6,6 +6,9 @@
 //   k_ground_rays   phys_body_ground_collide's ray and decision (physics.c:695-744) for a batch of bodies; the moves
 //                   themselves are applied by physics2.hip's k_ground_apply (the device function the step writes
 //                   geoms with lives there)
+//   k_ray_trimesh   the mesh pass behind either of them: one lane per ray, the walk of the mesh set's BVH
+//                   (trimesh_dev.h; built by trimesh.hip) and the watertight ray-triangle test, merged with the best
+//                   hit the first pass found (see "mesh pass" below)
 //
 // The colliders restate ODE 0.16's ray.cpp (dCollideRaySphere + ray_sphere_helper, dCollideRayCapsule, dCollideRayBox)
 // for the flags physics.c:485-487 sets; a box is its AABB.  ODE is an absent submodule of the reference: PARITY UNPINNED.
@@ -25,7 +28,8 @@
 #include "phys_dev.h"
 #include "geoms_dev.h"
 #include "bp_grid.h"
-#include "rays_dev.h"
+#include "trimesh_dev.h"
+#include "tricontact_dev.h"
 
 struct clapgpu_bp;
 int clapgpu_bodies_ground_apply(void *stream, const clapgpu_bodies *b, uint32_t n, const uint32_t *body, const double *ray_off,
@@ -35,7 +39,88 @@ int clapgpu_bodies_ground_apply(void *stream, const clapgpu_bodies *b, uint32_t 
 namespace clapgpu {
 
 constexpr int RB = 256;                                 // 4 rays per workgroup
+constexpr int RT = WAVE;                                // k_ray_trimesh: one wave per workgroup (the walk's LDS stack)
 
+// ------------------------------------------------------------------------------------------------- rays and hit keys
+constexpr uint32_t KEY_NONE = 0xffffffffu, KEY_STATIC = 0x80000000u;   // body i: i; static s: KEY_STATIC | s
+
+struct Ray { double s[3], u[3], len; };
+
+// the ray as dGeomRaySet stores it; false: CLAPGPU_RAY_INVALID
+__device__ __forceinline__ bool make_ray(const double *in, Ray &r)
+{
+    double d[3] = { in[3], in[4], in[5] };
+    r.s[0] = in[0]; r.s[1] = in[1]; r.s[2] = in[2];
+    r.len = in[6];
+    const bool finite_dir = isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]);
+    if (!finite_dir || (d[0] == 0 && d[1] == 0 && d[2] == 0) || r.s[0] != r.s[0] || r.s[1] != r.s[1] || r.s[2] != r.s[2] ||
+        !(r.len >= 0))
+        return false;
+    phd::safe_normalize3(d);                                                 // dNormalize3
+    r.u[0] = d[0]; r.u[1] = d[1]; r.u[2] = d[2];
+    return true;
+}
+
+__device__ __forceinline__ uint32_t skip_key_of(int32_t skip)
+{
+    return skip >= 0 ? (uint32_t)skip : skip <= -2 ? KEY_STATIC | (uint32_t)(-2 - skip) : KEY_NONE;
+}
+
+__device__ __forceinline__ int32_t hit_of(uint32_t key)
+{
+    return key == KEY_NONE ? -1 : (key & KEY_STATIC) ? -2 - (int32_t)(key & ~KEY_STATIC) : (int32_t)key;
+}
+
+__device__ __forceinline__ uint32_t key_of(int32_t hit)
+{
+    return hit == -1 ? KEY_NONE : hit >= 0 ? (uint32_t)hit : KEY_STATIC | (uint32_t)(-2 - hit);
+}
+
+// phys_body_ground_collide's ray for body i: start (float) below the body's position, straight down, 2 * ray_len long;
+// false: CLAPGPU_RAY_INVALID
+__device__ __forceinline__ bool ground_ray(const double *pos, const double *yoffset, uint32_t i, double ray_off, Ray &r,
+                                           double &ray_len)
+{
+    double roff;
+    ray_len = phd::ground_ray_len(ray_off, yoffset[i], roff);
+    const double *p = pos + 3 * (size_t)i;
+    const float start[3] = { (float)p[0], (float)(p[1] - roff), (float)p[2] };   // through a vec3
+    r.s[0] = start[0]; r.s[1] = start[1]; r.s[2] = start[2];
+    r.u[0] = 0.0; r.u[1] = -1.0; r.u[2] = 0.0;
+    r.len = ray_len * 2;
+    return r.len >= 0 && r.s[0] == r.s[0] && r.s[1] == r.s[1] && r.s[2] == r.s[2];
+}
+
+// ... and its decision on the (final) hit of ray j for body i: hit / dist / grounded_out / flags, the float normal (unless
+// write_nrm is false: already written), and bit 0 of moved[i] when the apply launch is to move the body
+__device__ __forceinline__ void ground_decide(uint32_t j, uint32_t i, double ray_len, uint32_t key, double depth,
+                                              const double (&nrm)[3], bool write_nrm, uint32_t f, const uint8_t *grounded,
+                                              uint8_t *grounded_out, float *normal,
+                                              double *dist, int32_t *hit, uint32_t *flags, uint32_t *moved)
+{
+    bool res = false;
+    hit[j] = hit_of(key);
+    if (key != KEY_NONE && !f) {
+        if (write_nrm)
+            for (int a = 0; a < 3; a++) normal[3 * (size_t)j + a] = (float)nrm[a];
+        float dy;
+        bool mv;
+        res = phd::ground_branch(depth, ray_len, grounded[j] != 0, dy, mv);
+        if (mv) atomicOr(&moved[i], 1u);
+    }
+    if (key != KEY_NONE) dist[j] = depth;
+    grounded_out[j] = res ? 1 : 0;
+    flags[j] = f;
+}
+
+// the UNRESOLVED rule on a ray's final hit: the segment enters an OTHER static without a mesh (first entry `other`)
+// before the hit, or there is no hit
+__device__ __forceinline__ uint32_t unresolved(double other, double len, uint32_t key, double depth)
+{
+    return (other <= len && (key == KEY_NONE || other <= depth)) ? CLAPGPU_RAY_UNRESOLVED : 0u;
+}
+
+// ------------------------------------------------------------------------------------------------- bodies and statics
 // ray_sphere_helper (ray.cpp): mode = the ray starts inside the capsule this cap belongs to
 __device__ __forceinline__ bool ray_sphere(const Ray &r, const double (&c)[3], double radius, bool mode, phd::CGeom &o)
 {
@@ -188,7 +273,7 @@ struct Best {
 };
 
 // one geom of a set: the collider of its kind, or, for CLAPGPU_GEOM_OTHER, where the segment enters its AABB.  A static
-// with a triangle mesh (meshed[s] >= 0) is left to the mesh pass (trimesh.hip)
+// with a triangle mesh (meshed[s] >= 0) is left to the mesh pass (below)
 __device__ __forceinline__ void test_geom(const Ray &r, const GeomsK &g, uint32_t i, uint32_t key, uint32_t skip_key, Best &b,
                                           const int32_t *meshed)
 {
@@ -446,9 +531,187 @@ void k_ground_rays(CastK k, uint32_t n, const double *pos, const double *yoffset
     }
 }
 
+// ------------------------------------------------------------------------------------------------- mesh pass
+// The pass behind k_ray_cast / k_ground_rays when a mesh set is given: those wrote the best hit, the flags and `other`
+// of every ray and left the statics that own a mesh alone.
+//
+// The test: ODE's dCollideRTL runs OPCODE's float ray-triangle test with ClosestHit = 1, BackfaceCull = 1 (physics.c:485-487).
+// Here the triangles are tested in fp64 with the watertight test of Woop, Benthin and Wald (JCGT 2013): the ray's dominant
+// axis is z, the other two are sheared onto it once per ray, and the three edge functions U, V, W of the projected
+// triangle decide.  A shared edge gets the same edge function with opposite sign in both triangles (the products
+// commute and the difference is negated exactly; no FMA contraction), so a ray through an edge or a vertex of front faces
+// hits at least one of them: no ray falls through the terrain.  Front face: U, V, W >= 0 and det = U + V + W > 0, which is
+// u . n < 0 for n = (v1 - v0) x (v2 - v0).  n == 0 never hits (ODE's dSafeNormalize3 fails there); a hit needs
+// 0 <= depth <= length.  Contact: pos = start + depth * u, normal = n / |n| (dSafeNormalize3), pointing back towards the
+// start.  Our reading is that dCollideRTL forms the reversed cross product and dCollide flips it again when it swaps
+// (trimesh, ray) into (ray, trimesh); ODE is an absent submodule of the reference, so this is PARITY UNPINNED.
+//
+// Ties: the smallest depth, then bodies before statics, then the lower static index, then the lower triangle index of
+// the mesh.  The walk prunes with the best depth so far inclusively (the ray's length while there is none), enters the
+// nearer child first, and takes the minimum of (depth, key, triangle), which does not depend on the order the leaves
+// are reached in.
+constexpr uint32_t NO_SLOT = 0xffffffffu;
+
+struct Shear {
+    int kx, ky, kz;
+    double Sx, Sy, Sz;
+    double inv[3];
+};
+
+__device__ __forceinline__ double pick(const double (&v)[3], int k) { return k == 0 ? v[0] : k == 1 ? v[1] : v[2]; }
+
+__device__ __forceinline__ void shear_of(const Ray &r, Shear &q)
+{
+    const double ax = fabs(r.u[0]), ay = fabs(r.u[1]), az = fabs(r.u[2]);
+    q.kz = ax >= ay ? (ax >= az ? 0 : 2) : (ay >= az ? 1 : 2);
+    q.kx = q.kz == 2 ? 0 : q.kz + 1;
+    q.ky = q.kx == 2 ? 0 : q.kx + 1;
+    const double uz = pick(r.u, q.kz);
+    if (uz < 0) { const int t = q.kx; q.kx = q.ky; q.ky = t; }                 // keeps the winding
+    q.Sx = pick(r.u, q.kx) / uz;
+    q.Sy = pick(r.u, q.ky) / uz;
+    q.Sz = 1.0 / uz;
+    for (int a = 0; a < 3; a++) q.inv[a] = r.u[a] == 0 ? 0.0 : 1.0 / r.u[a];             // 0: see box_hit
+}
+
+// where the segment [0, tmax] enters a float box, conservatively: a box holding a hit point at t <= tmax passes.  An axis
+// the ray does not move along is a containment test (a start on the slab's face is inside it)
+__device__ __forceinline__ bool box_hit(const Ray &r, const Shear &q, const float *b, double tmax, double &tn)
+{
+    double lo = 0.0, hi = INFINITY;
+    for (int a = 0; a < 3; a++) {
+        const double ta = ((double)b[a] - r.s[a]) * q.inv[a], tb = ((double)b[3 + a] - r.s[a]) * q.inv[a];
+        const bool in = (double)b[a] <= r.s[a] && r.s[a] <= (double)b[3 + a];
+        const bool flat = r.u[a] == 0;
+        lo = fmax(lo, flat ? (in ? -INFINITY : INFINITY) : fmin(ta, tb));
+        hi = fmin(hi, flat ? (in ? INFINITY : -INFINITY) : fmax(ta, tb));
+    }
+    tn = lo;
+    return lo * (1.0 - 0x1p-48) <= fmin(hi * (1.0 + 0x1p-48), tmax);
+}
+
+struct MeshBest { double t; uint32_t key, tri, slot; };
+
+__device__ __forceinline__ void test_tri(const MeshSet &m, const Ray &r, const Shear &q, uint32_t slot, uint32_t skip_key,
+                                         MeshBest &b)
+{
+    const uint2 kt = m.key[slot];
+    const uint32_t key = KEY_STATIC | kt.x;
+    if (key == skip_key) return;
+    const double *v = m.tri + 9 * (size_t)slot;
+    const double A[3] = { v[0] - r.s[0], v[1] - r.s[1], v[2] - r.s[2] };
+    const double B[3] = { v[3] - r.s[0], v[4] - r.s[1], v[5] - r.s[2] };
+    const double C[3] = { v[6] - r.s[0], v[7] - r.s[1], v[8] - r.s[2] };
+    const double Az = pick(A, q.kz), Bz = pick(B, q.kz), Cz = pick(C, q.kz);
+    const double Ax = pick(A, q.kx) - q.Sx * Az, Ay = pick(A, q.ky) - q.Sy * Az;
+    const double Bx = pick(B, q.kx) - q.Sx * Bz, By = pick(B, q.ky) - q.Sy * Bz;
+    const double Cx = pick(C, q.kx) - q.Sx * Cz, Cy = pick(C, q.ky) - q.Sy * Cz;
+    const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    if (!(U >= 0 && V >= 0 && W >= 0)) return;                              // outside, or a back face
+    const double det = U + V + W;
+    if (!(det > 0)) return;                                                   // edge-on or parallel
+    const double T = U * (q.Sz * Az) + V * (q.Sz * Bz) + W * (q.Sz * Cz);
+    const double t = T / det;
+    if (!(t >= 0 && t <= r.len)) return;
+    if (!(t < b.t || (t == b.t && (key < b.key || (key == b.key && kt.y < b.tri))))) return;
+    double n[3];
+    phd::tri_normal(v, n);
+    if (n[0] == 0 && n[1] == 0 && n[2] == 0) return;                          // zero area: never a hit
+    b.t = t; b.key = key; b.tri = kt.y; b.slot = slot;
+}
+
+// Cast rays: ray / skip / dist / hit / contact / flags as clapgpu_ray_cast.  Ground rays (ray == NULL): the rays of
+// clapgpu_bodies_ground_collide, and the decision on the merged hit.
+struct MeshPass {
+    uint32_t n;
+    const double *ray;                   // cast rays [n][8]; NULL: ground rays
+    const int32_t *skip;
+    double *dist, *contact;
+    int32_t *hit;
+    uint32_t *flags;
+    const double *other;                 // [n] first entry into an OTHER static without a mesh (first pass)
+    // ground rays
+    uint32_t n_bodies;
+    const double *pos, *yoffset, *ray_off;
+    const uint32_t *body;
+    const uint8_t *grounded;
+    uint8_t *grounded_out;
+    float *normal;
+    uint32_t *moved;
+};
+
+template <bool GROUND>
+__global__ __launch_bounds__(RT)
+void k_ray_trimesh(MeshSet m, MeshPass p)
+{
+    __shared__ uint32_t stk[TM_STACK * RT];
+    const uint32_t j = blockIdx.x * RT + threadIdx.x;
+    if (j >= p.n) return;
+    Ray r;
+    double ray_len = 0;
+    uint32_t i = 0, skip_key;
+    if (GROUND) {
+        i = p.body[j];
+        if (i >= p.n_bodies || (p.flags[j] & CLAPGPU_RAY_INVALID)) return;   // decided by the first pass
+        ground_ray(p.pos, p.yoffset, i, p.ray_off[j], r, ray_len);
+        skip_key = i;
+    } else {
+        if (!make_ray(p.ray + 8 * (size_t)j, r)) return;
+        skip_key = skip_key_of(p.skip ? p.skip[j] : -1);
+    }
+    MeshBest b;
+    b.key = key_of(p.hit[j]);
+    b.t = b.key == KEY_NONE ? r.len : p.dist[j];        // the walk stays within the segment (KEY_NONE: t == len still wins)
+    b.tri = 0;
+    b.slot = NO_SLOT;
+    Shear q;
+    shear_of(r, q);
+    bvh_walk(m, stk + threadIdx.x,
+             [&](const float *box, double &tn) { return box_hit(r, q, box, b.t, tn); },   // b.t tightens as leaves are visited
+             [&](uint32_t slot) { test_tri(m, r, q, slot, skip_key, b); });
+    const bool won = b.slot != NO_SLOT;
+    double nrm[3] = { 0, 0, 0 };
+    if (won) {
+        phd::tri_normal(m.tri + 9 * (size_t)b.slot, nrm);
+        phd::safe_normalize3(nrm);
+    }
+    const uint32_t f = p.other ? unresolved(p.other[j], r.len, b.key, b.t) : 0u;
+    if (GROUND) {
+        ground_decide(j, i, ray_len, b.key, b.t, nrm, won, f, p.grounded, p.grounded_out, p.normal, p.dist, p.hit,
+                      p.flags, p.moved);
+    } else {
+        if (won) {
+            p.hit[j] = hit_of(b.key);
+            p.dist[j] = b.t;
+            if (p.contact)
+                for (int a = 0; a < 3; a++) {
+                    p.contact[6 * (size_t)j + a] = r.s[a] + b.t * r.u[a];
+                    p.contact[6 * (size_t)j + 3 + a] = nrm[a];
+                }
+        }
+        if (p.flags) p.flags[j] = f;
+    }
+}
+
 } // namespace clapgpu
 
 using namespace clapgpu;
+
+// what both passes of an entry point read: the geom sets, the statics the mesh pass owns, and bp's grid when it is
+// indexed over these bodies (their boxes body_aabb, or NULL) and statics
+static int cast_scene(CastK &k, clapgpu_bp *bp, const clapgpu_geoms *bodies, const double *body_aabb,
+                      const clapgpu_geoms *statics, const clapgpu_trimesh *meshes)
+{
+    memset(&k, 0, sizeof(k));
+    k.bodies = geoms_k(bodies); k.statics = geoms_k(statics);
+    k.meshed = meshes ? trimesh_set(meshes).static_mesh : nullptr;
+    if (bp) {
+        if (!clapgpu_bp_grid_view(bp, bodies->n, body_aabb, &k.g) || k.g.n_static != statics->n)
+            return CLAPGPU_ERR_INVALID_ARGUMENTS;                           // not indexed over these bodies and statics
+        k.grid = true;
+    }
+    return CLAPGPU_OK;
+}
 
 // scratch for `other` between the passes: stream-ordered, freed behind the mesh pass
 static int mesh_scratch(hipStream_t s, const clapgpu_trimesh *meshes, uint32_t n, double **other)
@@ -468,25 +731,30 @@ static int free_scratch(hipStream_t s, double *other, int rc)
     return rc;
 }
 
+// the mesh pass over p.n > 0 rays
+static int mesh_pass(hipStream_t s, const clapgpu_trimesh *meshes, const MeshPass &p)
+{
+    const MeshSet m = trimesh_set(meshes);
+    const dim3 grid((p.n + RT - 1) / RT);
+    if (p.ray) hipLaunchKernelGGL(k_ray_trimesh<false>, grid, dim3(RT), 0, s, m, p);
+    else hipLaunchKernelGGL(k_ray_trimesh<true>, grid, dim3(RT), 0, s, m, p);
+    CLAPGPU_LAUNCH_CHECK("k_ray_trimesh");
+    return CLAPGPU_OK;
+}
+
 extern "C" int clapgpu_ray_cast_meshes(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
                                        const clapgpu_trimesh *meshes, uint32_t n_rays, const double *ray, const int32_t *skip,
                                        double *dist, int32_t *hit, double *contact, uint32_t *flags)
 {
     if (!bodies || !statics || (n_rays && (!ray || !dist || !hit))) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (meshes && trimesh_n_statics(meshes) != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;   // built for other statics
+    if (meshes && trimesh_set(meshes).n_statics != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;   // built for other statics
     CastK k;
-    memset(&k, 0, sizeof(k));
-    k.bodies = geoms_k(bodies); k.statics = geoms_k(statics);
-    k.meshed = meshes ? trimesh_static_mesh(meshes) : nullptr;
-    if (bp) {
-        if (!clapgpu_bp_grid_view(bp, bodies->n, nullptr, &k.g) || k.g.n_static != statics->n)
-            return CLAPGPU_ERR_INVALID_ARGUMENTS;                           // not indexed over these bodies and statics
-        k.grid = true;
-    }
+    int rc = cast_scene(k, bp, bodies, nullptr, statics, meshes);
+    if (rc) return rc;
     if (n_rays == 0) return CLAPGPU_OK;
     hipStream_t s = as_stream(stream);
     double *other;
-    int rc = mesh_scratch(s, flags ? meshes : nullptr, n_rays, &other);     // no flags asked for: `other` is not needed
+    rc = mesh_scratch(s, flags ? meshes : nullptr, n_rays, &other);         // no flags asked for: `other` is not needed
     if (rc) return rc;
     hipLaunchKernelGGL(k_ray_cast, dim3((n_rays + RB / WAVE - 1) / (RB / WAVE)), dim3(RB), 0, s, k, n_rays, ray, skip, dist, hit,
                        contact, flags, other);
@@ -496,7 +764,7 @@ extern "C" int clapgpu_ray_cast_meshes(void *stream, clapgpu_bp *bp, const clapg
         MeshPass p;
         memset(&p, 0, sizeof(p));
         p.n = n_rays; p.ray = ray; p.skip = skip; p.dist = dist; p.contact = contact; p.hit = hit; p.flags = flags; p.other = other;
-        rc = trimesh_pass(s, meshes, p);
+        rc = mesh_pass(s, meshes, p);
     }
     return free_scratch(s, other, rc);
 }
@@ -518,25 +786,19 @@ extern "C" int clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (n && (!body || !ray_off || !grounded || !grounded_out || !normal || !dist || !hit || !flags || !scratch))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (meshes && trimesh_n_statics(meshes) != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (meshes && trimesh_set(meshes).n_statics != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     clapgpu_geoms g;                                                         // the bodies' geoms, as PhysWorld.body_geoms
     memset(&g, 0, sizeof(g));
     g.n = b->n; g.pos = b->pos; g.axis = b->axis; g.radius = b->radius; g.length = b->length; g.records = b->geom_records;
     if (b->length && !b->axis && !b->geom_records) return CLAPGPU_ERR_INVALID_ARGUMENTS;   // capsules need their axis
     CastK k;
-    memset(&k, 0, sizeof(k));
-    k.bodies = geoms_k(&g); k.statics = geoms_k(statics);
-    k.meshed = meshes ? trimesh_static_mesh(meshes) : nullptr;
-    if (bp) {
-        if (!clapgpu_bp_grid_view(bp, b->n, b->aabb, &k.g) || k.g.n_static != statics->n)
-            return CLAPGPU_ERR_INVALID_ARGUMENTS;
-        k.grid = true;
-    }
+    int rc = cast_scene(k, bp, &g, b->aabb, statics, meshes);
+    if (rc) return rc;
     if (n == 0) return CLAPGPU_OK;
     hipStream_t s = as_stream(stream);
     CLAPGPU_HIP(hipMemsetAsync(scratch, 0, (size_t)(b->n ? b->n : 1) * sizeof(uint32_t), s));
     double *other;
-    int rc = mesh_scratch(s, meshes, n, &other);
+    rc = mesh_scratch(s, meshes, n, &other);
     if (rc) return rc;
     hipLaunchKernelGGL(k_ground_rays, dim3((n + RB / WAVE - 1) / (RB / WAVE)), dim3(RB), 0, s, k, n, b->pos, b->yoffset, body,
                        ray_off, grounded, grounded_out, normal, dist, hit, flags, scratch, other);
@@ -548,7 +810,7 @@ extern "C" int clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp
         p.n = n; p.dist = dist; p.hit = hit; p.flags = flags; p.other = other;
         p.n_bodies = b->n; p.pos = b->pos; p.yoffset = b->yoffset; p.ray_off = ray_off; p.body = body; p.grounded = grounded;
         p.grounded_out = grounded_out; p.normal = normal; p.moved = scratch;
-        rc = trimesh_pass(s, meshes, p);
+        rc = mesh_pass(s, meshes, p);
     }
     rc = free_scratch(s, other, rc);
     if (rc) return rc;

@@ -1,5 +1,6 @@
 // tricontact_dev.h -- a sphere or capsule against one static triangle, shared by the mesh contact pass and the capsule
-// sweep against meshes (contacts.hip).  fp64, no FMA contraction (the Makefile builds with -ffp-contract=off).
+// sweep against meshes (contacts.hip), and the triangle normal every mesh kernel uses (tri_normal; rays.hip too).
+// fp64, no FMA contraction (the Makefile builds with -ffp-contract=off).
 //
 // The body geom is a segment a, b with radius r (a sphere: a == b); the triangle is (v0, v1, v2) as the mesh set bakes
 // it (trimesh.hip).  This is the project's own contract: ODE's trimesh colliders (dCollideSTL / dCollideCCTL, OPCODE)
@@ -25,6 +26,16 @@ PHD void cross3(const double (&x)[3], const double (&y)[3], double (&o)[3])
     o[0] = x[1] * y[2] - x[2] * y[1];
     o[1] = x[2] * y[0] - x[0] * y[2];
     o[2] = x[0] * y[1] - x[1] * y[0];
+}
+
+// n = (v1 - v0) x (v2 - v0) of a baked triangle v[9], not normalised: the one normal of the mesh rays (rays.hip) and of
+// the rule above
+PHD void tri_normal(const double *v, double (&n)[3])
+{
+    double e1[3], e2[3];
+    sub3(v + 3, v, e1);
+    sub3(v + 6, v, e2);
+    cross3(e1, e2, n);
 }
 
 // ((v_k+1 - v_k) x (x - v_k)) . n >= 0 for every edge: x (anywhere along n) projects into the closed triangle
@@ -87,10 +98,8 @@ PHD void closest_to_edge(const double (&a)[3], const double (&b)[3], bool point,
 // the rule above: 0, 1 or 2 contacts (c0, c1)
 PHD int collide_segment_triangle(const double (&a)[3], const double (&b)[3], double r, const double *v, CGeom &c0, CGeom &c1)
 {
-    double e1[3], e2[3], n[3];
-    sub3(v + 3, v, e1);
-    sub3(v + 6, v, e2);
-    cross3(e1, e2, n);
+    double n[3];
+    tri_normal(v, n);
     if (n[0] == 0 && n[1] == 0 && n[2] == 0) return 0;
     const double nl = sqrt(dot3(n, n));
     const double nh[3] = { n[0] / nl, n[1] / nl, n[2] / nl };

@@ -1,4 +1,6 @@
-// trimesh.hip -- the triangle meshes of static trimesh geoms on the device, and ray casts against them, for gfx950:
+// trimesh.hip -- the triangle meshes of static trimesh geoms on the device, for gfx950: the mesh set, its bake and its
+// BVH.  The kernels that read the set are elsewhere: ray casts in rays.hip (k_ray_trimesh), contacts and the capsule
+// sweep in contacts.hip, all through trimesh_dev.h (the node layout, the MeshSet view, the walk).
 //
 //   k_tm_check      the index check of clapgpu_trimesh_create: every vertex index below its mesh's vertex count, every
 //                   static at most once and in range; fills static -> mesh and triangle -> mesh
@@ -8,57 +10,26 @@
 //   k_tm_gather     the triangles and their (static, triangle of its mesh) in leaf order
 //   k_tm_hierarchy  Karras 2012: the binary radix tree over the sorted keys (all distinct: the index breaks ties)
 //   k_tm_boxes      bottom-up: each node's two child boxes (float, rounded outward) and its subtree height
-//   k_ray_trimesh   one lane per ray: the BVH walk and the watertight ray-triangle test, merged with the best hit the
-//                   pass over bodies and statics (rays.hip) found
 //
 // The mesh: model3d.collision_vx scaled by the entity's scale in float the way mat4x4_scale_aniso + mat4x4_mul_vec4
 // compute it (each row starts from 0.f and adds the products, so -0 becomes +0; w == 1), widened to double, then
 // R * v + pos in fp64 with R = dQtoR(w, x, y, z) of the entity quaternion and pos the entity position (yoffset is 0 for a
 // trimesh).  Triangles are the u16 index triples in order, winding kept (physics.c:898-903).
 //
-// The test: ODE's dCollideRTL runs OPCODE's float ray-triangle test with ClosestHit = 1, BackfaceCull = 1 (physics.c:485-487).
-// Here the triangles are tested in fp64 with the watertight test of Woop, Benthin and Wald (JCGT 2013): the ray's dominant
-// axis is z, the other two are sheared onto it once per ray, and the three edge functions U, V, W of the projected
-// triangle decide.  A shared edge gets the same edge function with opposite sign in both triangles (the products
-// commute and the difference is negated exactly; no FMA contraction), so a ray through an edge or a vertex of front faces
-// hits at least one of them: no ray falls through the terrain.  Front face: U, V, W >= 0 and det = U + V + W > 0, which is
-// u . n < 0 for n = (v1 - v0) x (v2 - v0).  n == 0 never hits (ODE's dSafeNormalize3 fails there); a hit needs
-// 0 <= depth <= length.  Contact: pos = start + depth * u, normal = n / |n| (dSafeNormalize3), pointing back towards the
-// start.  Our reading is that dCollideRTL forms the reversed cross product and dCollide flips it again when it swaps
-// (trimesh, ray) into (ray, trimesh); ODE is an absent submodule of the reference, so this is PARITY UNPINNED.
-//
-// Ties: the smallest depth, then bodies before statics, then the lower static index, then the lower triangle index of
-// the mesh.  The walk prunes with the best depth so far inclusively (the ray's length while there is none) and takes
-// the minimum of (depth, key, triangle), which does not depend on the order the leaves are reached in.
-//
-// Tree: one BVH2 over every triangle of every mesh.  A node is 64 B: both children's boxes (float, min xyz / max xyz,
-// rounded outward from the fp64 triangles so that a box never excludes a point of a triangle it holds) and both links
-// (bit 31: a leaf = one triangle in leaf order).  The keys are distinct and the Morton part leaves the top two bits
-// clear, so the prefix length grows by at least one per level: the height is at most 62 (see clapgpu_trimesh_status).
-// The walk's stack is in LDS, [64 entries][64 lanes] of u32 (16 KiB per one-wave workgroup): a register array indexed by
-// a per-lane stack pointer would live in scratch memory, and the deep trees of degenerate meshes need all 64.
+// Tree: one BVH2 over every triangle of every mesh, nodes as trimesh_dev.h lays them out.  The keys are distinct and the
+// Morton part leaves the top two bits clear, so the prefix length grows by at least one per level: the height is at most
+// 62 (see clapgpu_trimesh_status), within the walk's stack.
 #include <string.h>
 #include <stdlib.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include "common.h"
 #include "phys_dev.h"
 #include "bp_grid.h"
-#include "rays_dev.h"
 #include "trimesh_dev.h"
 
 namespace clapgpu {
 
 constexpr int TB = 256;                                 // set-up kernels
-constexpr int RT = 64;                                  // k_ray_trimesh: one wave per workgroup
-constexpr int STACK = 64;
-constexpr uint32_t LEAF = 0x80000000u, NO_SLOT = 0xffffffffu;
-
-struct MeshK {
-    const Node *nodes;
-    const double *tri;                                  // [T][9] in leaf order
-    const uint2 *key;                                   // [T]: (static, triangle of its mesh) in leaf order
-    uint32_t n_tris;
-};
 
 } // namespace clapgpu
 
@@ -237,13 +208,13 @@ void k_tm_hierarchy(uint32_t T, const uint64_t *k, Node *nodes, uint32_t *parent
     } while (t > 1);
     const int64_t g = i + s * d + (d < 0 ? -1 : 0);
     const int64_t lo = i < j ? i : j, hi = i < j ? j : i;
-    const uint32_t c0 = lo == g ? LEAF | (uint32_t)g : (uint32_t)g;
-    const uint32_t c1 = hi == g + 1 ? LEAF | (uint32_t)(g + 1) : (uint32_t)(g + 1);
+    const uint32_t c0 = lo == g ? TM_LEAF | (uint32_t)g : (uint32_t)g;
+    const uint32_t c1 = hi == g + 1 ? TM_LEAF | (uint32_t)(g + 1) : (uint32_t)(g + 1);
     nodes[i].child[0] = c0;
     nodes[i].child[1] = c1;
     nodes[i].pad[0] = nodes[i].pad[1] = 0;
-    parent[(c0 & LEAF) ? (n - 1) + (c0 & ~LEAF) : c0] = (uint32_t)i;
-    parent[(c1 & LEAF) ? (n - 1) + (c1 & ~LEAF) : c1] = (uint32_t)i;
+    parent[(c0 & TM_LEAF) ? (n - 1) + (c0 & ~TM_LEAF) : c0] = (uint32_t)i;
+    parent[(c1 & TM_LEAF) ? (n - 1) + (c1 & ~TM_LEAF) : c1] = (uint32_t)i;
 }
 
 __device__ __forceinline__ float round_down(double d)
@@ -280,12 +251,12 @@ void k_tm_boxes(uint32_t T, const double *stri, Node *nodes, const uint32_t *par
     }
     if (T == 1) {                                       // a root holding the one leaf twice
         for (int a = 0; a < 6; a++) { nodes[0].box[a] = b[a]; nodes[0].box[6 + a] = b[a]; }
-        nodes[0].child[0] = nodes[0].child[1] = LEAF;
+        nodes[0].child[0] = nodes[0].child[1] = TM_LEAF;
         nodes[0].pad[0] = nodes[0].pad[1] = 0;
         ctl[1] = 1;
         return;
     }
-    uint32_t x = LEAF | i, h = 0, p = parent[(T - 1) + i];
+    uint32_t x = TM_LEAF | i, h = 0, p = parent[(T - 1) + i];
     for (;;) {
         Node &n = nodes[p];
         const int side = n.child[0] == x ? 0 : 1;
@@ -297,7 +268,7 @@ void k_tm_boxes(uint32_t T, const double *stri, Node *nodes, const uint32_t *par
             b[a] = fminf(b[a], load_agent(&n.box[6 * (1 - side) + a]));
             b[3 + a] = fmaxf(b[3 + a], load_agent(&n.box[6 * (1 - side) + 3 + a]));
         }
-        const uint32_t hs = (sib & LEAF) ? 0u : __hip_atomic_load(&height[sib], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t hs = (sib & TM_LEAF) ? 0u : __hip_atomic_load(&height[sib], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         h = 1 + (h > hs ? h : hs);
         __hip_atomic_store(&height[p], h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (p == 0) { ctl[1] = h; return; }
@@ -305,180 +276,13 @@ void k_tm_boxes(uint32_t T, const double *stri, Node *nodes, const uint32_t *par
         p = parent[p];
     }
 }
-
-// ------------------------------------------------------------------------------------------------- ray pass
-struct Shear {
-    int kx, ky, kz;
-    double Sx, Sy, Sz;
-    double inv[3];
-};
-
-__device__ __forceinline__ double pick(const double (&v)[3], int k) { return k == 0 ? v[0] : k == 1 ? v[1] : v[2]; }
-
-__device__ __forceinline__ void shear_of(const Ray &r, Shear &q)
-{
-    const double ax = fabs(r.u[0]), ay = fabs(r.u[1]), az = fabs(r.u[2]);
-    q.kz = ax >= ay ? (ax >= az ? 0 : 2) : (ay >= az ? 1 : 2);
-    q.kx = q.kz == 2 ? 0 : q.kz + 1;
-    q.ky = q.kx == 2 ? 0 : q.kx + 1;
-    const double uz = pick(r.u, q.kz);
-    if (uz < 0) { const int t = q.kx; q.kx = q.ky; q.ky = t; }                 // keeps the winding
-    q.Sx = pick(r.u, q.kx) / uz;
-    q.Sy = pick(r.u, q.ky) / uz;
-    q.Sz = 1.0 / uz;
-    for (int a = 0; a < 3; a++) q.inv[a] = r.u[a] == 0 ? 0.0 : 1.0 / r.u[a];             // 0: see box_hit
-}
-
-// where the segment [0, tmax] enters a float box, conservatively: a box holding a hit point at t <= tmax passes.  An axis
-// the ray does not move along is a containment test (a start on the slab's face is inside it)
-__device__ __forceinline__ bool box_hit(const Ray &r, const Shear &q, const float *b, double tmax, double &tn)
-{
-    double lo = 0.0, hi = INFINITY;
-    for (int a = 0; a < 3; a++) {
-        const double ta = ((double)b[a] - r.s[a]) * q.inv[a], tb = ((double)b[3 + a] - r.s[a]) * q.inv[a];
-        const bool in = (double)b[a] <= r.s[a] && r.s[a] <= (double)b[3 + a];
-        const bool flat = r.u[a] == 0;
-        lo = fmax(lo, flat ? (in ? -INFINITY : INFINITY) : fmin(ta, tb));
-        hi = fmin(hi, flat ? (in ? INFINITY : -INFINITY) : fmax(ta, tb));
-    }
-    tn = lo;
-    return lo * (1.0 - 0x1p-48) <= fmin(hi * (1.0 + 0x1p-48), tmax);
-}
-
-struct MeshBest { double t; uint32_t key, tri, slot; };
-
-__device__ __forceinline__ void test_tri(const MeshK &m, const Ray &r, const Shear &q, uint32_t slot, uint32_t skip_key,
-                                         MeshBest &b)
-{
-    const uint2 kt = m.key[slot];
-    const uint32_t key = KEY_STATIC | kt.x;
-    if (key == skip_key) return;
-    const double *v = m.tri + 9 * (size_t)slot;
-    const double A[3] = { v[0] - r.s[0], v[1] - r.s[1], v[2] - r.s[2] };
-    const double B[3] = { v[3] - r.s[0], v[4] - r.s[1], v[5] - r.s[2] };
-    const double C[3] = { v[6] - r.s[0], v[7] - r.s[1], v[8] - r.s[2] };
-    const double Az = pick(A, q.kz), Bz = pick(B, q.kz), Cz = pick(C, q.kz);
-    const double Ax = pick(A, q.kx) - q.Sx * Az, Ay = pick(A, q.ky) - q.Sy * Az;
-    const double Bx = pick(B, q.kx) - q.Sx * Bz, By = pick(B, q.ky) - q.Sy * Bz;
-    const double Cx = pick(C, q.kx) - q.Sx * Cz, Cy = pick(C, q.ky) - q.Sy * Cz;
-    const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
-    if (!(U >= 0 && V >= 0 && W >= 0)) return;                              // outside, or a back face
-    const double det = U + V + W;
-    if (!(det > 0)) return;                                                   // edge-on or parallel
-    const double T = U * (q.Sz * Az) + V * (q.Sz * Bz) + W * (q.Sz * Cz);
-    const double t = T / det;
-    if (!(t >= 0 && t <= r.len)) return;
-    if (!(t < b.t || (t == b.t && (key < b.key || (key == b.key && kt.y < b.tri))))) return;
-    const double e1[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, e2[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
-    const double n[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
-    if (n[0] == 0 && n[1] == 0 && n[2] == 0) return;                          // zero area: never a hit
-    b.t = t; b.key = key; b.tri = kt.y; b.slot = slot;
-}
-
-__device__ void trace(const MeshK &m, const Ray &r, uint32_t skip_key, MeshBest &b, uint32_t *stk)
-{
-    if (m.n_tris == 0) return;
-    Shear q;
-    shear_of(r, q);
-    uint32_t node = 0;
-    int sp = 0;
-    for (;;) {
-        const float4 *np = reinterpret_cast<const float4 *>(m.nodes + node);
-        const float4 f0 = np[0], f1 = np[1], f2 = np[2];
-        const uint4 c = reinterpret_cast<const uint4 *>(np)[3];
-        const float bl[6] = { f0.x, f0.y, f0.z, f0.w, f1.x, f1.y }, br[6] = { f1.z, f1.w, f2.x, f2.y, f2.z, f2.w };
-        double tl, tr;
-        bool hl = box_hit(r, q, bl, b.t, tl), hr = box_hit(r, q, br, b.t, tr);
-        if (hl && (c.x & LEAF)) { test_tri(m, r, q, c.x & ~LEAF, skip_key, b); hl = false; }
-        if (hr && (c.y & LEAF)) { test_tri(m, r, q, c.y & ~LEAF, skip_key, b); hr = false; }
-        if (hl && hr) {
-            const bool lfirst = tl <= tr;
-            if (sp < STACK) stk[sp++ * RT] = lfirst ? c.y : c.x;
-            node = lfirst ? c.x : c.y;
-        } else if (hl) {
-            node = c.x;
-        } else if (hr) {
-            node = c.y;
-        } else {
-            if (sp == 0) break;
-            node = stk[--sp * RT];
-        }
-    }
-}
-
-template <bool GROUND>
-__global__ __launch_bounds__(RT)
-void k_ray_trimesh(MeshK m, MeshPass p)
-{
-    __shared__ uint32_t stk[STACK * RT];
-    const uint32_t j = blockIdx.x * RT + threadIdx.x;
-    if (j >= p.n) return;
-    Ray r;
-    double ray_len = 0;
-    uint32_t i = 0, skip_key;
-    if (GROUND) {
-        i = p.body[j];
-        if (i >= p.n_bodies || (p.flags[j] & CLAPGPU_RAY_INVALID)) return;   // decided by rays.hip
-        ground_ray(p.pos, p.yoffset, i, p.ray_off[j], r, ray_len);
-        skip_key = i;
-    } else {
-        if (!make_ray(p.ray + 8 * (size_t)j, r)) return;
-        skip_key = skip_key_of(p.skip ? p.skip[j] : -1);
-    }
-    MeshBest b;
-    b.key = key_of(p.hit[j]);
-    b.t = b.key == KEY_NONE ? r.len : p.dist[j];        // the walk stays within the segment (KEY_NONE: t == len still wins)
-    b.tri = 0;
-    b.slot = NO_SLOT;
-    trace(m, r, skip_key, b, stk + threadIdx.x);
-    const bool won = b.slot != NO_SLOT;
-    double nrm[3] = { 0, 0, 0 };
-    if (won) {
-        const double *v = m.tri + 9 * (size_t)b.slot;
-        const double e1[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, e2[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
-        nrm[0] = e1[1] * e2[2] - e1[2] * e2[1];
-        nrm[1] = e1[2] * e2[0] - e1[0] * e2[2];
-        nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
-        phd::safe_normalize3(nrm);
-    }
-    const uint32_t f = p.other ? unresolved(p.other[j], r.len, b.key, b.t) : 0u;
-    if (GROUND) {
-        ground_decide(j, i, ray_len, b.key, b.t, nrm, won, f, p.grounded, p.grounded_out, p.normal, p.dist, p.hit,
-                      p.flags, p.moved);
-    } else {
-        if (won) {
-            p.hit[j] = hit_of(b.key);
-            p.dist[j] = b.t;
-            if (p.contact)
-                for (int a = 0; a < 3; a++) {
-                    p.contact[6 * (size_t)j + a] = r.s[a] + b.t * r.u[a];
-                    p.contact[6 * (size_t)j + 3 + a] = nrm[a];
-                }
-        }
-        if (p.flags) p.flags[j] = f;
-    }
-}
-
-const int32_t *trimesh_static_mesh(const clapgpu_trimesh *m) { return m->static_mesh; }
-uint32_t trimesh_n_statics(const clapgpu_trimesh *m) { return m->n_statics; }
-
+// the one place a kernel's view of the set is filled
 MeshSet trimesh_set(const clapgpu_trimesh *m)
 {
     MeshSet s;
     s.nodes = m->nodes; s.tri = m->stri; s.key = m->skey; s.static_mesh = m->static_mesh;
     s.n_tris = m->n_tris; s.n_statics = m->n_statics;
     return s;
-}
-
-int trimesh_pass(hipStream_t s, const clapgpu_trimesh *tm, const MeshPass &p)
-{
-    if (p.n == 0) return CLAPGPU_OK;
-    MeshK m;
-    m.nodes = tm->nodes; m.tri = tm->stri; m.key = tm->skey; m.n_tris = tm->n_tris;
-    if (p.ray) hipLaunchKernelGGL(k_ray_trimesh<false>, dim3((p.n + RT - 1) / RT), dim3(RT), 0, s, m, p);
-    else hipLaunchKernelGGL(k_ray_trimesh<true>, dim3((p.n + RT - 1) / RT), dim3(RT), 0, s, m, p);
-    CLAPGPU_LAUNCH_CHECK("k_ray_trimesh");
-    return CLAPGPU_OK;
 }
 
 // bake + tree from the current poses: the one rebuild path of create and pose
@@ -560,7 +364,7 @@ extern "C" int clapgpu_trimesh_create(void *stream, clapgpu_trimesh **out, const
     m->n_vx = hf[M];
     m->n_tris = hf[2 * M + 1];
     free(hf);
-    if (!ok || m->n_tris >= LEAF) { clapgpu_trimesh_destroy(m); return CLAPGPU_ERR_INVALID_ARGUMENTS; }
+    if (!ok || m->n_tris >= TM_LEAF) { clapgpu_trimesh_destroy(m); return CLAPGPU_ERR_INVALID_ARGUMENTS; }
     const size_t V = m->n_vx, T = m->n_tris;
     TRY(dev_alloc(m->static_index, M)); TRY(dev_alloc(m->vx_first, M + 1)); TRY(dev_alloc(m->tri_first, M + 1));
     TRY(dev_alloc(m->tri_mesh, T)); TRY(dev_alloc(m->vx, 3 * V)); TRY(dev_alloc(m->scale, M)); TRY(dev_alloc(m->quat, 4 * M));

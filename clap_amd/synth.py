@@ -528,6 +528,78 @@ def static_boxes(n=64, box=64.0, seed=5):
     return out
 
 
+def geoms_of_aabbs(bb, kind):
+    """Static geoms that fill their AABBs: (pos, axis, radius, length) with the centre, the longest axis, the smallest
+    half extent as the radius and, for capsules (kind 1), the cylinder length that reaches both ends of that axis."""
+    n = len(bb)
+    c, h = (bb[:, 0::2] + bb[:, 1::2]) / 2, (bb[:, 1::2] - bb[:, 0::2]) / 2
+    big, r = np.argmax(h, 1), h.min(1)
+    axis = np.zeros((n, 3))
+    axis[np.arange(n), big] = 1.0
+    length = np.where(kind == 1, 2 * (h[np.arange(n), big] - r), 0.0)
+    return c, axis, r, length
+
+
+def terrain_y(x, z, y0=0.0, amp=1.0):
+    """The height of the rolling terrain of heightfield() over (x, z)."""
+    return y0 + amp * np.sin(x * 0.37) * np.cos(z * 0.29)
+
+
+def heightfield(nv, side, y0=0.0, amp=1.0, integer=False):
+    """A triangle mesh (vx [nv * nv, 3] float32, idx [T, 3] uint16) of nv x nv vertices over [0, side]^2 in x / z, front
+    faces up: terrain_y, or integer heights 0..3 (exact in every format)."""
+    g = np.linspace(0.0, side, nv)
+    x, z = np.meshgrid(g, g, indexing="ij")
+    y = ((x * 3 + z * 5) % 4) if integer else terrain_y(x, z, y0, amp)
+    vx = np.stack([x, y, z], -1).reshape(-1, 3).astype(np.float32)
+    i, j = np.meshgrid(np.arange(nv - 1), np.arange(nv - 1), indexing="ij")
+    v00, v10, v01, v11 = i * nv + j, (i + 1) * nv + j, i * nv + j + 1, (i + 1) * nv + j + 1
+    idx = np.stack([np.stack([v00, v01, v10], -1), np.stack([v10, v01, v11], -1)], 2).reshape(-1, 3)
+    return vx, idx.astype(np.uint16)
+
+
+def _faces_outward(v, idx):
+    """idx with every triangle of a mesh around the origin wound so that its front face looks away from it"""
+    n = np.cross(v[idx[:, 1]] - v[idx[:, 0]], v[idx[:, 2]] - v[idx[:, 0]])
+    flip = (n * v[idx].mean(1)).sum(1) < 0
+    idx[flip] = idx[flip][:, [0, 2, 1]]
+    return idx
+
+
+def box_mesh(h=0.5):
+    """a closed cube, outward front faces"""
+    v = np.array([[x, y, z] for x in (-h, h) for y in (-h, h) for z in (-h, h)], np.float32)
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    idx = np.array([t for a, b, c, d in quads for t in ((a, b, c), (a, c, d))], np.uint16)
+    return v, _faces_outward(v, idx)
+
+
+def icosphere(r=0.7, sub=1):
+    """an icosahedron subdivided `sub` times on the sphere of radius r, outward front faces"""
+    unit = lambda p: np.asarray(p, float) / np.linalg.norm(np.asarray(p, float), axis=-1, keepdims=True)
+    t = (1 + 5 ** 0.5) / 2
+    v = [[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t], [t, 0, -1], [t, 0, 1],
+         [-t, 0, -1], [-t, 0, 1]]
+    f = [[0, 11, 5], [0, 5, 1], [0, 1, 7], [0, 7, 10], [0, 10, 11], [1, 5, 9], [5, 11, 4], [11, 10, 2], [10, 7, 6], [7, 1, 8],
+         [3, 9, 4], [3, 4, 2], [3, 2, 6], [3, 6, 8], [3, 8, 9], [4, 9, 5], [2, 4, 11], [6, 2, 10], [8, 6, 7], [9, 8, 1]]
+    v = [list(unit(p)) for p in v]
+    for _ in range(sub):
+        nf, cache = [], {}
+
+        def mid(a, b):
+            k = (min(a, b), max(a, b))
+            if k not in cache:
+                v.append(list(unit((np.array(v[a]) + np.array(v[b])) / 2)))
+                cache[k] = len(v) - 1
+            return cache[k]
+        for a, b, c in f:
+            ab, bc, ca = mid(a, b), mid(b, c), mid(c, a)
+            nf += [[a, ab, ca], [b, bc, ab], [c, ca, bc], [ab, bc, ca]]
+        f = nf
+    v = np.array(v) * r
+    return v.astype(np.float32), _faces_outward(v, np.array(f, np.uint16))
+
+
 LIGHTS_MAX = 128            # shader_constants.h:8
 LIGHT_TILE = 64             # TILE_WIDTH, shader_constants.h:16 (light.c:210)
 

@@ -9,109 +9,22 @@ import pytest
 import torch
 
 from clap_amd import _lib, synth
+from clap_amd.synth import box_mesh, heightfield
 import meshcontactref as mc
+import meshscene
+from meshscene import C2, IDENT, rng
 import trimeshref as tr
 
 pytestmark = pytest.mark.gpu
 
-OTHER, BOX = _lib.GEOM_OTHER, _lib.GEOM_BOX
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-IDENT = [0.0, 0.0, 0.0, 1.0]
 TOL = 1e-9
-C2 = np.dtype([("pos", np.float64, 3), ("normal", np.float64, 3), ("depth", np.float64), ("mu", np.float64),
-               ("bounce", np.float64), ("bounce_vel", np.float64), ("soft_erp", np.float64), ("soft_cfm", np.float64),
-               ("mode", np.uint32), ("nc", np.uint32), ("pos2", np.float64, 3), ("normal2", np.float64, 3),
-               ("depth2", np.float64)])
 RAW = np.dtype([("b", np.uint8, 160)])
 
 
-def rng(seed):
-    return np.random.Generator(np.random.PCG64(seed))
-
-
-def heightfield(nv, side, amp=1.0):
-    g = np.linspace(0.0, side, nv)
-    x, z = np.meshgrid(g, g, indexing="ij")
-    y = amp * np.sin(x * 0.37) * np.cos(z * 0.29)
-    vx = np.stack([x, y, z], -1).reshape(-1, 3).astype(np.float32)
-    i, j = np.meshgrid(np.arange(nv - 1), np.arange(nv - 1), indexing="ij")
-    v00, v10, v01, v11 = i * nv + j, (i + 1) * nv + j, i * nv + j + 1, (i + 1) * nv + j + 1
-    idx = np.stack([np.stack([v00, v01, v10], -1), np.stack([v10, v01, v11], -1)], 2).reshape(-1, 3)
-    return vx, idx.astype(np.uint16)
-
-
-def box_mesh(h=0.5):
-    """a closed cube, outward front faces"""
-    v = np.array([[x, y, z] for x in (-h, h) for y in (-h, h) for z in (-h, h)], np.float32)
-    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
-    idx = np.array([t for a, b, c, d in quads for t in ((a, b, c), (a, c, d))], np.uint16)
-    n = np.cross(v[idx[:, 1]] - v[idx[:, 0]], v[idx[:, 2]] - v[idx[:, 0]])
-    flip = (n * v[idx].mean(1)).sum(1) < 0
-    idx[flip] = idx[flip][:, [0, 2, 1]]
-    return v, idx
-
-
-class Scene:
-    """A PhysWorld whose statics are `boxes` (BOX kind) then one OTHER static per mesh (its baked AABB, grown a little),
-    with the meshes set; bodies from `bodies` (synth dict)."""
-
-    def __init__(self, dev, bodies, meshes, boxes=(), material=None, static_material=None, cap=1 << 20):
-        from clap_amd import physics
-        self.meshes = meshes
-        self.tris = [tr.bake(*m) for m in meshes]
-        bb = np.asarray(list(boxes), float).reshape(-1, 6)
-        mbb = np.zeros((len(meshes), 6))
-        for k, t in enumerate(self.tris):
-            f = t.reshape(-1, 3)
-            mbb[k, 0::2], mbb[k, 1::2] = f.min(0) - 1e-6, f.max(0) + 1e-6
-        allbb = np.concatenate([bb, mbb])
-        kind = np.concatenate([np.full(len(bb), BOX, np.uint8), np.full(len(meshes), OTHER, np.uint8)])
-        self.base = len(bb)
-        self.w = w = physics.PhysWorld(bodies, allbb, pair_capacity=cap, static_pair_capacity=cap, device=dev)
-        c = (allbb[:, 0::2] + allbb[:, 1::2]) / 2
-        w.set_static_geoms(kind, c, np.tile([0, 0, 1.0], (len(allbb), 1)), np.zeros(len(allbb)), np.zeros(len(allbb)))
-        if material is not None:
-            w.set_materials(material)
-        if static_material is not None:
-            w.static_material = torch.from_numpy(np.ascontiguousarray(static_material, np.float64)).to(w.device)
-        self.mesh_static = self.base + np.arange(len(meshes))
-        if meshes:
-            w.set_static_meshes(self.mesh_static, [m[0] for m in meshes], [m[1] for m in meshes], [m[2] for m in meshes],
-                                [m[3] for m in meshes], [m[4] for m in meshes])
-        self.bodies = bodies
-
-    def run(self, capacity=None, flags=True):
-        w = self.w
-        w.bodies_aabb()
-        w.broadphase()
-        w.contacts_meshes(set_joint_flags=flags, capacity=capacity)
-        rec, ref, total, capped = w.download_mesh_contacts(C2)
-        return rec, ref, total, capped
-
-    def segments(self):
-        d = self.w.download()
-        L = self.bodies.get("length", np.zeros(self.w.n))
-        return [mc.segment_of(self.bodies["pos"][i], d["axis"][i], float(L[i])) for i in range(self.w.n)], d
-
-    def truth(self):
-        """[(pair, tri, contacts, margin)] in canonical order, capped pairs, the (pair, tri) near a margin"""
-        segs, d = self.segments()
-        pairs = d["static_pairs"]
-        out, capped, near = [], 0, set()
-        for p, (body, st) in enumerate(pairs):
-            k = int(st) - self.base
-            if k < 0:
-                continue
-            a, b = segs[body]
-            P = mc.Pair(a, b, float(self.bodies["radius"][body]), self.tris[k])
-            capped += P.capped
-            for t, cs, mg in P.kept:
-                out.append((p, t, cs, mg))
-            for t, _cs, mg in P.records:
-                if mg:
-                    near.add((p, t))
-            near.update((p, t) for t in P.near)
-        return out, capped, near, segs, pairs
+def Scene(dev, bodies, meshes, cap=1 << 20, **kw):
+    """meshscene.Scene as these tests build it: the meshes' boxes grown a little, both pair capacities `cap`"""
+    return meshscene.Scene(dev, bodies, meshes, cap=(cap, cap), grow=1e-6, **kw)
 
 
 def on_closest_set(pos, seg, depth, r, tri, tol):

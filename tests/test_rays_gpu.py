@@ -7,18 +7,12 @@ import numpy as np
 import pytest
 
 from clap_amd import _lib, synth
+from meshscene import far_body, fetch, rng, same_bits, unit
 import rayref
 
 pytestmark = pytest.mark.gpu
 
 SPHERE, CAPSULE, BOX, OTHER = _lib.GEOM_SPHERE, _lib.GEOM_CAPSULE, _lib.GEOM_BOX, _lib.GEOM_OTHER
-
-
-def far_body():
-    b = synth.sphere_bodies(1, box=1.0, seed=1)
-    b["pos"][0] = [-500.0, -500.0, -500.0]
-    b["lvel"][:] = 0
-    return b
 
 
 def static_world(geoms, cuda_device, bodies=None):
@@ -44,19 +38,6 @@ def static_world(geoms, cuda_device, bodies=None):
     w = physics.PhysWorld(bodies or far_body(), bb, device=cuda_device)
     w.set_static_geoms(kind, pos, axis, rad, length)
     return w
-
-
-def fetch(res):
-    return [t.cpu().numpy() for t in res]
-
-
-def rng(seed):
-    return np.random.Generator(np.random.PCG64(seed))
-
-
-def unit(v):
-    v = np.asarray(v, float)
-    return v / np.linalg.norm(v, axis=-1, keepdims=True)
 
 
 def fixture_rays(seed):
@@ -200,12 +181,7 @@ def grid_scene(cuda_device, oversized=False):
     kind = R.choice([SPHERE, CAPSULE, BOX, OTHER], ns, p=[0.3, 0.3, 0.3, 0.1]).astype(np.uint8)
     kind[0] = BOX
     kind[1] = OTHER
-    c, h = (bb[:, 0::2] + bb[:, 1::2]) / 2, (bb[:, 1::2] - bb[:, 0::2]) / 2
-    big = np.argmax(h, 1)
-    r = h.min(1)
-    axis = np.zeros((ns, 3))
-    axis[np.arange(ns), big] = 1.0
-    length = np.where(kind == CAPSULE, 2 * (h[np.arange(ns), big] - r), 0.0)
+    c, axis, r, length = synth.geoms_of_aabbs(bb, kind)
     w = physics.PhysWorld(b, bb, pair_capacity=4_000_000, static_pair_capacity=8_000_000, device=cuda_device)
     w.set_static_geoms(kind, c, axis, r, length)
     return w, b, bb, kind
@@ -234,11 +210,6 @@ def grid_rays(cell, n=65536, seed=9):
     d[5 * q + 90:5 * q + 100, 1] = np.nan                                    # NaN direction
     L[5 * q + 100:5 * q + 104] = -1.0
     return s, d, L
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def test_grid_equals_brute_force(cuda_device):

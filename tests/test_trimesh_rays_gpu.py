@@ -9,143 +9,20 @@ import numpy as np
 import pytest
 
 from clap_amd import _lib, synth
+from clap_amd.synth import box_mesh, heightfield, icosphere
+from meshscene import IDENT, Scene, far_body, fetch, rng, same_bits, unit
 import trimeshref as tr
 
 pytestmark = pytest.mark.gpu
 
 SPHERE, CAPSULE, BOX, OTHER = _lib.GEOM_SPHERE, _lib.GEOM_CAPSULE, _lib.GEOM_BOX, _lib.GEOM_OTHER
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-IDENT = [0.0, 0.0, 0.0, 1.0]
 WORST = {}
-
-
-def rng(seed):
-    return np.random.Generator(np.random.PCG64(seed))
-
-
-def fetch(res):
-    return [t.cpu().numpy() for t in res]
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def unit(v):
-    v = np.asarray(v, float)
-    return v / np.linalg.norm(v, axis=-1, keepdims=True)
-
-
-# ------------------------------------------------------------------------------------------- meshes
-def heightfield(nv, side, y0=0.0, amp=1.0, integer=False):
-    """nv x nv vertices over [0, side]^2 in x / z, front faces up"""
-    g = np.linspace(0.0, side, nv)
-    x, z = np.meshgrid(g, g, indexing="ij")
-    y = ((x * 3 + z * 5) % 4) if integer else y0 + amp * np.sin(x * 0.37) * np.cos(z * 0.29)
-    vx = np.stack([x, y, z], -1).reshape(-1, 3).astype(np.float32)
-    i, j = np.meshgrid(np.arange(nv - 1), np.arange(nv - 1), indexing="ij")
-    v00, v10, v01, v11 = i * nv + j, (i + 1) * nv + j, i * nv + j + 1, (i + 1) * nv + j + 1
-    idx = np.stack([np.stack([v00, v01, v10], -1), np.stack([v10, v01, v11], -1)], 2).reshape(-1, 3)
-    return vx, idx.astype(np.uint16)
-
-
-def box_mesh(h=0.5):
-    """a closed cube, outward front faces"""
-    v = np.array([[x, y, z] for x in (-h, h) for y in (-h, h) for z in (-h, h)], np.float32)
-    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
-    tris = []
-    for a, b, c, d in quads:
-        tris += [(a, b, c), (a, c, d)]
-    idx = np.array(tris, np.uint16)
-    c = v[idx].mean(1)
-    n = np.cross(v[idx[:, 1]] - v[idx[:, 0]], v[idx[:, 2]] - v[idx[:, 0]])
-    flip = (n * c).sum(1) < 0
-    idx[flip] = idx[flip][:, [0, 2, 1]]
-    return v, idx
-
-
-def icosphere(r=0.7, sub=1):
-    t = (1 + 5 ** 0.5) / 2
-    v = [[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t], [t, 0, -1], [t, 0, 1],
-         [-t, 0, -1], [-t, 0, 1]]
-    f = [[0, 11, 5], [0, 5, 1], [0, 1, 7], [0, 7, 10], [0, 10, 11], [1, 5, 9], [5, 11, 4], [11, 10, 2], [10, 7, 6], [7, 1, 8],
-         [3, 9, 4], [3, 4, 2], [3, 2, 6], [3, 6, 8], [3, 8, 9], [4, 9, 5], [2, 4, 11], [6, 2, 10], [8, 6, 7], [9, 8, 1]]
-    v = [list(unit(p)) for p in v]
-    for _ in range(sub):
-        nf, cache = [], {}
-
-        def mid(a, b):
-            k = (min(a, b), max(a, b))
-            if k not in cache:
-                v.append(list(unit((np.array(v[a]) + np.array(v[b])) / 2)))
-                cache[k] = len(v) - 1
-            return cache[k]
-        for a, b, c in f:
-            ab, bc, ca = mid(a, b), mid(b, c), mid(c, a)
-            nf += [[a, ab, ca], [b, bc, ab], [c, ca, bc], [ab, bc, ca]]
-        f = nf
-    v = np.array(v) * r
-    idx = np.array(f, np.uint16)
-    n = np.cross(v[idx[:, 1]] - v[idx[:, 0]], v[idx[:, 2]] - v[idx[:, 0]])
-    flip = (n * v[idx].mean(1)).sum(1) < 0
-    idx[flip] = idx[flip][:, [0, 2, 1]]
-    return v.astype(np.float32), idx
 
 
 def rand_quat(R):
     q = unit(R.normal(size=4))
     return q.astype(np.float32)                             # x, y, z, w
-
-
-class Scene:
-    """A PhysWorld whose statics are `bb` / kinds plus one OTHER static per mesh (its baked AABB), with the meshes set."""
-
-    def __init__(self, cuda_device, bodies, meshes, bb=None, kind=None, geo=None, unmeshed=(), tail_boxes=()):
-        from clap_amd import physics
-        bb = np.zeros((0, 6)) if bb is None else np.asarray(bb, float)
-        kind = np.zeros(0, np.uint8) if kind is None else np.asarray(kind, np.uint8)
-        self.base = len(bb)
-        self.meshes = meshes                                # [(vx, idx, scale, pos, quat)]
-        tris = [tr.bake(*m) for m in meshes]
-        mbb = np.zeros((len(tris), 6))
-        for k, t in enumerate(tris):
-            lo, hi = t.reshape(-1, 3).min(0), t.reshape(-1, 3).max(0)
-            mbb[k, 0::2], mbb[k, 1::2] = lo, hi
-        ub = np.asarray(list(unmeshed), float).reshape(-1, 6)
-        tb = np.asarray(list(tail_boxes), float).reshape(-1, 6)            # boxes after the meshes (higher indices)
-        allbb = np.concatenate([bb, mbb, ub, tb])
-        allkind = np.concatenate([kind, np.full(len(tris) + len(ub), OTHER, np.uint8), np.full(len(tb), BOX, np.uint8)])
-        ns = len(allbb)
-        g = geo or {}
-        pad = lambda a, shape: np.concatenate([np.asarray(a, float).reshape((-1,) + shape), np.zeros((ns - self.base,) + shape)])
-        c = (allbb[:, 0::2] + allbb[:, 1::2]) / 2
-        self.w = physics.PhysWorld(bodies, allbb, pair_capacity=4_000_000, static_pair_capacity=8_000_000, device=cuda_device)
-        self.w.set_static_geoms(allkind, pad(g["pos"], (3,)) if "pos" in g else c,
-                                pad(g["axis"], (3,)) if "axis" in g else np.tile([0, 0, 1.0], (ns, 1)),
-                                pad(g["radius"], ()) if "radius" in g else np.zeros(ns),
-                                pad(g["length"], ()) if "length" in g else np.zeros(ns))
-        self.mesh_static = self.base + np.arange(len(tris))
-        self.ref = tr.Meshes.from_list([(self.base + k, t) for k, t in enumerate(tris)])
-        if meshes:
-            self.w.set_static_meshes(self.mesh_static, [m[0] for m in meshes], [m[1] for m in meshes], [m[2] for m in meshes],
-                                     [m[3] for m in meshes], [m[4] for m in meshes])
-
-
-def _cast(self, *a, **k):
-    """brute force: these scenes have no broadphase index"""
-    k.setdefault("grid", False)
-    return self.w.ray_cast(*a, **k)
-
-
-Scene.cast = _cast
-
-
-def far_body(n=1):
-    b = synth.sphere_bodies(n, box=1.0, seed=1)
-    b["pos"][:] = [-500.0, -500.0, -500.0]
-    b["lvel"][:] = 0
-    return b
 
 
 def check_against_truth(sc, s, d, L, skip, got, base, name):
@@ -196,12 +73,7 @@ def big_scene(cuda_device):
     bb[0] = [-1e3, 1e3, -10.0, -3.0, -1e3, 1e3]
     kind = R.choice([SPHERE, CAPSULE, BOX, OTHER], ns, p=[0.3, 0.3, 0.3, 0.1]).astype(np.uint8)
     kind[0] = BOX
-    c, h = (bb[:, 0::2] + bb[:, 1::2]) / 2, (bb[:, 1::2] - bb[:, 0::2]) / 2
-    big = np.argmax(h, 1)
-    r = h.min(1)
-    axis = np.zeros((ns, 3))
-    axis[np.arange(ns), big] = 1.0
-    length = np.where(kind == CAPSULE, 2 * (h[np.arange(ns), big] - r), 0.0)
+    c, axis, r, length = synth.geoms_of_aabbs(bb, kind)
     vx, idx = heightfield(256, 64.0, y0=-1.0, amp=1.0)
     meshes = [(vx, idx, 1.0, [-2.0, 0.0, -2.0], IDENT)]
     bv, bi = box_mesh()
@@ -435,12 +307,7 @@ def big_scene_small(cuda_device):
     bb = np.empty((ns, 6))
     bb[:, 0::2], bb[:, 1::2] = lo, lo + R.uniform(0.1, 3.0, (ns, 3))
     kind = R.choice([SPHERE, CAPSULE, BOX], ns).astype(np.uint8)
-    c, h = (bb[:, 0::2] + bb[:, 1::2]) / 2, (bb[:, 1::2] - bb[:, 0::2]) / 2
-    big = np.argmax(h, 1)
-    r = h.min(1)
-    axis = np.zeros((ns, 3))
-    axis[np.arange(ns), big] = 1.0
-    length = np.where(kind == CAPSULE, 2 * (h[np.arange(ns), big] - r), 0.0)
+    c, axis, r, length = synth.geoms_of_aabbs(bb, kind)
     meshes = [((bv, bi) if k % 2 else (iv, ii)) + (float(R.uniform(1, 4)), R.uniform(0, 60, 3), rand_quat(R)) for k in range(60)]
     return Scene(cuda_device, b, meshes, bb, kind, dict(pos=c, axis=axis, radius=r, length=length)), b
 

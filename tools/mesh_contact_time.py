@@ -19,18 +19,18 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from clap_amd import _lib, entities, frame, physics, synth  # noqa: E402
 from ray_time import timed  # noqa: E402
-from trimesh_ray_time import heightfield  # noqa: E402
+from trimesh_ray_time import terrain  # noqa: E402
 
 
 def ground(x, z):
-    return np.sin((x + 2.0) * 0.37) * np.cos((z + 2.0) * 0.29) - 1.0     # the terrain of heightfield(256, 64, (-2, 0, -2))
+    return synth.terrain_y(x + 2.0, z + 2.0, y0=-1.0)                    # the surface of terrain(256, 64, (-2, 0, -2))
 
 
 def scene(workload):
     R = np.random.Generator(np.random.PCG64(9))
-    meshes = [heightfield(256, 64.0, [-2.0, 0.0, -2.0])]
+    meshes = [terrain(256, 64.0, [-2.0, 0.0, -2.0])]
     if workload == "B":
-        small = heightfield(17, 4.0, [0, 0, 0])
+        small = terrain(17, 4.0, [0, 0, 0])
         for _ in range(2048):
             meshes.append((small[0], small[1], R.uniform(-5, 60, 3)))
     b = synth.capsule_bodies(262_144, box=60.0, seed=4)
@@ -53,11 +53,7 @@ def scene(workload):
     for k, (vx, _i, org) in enumerate(meshes):
         v = vx.astype(np.float64) + org
         bb[sidx[k], 0::2], bb[sidx[k], 1::2] = v.min(0) - 1e-3, v.max(0) + 1e-3
-    c, h = (bb[:, 0::2] + bb[:, 1::2]) / 2, (bb[:, 1::2] - bb[:, 0::2]) / 2
-    big, r = np.argmax(h, 1), h.min(1)
-    axis = np.zeros((ns, 3))
-    axis[np.arange(ns), big] = 1.0
-    length = np.where(kind == 1, 2 * (h[np.arange(ns), big] - r), 0.0)
+    c, axis, r, length = synth.geoms_of_aabbs(bb, kind)
     w = physics.PhysWorld(b, bb, pair_capacity=4_000_000, static_pair_capacity=8_000_000, device="cuda:0")
     w.set_static_geoms(kind, c, axis, r, length)
     quats = np.tile(np.float32([0, 0, 0, 1]), (len(meshes), 1))

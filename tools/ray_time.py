@@ -41,11 +41,7 @@ def scene():
     bb[0] = [-1e3, 1e3, -10.0, 0.0, -1e3, 1e3]
     kind = R.choice([0, 1, 2, 3], ns, p=[0.3, 0.3, 0.3, 0.1]).astype(np.uint8)
     kind[0] = 2
-    c, h = (bb[:, 0::2] + bb[:, 1::2]) / 2, (bb[:, 1::2] - bb[:, 0::2]) / 2
-    big, r = np.argmax(h, 1), h.min(1)
-    axis = np.zeros((ns, 3))
-    axis[np.arange(ns), big] = 1.0
-    length = np.where(kind == 1, 2 * (h[np.arange(ns), big] - r), 0.0)
+    c, axis, r, length = synth.geoms_of_aabbs(bb, kind)
     w = physics.PhysWorld(b, bb, pair_capacity=4_000_000, static_pair_capacity=8_000_000, device="cuda:0")
     w.set_static_geoms(kind, c, axis, r, length)
     return w, b

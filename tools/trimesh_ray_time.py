@@ -17,27 +17,21 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from clap_amd import _lib, physics  # noqa: E402
+from clap_amd import _lib, physics, synth  # noqa: E402
 from ray_time import scene, timed  # noqa: E402
 
 
-def heightfield(nv, side, origin):
-    g = np.linspace(0.0, side, nv)
-    x, z = np.meshgrid(g, g, indexing="ij")
-    y = np.sin(x * 0.37) * np.cos(z * 0.29) - 1.0
-    vx = np.stack([x, y, z], -1).reshape(-1, 3).astype(np.float32)
-    i, j = np.meshgrid(np.arange(nv - 1), np.arange(nv - 1), indexing="ij")
-    v00, v10, v01, v11 = i * nv + j, (i + 1) * nv + j, i * nv + j + 1, (i + 1) * nv + j + 1
-    idx = np.stack([np.stack([v00, v01, v10], -1), np.stack([v10, v01, v11], -1)], 2).reshape(-1, 3).astype(np.uint16)
-    return vx, idx, np.asarray(origin, float)
+def terrain(nv, side, origin):
+    """(vx, idx, origin) of a mesh: synth's heightfield a unit lower, its place in the world carried separately"""
+    return synth.heightfield(nv, side, y0=-1.0) + (np.asarray(origin, float),)
 
 
 def run(workload, reps):
     w, b = scene()
     R = np.random.Generator(np.random.PCG64(9))
-    meshes = [heightfield(256, 64.0, [-2.0, 0.0, -2.0])]
+    meshes = [terrain(256, 64.0, [-2.0, 0.0, -2.0])]
     if workload == "B":
-        small = heightfield(17, 4.0, [0, 0, 0])                            # 16 x 16 x 2 = 512 triangles
+        small = terrain(17, 4.0, [0, 0, 0])                                # 16 x 16 x 2 = 512 triangles
         for _ in range(2048):
             meshes.append((small[0], small[1], R.uniform(-5, 60, 3)))
     # the mesh statics: the first OTHER statics of the scene take the meshes (their AABBs are the broadphase's; the mesh
