@@ -1,6 +1,7 @@
-// bp_grid.h -- the broadphase's hash grid as other translation units see it: the cell and slot functions the five k_bp_*
-// launches bin with (physics2.hip) and the ray cast looks cells up with (rays.hip), and a read-only view of an INDEXED
-// clapgpu_bp (clapgpu_bp_index), handed out by a hidden accessor in physics2.hip.
+// bp_grid.h -- the broadphase's hash grid as other translation units see it: the cell and slot functions and the bin step
+// that the five k_bp_* launches (broadphase.hip) and the pre-binning body step (bodies.hip) bin with and the ray cast
+// looks cells up with (rays.hip), the record and the control words of a clapgpu_bp, a read-only view of an INDEXED
+// clapgpu_bp (clapgpu_bp_index), and the hidden accessors of broadphase.hip that hand these out.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,18 +27,42 @@ __host__ __device__ __forceinline__ uint32_t cell_slot(int32_t cx, int32_t cy, i
     return block_hash(cx >> 2, cy >> 2, cz >> 2, mask) << 6 | (uint32_t)(cx & 3) | (uint32_t)(cy & 3) << 2 | (uint32_t)(cz & 3) << 4;
 }
 
-// physics2.hip's BpRec, field for field (static_assert there)
-struct GridRec { double bb[6]; uint32_t idx; int32_t cell[3]; };
+struct GridRec { double bb[6]; uint32_t idx; int32_t cell[3]; };    // 64 bytes; cell = the box centre's cell (dynamic records)
 
-// Control words of the index (clapgpu_bp.ctrl has 160; the broadphase uses 2, 3, 8 and 9).  Seven 64-bit words, all
-// reduced by atomicMin and set to all ones in front of the reduction: the indexed boxes' minimum corner as order keys,
-// the maximum corner as complemented order keys, and a word that drops to 0 when a box edge exceeds `cell`.
-constexpr int CTRL_BIN_EPOCH = 3;                 // physics2.hip's CTRL_EPOCH
+// Control words (clapgpu_bp.ctrl has 160).  The broadphase's: the sticky status bits, the bin epoch (the frame counter
+// lives on the device: a captured graph replays the same arguments; counted up by every bin pass, k_bp_bin or a
+// pre-binning step) and [8..9]: clapgpu_contacts_geoms_both's ticket + counts, zero between launches.
+constexpr int CTRL_STATUS = 2, CTRL_EPOCH = 3, CTRL_CONTACT_WORD = 8;
+// The index's: seven 64-bit words, all reduced by atomicMin and set to all ones in front of the reduction: the indexed
+// boxes' minimum corner as order keys, the maximum corner as complemented order keys, and a word that drops to 0 when
+// a box edge exceeds `cell`.
 constexpr int CTRL_INDEX_WORD = 16;
 constexpr int INDEX_WORDS = 7, INDEX_OVERSIZE = 6;
-// ... and the bin epoch (ctrl[3], counted up by every bin pass on the device, k_bp_bin or a prebinning step) the index
-// saw last.  A graph replay bins without the host knowing; a differing epoch tells the ray kernel the index is stale.
+// ... and the bin epoch the index saw last.  A graph replay bins without the host knowing; a differing epoch tells the
+// ray kernel the index is stale.
 constexpr int CTRL_INDEX_EPOCH = CTRL_INDEX_WORD + 2 * INDEX_WORDS;       // word 30
+
+// One body into the grid: k_bp_bin's work per body, also done by the step that writes the box it would read
+// (clapgpu_bodies_step_prebin).  key == nullptr: off.
+struct BinK { double cell; uint32_t mask; uint32_t *key, *rank, *cell_cnt, *ctrl; };
+
+__device__ __forceinline__ void box_cell(const double (&bb)[6], double cell, int32_t &cx, int32_t &cy, int32_t &cz)
+{
+    cx = cell_coord((bb[0] + bb[1]) * 0.5, cell);
+    cy = cell_coord((bb[2] + bb[3]) * 0.5, cell);
+    cz = cell_coord((bb[4] + bb[5]) * 0.5, cell);
+}
+
+__device__ __forceinline__ void bin_body(const BinK &bin, uint32_t i, const double (&bb)[6])
+{
+    if (bb[1] - bb[0] > bin.cell || bb[3] - bb[2] > bin.cell || bb[5] - bb[4] > bin.cell)
+        atomicOr(&bin.ctrl[CTRL_STATUS], 1u);
+    int32_t cx, cy, cz;
+    box_cell(bb, bin.cell, cx, cy, cz);
+    const uint32_t slot = cell_slot(cx, cy, cz, bin.mask);
+    bin.key[i] = slot;
+    bin.rank[i] = atomicAdd(&bin.cell_cnt[slot], 1u);
+}
 
 __host__ __device__ __forceinline__ uint64_t order_key(double x)              // monotone in x (not for NaN)
 {
@@ -67,6 +92,12 @@ struct BpGridView {
 
 } // namespace clapgpu
 
+// ---- broadphase.hip's hidden accessors: struct clapgpu_bp is written and read in that file alone
 struct clapgpu_bp;
-// true when `bp` holds an index over exactly (n, aabb) (aabb == nullptr: any array of n boxes); fills *v
+// rays.hip: true when `bp` holds an index over exactly (n, aabb) (aabb == nullptr: any array of n boxes); fills *v
 __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp *bp, uint32_t n, const double *aabb, clapgpu::BpGridView *v);
+// contacts.hip: the one-launch form keeps its ticket + counts in the object's control words
+__attribute__((visibility("hidden"))) unsigned long long *clapgpu_bp_contact_ticket(clapgpu_bp *bp);
+// bodies.hip: the bin arrays for a step that is about to write and bin the n boxes of `aabb`, recorded as pre-binned
+// (an unconsumed prebin is undone first, an index dropped).  The caller launches that step or calls clapgpu_bp_invalidate.
+__attribute__((visibility("hidden"))) int clapgpu_bp_prebin(void *stream, clapgpu_bp *bp, uint32_t n, const double *aabb, clapgpu::BinK *bin);

@@ -1,232 +1,16 @@
-// physics2.hip -- capsule / sphere bodies: integrate, geom AABBs, broadphase over explicit AABBs, for gfx950
-// (narrowphase contact records and the capsule sweep: contacts.hip).
-//
-// What phys_step() (physics.c:773-787) does per fixed substep through ODE, for bodies without constraint rows:
-//   k_bodies_step     dWorldQuickStep's body stage (quickstep.cpp stage 0 + dxStepBody + auto-disable), fused with
-//                     the moved geom's axis / AABB (dxCapsule::computeAABB)                      HBM-bound, 1 lane / body
-//   k_bp_*            dSpaceCollide2(ground, bodies) + dSpaceCollide(bodies) (physics.c:751-753) as ascending
-//                     candidate-pair lists, five launches for both passes: bodies binned by AABB centre into a hash
-//                     grid of 4x4x4-cell blocks, copied into cell order, searched one wavefront per 16-body tile with
-//                     the candidates of each distinct cell listed once in LDS (section comment below)
-// fp64 throughout (the reference builds ODE with dDOUBLE, physics.h:5-9), no FMA contraction.
-// ODE is an absent submodule of the reference: PARITY UNPINNED (oracle/physics2.c states what is restated).
+// broadphase.hip -- the broadphase over explicit AABBs, for gfx950: dSpaceCollide2(ground, bodies) + dSpaceCollide(bodies)
+// (physics.c:751-753) as ascending candidate-pair lists, and the same grid as an index for the ray cast (rays.hip).
+// struct clapgpu_bp lives here alone; other translation units go through the hidden accessors of bp_grid.h.
+// fp64 boxes.  ODE is an absent submodule of the reference: PARITY UNPINNED (oracle/physics2.c states what is restated).
 #include <string.h>
 #include <stdlib.h>
 #include <vector>
 #include "common.h"
-#include "phys_dev.h"
 #include "bp_grid.h"
 
 namespace clapgpu {
 
 constexpr int PB = 256;
-
-struct WorldK2 {
-    double  gravity[3];
-    double  linear_damping;
-    double  linear_damping_threshold_sq;
-    double  adis_linear_threshold_sq;
-    double  adis_angular_threshold_sq;
-    double  adis_time;
-    int32_t adis_steps;
-    int32_t pad;
-};
-static_assert(sizeof(WorldK2) == sizeof(clapgpu_world), "world layout");
-static_assert(true, "");
-
-struct BodiesK {
-    uint32_t n, samples;
-    double *pos, *quat, *lvel, *avel;
-    const double *mass, *radius;
-    uint32_t *bflags;
-    int32_t *adis_steps_left;
-    double *adis_time_left;
-    const double *length, *inertia;
-    double Roff[12];
-    double *aabb, *axis, *adis_samples;
-    uint32_t *adis_counter;
-    double *geom_records;
-};
-
-// The next broadphase's first launch (k_bp_bin: one atomic per body on its cell's counter) done by the step that writes the
-// box it would read: clapgpu_bodies_step_prebin.  key == nullptr: off.
-struct BinK { double cell; uint32_t mask; uint32_t *key, *rank, *cell_cnt, *ctrl; };
-__device__ __forceinline__ void bin_body(const BinK &bin, uint32_t i, const double (&bb)[6]);
-
-__device__ __forceinline__ void write_geom(const BodiesK &b, uint32_t i, const double (&p)[3], const double (&q)[4],
-                                           double (*bb_out)[6] = nullptr)
-{
-    if (!b.aabb && !b.axis && !b.geom_records) return;
-    double R[12], axis[3], bb[6];
-    phd::q_to_R(q, R);
-    phd::capsule_axis(R, b.Roff, axis);
-    const double lz = b.length ? b.length[i] : 0.0;
-    phd::geom_aabb(p, b.radius[i], lz, axis, bb);
-    if (b.geom_records) {                                        // the narrowphase's view of this geom, one 64-byte sector
-        double2 *r = reinterpret_cast<double2 *>(b.geom_records + 8 * (size_t)i);
-        r[0] = make_double2(p[0], p[1]); r[1] = make_double2(p[2], axis[0]);
-        r[2] = make_double2(axis[1], axis[2]); r[3] = make_double2(b.radius[i], lz);
-    }
-    if (b.axis) { double *a = b.axis + 3 * (size_t)i; a[0] = axis[0]; a[1] = axis[1]; a[2] = axis[2]; }
-    if (b.aabb) {
-        double2 *o = reinterpret_cast<double2 *>(b.aabb + 6 * (size_t)i);
-        o[0] = make_double2(bb[0], bb[1]); o[1] = make_double2(bb[2], bb[3]); o[2] = make_double2(bb[4], bb[5]);
-    }
-    if (bb_out)
-#pragma unroll
-        for (int a = 0; a < 6; a++) (*bb_out)[a] = bb[a];
-}
-
-// a body the step leaves alone keeps its stored box: binned from there
-__device__ __forceinline__ void bin_stored(const BinK &bin, const BodiesK &b, uint32_t i)
-{
-    const double2 *p = reinterpret_cast<const double2 *>(b.aabb + 6 * (size_t)i);
-    const double2 x = p[0], y = p[1], z = p[2];
-    const double bb[6] = { x.x, x.y, y.x, y.y, z.x, z.y };
-    bin_body(bin, i, bb);
-}
-
-__global__ __launch_bounds__(PB)
-void k_bodies_aabb(BodiesK b)
-{
-    const uint32_t i = blockIdx.x * PB + threadIdx.x;
-    if (i >= b.n) return;
-    const double p[3] = { b.pos[3 * (size_t)i], b.pos[3 * (size_t)i + 1], b.pos[3 * (size_t)i + 2] };
-    const double q[4] = { b.quat[4 * (size_t)i], b.quat[4 * (size_t)i + 1], b.quat[4 * (size_t)i + 2], b.quat[4 * (size_t)i + 3] };
-    write_geom(b, i, p, q);
-}
-
-template <bool BIN>
-__global__ __launch_bounds__(PB)
-void k_bodies_step(BodiesK b, WorldK2 w, double h, BinK bin)
-{
-    const uint32_t i = blockIdx.x * PB + threadIdx.x;
-    if (BIN && i == 0) bin.ctrl[3] = bin.ctrl[3] + 1;                   // CTRL_EPOCH: what k_bp_bin's first thread does
-    if (i >= b.n) return;
-    uint32_t fl = b.bflags[i];
-    if (fl & CLAPGPU_BODY_DISABLED) { if (BIN) bin_stored(bin, b, i); return; }
-    double *pp = b.pos + 3 * (size_t)i, *qp = b.quat + 4 * (size_t)i, *vp = b.lvel + 3 * (size_t)i, *op = b.avel + 3 * (size_t)i;
-    double v[3] = { vp[0], vp[1], vp[2] }, om[3] = { op[0], op[1], op[2] };
-
-    // dInternalHandleAutoDisabling: enabled bodies with the flag that hold a joint
-    if ((fl & CLAPGPU_BODY_AUTO_DISABLE) && (fl & CLAPGPU_BODY_HAS_JOINT)) {
-        bool idle = false;
-        double al[3], aa[3];
-        const uint32_t S = b.samples > 1 ? b.samples : 1;
-        if (S == 1) {
-            for (int a = 0; a < 3; a++) { al[a] = v[a]; aa[a] = om[a]; }
-            idle = true;
-        } else {
-            double *ring = b.adis_samples + (size_t)i * S * 6;
-            uint32_t c = b.adis_counter[i] & 0x7fffffffu, ready = b.adis_counter[i] >> 31;
-            for (int a = 0; a < 3; a++) { ring[6 * (size_t)c + a] = v[a]; ring[6 * (size_t)c + 3 + a] = om[a]; }
-            if (++c >= S) { c = 0; ready = 1; }
-            b.adis_counter[i] = c | ready << 31;
-            if (ready) {
-                idle = true;
-                for (int a = 0; a < 3; a++) { al[a] = ring[a]; aa[a] = ring[3 + a]; }
-                for (uint32_t s = 1; s < S; s++)
-                    for (int a = 0; a < 3; a++) { al[a] += ring[6 * (size_t)s + a]; aa[a] += ring[6 * (size_t)s + 3 + a]; }
-                const double r1 = 1.0 / (double)S;
-                for (int a = 0; a < 3; a++) { al[a] *= r1; aa[a] *= r1; }
-            }
-        }
-        if (idle) {
-            if (al[0] * al[0] + al[1] * al[1] + al[2] * al[2] > w.adis_linear_threshold_sq) idle = false;
-            else if (aa[0] * aa[0] + aa[1] * aa[1] + aa[2] * aa[2] > w.adis_angular_threshold_sq) idle = false;
-        }
-        int32_t sl = b.adis_steps_left[i];
-        double tl = b.adis_time_left[i];
-        if (idle) { sl--; tl -= h; } else { sl = w.adis_steps; tl = w.adis_time; }
-        b.adis_steps_left[i] = sl;
-        b.adis_time_left[i] = tl;
-        if (sl <= 0 && tl <= 0) {
-            b.bflags[i] = (fl | CLAPGPU_BODY_DISABLED) & ~CLAPGPU_BODY_HAS_JOINT;
-            vp[0] = vp[1] = vp[2] = 0;
-            op[0] = op[1] = op[2] = 0;
-            if (BIN) bin_stored(bin, b, i);
-            return;
-        }
-    }
-    if (fl & CLAPGPU_BODY_HAS_JOINT)
-        b.bflags[i] = fl & ~CLAPGPU_BODY_HAS_JOINT;                   // dJointGroupEmpty after the step
-
-    double q[4] = { qp[0], qp[1], qp[2], qp[3] };
-    double tacc[3] = { 0, 0, 0 }, invIw[12];
-    const bool have_inertia = b.inertia != nullptr;
-    if (have_inertia) {
-        const double Ib[3] = { b.inertia[3 * (size_t)i], b.inertia[3 * (size_t)i + 1], b.inertia[3 * (size_t)i + 2] };
-        const double invIb[3] = { 1.0 / Ib[0], 1.0 / Ib[1], 1.0 / Ib[2] };
-        double R[12];
-        phd::q_to_R(q, R);
-        phd::world_tensor(R, invIb, invIw);
-        if (fl & CLAPGPU_BODY_GYROSCOPIC) {                             // implicit gyroscopic torque (quickstep.cpp stage 0)
-            double Iw[12], L[3], Itild[12], itInv[12];
-            phd::world_tensor(R, Ib, Iw);
-            phd::mul331(L, Iw, om);
-            for (int k = 0; k < 12; k++) Itild[k] = 0;
-            Itild[1] = L[2]; Itild[2] = -L[1];                          // dSetCrossMatrixMinus
-            Itild[4] = -L[2]; Itild[6] = L[0];
-            Itild[8] = L[1]; Itild[9] = -L[0];
-            for (int k = 0; k < 12; k++) Itild[k] = Itild[k] * h + Iw[k];
-            const double rh = 1.0 / h;
-            L[0] *= rh; L[1] *= rh; L[2] *= rh;
-            if (phd::invert3(itInv, Itild)) {
-                double T[12], tau0[3];
-                for (int r = 0; r < 3; r++) {
-                    for (int c = 0; c < 3; c++)
-                        T[4 * r + c] = Iw[4 * r] * itInv[c] + Iw[4 * r + 1] * itInv[4 + c] + Iw[4 * r + 2] * itInv[8 + c];
-                    T[4 * r + 3] = 0;
-                }
-                T[0] -= 1; T[5] -= 1; T[10] -= 1;
-                phd::mul331(tau0, T, L);
-                tacc[0] += tau0[0]; tacc[1] += tau0[1]; tacc[2] += tau0[2];
-            }
-        }
-    }
-    const double m = b.mass[i];
-    const double k = h * (1.0 / m);
-    const bool grav = !(fl & CLAPGPU_BODY_NO_GRAVITY);
-    for (int j = 0; j < 3; j++)
-        v[j] += k * (grav ? m * w.gravity[j] : 0.0);
-    if (have_inertia) {
-        double d[3];
-        tacc[0] *= h; tacc[1] *= h; tacc[2] *= h;
-        phd::mul331(d, invIw, tacc);
-        om[0] += d[0]; om[1] += d[1]; om[2] += d[2];
-        op[0] = om[0]; op[1] = om[1]; op[2] = om[2];
-    }
-    double p[3] = { pp[0], pp[1], pp[2] };
-    for (int j = 0; j < 3; j++) p[j] += h * v[j];                      // dxStepBody
-    pp[0] = p[0]; pp[1] = p[1]; pp[2] = p[2];
-    const double d0 = 0.5 * (-om[0] * q[1] - om[1] * q[2] - om[2] * q[3]);   // dWtoDQ
-    const double d1 = 0.5 * ( om[0] * q[0] + om[1] * q[3] - om[2] * q[2]);
-    const double d2 = 0.5 * (-om[0] * q[3] + om[1] * q[0] + om[2] * q[1]);
-    const double d3 = 0.5 * ( om[0] * q[2] - om[1] * q[1] + om[2] * q[0]);
-    q[0] += h * d0; q[1] += h * d1; q[2] += h * d2; q[3] += h * d3;
-    double l = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];   // dNormalize4
-    if (l > 0) {
-        l = 1.0 / sqrt(l);
-        q[0] *= l; q[1] *= l; q[2] *= l; q[3] *= l;
-    } else {
-        q[0] = 1; q[1] = q[2] = q[3] = 0;
-    }
-    qp[0] = q[0]; qp[1] = q[1]; qp[2] = q[2]; qp[3] = q[3];
-    if (w.linear_damping != 0.0) {
-        const double speed2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-        if (speed2 > w.linear_damping_threshold_sq) {
-            const double s = 1 - w.linear_damping;
-            v[0] *= s; v[1] *= s; v[2] *= s;
-        }
-    }
-    vp[0] = v[0]; vp[1] = v[1]; vp[2] = v[2];
-    if (BIN) {
-        double bb[6];
-        write_geom(b, i, p, q, &bb);
-        bin_body(bin, i, bb);
-    } else
-        write_geom(b, i, p, q);
-}
 
 // ================================================================================== broadphase
 // Hash grid over the AABB centres, cell >= the largest body AABB edge, so a body's partners have their centres in
@@ -255,14 +39,8 @@ constexpr int BP_EMIT_TILE = 1024;     // bodies per tile of the pair-offset sca
 #ifndef BP_SEARCH_IN_FLIGHT
 #define BP_SEARCH_IN_FLIGHT 1            // candidate records gathered per lane and round
 #endif
-constexpr int CTRL_STATUS = 2, CTRL_EPOCH = 3, CTRL_CONTACT_WORD = 8;   // [8..9]: clapgpu_contacts_geoms_both's ticket + counts, zero between launches     // the frame counter lives on the device: a captured graph replays the same arguments
 
-// block_hash, cell_coord, cell_slot: bp_grid.h (the ray cast looks cells up with the same functions)
-
-struct BpRec { double bb[6]; uint32_t idx; int32_t cell[3]; };    // 64 bytes; cell = the box centre's cell (dynamic records)
-static_assert(CTRL_EPOCH == CTRL_BIN_EPOCH, "bp_grid.h's view of the control words");
-static_assert(sizeof(BpRec) == sizeof(GridRec) && offsetof(BpRec, idx) == offsetof(GridRec, idx) &&
-              offsetof(BpRec, cell) == offsetof(GridRec, cell), "bp_grid.h's view of the records");
+// block_hash, cell_coord, cell_slot, box_cell, the record and the control words: bp_grid.h
 
 struct BpK {
     uint32_t n;
@@ -273,7 +51,7 @@ struct BpK {
     uint2    *cell_range;                // [buckets * 64] (first position in cell order, bodies) of every cell: one load per lookup
     uint32_t *key, *rank;                // [n] cell slot and rank inside the cell
     uint32_t *entries;                   // [n] body indices in cell order
-    struct BpRec *recs;                  // [n] the same with the boxes: what the search reads
+    GridRec *recs;                  // [n] the same with the boxes: what the search reads
     uint32_t *cnt, *scnt;                // [n] partners (larger index) / statics per body: atomics in the search
     uint32_t *partners, *spartners;      // [n][BP_LIST]
     uint64_t *lb_body, *lb_static;       // [tiles] look-back words of the pair-offset scan (k_bp_emit)
@@ -285,8 +63,8 @@ struct BpK {
     const uint32_t *s_entries;
     const double *s_aabb;
     const uint32_t *s_large;
-    const struct BpRec *s_recs;          // s_entries with their boxes (what the search gathers)
-    const struct BpRec *s_lrecs;         // the large statics with their boxes
+    const GridRec *s_recs;          // s_entries with their boxes (what the search gathers)
+    const GridRec *s_lrecs;         // the large statics with their boxes
     uint32_t n_large, n_static;
     // outputs
     uint32_t *pairs, capacity, *pair_total;
@@ -300,27 +78,9 @@ __device__ __forceinline__ void load_box(const double *aabb, uint32_t i, double 
     bb[0] = a.x; bb[1] = a.y; bb[2] = b.x; bb[3] = b.y; bb[4] = c.x; bb[5] = c.y;
 }
 
-__device__ __forceinline__ void box_cell(const double (&bb)[6], double cell, int32_t &cx, int32_t &cy, int32_t &cz)
-{
-    cx = cell_coord((bb[0] + bb[1]) * 0.5, cell);
-    cy = cell_coord((bb[2] + bb[3]) * 0.5, cell);
-    cz = cell_coord((bb[4] + bb[5]) * 0.5, cell);
-}
-
 __device__ __forceinline__ bool boxes_overlap(const double (&a)[6], const double (&b)[6])
 {
     return !(a[0] > b[1] || a[1] < b[0] || a[2] > b[3] || a[3] < b[2] || a[4] > b[5] || a[5] < b[4]);
-}
-
-__device__ __forceinline__ void bin_body(const BinK &bin, uint32_t i, const double (&bb)[6])
-{
-    if (bb[1] - bb[0] > bin.cell || bb[3] - bb[2] > bin.cell || bb[5] - bb[4] > bin.cell)
-        atomicOr(&bin.ctrl[CTRL_STATUS], 1u);
-    int32_t cx, cy, cz;
-    box_cell(bb, bin.cell, cx, cy, cz);
-    const uint32_t slot = cell_slot(cx, cy, cz, bin.mask);
-    bin.key[i] = slot;
-    bin.rank[i] = atomicAdd(&bin.cell_cnt[slot], 1u);
 }
 
 // Launch 1 (skipped when the step before it has binned the boxes it wrote: clapgpu_bodies_step_prebin)
@@ -467,7 +227,7 @@ void k_bp_search(BpK k)
     __shared__ int32_t lead[WAVES][2 * T][4];                           // cell leaders: (cx, cy, cz, range); then block leaders: (bucket, -, -, range)
     __shared__ uint32_t shits[WAVES][T];
     __shared__ uint32_t hits[WAVES][HITS][2], nhits[WAVES];
-    __shared__ BpRec large[LARGE_TILE];
+    __shared__ GridRec large[LARGE_TILE];
     const int lane = lane_id(), wave = threadIdx.x / WAVE;
     const uint32_t t0 = (blockIdx.x * WAVES + wave) * T;
     const uint32_t nA = t0 < k.n ? (k.n - t0 < (uint32_t)T ? k.n - t0 : (uint32_t)T) : 0;
@@ -480,7 +240,7 @@ void k_bp_search(BpK k)
     uint32_t ob = 0;
     const bool isA = (uint32_t)lane < nA;
     if (isA) {
-        const BpRec me = k.recs[t0 + lane];
+        const GridRec me = k.recs[t0 + lane];
 #pragma unroll
         for (int x = 0; x < 6; x++) abox[wave][lane][x] = me.bb[x];
         aidx[wave][lane] = me.idx;
@@ -572,7 +332,7 @@ void k_bp_search(BpK k)
         if (lane == 0) nhits[wave] = 0;
         wave_lds_fence();
     };
-    auto test = [&](uint32_t w, uint32_t range, const BpRec &r) {
+    auto test = [&](uint32_t w, uint32_t range, const GridRec &r) {
         const uint32_t j = r.idx, a_hi = range >> 8;
         for (uint32_t x = range & 0xffu; x < a_hi; x++) {
             const double2 *ab = reinterpret_cast<const double2 *>(abox[wave][x]);
@@ -616,7 +376,7 @@ void k_bp_search(BpK k)
             const uint2 e0 = v0 ? *reinterpret_cast<const uint2 *>(work[wave][e]) : make_uint2(0u, 0u);
             const uint2 e1 = v1 ? *reinterpret_cast<const uint2 *>(work[wave][e + WAVE]) : make_uint2(0u, 0u);
             const uint32_t w0 = e0.x, g0 = e0.y, w1 = e1.x, g1 = e1.y;
-            BpRec r0, r1;
+            GridRec r0, r1;
             if (v0) r0 = ((w0 & STAT) ? k.s_recs : k.recs)[w0 & IDX];
             if (v1) r1 = ((w1 & STAT) ? k.s_recs : k.recs)[w1 & IDX];
             if (v0) test(w0, g0, r0);
@@ -625,7 +385,7 @@ void k_bp_search(BpK k)
 #else
         for (uint32_t e = lane; e < todo; e += WAVE) {
             const uint2 e0 = *reinterpret_cast<const uint2 *>(work[wave][e]);
-            const BpRec r0 = ((e0.x & STAT) ? k.s_recs : k.recs)[e0.x & IDX];
+            const GridRec r0 = ((e0.x & STAT) ? k.s_recs : k.recs)[e0.x & IDX];
             test(e0.x, e0.y, r0);
         }
 #endif
@@ -852,165 +612,9 @@ void k_bp_index_bounds(BpK k)
     }
 }
 
-// clapgpu_bodies_ground_collide's second launch (rays.hip casts, this moves): phys_body_move of every body whose ray
-// said so, through a vec3 (float), then the geom as clapgpu_bodies_aabb writes it.  A ray whose hit body moved here is
-// flagged: it saw that body where it was before the call.
-__global__ __launch_bounds__(PB)
-void k_ground_apply(BodiesK b, const double *yoffset, uint32_t n, const uint32_t *body, const double *ray_off,
-                    const uint8_t *grounded, uint8_t *grounded_out, const double *dist, const int32_t *hit, uint32_t *flags,
-                    const uint32_t *moved)
-{
-    const uint32_t j = blockIdx.x * PB + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t f = flags[j];
-    const int32_t h = hit[j];
-    const uint32_t i = body[j];
-    if (i >= b.n) return;                                                   // flagged invalid by the ray launch
-    if ((moved[i] >> 1) > 1) {                                              // listed twice: none of its rays moves it
-        flags[j] = f | CLAPGPU_RAY_INVALID;
-        grounded_out[j] = 0;
-        return;
-    }
-    if (f || h == -1) return;                                               // invalid, unresolved or a miss: nothing moves
-    double roff;
-    const double ray_len = phd::ground_ray_len(ray_off[j], yoffset[i], roff);
-    float dy;
-    bool mv;
-    phd::ground_branch(dist[j], ray_len, grounded[j] != 0, dy, mv);
-    if (h >= 0 && (uint32_t)h < b.n && (moved[h] & 1u) && (moved[h] >> 1) == 1) flags[j] = f | CLAPGPU_RAY_MOVED_TARGET;
-    if (!mv) return;
-    const float d[3] = { 0.0f, dy, 0.0f };
-    double *pp = b.pos + 3 * (size_t)i;
-    const double p[3] = { pp[0] + d[0], pp[1] + d[1], pp[2] + d[2] };     // dBodySetPosition(pos + delta)
-    pp[0] = p[0]; pp[1] = p[1]; pp[2] = p[2];
-    const double q[4] = { b.quat[4 * (size_t)i], b.quat[4 * (size_t)i + 1], b.quat[4 * (size_t)i + 2], b.quat[4 * (size_t)i + 3] };
-    write_geom(b, i, p, q);
-}
-
 } // namespace clapgpu
 
 using namespace clapgpu;
-
-// ---------------------------------------------------------------------------------- host helpers
-static void h_q_from_axis_and_angle(double (&q)[4], double ax, double ay, double az, double angle)
-{
-    double l = ax * ax + ay * ay + az * az;
-    if (l > 0.0) {
-        angle *= 0.5;
-        q[0] = cos(angle);
-        l = sin(angle) * (1.0 / sqrt(l));
-        q[1] = ax * l; q[2] = ay * l; q[3] = az * l;
-    } else {
-        q[0] = 1; q[1] = q[2] = q[3] = 0;
-    }
-}
-
-extern "C" void clapgpu_geom_offset_rotation(double R[12])
-{
-    double q[4], M[12];
-    h_q_from_axis_and_angle(q, 1.0, 1.0, 1.0, -M_PI * 2.0 / 3.0);
-    phd::q_to_R(q, M);
-    memcpy(R, M, sizeof(M));
-}
-
-extern "C" void clapgpu_mass_sphere_total(double total_mass, double radius, double I[3])
-{
-    const double m1 = (4.0 / 3.0) * M_PI * radius * radius * radius * 1.0;      // dMassSetSphere(m, 1.0, r)
-    const double II = 0.4 * m1 * radius * radius;
-    const double scale = total_mass / m1;                                        // dMassAdjust
-    I[0] = I[1] = I[2] = II * scale;
-}
-
-extern "C" void clapgpu_mass_capsule_total(double total_mass, int direction, double a, double b, double I[3])
-{
-    if (direction < 1 || direction > 3) direction = 3;
-    const double M1 = M_PI * a * a * b * 1.0;
-    const double M2 = (4.0 / 3.0) * M_PI * a * a * a * 1.0;
-    const double m = M1 + M2;
-    const double Ia = M1 * (0.25 * a * a + (1.0 / 12.0) * b * b) + M2 * (0.4 * a * a + 0.375 * a * b + 0.25 * b * b);
-    const double Ib = (M1 * 0.5 + M2 * 0.4) * a * a;
-    const double scale = total_mass / m;
-    I[0] = I[1] = I[2] = Ia;
-    I[direction - 1] = Ib;
-    I[0] *= scale; I[1] *= scale; I[2] *= scale;
-}
-
-// physics.c:814-873
-extern "C" void clapgpu_capsule_geom(float X, float Y, float Z, double geom_radius, double geom_offset,
-                                     float *radius, float *length, float *yoffset, int *direction, float *ray_off)
-{
-    float r = 0.f, len = 0.f, off = 0.f, ro = 0.f;
-    float mx = Y > Z ? Y : Z;                                                   // max3 / xmax3 (util.h:203-209)
-    if (X > mx) mx = X;
-    int w = 0;
-    if (mx == Y) w = 1; else if (mx == Z) w = 2;
-    const int dir = w + 1;
-    if (dir == 3) {
-        r = geom_radius ? (float)geom_radius : X / 2;
-        len = Z - r * 2;
-        off = geom_offset ? (float)geom_offset : (Y - r * 2) / 2;
-        ro = r;
-    } else {
-        float mn = Y < Z ? Y : Z;
-        if (X < mn) mn = X;
-        r = geom_radius ? (float)geom_radius : mn / 2;
-        const float l = Y / 2 - r * 2;
-        len = l > 0 ? l : 0;
-        off = geom_offset ? (float)geom_offset : Y / 2;
-        ro = r + len / 2;
-    }
-    *radius = r; *length = len; *yoffset = off; *direction = dir; *ray_off = ro;
-}
-
-static int check_bodies2(const clapgpu_bodies *b)
-{
-    if (!b || !b->pos || !b->quat || !b->lvel || !b->avel || !b->mass || !b->radius || !b->bflags ||
-        !b->adis_steps_left || !b->adis_time_left)
-        return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (b->adis_average_samples > 1 && (!b->adis_samples || !b->adis_counter))
-        return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    return CLAPGPU_OK;
-}
-
-static BodiesK bodies_k(const clapgpu_bodies *b)
-{
-    BodiesK k;
-    k.n = b->n; k.samples = b->adis_average_samples;
-    k.pos = b->pos; k.quat = b->quat; k.lvel = b->lvel; k.avel = b->avel;
-    k.mass = b->mass; k.radius = b->radius; k.bflags = b->bflags;
-    k.adis_steps_left = b->adis_steps_left; k.adis_time_left = b->adis_time_left;
-    k.length = b->length; k.inertia = b->inertia;
-    memcpy(k.Roff, b->geom_offset_R, sizeof(k.Roff));
-    bool zero = true;
-    for (int i = 0; i < 12; i++) zero &= k.Roff[i] == 0.0;
-    if (zero) k.Roff[0] = k.Roff[5] = k.Roff[10] = 1.0;                          // unset = no offset rotation
-    k.aabb = b->aabb; k.axis = b->axis; k.adis_samples = b->adis_samples; k.adis_counter = b->adis_counter;
-    k.geom_records = (reinterpret_cast<uintptr_t>(b->geom_records) & 15u) ? nullptr : b->geom_records;
-    return k;
-}
-
-extern "C" int clapgpu_bodies_aabb(void *stream, const clapgpu_bodies *b)
-{
-    int rc = check_bodies2(b);
-    if (rc) return rc;
-    if (b->n == 0) return CLAPGPU_OK;
-    hipLaunchKernelGGL(k_bodies_aabb, dim3((b->n + PB - 1) / PB), dim3(PB), 0, as_stream(stream), bodies_k(b));
-    CLAPGPU_LAUNCH_CHECK("k_bodies_aabb");
-    return CLAPGPU_OK;
-}
-
-extern "C" int clapgpu_bodies_step(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, double h)
-{
-    int rc = check_bodies2(b);
-    if (rc) return rc;
-    if (!w) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (b->n == 0) return CLAPGPU_OK;
-    WorldK2 wk;
-    memcpy(&wk, w, sizeof(wk));
-    hipLaunchKernelGGL(k_bodies_step<false>, dim3((b->n + PB - 1) / PB), dim3(PB), 0, as_stream(stream), bodies_k(b), wk, h, BinK{});
-    CLAPGPU_LAUNCH_CHECK("k_bodies_step");
-    return CLAPGPU_OK;
-}
 
 // ---------------------------------------------------------------------------------- broadphase object
 struct clapgpu_bp {
@@ -1028,30 +632,6 @@ struct clapgpu_bp {
     uint32_t indexed_n;
     double s_bounds[6];            // union of the statics registered per block (not the large list); min > max: none
 };
-
-// The step + the NEXT broadphase's bin pass in one launch (the bin pass reads nothing but the box the step has in
-// registers, and its one atomic per body hides under the step's fp64 traffic): -1 launch and the boxes' re-read per substep.
-extern "C" int clapgpu_bodies_step_prebin(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, double h, clapgpu_bp *bp)
-{
-    int rc = check_bodies2(b);
-    if (rc) return rc;
-    if (!w || !bp) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (!b->aabb || b->n > bp->n_max) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (b->n == 0) return CLAPGPU_OK;
-    bp->indexed = false;                                         // the step moves the boxes and rebins: the index is stale
-    if (bp->prebinned_aabb) {                                    // a step binned already and no collide consumed it: start over
-        rc = clapgpu_bp_invalidate(stream, bp);
-        if (rc) return rc;
-    }
-    WorldK2 wk;
-    memcpy(&wk, w, sizeof(wk));
-    BinK bin = { bp->cell, bp->k.mask, bp->k.key, bp->k.rank, bp->k.cell_cnt, bp->k.ctrl };
-    hipLaunchKernelGGL(k_bodies_step<true>, dim3((b->n + PB - 1) / PB), dim3(PB), 0, as_stream(stream), bodies_k(b), wk, h, bin);
-    CLAPGPU_LAUNCH_CHECK("k_bodies_step<prebin>");
-    bp->prebinned_aabb = b->aabb;
-    bp->prebinned_n = b->n;
-    return CLAPGPU_OK;
-}
 
 // The boxes a step pre-binned were changed by somebody else (clapgpu_bodies_aabb, an upload, another body count): the cell
 // counters go back to zero -- what k_bp_cells leaves between frames -- and the next collide bins for itself.
@@ -1125,16 +705,16 @@ extern "C" int clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, 
         for (auto &e : ins) s_entries[cur[e.first]++] = e.second;                 // ascending static index inside a bucket
     }
     bp->n_large = (uint32_t)s_large.size();
-    std::vector<BpRec> s_recs(s_entries.size()), s_lrecs(s_large.size() ? s_large.size() : 1);
-    auto fill_rec = [&](BpRec &r, uint32_t sidx) {
+    std::vector<GridRec> s_recs(s_entries.size()), s_lrecs(s_large.size() ? s_large.size() : 1);
+    auto fill_rec = [&](GridRec &r, uint32_t sidx) {
         memset(&r, 0, sizeof(r));
         if (n_static) memcpy(r.bb, static_aabb + 6 * (size_t)sidx, sizeof(r.bb));
         r.idx = sidx;
     };
     for (size_t e = 0; e < ins.size(); e++) fill_rec(s_recs[e], s_entries[e]);
     for (size_t e = 0; e < s_large.size(); e++) fill_rec(s_lrecs[e], s_large[e]);
-    if (ins.empty()) memset(&s_recs[0], 0, sizeof(BpRec));
-    if (s_large.empty()) { memset(&s_lrecs[0], 0, sizeof(BpRec)); s_large.push_back(0); }
+    if (ins.empty()) memset(&s_recs[0], 0, sizeof(GridRec));
+    if (s_large.empty()) { memset(&s_lrecs[0], 0, sizeof(GridRec)); s_large.push_back(0); }
 
     // one device allocation, carved
     size_t off = 0;
@@ -1147,7 +727,7 @@ extern "C" int clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, 
     const size_t o_ctrl = take(4 * 160);
     const size_t o_sstart = take(4 * ((size_t)nb + 1)), o_sent = take(4 * s_entries.size()), o_slarge = take(4 * s_large.size());
     const size_t o_saabb = take(48 * (size_t)(n_static ? n_static : 1));
-    const size_t o_srecs = take(sizeof(BpRec) * s_recs.size()), o_slrecs = take(sizeof(BpRec) * s_lrecs.size());
+    const size_t o_srecs = take(sizeof(GridRec) * s_recs.size()), o_slrecs = take(sizeof(GridRec) * s_lrecs.size());
     const size_t fixed = off;
     if (hipMalloc(&bp->dev, fixed) != hipSuccess) {
         (void)hipGetLastError();
@@ -1159,8 +739,8 @@ extern "C" int clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, 
         hipMemcpy(d + o_sstart, s_count.data(), 4 * ((size_t)nb + 1), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d + o_sent, s_entries.data(), 4 * s_entries.size(), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d + o_slarge, s_large.data(), 4 * s_large.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + o_srecs, s_recs.data(), sizeof(BpRec) * s_recs.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + o_slrecs, s_lrecs.data(), sizeof(BpRec) * s_lrecs.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d + o_srecs, s_recs.data(), sizeof(GridRec) * s_recs.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d + o_slrecs, s_lrecs.data(), sizeof(GridRec) * s_lrecs.size(), hipMemcpyHostToDevice) != hipSuccess ||
         (n_static && hipMemcpy(d + o_saabb, static_aabb, 48 * (size_t)n_static, hipMemcpyHostToDevice) != hipSuccess)) {
         (void)hipGetLastError();
         (void)hipFree(bp->dev);
@@ -1172,7 +752,7 @@ extern "C" int clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, 
     k.cell = cell; k.mask = nb - 1;
     k.cell_cnt = reinterpret_cast<uint32_t *>(d + o_ccnt); k.cell_range = reinterpret_cast<uint2 *>(d + o_crange);
     k.key = reinterpret_cast<uint32_t *>(d + o_key); k.rank = reinterpret_cast<uint32_t *>(d + o_ranks);
-    k.entries = reinterpret_cast<uint32_t *>(d + o_entries); k.recs = reinterpret_cast<BpRec *>(d + o_recs);
+    k.entries = reinterpret_cast<uint32_t *>(d + o_entries); k.recs = reinterpret_cast<GridRec *>(d + o_recs);
     k.cnt = reinterpret_cast<uint32_t *>(d + o_cnt); k.scnt = reinterpret_cast<uint32_t *>(d + o_scnt);
     k.partners = reinterpret_cast<uint32_t *>(d + o_part); k.spartners = reinterpret_cast<uint32_t *>(d + o_spart);
     k.lb_body = reinterpret_cast<uint64_t *>(d + o_lbb); k.lb_static = reinterpret_cast<uint64_t *>(d + o_lbs);
@@ -1180,7 +760,7 @@ extern "C" int clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, 
     k.ctrl = reinterpret_cast<uint32_t *>(d + o_ctrl);
     k.s_start = reinterpret_cast<const uint32_t *>(d + o_sstart); k.s_entries = reinterpret_cast<const uint32_t *>(d + o_sent);
     k.s_large = reinterpret_cast<const uint32_t *>(d + o_slarge); k.s_aabb = reinterpret_cast<const double *>(d + o_saabb);
-    k.s_recs = reinterpret_cast<const BpRec *>(d + o_srecs); k.s_lrecs = reinterpret_cast<const BpRec *>(d + o_slrecs);
+    k.s_recs = reinterpret_cast<const GridRec *>(d + o_srecs); k.s_lrecs = reinterpret_cast<const GridRec *>(d + o_slrecs);
     k.n_large = bp->n_large; k.n_static = n_static;
     *out = bp;
     return CLAPGPU_OK;
@@ -1194,6 +774,45 @@ extern "C" void clapgpu_bp_destroy(clapgpu_bp *bp)
 }
 
 extern "C" const double *clapgpu_bp_static_aabb(const clapgpu_bp *bp) { return bp ? bp->k.s_aabb : nullptr; }
+
+// The object's kernel arguments for the n boxes of `aabb`
+static BpK grid_k(const clapgpu_bp *bp, uint32_t n, const double *aabb)
+{
+    BpK k = bp->k;
+    k.n = n; k.aabb = aabb; k.n_tiles = (n + BP_EMIT_TILE - 1) / BP_EMIT_TILE;
+    return k;
+}
+
+static int launch_bin(hipStream_t s, const BpK &k)
+{
+    hipLaunchKernelGGL(k_bp_bin, dim3((k.n + PB - 1) / PB), dim3(PB), 0, s, k);
+    CLAPGPU_LAUNCH_CHECK("k_bp_bin");
+    return CLAPGPU_OK;
+}
+
+// Launches 1 to 3: the grid of k's boxes in cell order.  Launch 1 is skipped when the step that wrote these boxes binned
+// them (clapgpu_bodies_step_prebin; returned in *prebinned, and used up if `consume`: k_bp_cells zeroes the counters);
+// a prebin for other boxes is undone first.
+static int build_grid(void *stream, clapgpu_bp *bp, const BpK &k, bool consume, bool *prebinned)
+{
+    hipStream_t s = as_stream(stream);
+    *prebinned = bp->prebinned_aabb == k.aabb && bp->prebinned_n == k.n;
+    if (*prebinned) {
+        if (consume) { bp->prebinned_aabb = nullptr; bp->prebinned_n = 0; }
+    } else {
+        if (bp->prebinned_aabb) {                                // binned for other boxes: undo
+            int rc = clapgpu_bp_invalidate(stream, bp);
+            if (rc) return rc;
+        }
+        int rc = launch_bin(s, k);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_bp_cells, dim3((bp->buckets + BP_CELLS_BLOCK / WAVE - 1) / (BP_CELLS_BLOCK / WAVE)), dim3(BP_CELLS_BLOCK), 0, s, k);
+    CLAPGPU_LAUNCH_CHECK("k_bp_cells");
+    hipLaunchKernelGGL(k_bp_scatter, dim3((k.n + PB - 1) / PB), dim3(PB), 0, s, k);
+    CLAPGPU_LAUNCH_CHECK("k_bp_scatter");
+    return CLAPGPU_OK;
+}
 
 extern "C" int clapgpu_bp_collide(void *stream, clapgpu_bp *bp, uint32_t n, const double *aabb,
                                   uint32_t *pairs, uint32_t capacity, uint32_t *pair_total,
@@ -1210,29 +829,30 @@ extern "C" int clapgpu_bp_collide(void *stream, clapgpu_bp *bp, uint32_t n, cons
         if (static_pair_total) CLAPGPU_HIP(hipMemsetAsync(static_pair_total, 0, sizeof(uint32_t), s));
         return clapgpu_bp_invalidate(stream, bp);
     }
-    BpK k = bp->k;
-    k.n = n; k.aabb = aabb; k.n_tiles = (n + BP_EMIT_TILE - 1) / BP_EMIT_TILE;
+    BpK k = grid_k(bp, n, aabb);
     k.pairs = pairs; k.capacity = capacity; k.pair_total = pair_total;
     k.spairs = static_pairs; k.scapacity = static_capacity; k.spair_total = static_pair_total;
     if (!statics) { k.n_static = 0; k.n_large = 0; if (static_pair_total) CLAPGPU_HIP(hipMemsetAsync(static_pair_total, 0, 4, s)); }
-    if (bp->prebinned_aabb == aabb && bp->prebinned_n == n) {
-        bp->prebinned_aabb = nullptr; bp->prebinned_n = 0;       // the step that wrote these boxes binned them: launch 1 is done
-    } else {
-        if (bp->prebinned_aabb) {                                // binned for other boxes: undo
-            int rc = clapgpu_bp_invalidate(stream, bp);
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL(k_bp_bin, dim3((n + PB - 1) / PB), dim3(PB), 0, s, k);
-        CLAPGPU_LAUNCH_CHECK("k_bp_bin");
-    }
-    hipLaunchKernelGGL(k_bp_cells, dim3((bp->buckets + BP_CELLS_BLOCK / WAVE - 1) / (BP_CELLS_BLOCK / WAVE)), dim3(BP_CELLS_BLOCK), 0, s, k);
-    CLAPGPU_LAUNCH_CHECK("k_bp_cells");
-    hipLaunchKernelGGL(k_bp_scatter, dim3((n + PB - 1) / PB), dim3(PB), 0, s, k);
-    CLAPGPU_LAUNCH_CHECK("k_bp_scatter");
+    bool prebinned;
+    int rc = build_grid(stream, bp, k, true, &prebinned);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_bp_search, dim3((n + (PB / WAVE) * BP_TILE - 1) / ((PB / WAVE) * BP_TILE)), dim3(PB), 0, s, k);
     CLAPGPU_LAUNCH_CHECK("k_bp_search");
     hipLaunchKernelGGL(k_bp_emit, dim3(k.n_tiles), dim3(BP_EMIT_TILE), 0, s, k);
     CLAPGPU_LAUNCH_CHECK("k_bp_emit");
+    return CLAPGPU_OK;
+}
+
+// bodies.hip's clapgpu_bodies_step_prebin (bp_grid.h)
+__attribute__((visibility("hidden"))) int clapgpu_bp_prebin(void *stream, clapgpu_bp *bp, uint32_t n, const double *aabb, BinK *bin)
+{
+    if (n > bp->n_max) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    *bin = BinK{ bp->cell, bp->k.mask, bp->k.key, bp->k.rank, bp->k.cell_cnt, bp->k.ctrl };
+    if (n == 0) return CLAPGPU_OK;
+    int rc = clapgpu_bp_invalidate(stream, bp);                  // the step moves the boxes and rebins: the index is stale; a step
+    if (rc) return rc;                                           // binned already and no collide consumed it: start over
+    bp->prebinned_aabb = aabb;
+    bp->prebinned_n = n;
     return CLAPGPU_OK;
 }
 
@@ -1263,26 +883,15 @@ extern "C" int clapgpu_bp_index(void *stream, clapgpu_bp *bp, uint32_t n, const 
     if (n > bp->n_max) return CLAPGPU_ERR_TOO_LARGE;
     bp->indexed = false;
     hipStream_t s = as_stream(stream);
-    BpK k = bp->k;
-    k.n = n; k.aabb = aabb; k.n_tiles = (n + BP_EMIT_TILE - 1) / BP_EMIT_TILE;
+    const BpK k = grid_k(bp, n, aabb);
     CLAPGPU_HIP(hipMemsetAsync(k.ctrl + CTRL_INDEX_WORD, 0xff, INDEX_WORDS * sizeof(uint64_t), s));
     if (n) {
-        const bool prebinned = bp->prebinned_aabb == aabb && bp->prebinned_n == n;
-        if (!prebinned) {
-            if (bp->prebinned_aabb) {                            // binned for other boxes: undo
-                int rc = clapgpu_bp_invalidate(stream, bp);
-                if (rc) return rc;
-            }
-            hipLaunchKernelGGL(k_bp_bin, dim3((n + PB - 1) / PB), dim3(PB), 0, s, k);
-            CLAPGPU_LAUNCH_CHECK("k_bp_bin");
-        }
-        hipLaunchKernelGGL(k_bp_cells, dim3((bp->buckets + BP_CELLS_BLOCK / WAVE - 1) / (BP_CELLS_BLOCK / WAVE)), dim3(BP_CELLS_BLOCK), 0, s, k);
-        CLAPGPU_LAUNCH_CHECK("k_bp_cells");
-        hipLaunchKernelGGL(k_bp_scatter, dim3((n + PB - 1) / PB), dim3(PB), 0, s, k);
-        CLAPGPU_LAUNCH_CHECK("k_bp_scatter");
+        bool prebinned;
+        int rc = build_grid(stream, bp, k, false, &prebinned);
+        if (rc) return rc;
         if (prebinned) {                                         // the counters back, as the prebinning step left them
-            hipLaunchKernelGGL(k_bp_bin, dim3((n + PB - 1) / PB), dim3(PB), 0, s, k);
-            CLAPGPU_LAUNCH_CHECK("k_bp_bin");
+            rc = launch_bin(s, k);
+            if (rc) return rc;
         }
         const uint32_t blocks = (n + PB - 1) / PB;
         hipLaunchKernelGGL(k_bp_index_bounds, dim3(blocks < BP_BOUNDS_BLOCKS ? blocks : BP_BOUNDS_BLOCKS), dim3(PB), 0, s, k);
@@ -1302,30 +911,14 @@ __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp
     if (!bp || !bp->indexed || bp->indexed_n != n || (aabb && bp->indexed_aabb != aabb)) return false;
     v->n = n; v->n_static = bp->n_static; v->cell = bp->cell; v->mask = bp->k.mask; v->n_large = bp->n_large;
     v->cell_range = bp->k.cell_range;
-    v->recs = reinterpret_cast<const GridRec *>(bp->k.recs);
+    v->recs = bp->k.recs;
     v->s_start = bp->k.s_start;
-    v->s_recs = reinterpret_cast<const GridRec *>(bp->k.s_recs);
-    v->s_lrecs = reinterpret_cast<const GridRec *>(bp->k.s_lrecs);
+    v->s_recs = bp->k.s_recs;
+    v->s_lrecs = bp->k.s_lrecs;
     v->index = reinterpret_cast<const uint64_t *>(bp->k.ctrl + CTRL_INDEX_WORD);
     v->ctrl = bp->k.ctrl;
     memcpy(v->s_bounds, bp->s_bounds, sizeof(v->s_bounds));
     return true;
-}
-
-// rays.hip's clapgpu_bodies_ground_collide: the moves
-__attribute__((visibility("hidden"))) int clapgpu_bodies_ground_apply(void *stream, const clapgpu_bodies *b, uint32_t n,
-                                                                      const uint32_t *body, const double *ray_off,
-                                                                      const uint8_t *grounded, uint8_t *grounded_out,
-                                                                      const double *dist, const int32_t *hit, uint32_t *flags,
-                                                                      const uint32_t *moved)
-{
-    int rc = check_bodies2(b);
-    if (rc) return rc;
-    if (n == 0) return CLAPGPU_OK;
-    hipLaunchKernelGGL(k_ground_apply, dim3((n + PB - 1) / PB), dim3(PB), 0, as_stream(stream), bodies_k(b), b->yoffset, n, body,
-                       ray_off, grounded, grounded_out, dist, hit, flags, moved);
-    CLAPGPU_LAUNCH_CHECK("k_ground_apply");
-    return CLAPGPU_OK;
 }
 
 extern "C" int clapgpu_bp_index_status(void *stream, clapgpu_bp *bp, uint32_t *status)

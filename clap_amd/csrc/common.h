@@ -30,6 +30,9 @@ hipError_t launch_error();
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// bodies.hip: what every entry point that takes a clapgpu_bodies asks of it (include/clapgpu.h)
+__attribute__((visibility("hidden"))) int check_bodies(const clapgpu_bodies *b);
+
 // ---------------------------------------------------------------- device side
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 
@@ -179,3 +182,10 @@ __device__ __forceinline__ uint32_t wave_byte_sum(const uint8_t *bytes, uint32_t
 }
 
 } // namespace clapgpu
+
+// bodies.hip: clapgpu_bodies_ground_collide's second launch (rays.hip casts and decides, this moves)
+__attribute__((visibility("hidden"))) int clapgpu_bodies_ground_apply(void *stream, const clapgpu_bodies *b, uint32_t n,
+                                                                      const uint32_t *body, const double *ray_off,
+                                                                      const uint8_t *grounded, uint8_t *grounded_out,
+                                                                      const double *dist, const int32_t *hit, uint32_t *flags,
+                                                                      const uint32_t *moved);

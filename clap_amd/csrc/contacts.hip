@@ -1,7 +1,8 @@
-// contacts.hip -- narrowphase contact records and the capsule sweep, for gfx950 (split from physics2.hip so that this
-// translation unit alone is built with -mllvm -simplifycfg-sink-common=false, see the Makefile).
+// contacts.hip -- narrowphase contact records and the capsule sweep, for gfx950 (a translation unit of its own so that
+// it alone is built with -mllvm -simplifycfg-sink-common=false, see the Makefile).
 //
 //   k_contacts_geoms[_both]  near_callback's dCollide + phys_contact_surface (physics.c:399-449, 291-330)
+//   k_contacts<BOX>          the same for sphere bodies against each other / against static boxes: 104-byte records
 //   k_sweep_capsules         phys_body_sweep_capsule (physics.c:559-670), one wavefront per sweep; <true>: candidates
 //                            that own a mesh of the mesh set collide through its triangles (tricontact_dev.h)
 //   k_mesh_contacts_count / _scan / _write   near_callback for (body, static) pairs whose static owns a mesh: the
@@ -17,11 +18,9 @@
 #include "common.h"
 #include "phys_dev.h"
 #include "geoms_dev.h"
+#include "bp_grid.h"
 #include "trimesh_dev.h"
 #include "tricontact_dev.h"
-
-struct clapgpu_bp;
-unsigned long long *clapgpu_bp_contact_ticket(clapgpu_bp *bp);       // physics2.hip
 
 namespace clapgpu {
 
@@ -30,7 +29,10 @@ constexpr int PB = 256;
 // ================================================================================== narrowphase
 // GeomsK, load_geom, geoms_k: geoms_dev.h (shared with the ray cast)
 
-__device__ __forceinline__ void contact_surface2(clapgpu_contact2 &c, const double *m1, const double *m2)
+// phys_contact_surface (physics.c:291-330) for the two colliders' parameter rows (NULL: defaults), into either record
+// type; nc is the caller's
+template <typename Rec>
+__device__ __forceinline__ void contact_surface(Rec &c, const double *m1, const double *m2)
 {
     double bounce = 0, bounce_vel = 0, mu = 0, soft_erp = 0.05, soft_cfm = 0.01;   // physics.c:293-294
     if (m1 && m2) {
@@ -71,8 +73,8 @@ __device__ __forceinline__ bool contact_of_pair(const GeomsK &A, const GeomsK &B
                 for (int a = 0; a < 3; a++) { c.pos2[a] = c1.pos[a]; c.normal2[a] = c1.normal[a]; }
                 c.depth2 = c1.depth;
             }
-            contact_surface2(c, (A.material && B.material) ? A.material + 5 * (size_t)pr.x : nullptr,
-                             (A.material && B.material) ? B.material + 5 * (size_t)pr.y : nullptr);
+            contact_surface(c, (A.material && B.material) ? A.material + 5 * (size_t)pr.x : nullptr,
+                            (A.material && B.material) ? B.material + 5 * (size_t)pr.y : nullptr);
             c.nc = (uint32_t)nc;
             counted = true;
             // plain read-modify-write: every writer of this launch sets the same bit and nothing else changes the word
@@ -87,16 +89,10 @@ __device__ __forceinline__ bool contact_of_pair(const GeomsK &A, const GeomsK &B
 // (rows padded to 176 bytes: the 16-byte writes of eight neighbouring lanes then fall on all 32 banks) and leaves as ten
 // 1 KiB stores -- written per lane, ten 16-byte pieces at a 160-byte stride touched 64 cache lines per instruction.
 constexpr int CONTACT_ROW = 11;                                          // uint4 per staged record (10 used)
-__device__ __forceinline__ uint32_t contacts_chunk(const GeomsK &A, const GeomsK &B, const uint2 *pairs, uint32_t p0, uint32_t np,
-                                                    clapgpu_contact2 *out, uint32_t *flags_a, uint32_t *flags_b, uint4 *tile)
+__device__ __forceinline__ void store_chunk(const clapgpu_contact2 &c, clapgpu_contact2 *out, uint32_t p0, uint32_t np, uint4 *tile)
 {
     static_assert(sizeof(clapgpu_contact2) == 160, "ten 16-byte pieces");
     const int lane = lane_id();
-    const uint32_t p = p0 + lane;
-    clapgpu_contact2 c;
-    memset(&c, 0, sizeof(c));
-    uint32_t counted = 0;
-    if (p < np) counted = contact_of_pair(A, B, pairs[p], c, flags_a, flags_b);
     uint4 v[10];
     memcpy(v, &c, sizeof(c));
 #pragma unroll
@@ -110,6 +106,17 @@ __device__ __forceinline__ uint32_t contacts_chunk(const GeomsK &A, const GeomsK
         if (idx < pieces) o[idx] = tile[(idx / 10u) * CONTACT_ROW + idx % 10u];
     }
     wave_lds_fence();
+}
+
+__device__ __forceinline__ uint32_t contacts_chunk(const GeomsK &A, const GeomsK &B, const uint2 *pairs, uint32_t p0, uint32_t np,
+                                                    clapgpu_contact2 *out, uint32_t *flags_a, uint32_t *flags_b, uint4 *tile)
+{
+    const uint32_t p = p0 + lane_id();
+    clapgpu_contact2 c;
+    memset(&c, 0, sizeof(c));
+    uint32_t counted = 0;
+    if (p < np) counted = contact_of_pair(A, B, pairs[p], c, flags_a, flags_b);
+    store_chunk(c, out, p0, np, tile);
     return counted;
 }
 
@@ -151,31 +158,12 @@ __device__ __forceinline__ uint32_t contact_from_inputs(const GeomsK &A, const G
         for (int a = 0; a < 3; a++) { c.pos2[a] = c1.pos[a]; c.normal2[a] = c1.normal[a]; }
         c.depth2 = c1.depth;
     }
-    contact_surface2(c, (A.material && B.material) ? A.material + 5 * (size_t)in.pr.x : nullptr,
-                     (A.material && B.material) ? B.material + 5 * (size_t)in.pr.y : nullptr);
+    contact_surface(c, (A.material && B.material) ? A.material + 5 * (size_t)in.pr.x : nullptr,
+                    (A.material && B.material) ? B.material + 5 * (size_t)in.pr.y : nullptr);
     c.nc = (uint32_t)nc;
     if (flags_a && !(in.fa & CLAPGPU_BODY_HAS_JOINT)) flags_a[in.pr.x] = in.fa | CLAPGPU_BODY_HAS_JOINT;
     if (flags_b && !(in.fb & CLAPGPU_BODY_HAS_JOINT)) flags_b[in.pr.y] = in.fb | CLAPGPU_BODY_HAS_JOINT;
     return 1;
-}
-
-// a chunk's 64 records through the wave-private tile and out as ten 1 KiB stores (see contacts_chunk)
-__device__ __forceinline__ void store_chunk(const clapgpu_contact2 &c, clapgpu_contact2 *out, uint32_t p0, uint32_t np, uint4 *tile)
-{
-    const int lane = lane_id();
-    uint4 v[10];
-    memcpy(v, &c, sizeof(c));
-#pragma unroll
-    for (int k = 0; k < 10; k++) tile[lane * CONTACT_ROW + k] = v[k];
-    wave_lds_fence();
-    const uint32_t pieces = (np - p0 < (uint32_t)WAVE ? np - p0 : (uint32_t)WAVE) * 10u;
-    uint4 *o = reinterpret_cast<uint4 *>(out + p0);
-#pragma unroll
-    for (int k = 0; k < 10; k++) {
-        const uint32_t idx = (uint32_t)(k * WAVE + lane);
-        if (idx < pieces) o[idx] = tile[(idx / 10u) * CONTACT_ROW + idx % 10u];
-    }
-    wave_lds_fence();
 }
 
 __device__ __forceinline__ uint32_t chunk_from_pair(const GeomsK &A, const GeomsK &B, uint2 pr, bool in_range, uint32_t p0, uint32_t np,
@@ -270,6 +258,88 @@ void k_contacts_geoms_both(GeomsK A, GeomsK B, const uint2 *pairs, const uint32_
             *word = 0;                                                   // ready for the next launch (stream order)
         }
     }
+}
+
+// ---- sphere bodies, 104-byte records: near_callback's dCollide + phys_contact_surface (see include/clapgpu.h), one lane
+// per candidate pair, IEEE fp64 (sqrt, divide), no contraction.  BOX = false: (body, body) sphere pairs; BOX = true: (body,
+// static box) pairs, `other` = static_aabb, `other_material` = the static colliders' parameter rows.
+template <bool BOX>
+__global__ __launch_bounds__(PB)
+void k_contacts(const double *pos, const double *radius, uint32_t n_bodies, const double *other, uint32_t n_other,
+                const uint2 *pairs, const uint32_t *pair_total, uint32_t capacity, const double *material,
+                const double *other_material, clapgpu_contact *out, uint32_t *contact_total)
+{
+    __shared__ __attribute__((aligned(16))) double recs[PB / WAVE][WAVE * 13];
+    static_assert(sizeof(clapgpu_contact) == 13 * sizeof(double), "contact record layout");
+    const uint32_t n_pairs = *pair_total < capacity ? *pair_total : capacity;
+    const int lane = lane_id();
+    uint32_t found = 0;
+    // the pair count is only known on the device: a fixed grid strides over the pairs (a grid sized for
+    // the capacity spends 50 us launching empty workgroups)
+    for (uint32_t k = blockIdx.x * PB + threadIdx.x; k - lane < n_pairs; k += gridDim.x * PB) {
+    double *rec = recs[threadIdx.x / WAVE];
+    bool touch = false;
+    if (k < n_pairs) {
+        const uint2 pr = pairs[k];
+        clapgpu_contact c;
+        memset(&c, 0, sizeof(c));
+        if (pr.x < n_bodies && pr.y < (BOX ? n_other : n_bodies)) {
+            const double *p1 = pos + 3 * (size_t)pr.x;
+            const double c1[3] = { p1[0], p1[1], p1[2] };
+            phd::CGeom g;
+            const double *m1 = nullptr, *m2 = nullptr;
+            if (BOX) {
+                const double *o = other + 6 * (size_t)pr.y;
+                const double bb[6] = { o[0], o[1], o[2], o[3], o[4], o[5] };
+                touch = phd::collide_sphere_box(c1, radius[pr.x], bb, g) != 0;
+                if (material && other_material) { m1 = material + 5 * (size_t)pr.x; m2 = other_material + 5 * (size_t)pr.y; }
+            } else {
+                const double *o = pos + 3 * (size_t)pr.y;
+                const double c2[3] = { o[0], o[1], o[2] };
+                touch = phd::collide_spheres(c1, radius[pr.x], c2, radius[pr.y], g) != 0;
+                if (material) { m1 = material + 5 * (size_t)pr.x; m2 = material + 5 * (size_t)pr.y; }
+            }
+            if (touch || BOX) {                                              // collide_sphere_box leaves zeros without a contact
+                for (int a = 0; a < 3; a++) { c.pos[a] = g.pos[a]; c.normal[a] = g.normal[a]; }
+                c.depth = g.depth;
+            }
+            if (touch) {
+                contact_surface(c, m1, m2);
+                c.nc = 1;
+            }
+        }
+        // the 104-byte records of a wave are contiguous in memory: stage them in LDS and write the run as
+        // 16-byte pieces (a record per lane straight to memory is 13 scattered 8-byte stores per lane)
+        memcpy(rec + (size_t)lane * 13, &c, sizeof(c));
+    }
+    wave_lds_fence();
+    {
+        const uint32_t wave_first = k - lane;                       // first pair of this wave
+        const uint32_t n_here = wave_first < n_pairs ? (n_pairs - wave_first < WAVE ? n_pairs - wave_first : WAVE) : 0;
+        const uint32_t n16 = n_here * (uint32_t)(sizeof(clapgpu_contact) / 8) / 2;      // 16-byte pieces (104 * 64 % 16 == 0 only for even counts)
+        const double2 *src = reinterpret_cast<const double2 *>(rec);
+        double2 *dst = reinterpret_cast<double2 *>(out + wave_first);
+        if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+            for (uint32_t q = lane; q < n16; q += WAVE) dst[q] = src[q];
+            if ((n_here & 1) && lane == 0)                          // odd count: the last 8 bytes
+                reinterpret_cast<double *>(out + wave_first)[n_here * 13 - 1] = rec[n_here * 13 - 1];
+        } else {
+            for (uint32_t q = lane; q < n_here * 13; q += WAVE)
+                reinterpret_cast<double *>(out + wave_first)[q] = rec[q];
+        }
+    }
+    found += (uint32_t)__popcll(__ballot(touch));
+    wave_lds_fence();                                               // the staging tile is reused by the next trip
+    }
+    // one global atomic per workgroup: same-address atomics serialise at ~12 ns each (4096 of them were
+    // 50 us of this kernel)
+    __shared__ uint32_t block_found;
+    if (threadIdx.x == 0) block_found = 0;
+    __syncthreads();
+    if (lane == 0 && found) atomicAdd(&block_found, found);
+    __syncthreads();
+    if (contact_total && threadIdx.x == 0 && block_found)
+        atomicAdd(contact_total, block_found);
 }
 
 // the probe's box for a BVH query: the segment's box grown by the radius, and by a relative margin so that a triangle
@@ -605,7 +675,7 @@ void k_mesh_contacts_write(GeomsK A, GeomsK B, MeshSet M, const uint2 *pairs, co
             for (int i = 0; i < 3; i++) { c.pos2[i] = c1.pos[i]; c.normal2[i] = c1.normal[i]; }
             c.depth2 = c1.depth;
         }
-        contact_surface2(c, m1, m2);
+        contact_surface(c, m1, m2);
         c.nc = (uint32_t)nc;
         out[o] = c;
         mesh_ref[2 * (size_t)o] = p;
@@ -693,6 +763,50 @@ extern "C" int clapgpu_contacts_geoms_both(void *stream, clapgpu_bp *bp, const c
                        static_contacts, static_contact_total, body_flags,
                        clapgpu_bp_contact_ticket(bp));
     CLAPGPU_LAUNCH_CHECK("k_contacts_geoms_both");
+    return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_contacts_spheres(void *stream, const clapgpu_bodies *b, const uint32_t *pairs,
+                                        const uint32_t *pair_total, uint32_t capacity, const double *material,
+                                        clapgpu_contact *contacts, uint32_t *contact_total)
+{
+    int rc = check_bodies(b);
+    if (rc) return rc;
+    if (!pair_total || (capacity && (!pairs || !contacts)))
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    hipStream_t s = as_stream(stream);
+    if (contact_total)
+        CLAPGPU_HIP(hipMemsetAsync(contact_total, 0, sizeof(uint32_t), s));
+    if (capacity == 0 || b->n == 0)
+        return CLAPGPU_OK;
+    // the pair count lives on the device: launch for the capacity, lanes past the count retire at once
+    const uint32_t blocks = (capacity + PB - 1) / PB;
+    hipLaunchKernelGGL(k_contacts<false>, dim3(blocks < 512 ? blocks : 512), dim3(PB), 0, s,
+                       b->pos, b->radius, b->n, nullptr, 0u, reinterpret_cast<const uint2 *>(pairs), pair_total, capacity,
+                       material, nullptr, contacts, contact_total);
+    CLAPGPU_LAUNCH_CHECK("k_contacts<spheres>");
+    return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_contacts_sphere_box(void *stream, const clapgpu_bodies *b, uint32_t n_static,
+                                           const double *static_aabb, const uint32_t *pairs, const uint32_t *pair_total,
+                                           uint32_t capacity, const double *material, const double *static_material,
+                                           clapgpu_contact *contacts, uint32_t *contact_total)
+{
+    int rc = check_bodies(b);
+    if (rc) return rc;
+    if (!pair_total || (n_static && !static_aabb) || (capacity && (!pairs || !contacts)))
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    hipStream_t s = as_stream(stream);
+    if (contact_total)
+        CLAPGPU_HIP(hipMemsetAsync(contact_total, 0, sizeof(uint32_t), s));
+    if (capacity == 0 || b->n == 0 || n_static == 0)
+        return CLAPGPU_OK;
+    const uint32_t blocks = (capacity + PB - 1) / PB;
+    hipLaunchKernelGGL(k_contacts<true>, dim3(blocks < 512 ? blocks : 512), dim3(PB), 0, s,
+                       b->pos, b->radius, b->n, static_aabb, n_static, reinterpret_cast<const uint2 *>(pairs), pair_total,
+                       capacity, material, static_material, contacts, contact_total);
+    CLAPGPU_LAUNCH_CHECK("k_contacts<sphere_box>");
     return CLAPGPU_OK;
 }
 

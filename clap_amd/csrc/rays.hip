@@ -4,7 +4,7 @@
 //                   that is not the caster; one wavefront per ray, brute force or through an index of the broadphase
 //                   grid (clapgpu_bp_index)
 //   k_ground_rays   phys_body_ground_collide's ray and decision (physics.c:695-744) for a batch of bodies; the moves
-//                   themselves are applied by physics2.hip's k_ground_apply (the device function the step writes
+//                   themselves are applied by bodies.hip's k_ground_apply (the device function the step writes
 //                   geoms with lives there)
 //   k_ray_trimesh   the mesh pass behind either of them: one lane per ray, the walk of the mesh set's BVH
 //                   (trimesh_dev.h; built by trimesh.hip) and the watertight ray-triangle test, merged with the best
@@ -30,11 +30,6 @@
 #include "bp_grid.h"
 #include "trimesh_dev.h"
 #include "tricontact_dev.h"
-
-struct clapgpu_bp;
-int clapgpu_bodies_ground_apply(void *stream, const clapgpu_bodies *b, uint32_t n, const uint32_t *body, const double *ray_off,
-                                const uint8_t *grounded, uint8_t *grounded_out, const double *dist, const int32_t *hit,
-                                uint32_t *flags, const uint32_t *moved);                                      // physics2.hip
 
 namespace clapgpu {
 
@@ -454,7 +449,7 @@ __device__ __forceinline__ uint32_t cast(const CastK &k, const Ray &r, uint32_t 
     // the grid, unless: no index; a box too large for it; boxes binned again since the index (a replayed graph moved
     // them: the device's bin epoch differs); or more pieces than the scan's work
     const bool grid = k.grid && k.g.index[INDEX_OVERSIZE] == ~0ull &&
-                      (k.g.n == 0 || k.g.ctrl[CTRL_BIN_EPOCH] == k.g.ctrl[CTRL_INDEX_EPOCH]);
+                      (k.g.n == 0 || k.g.ctrl[CTRL_EPOCH] == k.g.ctrl[CTRL_INDEX_EPOCH]);
     if (!grid || !scan_grid(k, r, skip_key, b)) scan_all(k, r, skip_key, b);
     reduce_best(b);
     return unresolved(b.other, r.len, b.key, b.depth);
