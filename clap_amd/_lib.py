@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 OK = 0
 ERR_NOMEM = -1
@@ -29,6 +29,9 @@ E_ALIVE = 1 << 31
 RAY_INVALID = 1 << 0
 RAY_UNRESOLVED = 1 << 1
 RAY_MOVED_TARGET = 1 << 2
+SLIDE_INVALID = 1 << 0
+SLIDE_UNRESOLVED = 1 << 1
+SLIDE_MOVED_TARGET = 1 << 2
 UPDATE_ALL_DIRTY = 1 << 0
 
 _ERR_NAMES = {ERR_NOMEM: "NOMEM", ERR_INVALID_ARGUMENTS: "INVALID_ARGUMENTS", ERR_NOT_SUPPORTED: "NOT_SUPPORTED",
@@ -158,6 +161,12 @@ CONTACT_DEEP = 0x80000000
 def mesh_contact_scratch(static_capacity):
     """CLAPGPU_MESH_CONTACT_SCRATCH: uint32 words of scratch clapgpu_contacts_meshes takes."""
     return (int(static_capacity) + 63) // 64 + 1
+
+
+class Slide(C.Structure):
+    """clapgpu_slide (include/clapgpu.h): a batch of movers for clapgpu_characters_slide."""
+    _fields_ = [("n", C.c_uint32), ("body", C.c_void_p), ("velocity", C.c_void_p), ("airborne", C.c_void_p),
+                ("first_frac", C.c_void_p), ("push_hit", C.c_void_p), ("flags", C.c_void_p)]
 
 
 class Characters(C.Structure):
@@ -297,6 +306,10 @@ SYMBOLS = {
                                           C.c_void_p]),
     "clapgpu_sweep_capsules_meshes": (C.c_int, [C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_void_p, C.c_uint32, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_sweep_capsules_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_void_p, C.c_uint32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_characters_slide": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_void_p, C.c_double,
+                                           C.POINTER(Slide), C.c_void_p]),
     "clapgpu_visible_compact_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_characters_update_clock": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),

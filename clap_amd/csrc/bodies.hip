@@ -7,6 +7,7 @@
 //                     <true>: ... and with the next broadphase's bin pass (bp_grid.h)
 //   k_bodies_aabb     the geoms alone
 //   k_ground_apply    phys_body_ground_collide's moves (the rays and the decision: rays.hip)
+//   k_slide_apply     character_apply_velocity's moves (the sweeps and the decision: slide.hip)
 //   k_phys_body_update, k_bodies_rotate_from_entities   body pose -> entity SoA (physics.c:789-812) and back
 //                     (physics.c:136-145)
 // and on the host: the fixed-step schedule, world defaults, and the masses and capsule geoms phys_body_new gives a body.
@@ -247,6 +248,32 @@ void k_ground_apply(BodiesK b, const double *yoffset, uint32_t n, const uint32_t
     write_geom(b, i, p, q);
 }
 
+// clapgpu_characters_slide's last launch (slide.hip sweeps and decides, this moves): the mover's final position, which
+// the decide launch left in its lvel, becomes its pos (dBodySetPosition), lvel becomes 0 (phys_body_set_velocity,
+// character.c:310), then the geom as clapgpu_bodies_aabb writes it.  flags[j] comes in as the decide launch's: an
+// INVALID or UNRESOLVED mover stays; else bits 8.. hold one mover of the batch that gave this mover's probe a contact
+// (index + 1) and bit 7 says there were several: CLAPGPU_SLIDE_MOVED_TARGET when that one moved (moved[] bit 0), or
+// outright when there were several.
+__global__ __launch_bounds__(PB)
+void k_slide_apply(BodiesK b, uint32_t n, const uint32_t *body, uint32_t *flags, const uint32_t *moved)
+{
+    const uint32_t j = blockIdx.x * PB + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t f = flags[j];
+    const uint32_t i = body[j];
+    if (i >= b.n || (f & (CLAPGPU_SLIDE_INVALID | CLAPGPU_SLIDE_UNRESOLVED))) return;
+    uint32_t out = 0;
+    const uint32_t one = f >> 8;
+    if ((f & 0x80u) || (one && one - 1 < b.n && (moved[one - 1] & 1u))) out = CLAPGPU_SLIDE_MOVED_TARGET;
+    flags[j] = out;
+    double *pp = b.pos + 3 * (size_t)i, *vp = b.lvel + 3 * (size_t)i;
+    const double p[3] = { vp[0], vp[1], vp[2] };
+    vp[0] = vp[1] = vp[2] = 0.0;
+    pp[0] = p[0]; pp[1] = p[1]; pp[2] = p[2];
+    const double q[4] = { b.quat[4 * (size_t)i], b.quat[4 * (size_t)i + 1], b.quat[4 * (size_t)i + 2], b.quat[4 * (size_t)i + 3] };
+    write_geom(b, i, p, q);
+}
+
 // phys_body_update (physics.c:789-812): scatter body pose into the entity SoA, mark it dirty
 __global__ __launch_bounds__(PB)
 void k_phys_body_update(uint32_t n, const double *pos, const double *quat, const double *lvel,
@@ -468,6 +495,18 @@ __attribute__((visibility("hidden"))) int clapgpu_bodies_ground_apply(void *stre
     hipLaunchKernelGGL(k_ground_apply, dim3((n + PB - 1) / PB), dim3(PB), 0, as_stream(stream), bodies_k(b), b->yoffset, n, body,
                        ray_off, grounded, grounded_out, dist, hit, flags, moved);
     CLAPGPU_LAUNCH_CHECK("k_ground_apply");
+    return CLAPGPU_OK;
+}
+
+// slide.hip's clapgpu_characters_slide: the moves
+__attribute__((visibility("hidden"))) int clapgpu_bodies_slide_apply(void *stream, const clapgpu_bodies *b, uint32_t n,
+                                                                     const uint32_t *body, uint32_t *flags, const uint32_t *moved)
+{
+    int rc = check_bodies(b);
+    if (rc) return rc;
+    if (n == 0) return CLAPGPU_OK;
+    hipLaunchKernelGGL(k_slide_apply, dim3((n + PB - 1) / PB), dim3(PB), 0, as_stream(stream), bodies_k(b), n, body, flags, moved);
+    CLAPGPU_LAUNCH_CHECK("k_slide_apply");
     return CLAPGPU_OK;
 }
 

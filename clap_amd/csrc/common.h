@@ -189,3 +189,6 @@ __attribute__((visibility("hidden"))) int clapgpu_bodies_ground_apply(void *stre
                                                                       const uint8_t *grounded, uint8_t *grounded_out,
                                                                       const double *dist, const int32_t *hit, uint32_t *flags,
                                                                       const uint32_t *moved);
+// bodies.hip: clapgpu_characters_slide's last launch (slide.hip sweeps and decides, this moves)
+__attribute__((visibility("hidden"))) int clapgpu_bodies_slide_apply(void *stream, const clapgpu_bodies *b, uint32_t n,
+                                                                     const uint32_t *body, uint32_t *flags, const uint32_t *moved);

@@ -215,6 +215,52 @@ class PhysWorld:
         self._sweep_keep = (sb, dl, cf, cd)
         return frac[:ns], normal[:ns], hit[:ns]
 
+    def sweep_capsules_grid(self, sweep_body, delta, grid=True, meshes=True):
+        """phys_body_sweep_capsule for a batch without candidate lists (clapgpu_sweep_capsules_grid): the candidates of a
+        sweep are gathered on the device, through the last bp_index() (grid) or from every geom's box.  Returns device
+        tensors (frac, normal [n, 3], hit, flags)."""
+        dev = self.device
+        ns = len(sweep_body)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt).view(np.int32 if dt == np.uint32 else dt)).to(dev)
+        sb, dl = up(sweep_body, np.uint32), up(np.asarray(delta, np.float32).reshape(-1, 3), np.float32)
+        n1 = max(ns, 1)
+        frac = torch.zeros(n1, dtype=torch.float32, device=dev)
+        normal = torch.zeros((n1, 3), dtype=torch.float32, device=dev)
+        hit = torch.zeros(n1, dtype=torch.int32, device=dev)
+        flags = torch.zeros(n1, dtype=torch.int32, device=dev)
+        sg = self.static_geoms()
+        _lib.check(_lib.lib().clapgpu_sweep_capsules_grid(_stream(), self._bp if grid else None, C.byref(self._desc), C.byref(sg),
+                                                          self._meshes if meshes else None, ns, _ptr(sb), _ptr(dl), _ptr(frac),
+                                                          _ptr(normal), _ptr(hit), _ptr(flags)), "clapgpu_sweep_capsules_grid")
+        self._sweep_grid_keep = (sb, dl)
+        return frac[:ns], normal[:ns], hit[:ns], flags[:ns]
+
+    def slide(self, bodies, velocity, airborne, dt_sec, grid=True, meshes=True):
+        """character_apply_velocity's physics branch for the bodies listed (clapgpu_characters_slide): sweeps and slides
+        them, zeroes their lvel and rewrites their geoms (a body listed twice is flagged SLIDE_INVALID and stays).
+        Returns device tensors (velocity [n, 3] float32, first_frac [n, 2], push_hit [n, 6], flags [n])."""
+        dev = self.device
+        nb = len(bodies)
+        up = lambda a, dt, view=None: torch.from_numpy(np.ascontiguousarray(a, dt).view(view or dt)).to(dev)
+        body_d = up(bodies, np.uint32, np.int32)
+        vel = up(np.asarray(velocity, np.float32).reshape(-1, 3), np.float32) if nb else \
+            torch.zeros((1, 3), dtype=torch.float32, device=dev)
+        air_d = up(np.asarray(airborne) != 0, np.uint8)
+        n1 = max(nb, 1)
+        first = torch.ones((n1, 2), dtype=torch.float32, device=dev)
+        push = torch.full((n1, 6), -1, dtype=torch.int32, device=dev)
+        flags = torch.zeros(n1, dtype=torch.int32, device=dev)
+        scratch = getattr(self, "_slide_scratch", None)          # [n] words of the call's own
+        if scratch is None:
+            scratch = self._slide_scratch = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dev)
+        sg = self.static_geoms()
+        s = _lib.Slide(nb, _ptr(body_d), _ptr(vel), _ptr(air_d), _ptr(first), _ptr(push), _ptr(flags))
+        _lib.check(_lib.lib().clapgpu_characters_slide(_stream(), self._bp if grid else None, C.byref(self._desc), C.byref(sg),
+                                                       self._meshes if meshes else None, float(dt_sec), C.byref(s),
+                                                       _ptr(scratch)), "clapgpu_characters_slide")
+        self._slide_keep = (body_d, air_d, vel, first, push, flags)
+        return vel[:nb], first[:nb], push[:nb], flags[:nb]
+
     def alloc_mesh_contacts(self, capacity=None):
         """The mesh contact list (clapgpu_contact2 records, mesh_ref [k][2]), its totals and scratch."""
         cap = int(capacity if capacity is not None else getattr(self, "mesh_contact_capacity", None) or

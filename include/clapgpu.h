@@ -1099,6 +1099,78 @@ int  clapgpu_sweep_capsules_meshes(void *stream, const clapgpu_geoms *A, const c
                                    uint32_t n_sweeps, const uint32_t *sweep_body, const float *delta, const uint32_t *cand_first,
                                    const uint32_t *cand, float *frac, float *normal, int32_t *hit);
 
+/*
+ * clapgpu_sweep_capsules_grid: clapgpu_sweep_capsules_meshes without candidate lists from the host, as
+ * phys_body_sweep_capsule takes none (it collides the probe with phys->space, physics.c:559-670).  Sweep k behaves as
+ * clapgpu_sweep_capsules_meshes would with this list: every static, then every body (bit 31 set), in ascending index,
+ * whose AABB (statics->aabb, b->aabb) meets the probe's swept box -- the union of b->aabb[sweep_body[k]] and the same
+ * box moved by delta[k], closed overlap.
+ *   - Contacts are taken in candidate order, 16 a step, and a candidate that does not touch contributes none: any
+ *     superset of that list in the same relative order gives the same bits.  The gather may hold more than the box asks
+ *     for (it grows the box by a relative 2^-40; without b->aabb or statics->aabb every geom of that set is held), never
+ *     less.
+ *   - The order is canonical whatever the gather: statics before bodies, each ascending, no geom twice.
+ * bp == NULL: every geom's box is tested (the brute-force path).  Else `bp` must hold an index over (b->n, b->aabb) and
+ * have been created with statics->n statics (CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, as clapgpu_ray_cast), and the
+ * swept box's cells and their blocks' static lists are looked up instead; same bits.  A sweep scans every geom when an
+ * indexed box is larger than a cell, when the boxes were binned again since the index, or when its swept box covers
+ * more cells than a scan tests geoms per lane, or when statics->aabb is NULL.  A list of more than 512 candidates is not kept: that sweep tests every
+ * geom's box at every step (same bits).  meshes: NULL, or created with n_statics == statics->n.
+ * One wavefront per sweep (with a mesh set: per workgroup); no host synchronisation, no allocation: a captured graph can
+ * hold the call.  Nothing moves and the index stays valid.  Out: frac / normal / hit as clapgpu_sweep_capsules, and
+ * flags[k] (may be NULL):
+ *   CLAPGPU_SLIDE_INVALID     sweep_body[k] >= b->n or a non-finite delta: frac 1, normal (0, 1, 0), hit -1
+ *   CLAPGPU_SLIDE_UNRESOLVED  the swept box meets the AABB of a CLAPGPU_GEOM_OTHER static that owns no mesh of `meshes`:
+ *                             the sweep saw nothing of it, the host redoes it
+ */
+#define CLAPGPU_SLIDE_INVALID      1u
+#define CLAPGPU_SLIDE_UNRESOLVED   2u
+#define CLAPGPU_SLIDE_MOVED_TARGET 4u  /* clapgpu_characters_slide: a mover that gave this one's probe a contact moved too */
+int  clapgpu_sweep_capsules_grid(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,
+                                 const clapgpu_trimesh *meshes, uint32_t n_sweeps, const uint32_t *sweep_body,
+                                 const float *delta, float *frac, float *normal, int32_t *hit, uint32_t *flags);
+
+/*
+ * clapgpu_characters_slide: the ENTITY3D_HAS_PHYSICS branch of character_apply_velocity (character.c:254-310) for the
+ * bodies body[k] of a batch, each at most once; velocity[k] = ch->velocity (in / out), airborne[k] = ch->airborne.
+ *   dt_sec   the raw frame delta: below 1e-6 the call changes nothing at all (:259-260, the goto also skips the
+ *            velocity reset); above 1.0 / 30.0 it is 1.0 / 30.0 (:262-263)
+ *   deltas   grounded, or airborne with velocity[1] > 0: vec3_scale(velocity, (float)dt), one character_sweep_delta
+ *            call (min_normal_y -1, stop_on_block true).  Falling: {0, (float)((double)velocity[1] * dt), 0} with
+ *            (0.5, false), then x and z likewise with (-1, true) (:293-298).  velocity[k][1] becomes 0 when the rising
+ *            call or the falling call's vertical sweep returns less than 1 (:283, :299)
+ *   character_sweep_delta (:193-243) in float as written: the |delta| < 1e-6f exit, the normal[1] < min_normal_y
+ *            filter, the move by vec3_scale(delta, frac) when frac > 0 as phys_body_move does it (pos + (double)step),
+ *            the two exits, the projection of the remaining delta with linmath's accumulation order; at most three
+ *            sweeps a call.  Each sweep is clapgpu_sweep_capsules_grid's from the mover's running position.
+ *   first_frac[k][2]  the return value of each character_sweep_delta call, 1 where not made
+ *   push_hit[k][6]    per sweep in call order (call * 3 + iteration): the body phys_body_push would push (frac < 1 after
+ *                     the filter and a body was hit), else -1.  The push itself (dBodyAddForce) is not applied
+ * Then phys_body_set_velocity(0) (:310): the mover's lvel is 0, and one launch writes its final pos, axis, aabb and
+ * geom record as clapgpu_bodies_aabb writes them.  Between the launches a mover's final position travels in its lvel.
+ * One batch, poses from before the call (as clapgpu_bodies_ground_collide): a mover sees its own running position and
+ * everything else where it was before the call.  flags[k]:
+ *   CLAPGPU_SLIDE_INVALID       body[k] >= b->n, a body listed more than once (every listing), or a non-finite delta
+ *   CLAPGPU_SLIDE_UNRESOLVED    a sweep's box met an OTHER static without a mesh
+ *                               -- both move nothing and keep velocity[k]; first_frac 1, push_hit -1
+ *   CLAPGPU_SLIDE_MOVED_TARGET  a body that gave this mover's probe a contact at any step is itself a mover of this
+ *                               batch that ended somewhere else.  The flag is a SUPERSET of that: with contacts from
+ *                               several movers of the batch it is set without asking whether they moved.  The mover has moved: redo those in list order
+ * scratch: [b->n] uint32 of device memory, overwritten.  bp: NULL or an index over (b->n, b->aabb); cleared on return
+ * (bodies moved) unless dt_sec < 1e-6.  No host synchronisation, no allocation.
+ */
+typedef struct clapgpu_slide {
+    uint32_t        n;
+    const uint32_t *body;        /* [n] index into the bodies, each at most once */
+    float          *velocity;    /* [n][3] in/out: character.velocity */
+    const uint8_t  *airborne;    /* [n] character.airborne */
+    float          *first_frac;  /* [n][2] out */
+    int32_t        *push_hit;    /* [n][6] out */
+    uint32_t       *flags;       /* [n] out: CLAPGPU_SLIDE_* */
+} clapgpu_slide;
+int  clapgpu_characters_slide(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,
+                              const clapgpu_trimesh *meshes, double dt_sec, const clapgpu_slide *s, uint32_t *scratch);
+
 /* ======================================================================== */
 /* Characters: the feeder in front of default_update (core/character.c)      */
 /* ======================================================================== */
