@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 OK = 0
 ERR_NOMEM = -1
@@ -135,7 +135,7 @@ class Bodies(C.Structure):
                 ("adis_time_left", C.c_void_p), ("body_entity", C.c_void_p),
                 ("length", C.c_void_p), ("inertia", C.c_void_p), ("geom_offset_R", C.c_double * 12),
                 ("aabb", C.c_void_p), ("axis", C.c_void_p), ("adis_samples", C.c_void_p), ("adis_counter", C.c_void_p),
-                ("geom_records", C.c_void_p)]
+                ("geom_records", C.c_void_p), ("facc", C.c_void_p)]
 
 
 class Geoms(C.Structure):
@@ -153,7 +153,7 @@ class TrimeshDesc(C.Structure):
 
 
 POSE_SKIP_TRS, POSE_SKIP_JOINT_POS, POSE_JOINT_POS_MODEL = 1, 2, 4
-BODY_DISABLED, BODY_AUTO_DISABLE, BODY_NO_GRAVITY, BODY_GYROSCOPIC, BODY_HAS_JOINT = 1, 2, 4, 8, 16
+BODY_DISABLED, BODY_AUTO_DISABLE, BODY_NO_GRAVITY, BODY_GYROSCOPIC, BODY_HAS_JOINT, BODY_KINEMATIC = 1, 2, 4, 8, 16, 32
 GEOM_SPHERE, GEOM_CAPSULE, GEOM_BOX, GEOM_OTHER = 0, 1, 2, 3
 CONTACT_DEEP = 0x80000000
 
@@ -161,6 +161,11 @@ CONTACT_DEEP = 0x80000000
 def mesh_contact_scratch(static_capacity):
     """CLAPGPU_MESH_CONTACT_SCRATCH: uint32 words of scratch clapgpu_contacts_meshes takes."""
     return (int(static_capacity) + 63) // 64 + 1
+
+
+def bodies_push_scratch_bytes(n):
+    """clapgpu_bodies_push_scratch_bytes: bytes of device scratch clapgpu_bodies_push takes for n movers (needs a device)."""
+    return int(lib().clapgpu_bodies_push_scratch_bytes(int(n)))
 
 
 class Slide(C.Structure):
@@ -310,6 +315,9 @@ SYMBOLS = {
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_characters_slide": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_void_p, C.c_double,
                                            C.POINTER(Slide), C.c_void_p]),
+    "clapgpu_bodies_push_scratch_bytes": (C.c_size_t, [C.c_uint32]),
+    "clapgpu_bodies_push": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.c_uint32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_visible_compact_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_characters_update_clock": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),

@@ -5,6 +5,8 @@
 //   k_bodies_step     dWorldQuickStep's body stage (quickstep.cpp stage 0 + dxStepBody + auto-disable), fused with
 //                     the moved geom's axis / AABB (dxCapsule::computeAABB)                      HBM-bound, 1 lane / body
 //                     <true>: ... and with the next broadphase's bin pass (bp_grid.h)
+//                     <.., true>: ... with the force accumulator (dxBody::facc) and kinematic bodies; the gravity-only
+//                     instantiations are what ran before the accumulator existed, instruction for instruction
 //   k_bodies_aabb     the geoms alone
 //   k_ground_apply    phys_body_ground_collide's moves (the rays and the decision: rays.hip)
 //   k_slide_apply     character_apply_velocity's moves (the sweeps and the decision: slide.hip)
@@ -81,9 +83,10 @@ void k_bodies_aabb(BodiesK b)
     write_geom(b, i, p, q);
 }
 
-template <bool BIN>
+// facc: [n][3], read by the FORCES instantiations alone (a trailing argument: the others keep their argument layout)
+template <bool BIN, bool FORCES = false>
 __global__ __launch_bounds__(PB)
-void k_bodies_step(BodiesK b, clapgpu_world w, double h, BinK bin)
+void k_bodies_step(BodiesK b, clapgpu_world w, double h, BinK bin, double *facc)
 {
     const uint32_t i = blockIdx.x * PB + threadIdx.x;
     if (BIN && i == 0) bin.ctrl[CTRL_EPOCH] = bin.ctrl[CTRL_EPOCH] + 1;   // what k_bp_bin's first thread does
@@ -136,6 +139,7 @@ void k_bodies_step(BodiesK b, clapgpu_world w, double h, BinK bin)
     if (fl & CLAPGPU_BODY_HAS_JOINT)
         b.bflags[i] = fl & ~CLAPGPU_BODY_HAS_JOINT;                   // dJointGroupEmpty after the step
 
+    const bool kin = FORCES && (fl & CLAPGPU_BODY_KINEMATIC);           // dBodySetKinematic: invMass 0, invI 0
     double q[4] = { qp[0], qp[1], qp[2], qp[3] };
     double tacc[3] = { 0, 0, 0 }, invIw[12];
     const bool have_inertia = b.inertia != nullptr;
@@ -145,6 +149,8 @@ void k_bodies_step(BodiesK b, clapgpu_world w, double h, BinK bin)
         double R[12];
         phd::q_to_R(q, R);
         phd::world_tensor(R, invIb, invIw);
+        if (FORCES && kin)
+            for (int k = 0; k < 12; k++) invIw[k] = 0;                  // the product below is still formed
         if (fl & CLAPGPU_BODY_GYROSCOPIC) {                             // implicit gyroscopic torque (quickstep.cpp stage 0)
             double Iw[12], L[3], Itild[12], itInv[12];
             phd::world_tensor(R, Ib, Iw);
@@ -170,10 +176,17 @@ void k_bodies_step(BodiesK b, clapgpu_world w, double h, BinK bin)
         }
     }
     const double m = b.mass[i];
-    const double k = h * (1.0 / m);
+    const double k = h * ((FORCES && kin) ? 0.0 : 1.0 / m);
     const bool grav = !(fl & CLAPGPU_BODY_NO_GRAVITY);
-    for (int j = 0; j < 3; j++)
-        v[j] += k * (grav ? m * w.gravity[j] : 0.0);
+    if (FORCES) {
+        double *fp = facc + 3 * (size_t)i;
+        for (int j = 0; j < 3; j++)
+            v[j] += k * (fp[j] + (grav ? m * w.gravity[j] : 0.0));     // facc += m * g, then lvel += (h * invMass) * facc
+        fp[0] = fp[1] = fp[2] = 0;
+    } else {
+        for (int j = 0; j < 3; j++)
+            v[j] += k * (grav ? m * w.gravity[j] : 0.0);
+    }
     if (have_inertia) {
         double d[3];
         tacc[0] *= h; tacc[1] *= h; tacc[2] *= h;
@@ -458,7 +471,12 @@ extern "C" int clapgpu_bodies_step(void *stream, const clapgpu_bodies *b, const 
     if (rc) return rc;
     if (!w) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (b->n == 0) return CLAPGPU_OK;
-    hipLaunchKernelGGL(k_bodies_step<false>, dim3((b->n + PB - 1) / PB), dim3(PB), 0, as_stream(stream), bodies_k(b), *w, h, BinK{});
+    const dim3 grid((b->n + PB - 1) / PB);
+    if (b->facc)
+        hipLaunchKernelGGL((k_bodies_step<false, true>), grid, dim3(PB), 0, as_stream(stream), bodies_k(b), *w, h, BinK{}, b->facc);
+    else
+        hipLaunchKernelGGL((k_bodies_step<false>), grid, dim3(PB), 0, as_stream(stream), bodies_k(b), *w, h, BinK{},
+                           static_cast<double *>(nullptr));
     CLAPGPU_LAUNCH_CHECK("k_bodies_step");
     return CLAPGPU_OK;
 }
@@ -473,7 +491,12 @@ extern "C" int clapgpu_bodies_step_prebin(void *stream, const clapgpu_bodies *b,
     BinK bin;
     rc = clapgpu_bp_prebin(stream, bp, b->n, b->aabb, &bin);
     if (rc || b->n == 0) return rc;
-    hipLaunchKernelGGL(k_bodies_step<true>, dim3((b->n + PB - 1) / PB), dim3(PB), 0, as_stream(stream), bodies_k(b), *w, h, bin);
+    const dim3 grid((b->n + PB - 1) / PB);
+    if (b->facc)
+        hipLaunchKernelGGL((k_bodies_step<true, true>), grid, dim3(PB), 0, as_stream(stream), bodies_k(b), *w, h, bin, b->facc);
+    else
+        hipLaunchKernelGGL((k_bodies_step<true>), grid, dim3(PB), 0, as_stream(stream), bodies_k(b), *w, h, bin,
+                           static_cast<double *>(nullptr));
     const hipError_t err = launch_error();
     if (err != hipSuccess) {                                     // nothing was binned
         (void)clapgpu_bp_invalidate(stream, bp);

@@ -23,9 +23,11 @@ def _stream():
 
 
 class PhysWorld:
-    def __init__(self, bodies, statics=None, pair_capacity=None, device="cuda:0", static_pair_capacity=None, geom_records=True):
+    def __init__(self, bodies, statics=None, pair_capacity=None, device="cuda:0", static_pair_capacity=None, geom_records=True,
+                 forces=False):
         """bodies: dict from synth.sphere_bodies() / synth.capsule_bodies(); statics: float64 [ns, 6]
-        (minx,maxx,miny,maxy,minz,maxz), host array: binned once by clapgpu_bp_create."""
+        (minx,maxx,miny,maxy,minz,maxz), host array: binned once by clapgpu_bp_create.  forces: give the bodies a force
+        accumulator (clapgpu_bodies.facc, zeros or bodies["facc"]): the step consumes it, bodies_push adds to it."""
         self.device = dev = torch.device(device)
         self.n = n = int(bodies["n"])
         t = lambda k, dt: torch.from_numpy(np.ascontiguousarray(bodies[k], dt)).to(dev)
@@ -59,7 +61,10 @@ class PhysWorld:
         # the narrowphase's one-sector view of every body geom (clapgpu_bodies.geom_records), kept by the step / aabb kernels
         self.geom_records = torch.zeros((max(n, 1), 8), dtype=torch.float64, device=dev) if geom_records else None
         d.geom_records = _ptr(self.geom_records)
+        self.facc = None
         self._desc = d
+        if forces:
+            self.enable_forces(bodies.get("facc"))
         self.capacity = int(pair_capacity if pair_capacity is not None else max(8 * n, 1024))
         self.static_capacity = int(static_pair_capacity if static_pair_capacity is not None else self.capacity)
         self.pairs = torch.zeros((self.capacity, 2), dtype=torch.int32, device=dev)
@@ -89,6 +94,14 @@ class PhysWorld:
                 _lib.lib().clapgpu_bp_destroy(bp)
             except Exception:
                 pass
+
+    def enable_forces(self, facc=None):
+        """Give the bodies a force accumulator (clapgpu_bodies.facc; zeros, or facc [n, 3]): from now on the step is the
+        force path -- it adds facc to gravity, honours BODY_KINEMATIC and clears what it consumed."""
+        self.facc = torch.zeros((max(self.n, 1), 3), dtype=torch.float64, device=self.device)
+        if facc is not None and self.n:
+            self.facc[:self.n] = torch.from_numpy(np.ascontiguousarray(facc, np.float64).reshape(-1, 3)).to(self.device)
+        self._desc.facc = _ptr(self.facc)
 
     # ---- __phys_step pieces -----------------------------------------------------------
     def bp_invalidate(self):
@@ -260,6 +273,46 @@ class PhysWorld:
                                                        _ptr(scratch)), "clapgpu_characters_slide")
         self._slide_keep = (body_d, air_d, vel, first, push, flags)
         return vel[:nb], first[:nb], push[:nb], flags[:nb]
+
+    def bodies_push(self, pusher, velocity, push_hit, flags=None, want_pushed=True):
+        """phys_body_push for a slide batch (clapgpu_bodies_push): pusher [n] bodies, velocity [n, 3] float32 as the slide
+        was GIVEN it, push_hit [n, 6] and flags [n] as the slide left them (host arrays or device tensors).  Adds the
+        forces to facc in the reference's order and wakes the pushed bodies.  Returns pushed [self.n] (device), or None."""
+        if self.facc is None:
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "bodies_push", "no force accumulator: PhysWorld(forces=True)")
+        dev = self.device
+
+        def up(a, dt, view=None):
+            if isinstance(a, torch.Tensor):
+                return a.contiguous()
+            return torch.from_numpy(np.ascontiguousarray(a, dt).view(view or dt)).to(dev)
+        n = len(pusher)
+        pu, ve, ph = up(pusher, np.uint32, np.int32), up(velocity, np.float32), up(push_hit, np.int32)
+        fl = None if flags is None else up(flags, np.uint32, np.int32)
+        pushed = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dev) if want_pushed else None
+        scratch = self._push_scratch(n)
+        _lib.check(_lib.lib().clapgpu_bodies_push(_stream(), C.byref(self._desc), C.byref(self.world), n, _ptr(pu), _ptr(ve),
+                                                  _ptr(ph), _ptr(fl), _ptr(pushed), _ptr(scratch)), "clapgpu_bodies_push")
+        self._push_keep = (pu, ve, ph, fl, scratch)
+        return None if pushed is None else pushed[:self.n]
+
+    def _push_scratch(self, n):
+        """the push's device scratch for n movers, kept between calls"""
+        need = _lib.bodies_push_scratch_bytes(n) if n else 0
+        have = getattr(self, "_push_scratch_buf", None)
+        if have is None or have.numel() < need:
+            have = self._push_scratch_buf = torch.zeros(max(need, 256), dtype=torch.uint8, device=self.device)
+        return have
+
+    def slide_and_push(self, bodies, velocity, airborne, dt_sec, grid=True, meshes=True):
+        """slide(), then the pushes of that batch (bodies_push) with the velocity the slide was given: the whole
+        ENTITY3D_HAS_PHYSICS branch of character_apply_velocity.  Returns slide()'s tuple and pushed [self.n]."""
+        given = torch.from_numpy(np.ascontiguousarray(np.asarray(velocity, np.float32).reshape(-1, 3))).to(self.device)
+        vel, first, push, flags = self.slide(bodies, velocity, airborne, dt_sec, grid=grid, meshes=meshes)
+        body_d = self._slide_keep[0]
+        nb = len(bodies)
+        pushed = self.bodies_push(body_d[:nb], given[:nb] if nb else given, push, flags)
+        return vel, first, push, flags, pushed
 
     def alloc_mesh_contacts(self, capacity=None):
         """The mesh contact list (clapgpu_contact2 records, mesh_ref [k][2]), its totals and scratch."""

@@ -692,6 +692,8 @@ typedef struct clapgpu_world {
 #define CLAPGPU_BODY_GYROSCOPIC    (1u << 3)   /* dxBodyGyroscopic: dBodyCreate sets it, dBodySetGyroscopicMode(b, 0) clears it */
 #define CLAPGPU_BODY_HAS_JOINT     (1u << 4)   /* the body holds a (contact) joint this step: ODE never auto-disables a jointless
                                                   body; set by clapgpu_contacts_geoms, cleared by clapgpu_bodies_step */
+#define CLAPGPU_BODY_KINEMATIC     (1u << 5)   /* dBodySetKinematic (physics.c:1031): ODE stores invMass = 0 and a zero invI.  Read by
+                                                  the step's force path only (clapgpu_bodies.facc given, see clapgpu_bodies_step) */
 #define CLAPGPU_GEOM_SPHERE  0
 #define CLAPGPU_GEOM_CAPSULE 1
 #define CLAPGPU_GEOM_BOX     2                 /* an axis-aligned box given by its AABB (stand-in for any static geom) */
@@ -717,6 +719,8 @@ typedef struct clapgpu_world {
  *   axis[n][3]      out: the capsule's axis in world space (column 2 of body R * offset R); may be NULL
  *   adis_average_samples  dBodySetAutoDisableAverageSamplesCount (ODE's default: 1 = the instantaneous
  *                   velocity); > 1 needs adis_samples[n][samples][6] (lvel, avel ring) and adis_counter[n]
+ *   facc[n][3]      in/out: the force accumulator (dxBody::facc): clapgpu_bodies_push adds to it, clapgpu_bodies_step
+ *                   consumes it and leaves 0.  NULL = no accumulated forces: the step integrates gravity alone
  */
 typedef struct clapgpu_bodies {
     uint32_t        n;
@@ -745,6 +749,7 @@ typedef struct clapgpu_bodies {
      * sector instead of four scattered ones (position, axis, radius, length) -- near_callback's gathers were 158 of the
      * contact kernel's 231 MB at configs[3].  16-byte aligned. */
     double         *geom_records;
+    double         *facc;           /* last, so that positional initialisers and zeroed structs keep their meaning */
 } clapgpu_bodies;
 
 /* host helpers for the set-up the reference does once per body (no device work) */
@@ -766,6 +771,21 @@ void clapgpu_world_defaults(clapgpu_world *w);
  * (bodies holding a joint only, averaged over adis_average_samples), gravity, the implicit gyroscopic torque
  * of CLAPGPU_BODY_GYROSCOPIC bodies with an inertia tensor, velocity and pose update, linear damping, then
  * the moved geom's axis and AABB.
+ * With b->facc (ODE 0.16 quickstep for a body without constraint rows, restated; PARITY UNPINNED like this block), for
+ * every enabled body:
+ *   f[j] = facc[j] + (NO_GRAVITY ? 0.0 : m * g[j])            ODE's facc += m * g, in that order
+ *   lvel[j] += (h * invMass) * f[j]                            invMass = 1.0 / m, or 0.0 for a CLAPGPU_BODY_KINEMATIC body
+ *   a KINEMATIC body's world inverse inertia is all zeros: its avel takes nothing from the gyroscopic torque (the
+ *   product with the zero tensor is still formed and added, as ODE does)
+ *   the rest as without forces; then facc[i] = 0 for every body the step stepped.
+ * The accumulator of a DISABLED body -- one that came in disabled, or that this step's auto-disable put to sleep -- is
+ * left untouched: this library's rule (ODE does not step such a body either); clapgpu_bodies_push wakes what it pushes.
+ * Without b->facc the launch is the gravity-only kernel, bit for bit what it was before the accumulator existed, and
+ * CLAPGPU_BODY_KINEMATIC is not looked at: give kinematic bodies an accumulator.
+ * clapgpu_bodies_step_prebin and clapgpu_frame_issue take the same descriptor and behave alike: forces added before a
+ * frame are consumed by its first substep, and survive a frame of 0 substeps.
+ * Waking by contact (ODE's island pass enabling a sleeping body joined to an awake one) is NOT done here: a sleeping body
+ * wakes through clapgpu_bodies_push or through the host clearing CLAPGPU_BODY_DISABLED.
  */
 int clapgpu_bodies_step(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, double h);
 /* The same step, which ALSO does the first launch of the next clapgpu_bp_collide(bp, b->n, b->aabb) -- the bin pass reads
@@ -1145,7 +1165,8 @@ int  clapgpu_sweep_capsules_grid(void *stream, clapgpu_bp *bp, const clapgpu_bod
  *            sweeps a call.  Each sweep is clapgpu_sweep_capsules_grid's from the mover's running position.
  *   first_frac[k][2]  the return value of each character_sweep_delta call, 1 where not made
  *   push_hit[k][6]    per sweep in call order (call * 3 + iteration): the body phys_body_push would push (frac < 1 after
- *                     the filter and a body was hit), else -1.  The push itself (dBodyAddForce) is not applied
+ *                     the filter and a body was hit), else -1.  The push itself (dBodyAddForce): clapgpu_bodies_push, with
+ *                     a copy of velocity[] taken BEFORE this call (it zeroes velocity[k][1])
  * Then phys_body_set_velocity(0) (:310): the mover's lvel is 0, and one launch writes its final pos, axis, aabb and
  * geom record as clapgpu_bodies_aabb writes them.  Between the launches a mover's final position travels in its lvel.
  * One batch, poses from before the call (as clapgpu_bodies_ground_collide): a mover sees its own running position and
@@ -1170,6 +1191,36 @@ typedef struct clapgpu_slide {
 } clapgpu_slide;
 int  clapgpu_characters_slide(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,
                               const clapgpu_trimesh *meshes, double dt_sec, const clapgpu_slide *s, uint32_t *scratch);
+
+/*
+ * clapgpu_bodies_push: the phys_body_push(hit, push_velocity, push_mass) calls of a slide batch (character.c:219-221,
+ * physics.c:677-693: dBodyEnable, then dBodyAddForce), applied as the reference applies them: mover 0's pushes in call
+ * order (slot q = call * 3 + iteration), then mover 1's, and so on.  PARITY UNPINNED (ODE absent).
+ *   pusher[k]     the mover's body (clapgpu_slide.body); its mass is (float)b->mass[pusher[k]], as phys_body_get_mass
+ *                 returns it
+ *   velocity[k]   the velocity character_sweep_delta was given: the slide's INPUT, copied before the slide zeroed
+ *                 velocity[k][1]
+ *   push_hit[k][6], flags[k] (may be NULL: all 0)   as clapgpu_characters_slide left them
+ * The force of slot (k, q) on body h = push_hit[k][q] is (double)(pusher_mass * velocity[k][j]), the product formed in
+ * float.  A slot with h < 0 or h >= b->n pushes nothing; a mover with pusher[k] >= b->n or flags[k] != 0 pushes nothing
+ * (an INVALID, UNRESOLVED or MOVED_TARGET mover is redone by the host, pushes included).  The same body may stand in
+ * many slots and under many movers.  Every pushed body h:
+ *   b->facc[h][j] += each force, one fp64 add per push, in ascending (k, q) order -- the reference's sequential sum, bit
+ *                 for bit, whatever the scheduling (no atomics on the doubles: the slots are sorted by (h, k, q) and one
+ *                 lane walks each body's run)
+ *   dBodyEnable, also on a KINEMATIC body: bflags[h] &= ~CLAPGPU_BODY_DISABLED, adis_steps_left[h] = w->adis_steps,
+ *                 adis_time_left[h] = w->adis_time; the sample ring is left alone
+ *   pushed[h]     (may be NULL) the number of pushes it received; written for all b->n bodies, 0 for the rest
+ * b->facc is required.  n == 0 returns CLAPGPU_OK and touches nothing.  n above 2^28 is CLAPGPU_ERR_TOO_LARGE.
+ * scratch: clapgpu_bodies_push_scratch_bytes(n) bytes of device memory, 256-byte aligned, overwritten (two key arrays and
+ * the sort's work space).  The size depends on the device's sort tuning: the helper needs clapgpu_init to have run and
+ * returns 0 when it cannot tell (or for n == 0 or n too large).  No host synchronisation, no allocation: a captured
+ * graph can hold the call, after the slide it belongs to.
+ */
+size_t clapgpu_bodies_push_scratch_bytes(uint32_t n);
+int  clapgpu_bodies_push(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, uint32_t n, const uint32_t *pusher,
+                         const float *velocity, const int32_t *push_hit, const uint32_t *flags, uint32_t *pushed,
+                         void *scratch);
 
 /* ======================================================================== */
 /* Characters: the feeder in front of default_update (core/character.c)      */
