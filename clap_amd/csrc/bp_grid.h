@@ -1,7 +1,8 @@
 // bp_grid.h -- the broadphase's hash grid as other translation units see it: the cell and slot functions and the bin step
-// that the five k_bp_* launches (broadphase.hip) and the pre-binning body step (bodies.hip) bin with and the ray cast
-// looks cells up with (rays.hip), the record and the control words of a clapgpu_bp, a read-only view of an INDEXED
-// clapgpu_bp (clapgpu_bp_index), and the hidden accessors of broadphase.hip that hand these out.
+// that the five k_bp_* launches (broadphase.hip) and the pre-binning body step (bodies.hip) bin with and the device
+// queries look cells up with (grid_query_dev.h, for rays.hip and slide.hip), the record and the control words of a
+// clapgpu_bp, a read-only view of an INDEXED clapgpu_bp (clapgpu_bp_index), and the hidden accessors of broadphase.hip
+// that hand these out.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,8 +39,8 @@ constexpr int CTRL_STATUS = 2, CTRL_EPOCH = 3, CTRL_CONTACT_WORD = 8;
 // a box edge exceeds `cell`.
 constexpr int CTRL_INDEX_WORD = 16;
 constexpr int INDEX_WORDS = 7, INDEX_OVERSIZE = 6;
-// ... and the bin epoch the index saw last.  A graph replay bins without the host knowing; a differing epoch tells the
-// ray kernel the index is stale.
+// ... and the bin epoch the index saw last.  A graph replay bins without the host knowing; a differing epoch tells a
+// query kernel the index is stale (grid_query_dev.h's grid_usable).
 constexpr int CTRL_INDEX_EPOCH = CTRL_INDEX_WORD + 2 * INDEX_WORDS;       // word 30
 
 // One body into the grid: k_bp_bin's work per body, also done by the step that writes the box it would read
@@ -94,7 +95,7 @@ struct BpGridView {
 
 // ---- broadphase.hip's hidden accessors: struct clapgpu_bp is written and read in that file alone
 struct clapgpu_bp;
-// rays.hip: true when `bp` holds an index over exactly (n, aabb) (aabb == nullptr: any array of n boxes); fills *v
+// geoms_dev.h's scene_grid, for rays.hip and slide.hip: true when `bp` holds an index over exactly (n, aabb) (aabb == nullptr: any array of n boxes); fills *v
 __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp *bp, uint32_t n, const double *aabb, clapgpu::BpGridView *v);
 // contacts.hip: the one-launch form keeps its ticket + counts in the object's control words
 __attribute__((visibility("hidden"))) unsigned long long *clapgpu_bp_contact_ticket(clapgpu_bp *bp);

@@ -36,6 +36,18 @@ __attribute__((visibility("hidden"))) int check_bodies(const clapgpu_bodies *b);
 // ---------------------------------------------------------------- device side
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 
+// The wave's inclusive prefix sum: lane l gets v of lanes 0 .. l (lane WAVE - 1: the total).  All 64 lanes must call it.
+__device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v)
+{
+    const int lane = lane_id();
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const uint32_t u = __shfl_up(v, o);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
 // Orders this wave's LDS writes before its later LDS reads of OTHER lanes' data.
 // The waves of a block use disjoint LDS regions, so no s_barrier is needed: DS
 // operations of one wave execute in issue order; the fence stops the compiler

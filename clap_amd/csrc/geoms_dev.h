@@ -1,9 +1,13 @@
-// geoms_dev.h -- a clapgpu_geoms set as the narrowphase kernels read it (contacts.hip, rays.hip).
+// geoms_dev.h -- a clapgpu_geoms set as the narrowphase kernels read it (contacts.hip, rays.hip, slide.hip), and the
+// host's checks of the scene a device query reads: the bodies' geoms, the mesh set and the broadphase index.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include "clapgpu.h"
 #include "phys_dev.h"
+#include "bp_grid.h"
+#include "trimesh_dev.h"
 
 namespace clapgpu {
 
@@ -46,5 +50,28 @@ static inline clapgpu::GeomsK geoms_k(const clapgpu_geoms *g)
     // the one-sector records stand in for (pos, axis, radius, length) of sphere / capsule sets only
     k.rec = (g->records && !g->kind && !g->aabb && !(reinterpret_cast<uintptr_t>(g->records) & 15u)) ? g->records : nullptr;
     return k;
+}
+
+// ---- the scene checks the device queries share (rays.hip, slide.hip)
+// the bodies' geoms, as PhysWorld.body_geoms; false: capsules need their axis
+static inline bool body_geoms(const clapgpu_bodies *b, clapgpu_geoms *g)
+{
+    memset(g, 0, sizeof(*g));
+    g->n = b->n; g->pos = b->pos; g->axis = b->axis; g->radius = b->radius; g->length = b->length; g->records = b->geom_records;
+    return !b->length || b->axis || b->geom_records;
+}
+
+// The index of a scene's query.  meshes (or NULL) must be built for n_static statics.  bp == NULL: *grid = false.
+// Otherwise bp must be indexed over exactly (n, aabb) (aabb == NULL: any n boxes) and created with n_static statics:
+// *v is its view and *grid = true.
+static inline int scene_grid(const clapgpu_bp *bp, uint32_t n, const double *aabb, uint32_t n_static, const clapgpu_trimesh *meshes,
+                             clapgpu::BpGridView *v, bool *grid)
+{
+    *grid = false;
+    if (meshes && clapgpu::trimesh_set(meshes).n_statics != n_static) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (!bp) return CLAPGPU_OK;
+    if (!clapgpu_bp_grid_view(bp, n, aabb, v) || v->n_static != n_static) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    *grid = true;
+    return CLAPGPU_OK;
 }
 

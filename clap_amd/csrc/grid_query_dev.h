@@ -1,0 +1,139 @@
+// grid_query_dev.h -- reading an INDEXED broadphase grid (bp_grid.h's BpGridView, clapgpu_bp_index) on one wavefront:
+// whether the index may be used, the cells and blocks a box asks for, and the one visit of their records that the ray
+// cast (rays.hip) and the sweep's gather (slide.hip) share.
+//
+// Why the range of a box is complete.  An indexed body is binned by the centre of its box (box_cell) and, while
+// grid_usable holds, no box edge exceeds `cell`: the centre of a body whose box meets [lo, hi] lies within cell / 2 of
+// it on every axis.  cell_coord is monotone, so that centre's cell is one of cell_coord(lo - grow) ..
+// cell_coord(hi + grow) with grow = cell / 2 * (1 + 1e-9), the relative 1e-9 against the rounding of the sums.  A
+// static is registered (clapgpu_bp_create) in every block its box grown by the same half cell reaches, or, when those
+// are too many, in the large list: the blocks of the range and the large list hold every static whose box meets
+// [lo, hi].  Cells and blocks are hashed into buckets, so a lookup may return records of other cells (rejected here by
+// the cell coordinates a body's record carries) and statics of other blocks, and a static comes once per block it is
+// registered in: a visitor sees a superset of the candidates, some of them more than once, and tests each itself.
+#pragma once
+#include "common.h"
+#include "bp_grid.h"
+
+namespace clapgpu {
+
+// The index may be used by this wavefront now: no indexed box is larger than a cell, and the boxes have not been binned
+// again since the index was made (a replayed graph bins without the host knowing: the device's bin epoch differs).
+__device__ __forceinline__ bool grid_usable(const BpGridView &g)
+{
+    return g.index[INDEX_OVERSIZE] == ~0ull && (g.n == 0 || g.ctrl[CTRL_EPOCH] == g.ctrl[CTRL_INDEX_EPOCH]);
+}
+
+struct GridRange {                                      // cells and blocks lo .. hi, inclusive; as constructed: none
+    int32_t c_lo[3] = { 1, 1, 1 }, c_hi[3] = { 0, 0, 0 }, b_lo[3] = { 1, 1, 1 }, b_hi[3] = { 0, 0, 0 };
+};
+
+// the cells, and their blocks, that hold every candidate of the box [lo, hi] (see above)
+__device__ __forceinline__ GridRange grid_range(const BpGridView &g, const double (&lo)[3], const double (&hi)[3])
+{
+    const double grow = g.cell * 0.5 * (1.0 + 1e-9);
+    GridRange r;
+    for (int a = 0; a < 3; a++) {
+        r.c_lo[a] = cell_coord(lo[a] - grow, g.cell);
+        r.c_hi[a] = cell_coord(hi[a] + grow, g.cell);
+        r.b_lo[a] = r.c_lo[a] >> 2; r.b_hi[a] = r.c_hi[a] >> 2;
+    }
+    return r;
+}
+
+// the lookups grid_visit makes for r, cells plus blocks (a double: a far-flung or inverted box's count passes 32 bits)
+__device__ __forceinline__ double grid_lookups(const BpGridView &g, const GridRange &r)
+{
+    double ncell = g.n ? 1.0 : 0.0, nblk = 1.0;
+    for (int a = 0; a < 3; a++) {
+        ncell *= (double)(uint32_t)(r.c_hi[a] - r.c_lo[a] + 1);
+        nblk *= (double)(uint32_t)(r.b_hi[a] - r.b_lo[a] + 1);
+    }
+    return ncell + nblk;
+}
+
+__device__ __forceinline__ bool in_box3(const int32_t (&lo)[3], const int32_t (&hi)[3], int32_t x, int32_t y, int32_t z)
+{
+    return x >= lo[0] && x <= hi[0] && y >= lo[1] && y <= hi[1] && z >= lo[2] && z <= hi[2];
+}
+
+// The visit: every body record of the cells of r and every static registered for its blocks, spread over the lanes.
+// visit(valid, is_static, idx) is called by every lane on every trip (a visitor may ballot); valid: idx is a body the
+// index holds (is_static false) or a registered static.  prev: NULL, or a range whose cells and blocks the caller has
+// visited already; they are not looked up again.  The caller keeps grid_lookups(r) small: the counts are 32-bit here.
+template <typename V>
+__device__ __forceinline__ void grid_visit(const BpGridView &g, const GridRange &r, const GridRange *prev, V &&visit)
+{
+    const int lane = lane_id();
+    uint32_t ext[3], bext[3];
+    for (int a = 0; a < 3; a++) {
+        ext[a] = (uint32_t)(r.c_hi[a] - r.c_lo[a] + 1); bext[a] = (uint32_t)(r.b_hi[a] - r.b_lo[a] + 1);
+    }
+    const uint32_t ncell = g.n ? ext[0] * ext[1] * ext[2] : 0u, nblk = bext[0] * bext[1] * bext[2];
+    const uint32_t items = ncell + nblk;
+    for (uint32_t base = 0; base < items; base += WAVE) {
+        // one lookup per lane: a cell of the range (bodies) or a block (statics)
+        const uint32_t it = base + lane;
+        uint32_t first = 0, count = 0, isstat = 0;
+        int32_t cx = 0, cy = 0, cz = 0;
+        if (it < ncell) {
+            cx = r.c_lo[0] + (int32_t)(it % ext[0]);
+            cy = r.c_lo[1] + (int32_t)((it / ext[0]) % ext[1]);
+            cz = r.c_lo[2] + (int32_t)(it / (ext[0] * ext[1]));
+            if (!prev || !in_box3(prev->c_lo, prev->c_hi, cx, cy, cz)) {
+                const uint2 cr = g.cell_range[cell_slot(cx, cy, cz, g.mask)];
+                first = cr.x; count = cr.y;
+            }
+        } else if (it < items) {
+            const uint32_t q = it - ncell;
+            const int32_t bx = r.b_lo[0] + (int32_t)(q % bext[0]), by = r.b_lo[1] + (int32_t)((q / bext[0]) % bext[1]),
+                          bz = r.b_lo[2] + (int32_t)(q / (bext[0] * bext[1]));
+            if (!prev || !in_box3(prev->b_lo, prev->b_hi, bx, by, bz)) {
+                const uint32_t h = block_hash(bx, by, bz, g.mask);
+                first = g.s_start[h]; count = g.s_start[h + 1] - first;
+            }
+            isstat = 1;
+        }
+        const uint32_t incl = wave_prefix_sum(count);
+        const uint32_t total = __shfl(incl, WAVE - 1), excl = incl - count;
+        // the records of these lookups spread over the lanes: record q belongs to the first lane with incl > q
+        for (uint32_t q0 = 0; q0 < total; q0 += WAVE) {
+            const uint32_t q = q0 + lane;
+            int o = 0;
+#pragma unroll
+            for (int step = 32; step > 0; step >>= 1) {
+                const uint32_t v = __shfl(incl, o + step - 1);
+                if (v <= q) o += step;
+            }
+            const uint32_t ofirst = __shfl(first, o), oexcl = __shfl(excl, o), ostat = __shfl(isstat, o);
+            const int32_t ox = __shfl(cx, o), oy = __shfl(cy, o), oz = __shfl(cz, o);
+            bool valid = q < total;
+            uint32_t idx = 0;
+            if (valid) {
+                const uint32_t e = ofirst + (q - oexcl);
+                if (ostat) {
+                    idx = g.s_recs[e].idx;
+                } else {
+                    const int4 t = reinterpret_cast<const int4 *>(g.recs + e)[3];      // idx, cell coordinates
+                    idx = (uint32_t)t.x;
+                    valid = t.y == ox && t.z == oy && t.w == oz && idx < g.n;          // not a hash neighbour
+                }
+            }
+            visit(valid, ostat != 0, idx);
+        }
+    }
+}
+
+// ... and the large statics, which every query visits whatever its box
+template <typename V>
+__device__ __forceinline__ void grid_visit_large(const BpGridView &g, V &&visit)
+{
+    const int lane = lane_id();
+    for (uint32_t base = 0; base < g.n_large; base += WAVE) {
+        const uint32_t j = base + lane;
+        const bool valid = j < g.n_large;
+        visit(valid, true, valid ? g.s_lrecs[j].idx : 0u);
+    }
+}
+
+} // namespace clapgpu

@@ -15,19 +15,17 @@
 // One deliberate difference: a hit needs 0 <= depth <= length as written, so NaN geometry never hits.
 // fp64 throughout, no FMA contraction.
 //
-// Grid path: the segment is clipped to the indexed boxes' bounds joined with the statics' (grown by a cell), cut into
-// pieces of at most one cell, and every cell in cell_coord(piece lo - grow) .. cell_coord(piece hi + grow) is looked up,
-// grow = cell / 2 * (1 + 1e-9).  A box edge is at most `cell` and a body is binned by its box centre, so a body the
-// segment touches has its centre cell in that range (cell_coord is monotone).  The statics registered for the blocks of
-// the range (their boxes grown by the same half cell at clapgpu_bp_create) and the large list complete the candidates.
-// Every candidate runs the same collider as the brute-force scan and the minimum of (depth, key) does not depend on the
-// order or on duplicates, so both paths give the same bits.
+// Grid path: the segment is clipped to the indexed boxes' bounds joined with the statics' (grown by a cell) and cut into
+// pieces of at most one cell; the cell range of every piece's box, its blocks' statics and the large list are visited
+// through grid_query_dev.h, which says why they hold every geom the piece touches.  Every candidate runs the same
+// collider as the brute-force scan and the minimum of (depth, key) does not depend on the order or on duplicates, so
+// both paths give the same bits.
 #include <string.h>
 #include <stdlib.h>
 #include "common.h"
 #include "phys_dev.h"
 #include "geoms_dev.h"
-#include "bp_grid.h"
+#include "grid_query_dev.h"
 #include "trimesh_dev.h"
 #include "tricontact_dev.h"
 
@@ -326,16 +324,10 @@ __device__ __forceinline__ void scan_all(const CastK &k, const Ray &r, uint32_t 
     for (uint32_t s = lane; s < k.statics.n; s += WAVE) test_geom(r, k.statics, s, KEY_STATIC | s, skip_key, b, k.meshed);
 }
 
-__device__ __forceinline__ bool in_box3(const int32_t (&lo)[3], const int32_t (&hi)[3], int32_t x, int32_t y, int32_t z)
-{
-    return x >= lo[0] && x <= hi[0] && y >= lo[1] && y <= hi[1] && z >= lo[2] && z <= hi[2];
-}
-
 // false: the clipped segment has more pieces than a scan of every geom has candidates per lane (far-flung boxes); the
 // caller scans instead, which also bounds the time one wavefront can spend on a ray
 __device__ bool scan_grid(const CastK &k, const Ray &r, uint32_t skip_key, Best &b)
 {
-    const int lane = lane_id();
     const BpGridView &g = k.g;
 
     // the scene's bounds: indexed boxes joined with the registered statics, grown by a cell
@@ -363,80 +355,24 @@ __device__ bool scan_grid(const CastK &k, const Ray &r, uint32_t skip_key, Best 
     const double limit = 64.0 + (double)(k.bodies.n + k.statics.n) / 256.0;
     if (!(np_d <= limit)) return false;
     const uint32_t np = !pieces ? 0u : np_d < 1.0 ? 1u : (uint32_t)np_d;
-    const double grow = g.cell * 0.5 * (1.0 + 1e-9);
 
-    for (uint32_t j = lane; j < g.n_large; j += WAVE)                       // the large statics: every ray
-        test_geom(r, k.statics, g.s_lrecs[j].idx, KEY_STATIC | g.s_lrecs[j].idx, skip_key, b, k.meshed);
-
-    int32_t pc_lo[3] = { 1, 1, 1 }, pc_hi[3] = { 0, 0, 0 }, pb_lo[3] = { 1, 1, 1 }, pb_hi[3] = { 0, 0, 0 };   // previous piece: none
+    auto test = [&](bool valid, bool is_static, uint32_t i) {
+        if (!valid) return;
+        if (is_static) test_geom(r, k.statics, i, KEY_STATIC | i, skip_key, b, k.meshed);
+        else test_geom(r, k.bodies, i, i, skip_key, b, k.meshed);
+    };
+    grid_visit_large(g, test);
+    GridRange prev;                                                          // the previous piece's: none
     for (uint32_t j = 0; j < np; j++) {
         const double ta = t0 + span * ((double)j / np), tb = (j + 1 == np) ? t1 : t0 + span * ((double)(j + 1) / np);
-        int32_t c_lo[3], c_hi[3], b_lo[3], b_hi[3];
-        uint32_t ext[3], bext[3];
+        double lo[3], hi[3];
         for (int a = 0; a < 3; a++) {
             const double pa = r.s[a] + ta * r.u[a], pb = r.s[a] + tb * r.u[a];
-            c_lo[a] = cell_coord(fmin(pa, pb) - grow, g.cell);
-            c_hi[a] = cell_coord(fmax(pa, pb) + grow, g.cell);
-            b_lo[a] = c_lo[a] >> 2; b_hi[a] = c_hi[a] >> 2;
-            ext[a] = (uint32_t)(c_hi[a] - c_lo[a] + 1); bext[a] = (uint32_t)(b_hi[a] - b_lo[a] + 1);
+            lo[a] = fmin(pa, pb); hi[a] = fmax(pa, pb);
         }
-        const uint32_t ncell = g.n ? ext[0] * ext[1] * ext[2] : 0u, nblk = bext[0] * bext[1] * bext[2];
-        const uint32_t items = ncell + nblk;
-        for (uint32_t base = 0; base < items; base += WAVE) {
-            // one lookup per lane: a cell of the piece's range (bodies) or a block (statics), unless the last piece had it
-            const uint32_t it = base + lane;
-            uint32_t first = 0, count = 0, isstat = 0;
-            int32_t cx = 0, cy = 0, cz = 0;
-            if (it < ncell) {
-                cx = c_lo[0] + (int32_t)(it % ext[0]);
-                cy = c_lo[1] + (int32_t)((it / ext[0]) % ext[1]);
-                cz = c_lo[2] + (int32_t)(it / (ext[0] * ext[1]));
-                if (!in_box3(pc_lo, pc_hi, cx, cy, cz)) {
-                    const uint2 cr = g.cell_range[cell_slot(cx, cy, cz, g.mask)];
-                    first = cr.x; count = cr.y;
-                }
-            } else if (it < items) {
-                const uint32_t q = it - ncell;
-                const int32_t bx = b_lo[0] + (int32_t)(q % bext[0]), by = b_lo[1] + (int32_t)((q / bext[0]) % bext[1]),
-                              bz = b_lo[2] + (int32_t)(q / (bext[0] * bext[1]));
-                if (!in_box3(pb_lo, pb_hi, bx, by, bz)) {
-                    const uint32_t h = block_hash(bx, by, bz, g.mask);
-                    first = g.s_start[h]; count = g.s_start[h + 1] - first;
-                }
-                isstat = 1;
-            }
-            uint32_t incl = count;
-#pragma unroll
-            for (int o = 1; o < WAVE; o <<= 1) {
-                const uint32_t u = __shfl_up(incl, o);
-                if (lane >= o) incl += u;
-            }
-            const uint32_t total = __shfl(incl, WAVE - 1), excl = incl - count;
-            // the candidates of these lookups spread over the lanes: candidate q belongs to the first lane with incl > q
-            for (uint32_t q0 = 0; q0 < total; q0 += WAVE) {
-                const uint32_t q = q0 + lane;
-                int o = 0;
-#pragma unroll
-                for (int step = 32; step > 0; step >>= 1) {
-                    const uint32_t v = __shfl(incl, o + step - 1);
-                    if (v <= q) o += step;
-                }
-                const uint32_t ofirst = __shfl(first, o), oexcl = __shfl(excl, o), ostat = __shfl(isstat, o);
-                const int32_t ox = __shfl(cx, o), oy = __shfl(cy, o), oz = __shfl(cz, o);
-                if (q < total) {
-                    const uint32_t e = ofirst + (q - oexcl);
-                    if (ostat) {
-                        const uint32_t s = g.s_recs[e].idx;
-                        test_geom(r, k.statics, s, KEY_STATIC | s, skip_key, b, k.meshed);
-                    } else {
-                        const int4 t = reinterpret_cast<const int4 *>(g.recs + e)[3];      // idx, cell coordinates
-                        if (t.y == ox && t.z == oy && t.w == oz && (uint32_t)t.x < g.n)    // not a hash neighbour
-                            test_geom(r, k.bodies, (uint32_t)t.x, (uint32_t)t.x, skip_key, b, k.meshed);
-                    }
-                }
-            }
-        }
-        for (int a = 0; a < 3; a++) { pc_lo[a] = c_lo[a]; pc_hi[a] = c_hi[a]; pb_lo[a] = b_lo[a]; pb_hi[a] = b_hi[a]; }
+        const GridRange piece = grid_range(g, lo, hi);
+        grid_visit(g, piece, &prev, test);                                   // what the last piece looked up is skipped
+        prev = piece;
     }
     return true;
 }
@@ -446,11 +382,8 @@ __device__ __forceinline__ uint32_t cast(const CastK &k, const Ray &r, uint32_t 
 {
     b.depth = INFINITY; b.key = KEY_NONE; b.other = INFINITY;
     for (int a = 0; a < 3; a++) { b.pos[a] = 0; b.normal[a] = 0; }
-    // the grid, unless: no index; a box too large for it; boxes binned again since the index (a replayed graph moved
-    // them: the device's bin epoch differs); or more pieces than the scan's work
-    const bool grid = k.grid && k.g.index[INDEX_OVERSIZE] == ~0ull &&
-                      (k.g.n == 0 || k.g.ctrl[CTRL_EPOCH] == k.g.ctrl[CTRL_INDEX_EPOCH]);
-    if (!grid || !scan_grid(k, r, skip_key, b)) scan_all(k, r, skip_key, b);
+    // the grid, unless: no index; the index may not be used (grid_usable); or more pieces than the scan's work
+    if (!k.grid || !grid_usable(k.g) || !scan_grid(k, r, skip_key, b)) scan_all(k, r, skip_key, b);
     reduce_best(b);
     return unresolved(b.other, r.len, b.key, b.depth);
 }
@@ -700,12 +633,7 @@ static int cast_scene(CastK &k, clapgpu_bp *bp, const clapgpu_geoms *bodies, con
     memset(&k, 0, sizeof(k));
     k.bodies = geoms_k(bodies); k.statics = geoms_k(statics);
     k.meshed = meshes ? trimesh_set(meshes).static_mesh : nullptr;
-    if (bp) {
-        if (!clapgpu_bp_grid_view(bp, bodies->n, body_aabb, &k.g) || k.g.n_static != statics->n)
-            return CLAPGPU_ERR_INVALID_ARGUMENTS;                           // not indexed over these bodies and statics
-        k.grid = true;
-    }
-    return CLAPGPU_OK;
+    return scene_grid(bp, bodies->n, body_aabb, statics->n, meshes, &k.g, &k.grid);
 }
 
 // scratch for `other` between the passes: stream-ordered, freed behind the mesh pass
@@ -742,7 +670,6 @@ extern "C" int clapgpu_ray_cast_meshes(void *stream, clapgpu_bp *bp, const clapg
                                        double *dist, int32_t *hit, double *contact, uint32_t *flags)
 {
     if (!bodies || !statics || (n_rays && (!ray || !dist || !hit))) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (meshes && trimesh_set(meshes).n_statics != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;   // built for other statics
     CastK k;
     int rc = cast_scene(k, bp, bodies, nullptr, statics, meshes);
     if (rc) return rc;
@@ -781,11 +708,8 @@ extern "C" int clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (n && (!body || !ray_off || !grounded || !grounded_out || !normal || !dist || !hit || !flags || !scratch))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (meshes && trimesh_set(meshes).n_statics != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    clapgpu_geoms g;                                                         // the bodies' geoms, as PhysWorld.body_geoms
-    memset(&g, 0, sizeof(g));
-    g.n = b->n; g.pos = b->pos; g.axis = b->axis; g.radius = b->radius; g.length = b->length; g.records = b->geom_records;
-    if (b->length && !b->axis && !b->geom_records) return CLAPGPU_ERR_INVALID_ARGUMENTS;   // capsules need their axis
+    clapgpu_geoms g;
+    if (!body_geoms(b, &g)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     CastK k;
     int rc = cast_scene(k, bp, &g, b->aabb, statics, meshes);
     if (rc) return rc;

@@ -18,18 +18,18 @@
 //      order: the grid gather, which meets the candidates in cell order, sorts the words and drops repeats (a static is
 //      registered in every block it reaches).
 // Gathers: the scan of every geom (bp == NULL, or the fallbacks of the ray cast: an indexed box larger than a cell, boxes
-// binned again since the index, or a swept box over more cells than a scan tests geoms per lane), or the cells
-// cell_coord(lo - grow) .. cell_coord(hi + grow) of the swept box and their blocks' statics, grow = cell / 2 * (1 + 1e-9),
-// as rays.hip's scan_grid looks them up (a body is binned by its box centre and its box edge is at most `cell`).  Both
-// keep the words that pass the box test, so they keep the same list.  A list longer than SLIDE_CAND words does not fit
-// the wavefront's LDS: that sweep tests every geom's box at every step instead (same order, same bits, scan time).
+// binned again since the index, or a swept box over more cells than a scan tests geoms per lane), or the swept box's cell
+// range, its blocks' statics and the large list, visited through grid_query_dev.h, which says why they hold every geom
+// whose box meets the swept box.  Both keep the words that pass the box test, so they keep the same list.  A list longer
+// than SLIDE_CAND words does not fit the wavefront's LDS: that sweep tests every geom's box at every step instead (same
+// order, same bits, scan time).
 // fp64 colliders, float sweep arithmetic as the reference writes it, no FMA contraction.
 #include <string.h>
 #include <stdlib.h>
 #include "common.h"
 #include "phys_dev.h"
 #include "geoms_dev.h"
-#include "bp_grid.h"
+#include "grid_query_dev.h"
 #include "trimesh_dev.h"
 #include "tricontact_dev.h"
 #include "sweep_dev.h"
@@ -102,88 +102,21 @@ __device__ __forceinline__ void gather_all(const SlideScene &k, uint32_t self, c
         append(list, count, body_meets(k, base + lane, self, lo, hi), 0x80000000u | (base + lane));
 }
 
-// the swept box's cells and blocks (rays.hip's scan_grid for one piece); false: more lookups than a scan tests geoms per lane
+// the swept box's cells, their blocks' statics and the large statics; false: more lookups than a scan tests geoms per lane
 __device__ bool gather_grid(const SlideScene &k, uint32_t self, const double (&lo)[3], const double (&hi)[3],
                             uint32_t *list, uint32_t &count, bool &other)
 {
-    const int lane = lane_id();
     const BpGridView &g = k.g;
     count = 0;
     other = false;
-    const double grow = g.cell * 0.5 * (1.0 + 1e-9);
-    int32_t c_lo[3], b_lo[3];
-    uint32_t ext[3], bext[3];
-    double ncell_d = g.n ? 1.0 : 0.0, nblk_d = 1.0;
-    for (int a = 0; a < 3; a++) {
-        c_lo[a] = cell_coord(lo[a] - grow, g.cell);
-        const int32_t c_hi = cell_coord(hi[a] + grow, g.cell);
-        b_lo[a] = c_lo[a] >> 2;
-        ext[a] = (uint32_t)(c_hi - c_lo[a] + 1); bext[a] = (uint32_t)((c_hi >> 2) - b_lo[a] + 1);
-        ncell_d *= (double)ext[a]; nblk_d *= (double)bext[a];
-    }
-    if (!(ncell_d + nblk_d <= 64.0 + (double)(k.bodies.n + k.statics.n) / 64.0)) return false;   // also a NaN box
-    const uint32_t ncell = g.n ? ext[0] * ext[1] * ext[2] : 0u, nblk = bext[0] * bext[1] * bext[2];
-    const uint32_t items = ncell + nblk;
-
-    for (uint32_t base = 0; base < g.n_large; base += WAVE) {               // the large statics: every sweep
-        const uint32_t j = base + lane;
-        const uint32_t s = j < g.n_large ? g.s_lrecs[j].idx : CAND_NONE;
-        append(list, count, static_meets(k, s, lo, hi, other), s);
-    }
-    for (uint32_t base = 0; base < items; base += WAVE) {
-        // one lookup per lane: a cell of the range (bodies) or a block (statics)
-        const uint32_t it = base + lane;
-        uint32_t first = 0, cnt = 0, isstat = 0;
-        int32_t cx = 0, cy = 0, cz = 0;
-        if (it < ncell) {
-            cx = c_lo[0] + (int32_t)(it % ext[0]);
-            cy = c_lo[1] + (int32_t)((it / ext[0]) % ext[1]);
-            cz = c_lo[2] + (int32_t)(it / (ext[0] * ext[1]));
-            const uint2 cr = g.cell_range[cell_slot(cx, cy, cz, g.mask)];
-            first = cr.x; cnt = cr.y;
-        } else if (it < items) {
-            const uint32_t q = it - ncell;
-            const int32_t bx = b_lo[0] + (int32_t)(q % bext[0]), by = b_lo[1] + (int32_t)((q / bext[0]) % bext[1]),
-                          bz = b_lo[2] + (int32_t)(q / (bext[0] * bext[1]));
-            const uint32_t h = block_hash(bx, by, bz, g.mask);
-            first = g.s_start[h]; cnt = g.s_start[h + 1] - first;
-            isstat = 1;
-        }
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int o = 1; o < WAVE; o <<= 1) {
-            const uint32_t u = __shfl_up(incl, o);
-            if (lane >= o) incl += u;
-        }
-        const uint32_t total = __shfl(incl, WAVE - 1), excl = incl - cnt;
-        // the records of these lookups spread over the lanes: record q belongs to the first lane with incl > q
-        for (uint32_t q0 = 0; q0 < total; q0 += WAVE) {
-            const uint32_t q = q0 + lane;
-            int o = 0;
-#pragma unroll
-            for (int step = 32; step > 0; step >>= 1) {
-                const uint32_t v = __shfl(incl, o + step - 1);
-                if (v <= q) o += step;
-            }
-            const uint32_t ofirst = __shfl(first, o), oexcl = __shfl(excl, o), ostat = __shfl(isstat, o);
-            const int32_t ox = __shfl(cx, o), oy = __shfl(cy, o), oz = __shfl(cz, o);
-            bool pred = false;
-            uint32_t word = 0;
-            if (q < total) {
-                const uint32_t e = ofirst + (q - oexcl);
-                if (ostat) {
-                    word = g.s_recs[e].idx;
-                    pred = static_meets(k, word, lo, hi, other);
-                } else {
-                    const int4 t = reinterpret_cast<const int4 *>(g.recs + e)[3];      // idx, cell coordinates
-                    if (t.y == ox && t.z == oy && t.w == oz && (uint32_t)t.x < g.n)    // not a hash neighbour
-                        pred = body_meets(k, (uint32_t)t.x, self, lo, hi);
-                    word = 0x80000000u | (uint32_t)t.x;
-                }
-            }
-            append(list, count, pred, word);
-        }
-    }
+    const GridRange range = grid_range(g, lo, hi);
+    if (!(grid_lookups(g, range) <= 64.0 + (double)(k.bodies.n + k.statics.n) / 64.0)) return false;
+    auto take = [&](bool valid, bool is_static, uint32_t i) {
+        const bool pred = valid && (is_static ? static_meets(k, i, lo, hi, other) : body_meets(k, i, self, lo, hi));
+        append(list, count, pred, is_static ? i : 0x80000000u | i);
+    };
+    grid_visit_large(g, take);
+    grid_visit(g, range, nullptr, take);
     return true;
 }
 
@@ -231,9 +164,8 @@ __device__ __forceinline__ uint32_t sweep_once(const SlideScene &k, phd::Geom &p
     swept_box(bb, delta, lo, hi);
     uint32_t count = 0;
     bool other = false;
-    // the grid, unless: no index; a box too large for it; boxes binned again since the index; or too many cells
-    const bool grid = k.grid && k.g.index[INDEX_OVERSIZE] == ~0ull &&
-                      (k.g.n == 0 || k.g.ctrl[CTRL_EPOCH] == k.g.ctrl[CTRL_INDEX_EPOCH]);
+    // the grid, unless: no index; the index may not be used (grid_usable); or too many cells
+    const bool grid = k.grid && grid_usable(k.g);
     wave_lds_fence();                                                        // the list's last readers are done
     if (grid && gather_grid(k, self, lo, hi, list, count, other)) {
         if (count <= SLIDE_CAND) {
@@ -462,22 +394,18 @@ static int slide_scene(SlideScene &k, clapgpu_bp *bp, const clapgpu_bodies *b, c
                        const clapgpu_trimesh *meshes)
 {
     if (!b || !statics || !b->pos || !b->quat || !b->radius) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (b->length && !b->axis && !b->geom_records) return CLAPGPU_ERR_INVALID_ARGUMENTS;   // capsules need their axis
+    clapgpu_geoms g;
+    if (!body_geoms(b, &g)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (b->n >= 0x7fffffffu || statics->n >= 0x7fffffffu) return CLAPGPU_ERR_TOO_LARGE;     // bit 31 of a candidate word
-    if (meshes && trimesh_set(meshes).n_statics != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (bp && !b->aabb) return CLAPGPU_ERR_INVALID_ARGUMENTS;                // an index is over the bodies' own boxes
     memset(&k, 0, sizeof(k));
-    clapgpu_geoms g;                                                         // the bodies' geoms, as PhysWorld.body_geoms
-    memset(&g, 0, sizeof(g));
-    g.n = b->n; g.pos = b->pos; g.axis = b->axis; g.radius = b->radius; g.length = b->length; g.records = b->geom_records;
+    const int rc = scene_grid(bp, b->n, b->aabb, statics->n, meshes, &k.g, &k.grid);
+    if (rc) return rc;
     k.bodies = geoms_k(&g); k.statics = geoms_k(statics);
     k.body_aabb = b->aabb;
     if (meshes) k.M = trimesh_set(meshes);
-    if (bp) {
-        if (!b->aabb || !clapgpu_bp_grid_view(bp, b->n, b->aabb, &k.g) || k.g.n_static != statics->n)
-            return CLAPGPU_ERR_INVALID_ARGUMENTS;                           // not indexed over these bodies and statics
-        // statics without boxes are candidates wherever they are: only the scan of every geom holds them all
-        k.grid = statics->aabb != nullptr || statics->n == 0;
-    }
+    // statics without boxes are candidates wherever they are: only the scan of every geom holds them all
+    if (statics->n && !statics->aabb) k.grid = false;
     return CLAPGPU_OK;
 }
 

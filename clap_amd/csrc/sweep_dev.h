@@ -113,12 +113,7 @@ __device__ __forceinline__ void sweep_march(const GeomsK &A, const GeomsK &B, co
                 }
             }
             // ordinal of this lane's first contact among the step's contacts
-            uint32_t incl = (uint32_t)nc;
-#pragma unroll
-            for (int o = 1; o < WAVE; o <<= 1) {
-                const uint32_t u = __shfl_up(incl, o);
-                if (lane >= o) incl += u;
-            }
+            const uint32_t incl = wave_prefix_sum((uint32_t)nc);
             const uint32_t first = taken + incl - (uint32_t)nc;
             auto take = [&](const phd::CGeom &g, uint32_t i) {
                 if (first + i >= 16) return;

@@ -126,6 +126,66 @@ def test_sweep_grid_oversized_body_scans(cuda_device):
     assert w.bp_index_status() == 1 and (hit[:16] == 7).sum() >= 4      # (the sixteen also stand in each other's way)
 
 
+def aliased_scene(dev):
+    """4 096 bodies, half in a clump and half scattered over a box some 40 blocks wide, so that more blocks are occupied
+    than the grid's 1 024 block buckets; 40 statics with boxes, two of them for the large list, one across a block
+    boundary"""
+    n = 4096
+    b = synth.capsule_bodies(n, box=12.0, seed=61)
+    R = rng(62)
+    b["pos"][n // 2:] = R.uniform(-150.0, 150.0, (n - n // 2, 3))
+    cell = b["cell"]
+    ns = 40
+    lo = R.uniform(-2.0, 14.0, (ns, 3))
+    lo[32:] = R.uniform(-150.0, 150.0, (ns - 32, 3))
+    bb = np.empty((ns, 6))
+    bb[:, 0::2], bb[:, 1::2] = lo, lo + R.uniform(0.5, 3.0, (ns, 3))
+    bb[0] = [-1e3, 1e3, -3.0, -1.0, -1e3, 1e3]              # a ground slab under the clump: the large list
+    bb[1] = [-200, 200, 14, 15, -200, 200]                  # large as well
+    bb[2] = [4 * cell - 0.5, 4 * cell + 0.5, 2, 3, 2, 3]    # across the block boundary at x = 4 cells
+    kind = R.choice([_lib.GEOM_SPHERE, _lib.GEOM_CAPSULE, _lib.GEOM_BOX], ns).astype(np.uint8)
+    kind[:3] = _lib.GEOM_BOX
+    w = physics.PhysWorld(b, bb, device=dev)
+    w.set_static_geoms(kind, *synth.geoms_of_aabbs(bb, kind))
+    return w, b, bb
+
+
+def test_rays_and_sweeps_share_one_lookup_of_an_aliased_index(cuda_device):
+    """both consumers of grid_query_dev.h on one index whose buckets hold several blocks each: the grid path's bytes are
+    the brute-force path's"""
+    w, b, bb = aliased_scene(cuda_device)
+    n = w.n
+    assert n < 32768                                        # the grid's minimum: 1 024 block buckets
+    blocks = np.floor(np.floor(b["pos"] / w.cell) / 4)
+    assert len(np.unique(blocks, axis=0)) > 1024            # pigeonhole: blocks share buckets
+    assert np.floor(bb[2, 0] / (4 * w.cell)) != np.floor(bb[2, 1] / (4 * w.cell))
+    w.bp_index()
+    assert w.bp_index_status() == 0
+    # rays: out of the clump and across the scattered half, from 1 to some 70 cells long (a piece is at most one cell, so
+    # the long ones skip what the piece before looked up), and straight down onto the slab
+    R = rng(63)
+    nr = 4096
+    s = R.uniform(-2.0, 14.0, (nr, 3))
+    s[nr // 2:] = R.uniform(-150.0, 150.0, (nr - nr // 2, 3))
+    d = R.normal(size=(nr, 3))
+    L = R.choice([2.0, 10.0, 40.0, 120.0], nr)
+    s[:256, 1], d[:256], L[:256] = 13.0, [0, -1.0, 0], 40.0
+    g = fetch(w.ray_cast(s, d, L, grid=True))
+    f = fetch(w.ray_cast(s, d, L, grid=False))
+    for name, x, y in zip(("dist", "hit", "contact", "flags"), g, f):
+        assert same_bits(x, y), name
+    sweeps = R.integers(0, n, nr).astype(np.uint32)
+    delta = R.normal(0, 0.7, (nr, 3)).astype(np.float32)
+    sweeps[:256] = np.argsort(b["pos"][:n // 2, 1])[:256]    # the lowest of the clump, down onto the slab
+    delta[:256] = [0, -4, 0]
+    sg = fetch(w.sweep_capsules_grid(sweeps, delta, grid=True))
+    sf = fetch(w.sweep_capsules_grid(sweeps, delta, grid=False))
+    for name, x, y in zip(("frac", "normal", "hit", "flags"), sg, sf):
+        assert same_bits(x, y), name
+    for hit in (g[1], f[1], sg[2], sf[2]):
+        assert (hit >= 0).any() and (hit <= -2).any() and (hit == -1).any()
+
+
 # ------------------------------------------------------------------------------------------------- layer 2
 KEYS = ("pos", "quat", "lvel", "aabb", "axis", "geom_records")
 

@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "clap_amd", "csrc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
          "-Wno-unused-function", "--cuda-device-only", "-S"]
-PER_FILE = {"contacts.hip": ["-mllvm", "-simplifycfg-sink-common=false"]}     # as in the Makefile
+NO_SINK = ["-mllvm", "-simplifycfg-sink-common=false"]
+PER_FILE = {"contacts.hip": NO_SINK, "slide.hip": NO_SINK}                    # as in the Makefile
 
 
 def main():
