@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 OK = 0
 ERR_NOMEM = -1
@@ -168,6 +168,11 @@ def bodies_push_scratch_bytes(n):
     return int(lib().clapgpu_bodies_push_scratch_bytes(int(n)))
 
 
+def bodies_islands_scratch_bytes(n):
+    """clapgpu_bodies_islands_scratch_bytes: bytes of device scratch clapgpu_bodies_islands takes for n bodies."""
+    return int(lib().clapgpu_bodies_islands_scratch_bytes(int(n)))
+
+
 class Slide(C.Structure):
     """clapgpu_slide (include/clapgpu.h): a batch of movers for clapgpu_characters_slide."""
     _fields_ = [("n", C.c_uint32), ("body", C.c_void_p), ("velocity", C.c_void_p), ("airborne", C.c_void_p),
@@ -213,7 +218,8 @@ class Frame(C.Structure):
                 ("flags", C.c_uint32),
                 ("meshes", C.c_void_p), ("mesh_contacts", C.c_void_p), ("mesh_ref", C.c_void_p),
                 ("mesh_contact_capacity", C.c_uint32), ("mesh_contact_total", C.c_void_p), ("mesh_capped", C.c_void_p),
-                ("mesh_scratch", C.c_void_p)]
+                ("mesh_scratch", C.c_void_p),
+                ("island_scratch", C.c_void_p), ("island", C.c_void_p), ("island_woken", C.c_void_p)]
 
 
 LIGHTS_MAX = 128
@@ -318,6 +324,9 @@ SYMBOLS = {
     "clapgpu_bodies_push_scratch_bytes": (C.c_size_t, [C.c_uint32]),
     "clapgpu_bodies_push": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.c_uint32, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_bodies_islands_scratch_bytes": (C.c_size_t, [C.c_uint32]),
+    "clapgpu_bodies_islands": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.c_double, C.c_void_p, C.c_void_p,
+                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_visible_compact_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_characters_update_clock": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),

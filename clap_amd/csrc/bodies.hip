@@ -96,7 +96,9 @@ void k_bodies_step(BodiesK b, clapgpu_world w, double h, BinK bin, double *facc)
     double *pp = b.pos + 3 * (size_t)i, *qp = b.quat + 4 * (size_t)i, *vp = b.lvel + 3 * (size_t)i, *op = b.avel + 3 * (size_t)i;
     double v[3] = { vp[0], vp[1], vp[2] }, om[3] = { op[0], op[1], op[2] };
 
-    // dInternalHandleAutoDisabling: enabled bodies with the flag that hold a joint
+    // dInternalHandleAutoDisabling: enabled bodies with the flag that hold a joint.  The same statements as auto_disable()
+    // of adis_dev.h, which k_islands_seed runs ahead of the island pass; written out here because calling that function
+    // moved this kernel over 128 VGPRs and out of the parent's timing spread (profiles/islands/README.md).  Change both.
     if ((fl & CLAPGPU_BODY_AUTO_DISABLE) && (fl & CLAPGPU_BODY_HAS_JOINT)) {
         bool idle = false;
         double al[3], aa[3];

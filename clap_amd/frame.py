@@ -19,7 +19,7 @@ from . import entities as ent_mod
 
 class FrameLoop:
     def __init__(self, batch, cam, world=None, feed=None, body_links=None, lights=None, characters=None,
-                 particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False):
+                 particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False):
         """batch: EntityBatch.  world: PhysWorld (dynamic bodies write their entities through
         body_entity; character bodies have body_entity = -1).  feed: CharacterFeed.  body_links:
         (link_body, link_entity) of characters / static colliders whose rotation follows the entity.
@@ -29,10 +29,12 @@ class FrameLoop:
         camera.c:191-205); the draw path and the skinning consume joint_transforms alone (model.c:1020-1022), so a frame
         whose skinning runs on the device registers none and the pose writes 64 of its 120 bytes per joint
         (clapgpu_pose_batch.skip).  A model with (joint, path) pairs that have no channel keeps "trs": such a path's
-        value lives there (model.c:1301)."""
+        value lives there (model.c:1301).  islands: every substep wakes sleeping bodies by contact
+        (clapgpu_bodies_islands between its contacts and its step; implies contacts)."""
         self.batch, self.world, self.feed, self.lights = batch, world, feed, lights
         self.characters, self.particles = characters, particles
-        self.body_links, self.contacts = body_links, contacts
+        self.body_links, self.contacts = body_links, contacts or islands
+        self.islands = islands
         self.prebin = prebin        # CLAPGPU_FRAME_PREBIN: the step bins its boxes for the next frame's broadphase (nothing else writes them)
         self._desc = None
         if characters is not None:
@@ -83,6 +85,14 @@ class FrameLoop:
                         f.mesh_contact_capacity = w.mesh_contact_capacity
                         f.mesh_contact_total, f.mesh_capped = w.mesh_contact_total.data_ptr(), w.mesh_capped.data_ptr()
                         f.mesh_scratch = w.mesh_scratch.data_ptr()
+            if self.islands:
+                need = _lib.bodies_islands_scratch_bytes(w.n)
+                if getattr(w, "island_scratch", None) is None or w.island_scratch.numel() < need:
+                    w.island_scratch = torch.zeros(max(need, 256), dtype=torch.uint8, device=w.device)
+                    w.island = torch.zeros(max(w.n, 1), dtype=torch.int32, device=w.device)
+                    w.island_woken = torch.zeros(1, dtype=torch.int32, device=w.device)
+                f.island_scratch, f.island = w.island_scratch.data_ptr(), w.island.data_ptr()
+                f.island_woken = w.island_woken.data_ptr()
             if self.body_links is not None:
                 lb, le = w.upload_links(*self.body_links)
                 f.n_body_links, f.link_body, f.link_entity = len(self.body_links[0]), lb.data_ptr(), le.data_ptr()

@@ -314,6 +314,27 @@ class PhysWorld:
         pushed = self.bodies_push(body_d[:nb], given[:nb] if nb else given, push, flags)
         return vel, first, push, flags, pushed
 
+    def islands(self, h, want_island=True, want_woken=True):
+        """The island pass of dWorldQuickStep (clapgpu_bodies_islands) over the body-body pairs of the last broadphase()
+        and the records of the last contacts_geoms(): the step's auto-disable bookkeeping, then every sleeping body in
+        touch -- directly or through others -- with an awake one is enabled.  Run it between the contacts and
+        world_step(h).  Returns device tensors (island [n]: the smallest body index of each body's component, woken [1]:
+        the number of bodies enabled), None for what was not asked for."""
+        self.alloc_contacts()
+        dev = self.device
+        need = _lib.bodies_islands_scratch_bytes(self.n)
+        if getattr(self, "island_scratch", None) is None or self.island_scratch.numel() < need:
+            self.island_scratch = torch.zeros(max(need, 256), dtype=torch.uint8, device=dev)
+            self.island = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dev)
+            self.island_woken = torch.zeros(1, dtype=torch.int32, device=dev)
+        island = self.island if want_island else None
+        woken = self.island_woken if want_woken else None
+        _lib.check(_lib.lib().clapgpu_bodies_islands(_stream(), C.byref(self._desc), C.byref(self.world), h, _ptr(self.pairs),
+                                                     _ptr(self.pair_total), self.capacity, _ptr(self.contact2_buf),
+                                                     _ptr(self.island_scratch), _ptr(island), _ptr(woken)),
+                   "clapgpu_bodies_islands")
+        return (None if island is None else island[:self.n]), woken
+
     def alloc_mesh_contacts(self, capacity=None):
         """The mesh contact list (clapgpu_contact2 records, mesh_ref [k][2]), its totals and scratch."""
         cap = int(capacity if capacity is not None else getattr(self, "mesh_contact_capacity", None) or
@@ -524,12 +545,23 @@ class PhysWorld:
         """The schedule half of phys_step (physics.c:773-787): number of fixed substeps for this frame."""
         return _lib.lib().clapgpu_phys_step_schedule(C.byref(self.time_acc), dt)
 
-    def phys_step(self, dt, broadphase=True):
-        """phys_step(phys, dt): returns the number of fixed substeps taken."""
+    def phys_step(self, dt, broadphase=True, islands=False):
+        """phys_step(phys, dt): returns the number of fixed substeps taken.  islands: every substep also collides its
+        pairs (contacts_geoms, mesh contacts when there are meshes) and wakes sleeping bodies by contact (islands())."""
         steps = _lib.lib().clapgpu_phys_step_schedule(C.byref(self.time_acc), dt)
+        if islands and not broadphase:
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "phys_step", "islands needs the broadphase's pairs")
         for _ in range(steps):
             if broadphase:
                 self.broadphase()
+            if islands:
+                if self.n_static:
+                    self.contacts_geoms_both()
+                    if self._meshes is not None:
+                        self.contacts_meshes()
+                else:
+                    self.contacts_geoms()
+                self.islands(1.0 / 120.0)
             self.world_step(1.0 / 120.0)
         return steps
 

@@ -691,7 +691,8 @@ typedef struct clapgpu_world {
 
 #define CLAPGPU_BODY_GYROSCOPIC    (1u << 3)   /* dxBodyGyroscopic: dBodyCreate sets it, dBodySetGyroscopicMode(b, 0) clears it */
 #define CLAPGPU_BODY_HAS_JOINT     (1u << 4)   /* the body holds a (contact) joint this step: ODE never auto-disables a jointless
-                                                  body; set by clapgpu_contacts_geoms, cleared by clapgpu_bodies_step */
+                                                  body; set by clapgpu_contacts_geoms, cleared by clapgpu_bodies_step (or, ahead
+                                                  of it, by clapgpu_bodies_islands) */
 #define CLAPGPU_BODY_KINEMATIC     (1u << 5)   /* dBodySetKinematic (physics.c:1031): ODE stores invMass = 0 and a zero invI.  Read by
                                                   the step's force path only (clapgpu_bodies.facc given, see clapgpu_bodies_step) */
 #define CLAPGPU_GEOM_SPHERE  0
@@ -784,8 +785,9 @@ void clapgpu_world_defaults(clapgpu_world *w);
  * CLAPGPU_BODY_KINEMATIC is not looked at: give kinematic bodies an accumulator.
  * clapgpu_bodies_step_prebin and clapgpu_frame_issue take the same descriptor and behave alike: forces added before a
  * frame are consumed by its first substep, and survive a frame of 0 substeps.
- * Waking by contact (ODE's island pass enabling a sleeping body joined to an awake one) is NOT done here: a sleeping body
- * wakes through clapgpu_bodies_push or through the host clearing CLAPGPU_BODY_DISABLED.
+ * Waking by contact (ODE's island pass enabling a sleeping body joined to an awake one) is clapgpu_bodies_islands, run in
+ * front of this call; without it a sleeping body wakes through clapgpu_bodies_push or through the host clearing
+ * CLAPGPU_BODY_DISABLED.
  */
 int clapgpu_bodies_step(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, double h);
 /* The same step, which ALSO does the first launch of the next clapgpu_bp_collide(bp, b->n, b->aabb) -- the bin pass reads
@@ -1222,6 +1224,40 @@ int  clapgpu_bodies_push(void *stream, const clapgpu_bodies *b, const clapgpu_wo
                          const float *velocity, const int32_t *push_hit, const uint32_t *flags, uint32_t *pushed,
                          void *scratch);
 
+/*
+ * clapgpu_bodies_islands: the island pass of dWorldQuickStep (physics.c:769) -- what phys_body_new relies on when it puts
+ * every dynamic body on auto-disable: "ODE re-enables them automatically when another enabled body collides with them"
+ * (physics.c:1034-1042).  ODE 0.16 util.cpp, dxProcessIslands, restated; PARITY UNPINNED (ODE absent).  Run it after a
+ * substep's contact launches (they give the pair list, the records' nc and CLAPGPU_BODY_HAS_JOINT) and before
+ * clapgpu_bodies_step / _step_prebin:
+ *   seed   every enabled body with CLAPGPU_BODY_AUTO_DISABLE and CLAPGPU_BODY_HAS_JOINT does the auto-disable bookkeeping
+ *          of clapgpu_bodies_step (h, the sample ring, both counters, DISABLED and zeroed velocities when both are spent:
+ *          the same statements, the same bits); then CLAPGPU_BODY_HAS_JOINT is cleared on EVERY body (dJointGroupEmpty moved
+ *          forward), so the step that follows does no bookkeeping of its own and integrates the enabled bodies
+ *   link   pair k < min(*pair_total, capacity) joins bodies pairs[2k] and pairs[2k+1] when
+ *          (contacts[k].nc & ~CLAPGPU_CONTACT_DEEP) >= 1; a pair with an index >= b->n or with both indices equal is
+ *          ignored, a pair listed twice is harmless.  A contact with a static or a mesh links nothing; a KINEMATIC body
+ *          links like any other
+ *   wake   a DISABLED body whose component holds at least one body that is enabled after the seed loses
+ *          CLAPGPU_BODY_DISABLED.  Nothing else of it changes (ODE clears the flag without dBodyEnable): counters, sample
+ *          ring, velocities and facc stay.  So a body the seed has just put to sleep beside an awake neighbour is stepped
+ *          in this very substep, from zero velocity, with spent counters; a component without an enabled body sleeps on
+ *   island[i]     (device, may be NULL) the smallest body index of i's component, i itself for a body in no touching pair:
+ *                 the same bits whatever order the atomics took
+ *   *woken_total  (device, may be NULL) the number of flags the wake cleared
+ * A KINEMATIC, DISABLED character that touches an awake dynamic body is enabled too; it has no AUTO_DISABLE flag, so it
+ * stays enabled, and the step treats it as kinematic only when the bodies have an accumulator (b->facc: the rule at
+ * clapgpu_bodies_step).
+ * scratch: clapgpu_bodies_islands_scratch_bytes(b->n) bytes of device memory, 256-byte aligned, overwritten (the
+ * union-find's n parent words, n marks, n roots).  Four launches (three when capacity is 0), no allocation, no host
+ * synchronisation: a captured graph can hold the call.  b->n == 0 returns CLAPGPU_OK and launches nothing.  pairs 8-byte,
+ * contacts 16-byte aligned.
+ */
+size_t clapgpu_bodies_islands_scratch_bytes(uint32_t n);
+int  clapgpu_bodies_islands(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, double h,
+                            const uint32_t *pairs, const uint32_t *pair_total, uint32_t capacity,
+                            const clapgpu_contact2 *contacts, void *scratch, uint32_t *island, uint32_t *woken_total);
+
 /* ======================================================================== */
 /* Characters: the feeder in front of default_update (core/character.c)      */
 /* ======================================================================== */
@@ -1366,6 +1402,11 @@ typedef struct clapgpu_frame {
     clapgpu_contact2 *mesh_contacts; uint32_t *mesh_ref; uint32_t mesh_contact_capacity;
     uint32_t *mesh_contact_total, *mesh_capped;
     uint32_t *mesh_scratch;                    /* CLAPGPU_MESH_CONTACT_SCRATCH(static_pair_capacity) uint32 */
+    /* waking by contact (clapgpu_bodies_islands) in every substep, after its last contact launch and before its step;
+     * island_scratch NULL: none, the frame issues the launches it issued before these fields existed.  Needs pairs,
+     * pair_total, contacts and body_geoms; island / island_woken may be NULL */
+    void     *island_scratch;                  /* clapgpu_bodies_islands_scratch_bytes(bodies->n) bytes, 256-byte aligned */
+    uint32_t *island, *island_woken;
 } clapgpu_frame;
 
 /* Default (0): everything on the caller's stream in the reference's order.  CLAPGPU_FRAME_OVERLAP: the frame's three
