@@ -2,7 +2,7 @@
  * tests/c/fake_clapgpu.c -- TEST INFRASTRUCTURE ONLY.  Never shipped, never linked into clap_amd/, earns no parity credit.
  *
  * A CPU stand-in for the entry points of libclapgpu.so (include/clapgpu.h) that the C host mirror
- * (clap_amd/host/clapgpu_scene.c) and the CLAP-side binding (clap_amd/binding/gpu-scene.c) call, so that those two --
+ * (clap_amd/host/clapgpu_scene*.c) and the CLAP-side binding (clap_amd/binding/gpu-scene.c) call, so that those two --
  * the largest and most pointer-heavy host C of the product: handle tables, tombstones, re-tiling, a hand-rolled worker
  * pool, the write-back policies -- can run in a container WITHOUT a GPU under -fsanitize=address,undefined and
  * -fsanitize=thread (tests/test_sanitize_host.py builds oracle/ref/dropin.c against it).  The reference's debug preset

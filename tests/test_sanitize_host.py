@@ -1,7 +1,7 @@
 """The host C of the product under sanitizers, in a container without a GPU.
 
 clap_amd/binding/gpu-scene.c (records, hash, tombstones, re-tiling, the worker pool, the write-back policies) and
-clap_amd/host/clapgpu_scene.c (handle table, tiler, upload image, stale / fetch bookkeeping) are the largest and most
+clap_amd/host/clapgpu_scene*.c (handle table, tiler, upload image, stale / fetch bookkeeping) are the largest and most
 pointer-heavy host C here; the reference's debug preset runs ASan + UBSan over ITS host code
 (the reference's CMakeLists.txt:17-18, 33-39).  The drop-in checker (oracle/ref/dropin.c: the reference's own mq /
 entity3d objects on both sides) is linked here against tests/c/fake_clapgpu.c -- a CPU stand-in for libclapgpu.so's
@@ -177,10 +177,13 @@ def test_api_orderings_fuzzed_under_asan():
 def test_mirror_edits_in_place_under_asan_ubsan():
     """tests/c/test_scene.c -- the host mirror driven like CLAP's frame loop, every frame against the oracle -- linked
     against the CPU stand-in and run under the sanitizers: its four frames of clapgpu_scene_entity_new_placed /
-    _delete_placed edit the standing layout (growth tiles included) without a re-tile."""
+    _delete_placed edit the standing layout (growth tiles included) without a re-tile.  Then the same twelve frames, tile and
+    level layout, with every slot staged through copies and with every slot zero-copy: both frame entry points
+    (clapgpu_scene_mq_update, clapgpu_scene_attached_update) on each of the mirror's three transports."""
     exe = os.path.join(OUT, "test_scene_fake")
     os.makedirs(OUT, exist_ok=True)
-    srcs = [os.path.join(ROOT, "tests", "c", "test_scene.c"), os.path.join(ROOT, "clap_amd", "host", "clapgpu_scene.c"),
+    import glob
+    srcs = [os.path.join(ROOT, "tests", "c", "test_scene.c"), *sorted(glob.glob(os.path.join(ROOT, "clap_amd", "host", "clapgpu_scene*.c"))),
             os.path.join(ROOT, "clap_amd", "host", "clapgpu_snapshot.c"), os.path.join(ROOT, "tests", "c", "fake_clapgpu.c"),
             os.path.join(ROOT, "oracle", "entity.c"), os.path.join(ROOT, "oracle", "lod.c")]
     p = subprocess.run(["gcc", "-O1", "-g", "-std=gnu11", "-fsanitize=address,undefined", "-w", "-I", os.path.join(ROOT, "include"),
@@ -202,6 +205,15 @@ def test_mirror_edits_in_place_under_asan_ubsan():
         assert "AddressSanitizer" not in p.stderr and "runtime error:" not in p.stderr, p.stderr[-3000:]
         layouts = re.findall(r"layout ([0-9a-f]{16})", p.stderr)
         assert len(layouts) >= 4 and layouts == re.findall(r"layout ([0-9a-f]{16})", q.stderr), "slot for slot the serial re-tile's layout"
+    # both frame entry points on the other two transports: staged copies (no slot is zero-copy) and mapped memory (every slot
+    # is; `wide` is the level layout, whose frames export through a second launch)
+    for mode in ([], ["wide"]):
+        for slots, path in (("0", "staged path"), ("4294967295", "small-frame path")):
+            p = subprocess.run([exe, *mode], capture_output=True, text=True, timeout=600,
+                               env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0", CLAPGPU_SCENE_ZERO_COPY_SLOTS=slots))
+            assert p.returncode == 0 and "PASS" in p.stdout and p.stdout.count("frame ok") == 12, p.stdout[-2000:] + p.stderr[-3000:]
+            assert path in p.stdout, (mode, slots, p.stdout[-2000:])
+            assert "AddressSanitizer" not in p.stderr and "runtime error:" not in p.stderr, p.stderr[-3000:]
     # a long run: lanes recycled, growth tiles, rows that fill up (the edit falls back, the frame re-tiles, then in place again)
     p = subprocess.run([exe, "tiles", "5", "80"], capture_output=True, text=True, timeout=900, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     assert p.returncode == 0 and "PASS" in p.stdout and p.stdout.count("frame ok") == 88, p.stdout[-1500:] + p.stderr[-2000:]

@@ -1,4 +1,4 @@
-"""The C host mirror (include/clapgpu_scene.h, clap_amd/host/clapgpu_scene.c).
+"""The C host mirror (include/clapgpu_scene.h, clap_amd/host/clapgpu_scene*.c).
 
 CPU: it builds as plain C11, exports what its header declares, and a C program using it links.
 GPU: tests/c/test_scene.c drives it like CLAP's frame loop (create in any order, move,
