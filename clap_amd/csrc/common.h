@@ -113,6 +113,14 @@ __device__ __forceinline__ void store_stream(float4 *dst, const float4 &v)
     __builtin_nontemporal_store(t, reinterpret_cast<clapgpu_f4 *>(dst));
 #endif
 }
+// ... and the pieces of a row that are no float4 (overloads, not a template: deduction drops clapgpu_f3's alignment)
+#ifdef CLAPGPU_PLAIN_STORES
+__device__ __forceinline__ void store_stream(clapgpu_f2 *dst, const clapgpu_f2 v) { *dst = v; }
+__device__ __forceinline__ void store_stream(clapgpu_f3 *dst, const clapgpu_f3 v) { *dst = v; }
+#else
+__device__ __forceinline__ void store_stream(clapgpu_f2 *dst, const clapgpu_f2 v) { __builtin_nontemporal_store(v, dst); }
+__device__ __forceinline__ void store_stream(clapgpu_f3 *dst, const clapgpu_f3 v) { __builtin_nontemporal_store(v, dst); }
+#endif
 
 // dst = first matrix of the wave's 64; nvalid = leading lanes whose matrix is stored
 template <bool STREAM = true>

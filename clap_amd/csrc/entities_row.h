@@ -1,8 +1,12 @@
-// entities_row.h -- what the entity kernels share: the kernel-argument structs, the per-row input loads and
-// process_row (one 64-entity row on one wavefront).  Included by entities.hip (the level / tile kernels) and by
-// entities_host.hip (the one-launch small frame of a host mirror); two translation units on purpose: with the small-frame
-// kernel in the same module the compiler scheduled k_entities_tiles differently (8 more instructions, registers
-// renumbered), and that kernel's store / wait structure is measured work that no other feature may move.
+// entities_row.h -- what the entity kernels share: the kernel-argument structs, the per-row input loads, process_row
+// (one 64-entity row on one wavefront), the further views' cull and the completion word of a launch a host polls.
+// Included by entities.hip (the level / tile kernels), by entities_host.hip (the one-launch small frame of a host
+// mirror), by visible.hip (the cull-only pass) and by entities_edit.hip (the export).  entities.hip and entities_host.hip
+// are two translation units on purpose: with the small-frame kernel in the same module the compiler scheduled
+// k_entities_tiles differently (8 more instructions, registers renumbered), and that kernel's store / wait structure is
+// measured work that no other feature may move.  The other two files were split off by concern; the kernels
+// they took left k_entities_tiles' module without moving it (profiles/entities_split).  The host side of the argument
+// structs is entities_args.h.
 #pragma once
 #include <string.h>
 #include <math.h>
@@ -47,6 +51,11 @@ struct XViewsK {
     uint64_t *o_mask[CLAPGPU_EXTRA_VIEWS_MAX];       // HOST kernels: the mirror's mapped words, or NULL
     lmd::FrustumK fr[CLAPGPU_EXTRA_VIEWS_MAX];
 };
+
+// The kernels that cull further views are the plain ones with an XViewsK as one more, trailing argument (a parameter pack
+// that is empty or that): the pointer process_row takes, for either.
+__device__ __forceinline__ const XViewsK *xviews_ptr() { return nullptr; }
+__device__ __forceinline__ const XViewsK *xviews_ptr(const XViewsK &xv) { return &xv; }
 
 // The further views of a row whose main view has just been tested: `base` = the lanes that are ALIVE and VISIBLE (the
 // draw predicate without its frustum term), bb = the boxes the main view was tested against.  Returns the union of the
@@ -218,6 +227,31 @@ __device__ __forceinline__ bool point_in_box(const float (&p)[3], const float (&
     return p[0] >= bb[0] && p[0] <= bb[3] && p[1] >= bb[1] && p[1] <= bb[4] && p[2] >= bb[2] && p[2] <= bb[5];
 }
 
+// The two heavy steps of a rebuilt row -- or, in the sensitivity builds only (tools/entities_sensitivity.sh; common.h
+// guards the switches), cheap stand-ins that keep the data flow and give WRONG results.
+__device__ __forceinline__ void row_inverse(float (&inv)[16], const float (&mx)[16])
+{
+#ifdef CLAPGPU_EXP_NO_INVERT
+#pragma unroll
+    for (int k = 0; k < 16; k++) inv[k] = mx[k];
+#else
+    lmd::invert(inv, mx);
+#endif
+}
+
+// lo, hi: the model's box as the model table holds it (min.xyz, max.xyz)
+__device__ __forceinline__ void row_box(float (&bb)[6], float (&ctr)[3], const float (&mx)[16], const float4 &lo, const float4 &hi)
+{
+#ifdef CLAPGPU_EXP_NO_AABB
+#pragma unroll
+    for (int k = 0; k < 6; k++) bb[k] = mx[12 + k % 3] + (k < 3 ? lo.x : hi.x);
+#pragma unroll
+    for (int k = 0; k < 3; k++) ctr[k] = mx[12 + k];
+#else
+    lmd::world_aabb(bb, ctr, mx, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z);
+#endif
+}
+
 // One 64-entity row (= one vis_mask word) processed by one wave.
 //   row_first  first entity of the row (multiple of 64), row_count valid lanes (1..64)
 //   tile       8 KiB of wave-private LDS
@@ -319,25 +353,11 @@ __device__ __forceinline__ void process_row(const EntK &e, const RowIn &in, floa
 #pragma unroll
             for (int k = 0; k < 16; k++) mx[k] = local_mx[k];
         }
-#ifdef CLAPGPU_EXP_NO_INVERT                                     // sensitivity experiments only (tools/entities_sensitivity.sh): wrong results
-#pragma unroll
-        for (int k = 0; k < 16; k++) inv[k] = mx[k];
-#else
-        lmd::invert(inv, mx);
-#endif
+        row_inverse(inv, mx);
 
         has_aabb = __float_as_uint(lo.w) == 0u;                  // model.c:1204
-#ifdef CLAPGPU_EXP_NO_AABB
-        if (has_aabb) {
-#pragma unroll
-            for (int k = 0; k < 6; k++) bb[k] = mx[12 + k % 3] + (k < 3 ? lo.x : hi.x);
-#pragma unroll
-            for (int k = 0; k < 3; k++) ctr[k] = mx[12 + k];
-        }
-#else
         if (has_aabb)
-            lmd::world_aabb(bb, ctr, mx, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z);
-#endif
+            row_box(bb, ctr, mx, lo, hi);
 
         seq = (seq + 1) & 0xffffu;                               // uint16 wrap (model.h:404)
         e.seqs[i] = seq | (pseq << 16);
@@ -501,6 +521,22 @@ __device__ __forceinline__ void process_row(const EntK &e, const RowIn &in, floa
     }
 }
 
+// How a launch tells a polling host that its results are in mapped memory.  Every thread of every workgroup calls this
+// last: each workgroup releases its stores to the system and arrives at the counter, the last one to arrive resets the
+// counter for the next launch (stream order) and raises the completion word.
+__device__ __forceinline__ void raise_done_when_last(uint32_t *counter, uint32_t *done, const uint32_t done_value)
+{
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t arrived = atomicAdd(counter, 1u);
+        if (arrived == gridDim.x - 1) {
+            *counter = 0;
+            __threadfence_system();
+            __hip_atomic_store(done, done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
 
 // entities_host.hip
 int launch_entities_tiles_host(hipStream_t stream, bool cull, const lmd::FrustumK &fr, const EntK &e, const HostIO &h,

@@ -232,7 +232,7 @@ LMD bool aabb_in_frustum(const Frustum &f, const float (&bb)[6])
 }
 
 // Kernel-side frustum: the reference's planes/corners plus per-axis extremes of the 8
-// frustum corners, precomputed on the host (make_frustum_k in entities.hip).
+// frustum corners, precomputed on the host (make_frustum_k in entities_args.h).
 struct FrustumK {
     Frustum  f;
     float    cmin[3];      // min_i corners[i][ax], NaN if any is NaN

@@ -12,7 +12,7 @@
 //                           prefix over the per-row popcounts + bits below it in its row), jumps
 //                           the LCG ahead by 7 * rank draws (affine-map power, mod 2^48) and
 //                           regenerates position and velocity.
-//      (above 4M particles: ordered compaction (entities.hip) + k_particles_respawn over the list)
+//      (above 4M particles: ordered compaction (visible.hip) + k_particles_respawn over the list)
 //
 // HBM: 36 B / particle (pos 12 + vel 12 read, pos 12 written; pos doubles as the pos_array
 // the renderer uploads, particle.c:116,124).  Respawns are rare, passes 2-3 are tiny.

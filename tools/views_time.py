@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What a further view costs inside the entity update's launch: BASELINE configs[1] (1 M entities, all dirty) with 0, 1, 2 and 4
-extra frusta culled by the same launch (k_entities_tiles<true> / k_entities_tiles_xv), against a separate k_entities_cull pass
+extra frusta culled by the same launch (k_entities_tiles<true> / k_entities_tiles<true, XViewsK>), against a separate k_entities_cull pass
 per view.      python tools/views_time.py [launches]
 """
 import os
