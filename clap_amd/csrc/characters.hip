@@ -8,6 +8,7 @@
 // only and stays host code, like character_move()'s ODE sweeps.  The chained orig_update =
 // default_update is the entity kernel: run this first, it sets CLAPGPU_E_DIRTY on what it moves.
 //
+// Also animated_update's clock (model.c:1563-1592), alone (k_animation_time) and fused with the hooks.
 // One lane per character; state is SoA (history 96 B + 5 B per character).  C3 has 50 k characters:
 // ~10 MB of traffic, launch-latency bound.
 #include <string.h>
@@ -46,10 +47,29 @@ void k_characters_update(CharK k)
     character_update(k, c);
 }
 
-// The character hooks and animated_update's clock (model.c:1563-1592; k_animation_time in pose.hip: the same four lines)
-// as ONE launch: two per-character passes over different state, neither reads what the other writes, and both sit in
-// front of kernels that need them (entity update / pose) -- as two launches the second cost a dependent launch's latency
-// for 7 us of work.  Blocks [0, char_blocks) run the hooks, the rest the clock.
+// animated_update's clock (model.c:1563-1592) for character c
+__device__ __forceinline__ void animation_clock_step(const clapgpu_anim_clock &k, uint32_t c, double now, const double *now_dev)
+{
+    if (now_dev) now = *now_dev;
+    const double ft = (now - k.ani_time[c]) * (double)k.speed[c];
+    k.frame_time[c] = (float)ft;
+    const uint32_t an = k.anim[c];
+    const bool ended = an < k.n_anims && ft >= (double)k.time_end[an];
+    k.ended[c] = ended ? 1 : 0;
+    if (ended && k.restart[c])
+        k.ani_time[c] = now;                                        // animation_next -> animation_start
+}
+
+__global__ __launch_bounds__(256)
+void k_animation_time(clapgpu_anim_clock k, double now, const double *now_dev)
+{
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c < k.n_chars) animation_clock_step(k, c, now, now_dev);
+}
+
+// The character hooks and the clock as ONE launch: two per-character passes over different state, neither reads what
+// the other writes, and both sit in front of kernels that need them (entity update / pose) -- as two launches the
+// second cost a dependent launch's latency for 7 us of work.  Blocks [0, char_blocks) run the hooks, the rest the clock.
 __global__ __launch_bounds__(CHAR_BLOCK)
 void k_characters_update_clock(CharK k, uint32_t char_blocks, clapgpu_anim_clock clk, double now, const double *now_dev)
 {
@@ -59,15 +79,7 @@ void k_characters_update_clock(CharK k, uint32_t char_blocks, clapgpu_anim_clock
         return;
     }
     const uint32_t c = (blockIdx.x - char_blocks) * CHAR_BLOCK + threadIdx.x;
-    if (c >= clk.n_chars) return;
-    if (now_dev) now = *now_dev;
-    const double ft = (now - clk.ani_time[c]) * (double)clk.speed[c];
-    clk.frame_time[c] = (float)ft;
-    const uint32_t an = clk.anim[c];
-    const bool ended = an < clk.n_anims && ft >= (double)clk.time_end[an];
-    clk.ended[c] = ended ? 1 : 0;
-    if (ended && clk.restart[c])
-        clk.ani_time[c] = now;                                      // animation_next -> animation_start
+    if (c < clk.n_chars) animation_clock_step(clk, c, now, now_dev);
 }
 
 __device__ __forceinline__ void character_update(const CharK &k, uint32_t c)
@@ -152,6 +164,31 @@ extern "C" int clapgpu_characters_update(void *stream, const clapgpu_characters 
                        as_stream(stream), k);
     CLAPGPU_LAUNCH_CHECK("k_characters_update");
     return CLAPGPU_OK;
+}
+
+static int animation_time_launch(void *stream, const clapgpu_anim_clock *clk, double now, const double *now_dev)
+{
+    if (!clk)
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (clk->n_chars == 0)
+        return CLAPGPU_OK;
+    if (!clk->anim || !clk->time_end || !clk->ani_time || !clk->speed || !clk->restart || !clk->frame_time || !clk->ended)
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    hipLaunchKernelGGL(k_animation_time, dim3((clk->n_chars + 255) / 256), dim3(256), 0, as_stream(stream), *clk, now, now_dev);
+    CLAPGPU_LAUNCH_CHECK("k_animation_time");
+    return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_animation_time(void *stream, const clapgpu_anim_clock *clk, double now)
+{
+    return animation_time_launch(stream, clk, now, nullptr);
+}
+
+extern "C" int clapgpu_animation_time_dev(void *stream, const clapgpu_anim_clock *clk, const double *now_dev)
+{
+    if (!now_dev)
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    return animation_time_launch(stream, clk, 0.0, now_dev);
 }
 
 // clapgpu_characters_update + clapgpu_animation_time(_dev) in one launch (now_dev != NULL: the clock's `now` from a device

@@ -30,6 +30,9 @@ hipError_t launch_error();
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// runtime.hip: the calling thread's current device and its CU count (asked of the runtime once per device)
+__attribute__((visibility("hidden"))) int current_device_cus(int *dev, int *n_cus);
+
 // bodies.hip: what every entry point that takes a clapgpu_bodies asks of it (include/clapgpu.h)
 __attribute__((visibility("hidden"))) int check_bodies(const clapgpu_bodies *b);
 

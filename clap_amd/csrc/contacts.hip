@@ -555,21 +555,21 @@ void k_mesh_contacts_write(GeomsK A, GeomsK B, MeshSet M, const uint2 *pairs, co
 
 using namespace clapgpu;
 
-// workgroups of PB threads of `kernel` that fit the device at once (`cached`: per kernel, asked once).
+// workgroups of PB threads of `kernel` that fit the current device at once (`cached`: per kernel and thread, asked once per device).
 // CLAPGPU_CONTACTS_GRID, read at every call, overrides it: the A/B knob, and how the tests make every wavefront walk many chunks
-static uint32_t resident_workgroups(const void *kernel, uint32_t *cached)
+struct Resident { int dev = -1; uint32_t groups = 0; };
+static uint32_t resident_workgroups(const void *kernel, Resident *cached)
 {
     const char *g = getenv("CLAPGPU_CONTACTS_GRID");
     if (g && atoi(g) > 0) return (uint32_t)atoi(g);
-    if (!*cached) {
-        int per_cu = 0, cus = 0, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, PB, 0) != hipSuccess)
-            *cached = 2048;
-        else
-            *cached = (uint32_t)(per_cu > 0 ? per_cu : 1) * (uint32_t)(cus > 0 ? cus : 1);
+    int per_cu = 0, cus = 0, dev = 0;
+    if (current_device_cus(&dev, &cus) != CLAPGPU_OK) return 2048;
+    if (cached->dev != dev) {
+        const bool ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, PB, 0) == hipSuccess;
+        cached->groups = ok ? (uint32_t)(per_cu > 0 ? per_cu : 1) * (uint32_t)(cus > 0 ? cus : 1) : 2048u;
+        cached->dev = dev;                                               // last: a matching dev means groups is set
     }
-    return *cached;
+    return cached->groups;
 }
 
 extern "C" int clapgpu_contacts_geoms(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B, const uint32_t *pairs,
@@ -586,7 +586,7 @@ extern "C" int clapgpu_contacts_geoms(void *stream, const clapgpu_geoms *A, cons
     if (capacity == 0 || A->n == 0 || B->n == 0)
         return CLAPGPU_OK;
     const uint32_t blocks = (capacity + PB - 1) / PB;
-    static uint32_t cached;                                              // (see clapgpu_contacts_geoms_both)
+    static thread_local Resident cached;                                 // (see clapgpu_contacts_geoms_both)
     const uint32_t resident = resident_workgroups(reinterpret_cast<const void *>(k_contacts_geoms), &cached);
     hipLaunchKernelGGL(k_contacts_geoms, dim3(blocks < resident ? blocks : resident), dim3(PB), 0, s, geoms_k(A), geoms_k(B),
                        reinterpret_cast<const uint2 *>(pairs), pair_total, capacity, contacts, contact_total, body_flags_a,
@@ -616,7 +616,7 @@ extern "C" int clapgpu_contacts_geoms_both(void *stream, clapgpu_bp *bp, const c
     }
     const uint32_t blocks = (capacity + static_capacity + PB - 1) / PB;
     // as many workgroups as are resident at once: a wavefront then walks its chunks with the next one's inputs in flight
-    static uint32_t cached;
+    static thread_local Resident cached;
     const uint32_t resident = resident_workgroups(reinterpret_cast<const void *>(k_contacts_geoms_both), &cached);
     uint32_t grid = blocks < resident ? blocks : resident;
     // the tickets are the word's top 16 bits: with more than 2^16 workgroups none would see the last one (totals never

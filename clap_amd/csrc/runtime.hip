@@ -47,6 +47,18 @@ hipError_t launch_error()
     return left == 0 ? hipErrorLaunchFailure : e;                // injected: the kernel itself ran
 }
 
+int current_device_cus(int *dev, int *n_cus)
+{
+    static thread_local struct { int dev, n_cus; } cache = { -1, 0 };
+    CLAPGPU_HIP(hipGetDevice(dev));
+    if (cache.dev != *dev) {
+        CLAPGPU_HIP(hipDeviceGetAttribute(&cache.n_cus, hipDeviceAttributeMultiprocessorCount, *dev));
+        cache.dev = *dev;
+    }
+    *n_cus = cache.n_cus;
+    return CLAPGPU_OK;
+}
+
 } // namespace clapgpu
 
 using namespace clapgpu;

@@ -38,7 +38,7 @@ class FrameLoop:
         self.prebin = prebin        # CLAPGPU_FRAME_PREBIN: the step bins its boxes for the next frame's broadphase (nothing else writes them)
         self._desc = None
         if characters is not None:
-            missing = bool(characters.model.anim_desc.packed_layout & 0x010)        # POSE_LAYOUT_MISSING (pose.hip)
+            missing = bool(characters.model.anim_desc.packed_layout & 0x010)        # POSE_LAYOUT_MISSING (pose_pack.h)
             characters.set_outputs(trs=("trs" in pose_readers) or missing, joint_pos="joint_pos" in pose_readers)
         self.set_camera(cam)
 

@@ -1,4 +1,4 @@
-/* tools/pose_exact_probe.c -- how often does k_pose's fp64 sin / cos (clap_amd/csrc/pose.hip sincos_halfpi: Taylor
+/* tools/pose_exact_probe.c -- how often does k_pose's fp64 sin / cos (clap_amd/csrc/pose_math_dev.h sincos_halfpi: Taylor
  * polynomials evaluated with FMAs on [0, pi/2]) round to a DIFFERENT float than glibc's sin / cos, the calls the
  * reference's quat_slerp makes (interp.h:107-113)?  The same polynomials, the same FMAs, on the host:
  *     gcc -O2 -fopenmp -ffp-contract=off -o /tmp/pose_exact_probe tools/pose_exact_probe.c -lm
@@ -15,7 +15,7 @@
  *    is no longer far below it.  Sampled with theta_0 uniform over the slerp's range (dot <= 0.9995) and fac uniform in
  *    [0, 1] -- the distribution a game's clock produces -- plus a leg with fac crowded against 1 (1 - 2^-k, k uniform in
  *    [1, 24]) that shows the mechanism.
- * The numbers of the last run are quoted in DESIGN.md section 4 and in pose.hip's header.
+ * The numbers of the last run are quoted in DESIGN.md section 4 and in pose_math_dev.h's header.
  */
 #include <math.h>
 #include <stdint.h>
