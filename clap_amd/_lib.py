@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 OK = 0
 ERR_NOMEM = -1
@@ -173,6 +173,11 @@ def bodies_islands_scratch_bytes(n):
     return int(lib().clapgpu_bodies_islands_scratch_bytes(int(n)))
 
 
+def bodies_solve_scratch_bytes(n, rows_capacity):
+    """clapgpu_bodies_solve_scratch_bytes: bytes of device scratch clapgpu_bodies_solve takes (needs a device)."""
+    return int(lib().clapgpu_bodies_solve_scratch_bytes(int(n), int(rows_capacity)))
+
+
 class Slide(C.Structure):
     """clapgpu_slide (include/clapgpu.h): a batch of movers for clapgpu_characters_slide."""
     _fields_ = [("n", C.c_uint32), ("body", C.c_void_p), ("velocity", C.c_void_p), ("airborne", C.c_void_p),
@@ -192,8 +197,14 @@ class Lights(C.Structure):
                 ("attenuation", C.c_void_p), ("is_dir", C.c_void_p), ("active", C.c_void_p)]
 
 
+class Solver(C.Structure):
+    """clapgpu_solver (include/clapgpu.h): quickstep's iteration count, SOR factor and global CFM."""
+    _fields_ = [("iterations", C.c_uint32), ("pad", C.c_uint32), ("sor_w", C.c_double), ("cfm", C.c_double)]
+
+
 class Frame(C.Structure):
-    """clapgpu_frame (include/clapgpu.h)."""
+    """The fields of clapgpu_frame (include/clapgpu.h) up to ABI 37.  The whole descriptor is FrameDesc, which appends what
+    later versions appended; clapgpu_frame_issue takes nothing shorter."""
     _fields_ = [("entities", C.POINTER(Entities)), ("tile_row_start", C.c_void_p), ("n_tiles", C.c_uint32),
                 ("level_start", C.c_void_p), ("n_levels", C.c_uint32), ("frustum", C.POINTER(Frustum)),
                 ("bodies", C.POINTER(Bodies)), ("world", C.POINTER(World)), ("bp", C.c_void_p),
@@ -220,6 +231,13 @@ class Frame(C.Structure):
                 ("mesh_contact_capacity", C.c_uint32), ("mesh_contact_total", C.c_void_p), ("mesh_capped", C.c_void_p),
                 ("mesh_scratch", C.c_void_p),
                 ("island_scratch", C.c_void_p), ("island", C.c_void_p), ("island_woken", C.c_void_p)]
+
+
+class FrameDesc(Frame):
+    """clapgpu_frame (include/clapgpu.h), whole: Frame's fields, then the contact solve's (ABI 38).  A ctypes subclass lays
+    its own fields out behind its base's, as the C struct has them."""
+    _fields_ = [("solver", C.POINTER(Solver)), ("solve_scratch", C.c_void_p), ("solve_rows_capacity", C.c_uint32),
+                ("solve_status", C.c_void_p)]
 
 
 LIGHTS_MAX = 128
@@ -327,6 +345,13 @@ SYMBOLS = {
     "clapgpu_bodies_islands_scratch_bytes": (C.c_size_t, [C.c_uint32]),
     "clapgpu_bodies_islands": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.c_double, C.c_void_p, C.c_void_p,
                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_solver_defaults": (None, [C.POINTER(Solver)]),
+    "clapgpu_bodies_solve_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "clapgpu_bodies_solve": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.POINTER(Solver), C.c_double, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_visible_compact_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_characters_update_clock": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
@@ -354,7 +379,7 @@ SYMBOLS = {
     "clapgpu_shard_bases": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "clapgpu_mat4_invert": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "clapgpu_mat4_from_quat": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
-    "clapgpu_frame_issue": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_double, C.c_uint32]),
+    "clapgpu_frame_issue": (C.c_int, [C.c_void_p, C.POINTER(FrameDesc), C.c_double, C.c_uint32]),
     "clapgpu_particles_update": (C.c_int, [C.c_void_p, C.POINTER(Particles), C.POINTER(C.c_float)]),
     "clapgpu_characters_update": (C.c_int, [C.c_void_p, C.POINTER(Characters), C.POINTER(Entities),
                                             C.POINTER(Bodies)]),

@@ -1,6 +1,6 @@
 // frame.hip -- one display frame of the batched path as ONE C call: the sequence clap_frame() runs
 // (core/clap.c:551-665) -- phys_step (clap.c:604: per fixed substep the two broadphase passes, near_callback's
-// contact records, the island pass when asked for, the world step) -> scene_update -> mq_update with every entity's hook in list order
+// contact records, the island pass and the contact solve when asked for, the world step) -> scene_update -> mq_update with every entity's hook in list order
 // (character_update in front of default_update: body read-back, rotation push to colliders, light hand-off, TRS
 // rebuild, animated_update; particles_update) -> light grid -> render-pass glue (visible list, LOD pick).
 // Nothing is read back.  Every part is optional (NULL).  The caller keeps the time base
@@ -176,6 +176,21 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
                 if (!f->bp || !f->body_geoms || !f->contacts) return CLAPGPU_ERR_INVALID_ARGUMENTS;
                 FR(clapgpu_bodies_islands(stream, f->bodies, f->world, 1.0 / 120.0, f->pairs, f->pair_total, f->pair_capacity,
                                           f->contacts, f->island_scratch, f->island, f->island_woken));
+            }
+            if (f->solve_scratch) {                              // the contact rows: between the island pass and the step
+                if (!f->island_scratch || !f->island) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+                clapgpu_solver sv;
+                if (f->solver) sv = *f->solver;
+                else clapgpu_solver_defaults(&sv);
+                const bool statics = f->static_pairs && f->static_pair_total && f->static_contacts && f->static_geoms;
+                const bool meshes = statics && f->meshes && f->mesh_contacts && f->mesh_ref && f->mesh_contact_total;
+                FR(clapgpu_bodies_solve(stream, f->bodies, f->world, &sv, 1.0 / 120.0, f->island,
+                                        statics ? f->static_pairs : nullptr, statics ? f->static_pair_total : nullptr,
+                                        statics ? f->static_pair_capacity : 0, statics ? f->static_contacts : nullptr,
+                                        meshes ? f->mesh_contacts : nullptr, meshes ? f->mesh_ref : nullptr,
+                                        meshes ? f->mesh_contact_total : nullptr, meshes ? f->mesh_contact_capacity : 0,
+                                        f->pairs, f->pair_total, f->pair_capacity, f->contacts, f->solve_rows_capacity,
+                                        f->solve_scratch, nullptr, nullptr, nullptr, f->solve_status));
             }
             if ((f->flags & CLAPGPU_FRAME_PREBIN) && f->bp && f->bodies->aabb)
                 FR(clapgpu_bodies_step_prebin(stream, f->bodies, f->world, 1.0 / 120.0, f->bp));

@@ -9,9 +9,9 @@
 #include "lm_dev.h"
 
 #ifdef CLAPGPU_EXPERIMENT               // an A/B or sensitivity build (common.h): never loadable as the product
-#define CLAPGPU_ABI_VERSION (37u | 0x80000000u)
+#define CLAPGPU_ABI_VERSION (38u | 0x80000000u)
 #else
-#define CLAPGPU_ABI_VERSION 37u
+#define CLAPGPU_ABI_VERSION 38u
 #endif
 
 namespace clapgpu {

@@ -19,7 +19,7 @@ from . import entities as ent_mod
 
 class FrameLoop:
     def __init__(self, batch, cam, world=None, feed=None, body_links=None, lights=None, characters=None,
-                 particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False):
+                 particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False, solve=False):
         """batch: EntityBatch.  world: PhysWorld (dynamic bodies write their entities through
         body_entity; character bodies have body_entity = -1).  feed: CharacterFeed.  body_links:
         (link_body, link_entity) of characters / static colliders whose rotation follows the entity.
@@ -30,7 +30,10 @@ class FrameLoop:
         whose skinning runs on the device registers none and the pose writes 64 of its 120 bytes per joint
         (clapgpu_pose_batch.skip).  A model with (joint, path) pairs that have no channel keeps "trs": such a path's
         value lives there (model.c:1301).  islands: every substep wakes sleeping bodies by contact
-        (clapgpu_bodies_islands between its contacts and its step; implies contacts)."""
+        (clapgpu_bodies_islands between its contacts and its step; implies contacts).  solve: every substep's contacts
+        act on the bodies (clapgpu_bodies_solve between the island pass and the step; implies islands)."""
+        islands = islands or solve
+        self.solve = solve
         self.batch, self.world, self.feed, self.lights = batch, world, feed, lights
         self.characters, self.particles = characters, particles
         self.body_links, self.contacts = body_links, contacts or islands
@@ -52,7 +55,7 @@ class FrameLoop:
         import ctypes as C
         from . import _lib
         b, w = self.batch, self.world
-        f = _lib.Frame()
+        f = _lib.FrameDesc()
         keep = []                                           # ctypes objects the descriptor points into
         f.entities = C.pointer(b._desc)
         if b.tiled:
@@ -93,6 +96,12 @@ class FrameLoop:
                     w.island_woken = torch.zeros(1, dtype=torch.int32, device=w.device)
                 f.island_scratch, f.island = w.island_scratch.data_ptr(), w.island.data_ptr()
                 f.island_woken = w.island_woken.data_ptr()
+            if self.solve:
+                w.alloc_solve()
+                keep.append(w.solver)
+                f.solver = C.pointer(w.solver)
+                f.solve_scratch, f.solve_rows_capacity = w.solve_scratch.data_ptr(), w.solve_rows_capacity
+                f.solve_status = w.solve_status.data_ptr()
             if self.body_links is not None:
                 lb, le = w.upload_links(*self.body_links)
                 f.n_body_links, f.link_body, f.link_entity = len(self.body_links[0]), lb.data_ptr(), le.data_ptr()

@@ -335,6 +335,49 @@ class PhysWorld:
                    "clapgpu_bodies_islands")
         return (None if island is None else island[:self.n]), woken
 
+    def alloc_solve(self, rows_capacity=None):
+        """The solve's scratch, outputs and parameters (clapgpu_solver_defaults in self.solver).  rows_capacity: the most
+        contact rows a substep may have (240 bytes of scratch each); by default 6 n + 1024."""
+        cap = int(rows_capacity if rows_capacity is not None else getattr(self, "solve_rows_capacity", None) or
+                  6 * self.n + 1024)
+        if getattr(self, "solve_scratch", None) is None or self.solve_rows_capacity != cap:
+            dev = self.device
+            self.solve_rows_capacity = cap
+            need = _lib.bodies_solve_scratch_bytes(self.n, cap)
+            self.solve_scratch = torch.zeros(max(need, 256), dtype=torch.uint8, device=dev)
+            self.row_lambda = torch.zeros(max(cap, 1), dtype=torch.float64, device=dev)
+            self.row_key = torch.zeros(max(cap, 1), dtype=torch.int64, device=dev)
+            self.rows_total = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.solve_status = torch.zeros(1, dtype=torch.int32, device=dev)
+        if getattr(self, "solver", None) is None:
+            self.solver = _lib.Solver()
+            _lib.lib().clapgpu_solver_defaults(C.byref(self.solver))
+
+    def solve(self, h, want_lambda=False, rows_capacity=None):
+        """Contact response (clapgpu_bodies_solve): the rows of the last contacts_geoms[_both]() / contacts_meshes() lists,
+        solved island by island with the islands of the last islands(); changes lvel / avel of the enabled bodies in
+        contact.  Run it between islands() and world_step(h).  Returns device tensors (rows_total [1], status [1]; bit 0:
+        the rows did not fit and nothing was applied; the caller clears it) and, with want_lambda, (row_lambda
+        [rows_capacity], row_key [rows_capacity]) in canonical row order."""
+        if getattr(self, "island", None) is None or getattr(self, "contact2_buf", None) is None:
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "solve", "no islands: call contacts_geoms and islands first")
+        self.alloc_solve(rows_capacity)
+        st = bool(self.n_static)
+        mesh = st and self._meshes is not None and getattr(self, "mesh_contact_buf", None) is not None
+        _lib.check(_lib.lib().clapgpu_bodies_solve(
+            _stream(), C.byref(self._desc), C.byref(self.world), C.byref(self.solver), h, _ptr(self.island),
+            _ptr(self.static_pairs) if st else None, _ptr(self.static_pair_total) if st else None,
+            self.static_capacity if st else 0, _ptr(self.static_contact2_buf) if st else None,
+            _ptr(self.mesh_contact_buf) if mesh else None, _ptr(self.mesh_ref) if mesh else None,
+            _ptr(self.mesh_contact_total) if mesh else None, self.mesh_contact_capacity if mesh else 0,
+            _ptr(self.pairs), _ptr(self.pair_total), self.capacity, _ptr(self.contact2_buf),
+            self.solve_rows_capacity, _ptr(self.solve_scratch),
+            _ptr(self.row_lambda) if want_lambda else None, _ptr(self.row_key) if want_lambda else None,
+            _ptr(self.rows_total), _ptr(self.solve_status)), "clapgpu_bodies_solve")
+        if want_lambda:
+            return self.rows_total, self.solve_status, self.row_lambda, self.row_key
+        return self.rows_total, self.solve_status
+
     def alloc_mesh_contacts(self, capacity=None):
         """The mesh contact list (clapgpu_contact2 records, mesh_ref [k][2]), its totals and scratch."""
         cap = int(capacity if capacity is not None else getattr(self, "mesh_contact_capacity", None) or
@@ -545,10 +588,12 @@ class PhysWorld:
         """The schedule half of phys_step (physics.c:773-787): number of fixed substeps for this frame."""
         return _lib.lib().clapgpu_phys_step_schedule(C.byref(self.time_acc), dt)
 
-    def phys_step(self, dt, broadphase=True, islands=False):
+    def phys_step(self, dt, broadphase=True, islands=False, solve=False):
         """phys_step(phys, dt): returns the number of fixed substeps taken.  islands: every substep also collides its
-        pairs (contacts_geoms, mesh contacts when there are meshes) and wakes sleeping bodies by contact (islands())."""
+        pairs (contacts_geoms, mesh contacts when there are meshes) and wakes sleeping bodies by contact (islands()).
+        solve: ... and its contacts act on the bodies (solve(), between the island pass and the step); implies islands."""
         steps = _lib.lib().clapgpu_phys_step_schedule(C.byref(self.time_acc), dt)
+        islands = islands or solve
         if islands and not broadphase:
             raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "phys_step", "islands needs the broadphase's pairs")
         for _ in range(steps):
@@ -562,6 +607,8 @@ class PhysWorld:
                 else:
                     self.contacts_geoms()
                 self.islands(1.0 / 120.0)
+                if solve:
+                    self.solve(1.0 / 120.0)
             self.world_step(1.0 / 120.0)
         return steps
 

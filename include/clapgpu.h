@@ -1258,6 +1258,86 @@ int  clapgpu_bodies_islands(void *stream, const clapgpu_bodies *b, const clapgpu
                             const uint32_t *pairs, const uint32_t *pair_total, uint32_t capacity,
                             const clapgpu_contact2 *contacts, void *scratch, uint32_t *island, uint32_t *woken_total);
 
+/*
+ * clapgpu_bodies_solve: contact response -- the constraint stage of dWorldQuickStep (physics.c:769) for the contact joints
+ * near_callback creates ("rely on contact joints and ERP for penetration resolution", physics.c:433-438).  The records of a
+ * substep's three contact lists become quickstep's contact rows and are relaxed by its SOR iteration, one sequential
+ * solve per island, islands in parallel.  ODE 0.16 (joints/contact.cpp, quickstep.cpp) restated, with ONE deliberate
+ * difference: ODE reorders its rows at random, here the row order is the canonical order of the lists.  The rule below is
+ * this library's own contract, restated independently in tests/solveref.py and held to bit equality; PARITY UNPINNED (ODE
+ * is absent from the reference).  fp64, no FMA contraction, every sum left to right in the order written.
+ *
+ * Call it after clapgpu_bodies_islands and before clapgpu_bodies_step[_prebin] of the same substep.  It changes lvel and
+ * avel of enabled, non-kinematic bodies that a row names, and nothing else of the bodies.
+ *
+ * Contacts and their order.  A record contributes min(nc & ~CLAPGPU_CONTACT_DEEP, 2) contacts (a DEEP record: none).
+ * Body 1 is the pair's first index; body 2 is the second index of a body pair and nothing for a static or a mesh contact,
+ * whose body is static_pairs[2 k] resp. static_pairs[2 mesh_ref[2 k]].  A contact is ACTIVE when body 1 is enabled (after
+ * the island pass all bodies of a component share that state).  Ignored like an inactive one: a record past
+ * min(*total, capacity) of its list, a body index >= b->n, a body pair with both indices equal, a mesh_ref past the
+ * static pairs, island[body 1] >= b->n.  The canonical contact order runs through the static list by record index, then
+ * the mesh list, then the body list; within a record slot 1, then slot 2 (the reference's joint-creation order: ground
+ * pass first, physics.c:751-753, with list order in place of the hash space's traversal).  A contact has its normal row
+ * and, when mu > 0, two friction rows behind it; the ordinal of a row is its position in that order.  The contact's
+ * island is island[body 1]; row_key = ((uint64_t)island << 32) | ordinal.
+ *
+ * Rows (dxJointContact::getInfo2 as the reference configures it: SoftERP | SoftCFM [| Bounce], mu2 unused, no Approx1).
+ * With r_i = pos - pos_i (b->pos), x the cross product (r x n = (r1 n2 - r2 n1, r2 n0 - r0 n2, r0 n1 - r1 n0)):
+ *   a row along direction u:  J1l = u, J1a = r1 x u, J2l = -u, J2a = -(r2 x u)
+ *   normal row    u = n; c = (soft_erp / h) * depth; when mode has CLAPGPU_CONTACT_BOUNCE: out = J . (v1, w1, v2, w2), and if
+ *                 bounce_vel >= 0 and -out > bounce_vel then newc = (-bounce) * out, c = newc if newc > c;
+ *                 cfm = soft_cfm, lo = 0, hi = +inf
+ *   friction rows u = t1, then u = t2, from dPlaneSpace(n): if |n[2]| > M_SQRT1_2: a = n1 n1 + n2 n2, k = 1 / sqrt(a),
+ *                 t1 = (0, -n2 k, n1 k), t2 = (a k, -n0 t1[2], n0 t1[1]); else a = n0 n0 + n1 n1, k = 1 / sqrt(a),
+ *                 t1 = (-n1 k, n0 k, 0), t2 = (-n2 t1[1], n2 t1[0], a k).  c = 0, cfm = s->cfm, lo = -mu, hi = +mu: a
+ *                 force limit, as ODE has it without Approx1
+ * n points from the static towards the body and from body 2 to body 1, so a positive lambda pushes body 1 out.
+ * Whatever belongs to an absent body 2 is skipped in every sum (not added as zero).
+ *
+ * Masses.  invM = 1 / mass, 0 for a CLAPGPU_BODY_KINEMATIC body; invI = R diag(1 / inertia) R^T with R = dQtoR(quat),
+ * built as the step builds its tensors (tmp = D R^T, invI = R tmp); all zeros for a kinematic body or when b->inertia is
+ * NULL.  iMJ = (invM1 J1l, invI1 J1a, invM2 J2l, invI2 J2a), a matrix row times the vector summed left to right.
+ * Right-hand side.  f_ext = facc + (NO_GRAVITY ? 0 : m g) (facc taken as 0 when b->facc is NULL); no external torque,
+ * the gyroscopic term stays the step's.
+ *   rhs = c / h - [ J1l . (v1 / h + invM1 f_ext1) + J1a . (w1 / h) + J2l . (v2 / h + invM2 f_ext2) + J2a . (w2 / h) ]
+ * one running sum over the twelve products in that order.  The step that follows adds h invM f_ext itself; the solve
+ * anticipates it, as quickstep does.
+ * Iteration.  d = iMJ . J (body 1 linear xyz, angular xyz, body 2 linear xyz, angular xyz) + cfm / h; Ad = sor_w / d.  A row
+ * with d == 0 is dropped: it keeps its ordinal and lambda = 0.  Each island starts from lambda = 0 and a = 0 (six doubles
+ * per body).  For `iterations` sweeps, for each row of the island in canonical order:
+ *   delta = Ad * ((rhs - (cfm / h) * lambda) - J . a)      J . a over body 1's six, then body 2's six
+ *   lambda' = lambda + delta; if lambda' < lo: lo; if lambda' > hi: hi
+ *   a += iMJ * (lambda' - lambda);  lambda = lambda'
+ * After the sweeps lvel += h * a_lin and avel += h * a_ang for every enabled, non-kinematic body named by an active row.
+ *
+ * One lane walks an island: the price of the sequential sweep.  A pile of thousands of bodies in one island costs that
+ * many dependent row updates, `iterations` times over, on one lane, while separate islands run side by side.
+ *
+ * Each list may be absent (a NULL pointer or capacity 0); the mesh list needs static_pairs and static_pair_total.
+ * rows_capacity: the most rows the call can hold.  When the rows do not fit, the launches -- which read the total on the
+ * device, where alone it is known -- apply nothing and OR 1 into *status (the caller clears it).  row_lambda
+ * [rows_capacity] and row_key [rows_capacity] (device, may be NULL) receive lambda and the key of every row at its
+ * ordinal; *rows_total (device, may be NULL) the number of rows.
+ * scratch: clapgpu_bodies_solve_scratch_bytes(b->n, rows_capacity) bytes of device memory, 256-byte aligned, overwritten;
+ * the caller need not clear it between calls.  Four launches and a rocPRIM radix sort of the row keys inside the scratch,
+ * no allocation, no host synchronisation: a captured graph can hold the call.  b->n == 0 returns CLAPGPU_OK and launches
+ * nothing; without any list nothing changes and *rows_total = 0.  Pairs 8-byte, records 16-byte aligned.
+ */
+typedef struct clapgpu_solver { uint32_t iterations; uint32_t pad; double sor_w; double cfm; } clapgpu_solver;
+void   clapgpu_solver_defaults(clapgpu_solver *s);    /* 20, 1.3, 1e-10: ODE's dDOUBLE defaults, physics.c:1127-1128 leave them */
+size_t clapgpu_bodies_solve_scratch_bytes(uint32_t n, uint32_t rows_capacity);
+int    clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_solver *s, double h,
+                            const uint32_t *island,   /* required: clapgpu_bodies_islands' output of this substep */
+                            const uint32_t *static_pairs, const uint32_t *static_pair_total, uint32_t static_capacity,
+                            const clapgpu_contact2 *static_contacts,
+                            const clapgpu_contact2 *mesh_contacts, const uint32_t *mesh_ref,
+                            const uint32_t *mesh_contact_total, uint32_t mesh_capacity,
+                            const uint32_t *pairs, const uint32_t *pair_total, uint32_t capacity,
+                            const clapgpu_contact2 *contacts,
+                            uint32_t rows_capacity, void *scratch,
+                            double *row_lambda, uint64_t *row_key,
+                            uint32_t *rows_total, uint32_t *status);
+
 /* ======================================================================== */
 /* Characters: the feeder in front of default_update (core/character.c)      */
 /* ======================================================================== */
@@ -1407,6 +1487,13 @@ typedef struct clapgpu_frame {
      * pair_total, contacts and body_geoms; island / island_woken may be NULL */
     void     *island_scratch;                  /* clapgpu_bodies_islands_scratch_bytes(bodies->n) bytes, 256-byte aligned */
     uint32_t *island, *island_woken;
+    /* contact response (clapgpu_bodies_solve) in every substep, between its island pass and its step; solve_scratch NULL:
+     * none, the frame issues the launches it issued before these fields existed.  Needs island_scratch and island;
+     * solver NULL: clapgpu_solver_defaults.  solve_status (may be NULL) as *status of clapgpu_bodies_solve */
+    const clapgpu_solver *solver;
+    void     *solve_scratch;                   /* clapgpu_bodies_solve_scratch_bytes(bodies->n, solve_rows_capacity), 256-byte aligned */
+    uint32_t  solve_rows_capacity;
+    uint32_t *solve_status;
 } clapgpu_frame;
 
 /* Default (0): everything on the caller's stream in the reference's order.  CLAPGPU_FRAME_OVERLAP: the frame's three
