@@ -1,8 +1,8 @@
 // bp_grid.h -- the broadphase's hash grid as other translation units see it: the cell and slot functions and the bin step
 // that the five k_bp_* launches (broadphase.hip) and the pre-binning body step (bodies.hip) bin with and the device
 // queries look cells up with (grid_query_dev.h, for rays.hip and slide.hip), the record and the control words of a
-// clapgpu_bp, a read-only view of an INDEXED clapgpu_bp (clapgpu_bp_index), and the hidden accessors of broadphase.hip
-// that hand these out.
+// clapgpu_bp, a read-only view of an INDEXED clapgpu_bp (clapgpu_bp_index), and the hidden accessors of the broadphase
+// code (broadphase.hip, bp_create.hip) that hand these out.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,7 +30,7 @@ __host__ __device__ __forceinline__ uint32_t cell_slot(int32_t cx, int32_t cy, i
 
 struct GridRec { double bb[6]; uint32_t idx; int32_t cell[3]; };    // 64 bytes; cell = the box centre's cell (dynamic records)
 
-// Control words (clapgpu_bp.ctrl has 160).  The broadphase's: the sticky status bits, the bin epoch (the frame counter
+// Control words.  The broadphase's: the sticky status bits, the bin epoch (the frame counter
 // lives on the device: a captured graph replays the same arguments; counted up by every bin pass, k_bp_bin or a
 // pre-binning step) and [8..9]: clapgpu_contacts_geoms_both's ticket + counts, zero between launches.
 constexpr int CTRL_STATUS = 2, CTRL_EPOCH = 3, CTRL_CONTACT_WORD = 8;
@@ -42,6 +42,8 @@ constexpr int INDEX_WORDS = 7, INDEX_OVERSIZE = 6;
 // ... and the bin epoch the index saw last.  A graph replay bins without the host knowing; a differing epoch tells a
 // query kernel the index is stale (grid_query_dev.h's grid_usable).
 constexpr int CTRL_INDEX_EPOCH = CTRL_INDEX_WORD + 2 * INDEX_WORDS;       // word 30
+constexpr int CTRL_WORDS = 160;                                           // clapgpu_bp.ctrl: every index above is below this
+static_assert(CTRL_INDEX_EPOCH < CTRL_WORDS, "control words");
 
 // One body into the grid: k_bp_bin's work per body, also done by the step that writes the box it would read
 // (clapgpu_bodies_step_prebin).  key == nullptr: off.
@@ -54,9 +56,27 @@ __device__ __forceinline__ void box_cell(const double (&bb)[6], double cell, int
     cz = cell_coord((bb[4] + bb[5]) * 0.5, cell);
 }
 
+__device__ __forceinline__ void load_box(const double *aabb, uint32_t i, double (&bb)[6])
+{
+    const double2 *p = reinterpret_cast<const double2 *>(aabb + 6 * (size_t)i);
+    const double2 a = p[0], b = p[1], c = p[2];
+    bb[0] = a.x; bb[1] = a.y; bb[2] = b.x; bb[3] = b.y; bb[4] = c.x; bb[5] = c.y;
+}
+
+__device__ __forceinline__ bool boxes_overlap(const double (&a)[6], const double (&b)[6])
+{
+    return !(a[0] > b[1] || a[1] < b[0] || a[2] > b[3] || a[3] < b[2] || a[4] > b[5] || a[5] < b[4]);
+}
+
+// an edge exceeds `cell`: the box's partners may lie outside the 27 cells around its own
+__device__ __forceinline__ bool box_oversized(const double (&bb)[6], double cell)
+{
+    return bb[1] - bb[0] > cell || bb[3] - bb[2] > cell || bb[5] - bb[4] > cell;
+}
+
 __device__ __forceinline__ void bin_body(const BinK &bin, uint32_t i, const double (&bb)[6])
 {
-    if (bb[1] - bb[0] > bin.cell || bb[3] - bb[2] > bin.cell || bb[5] - bb[4] > bin.cell)
+    if (box_oversized(bb, bin.cell))
         atomicOr(&bin.ctrl[CTRL_STATUS], 1u);
     int32_t cx, cy, cz;
     box_cell(bb, bin.cell, cx, cy, cz);
@@ -93,7 +113,8 @@ struct BpGridView {
 
 } // namespace clapgpu
 
-// ---- broadphase.hip's hidden accessors: struct clapgpu_bp is written and read in that file alone
+// ---- the broadphase's hidden accessors: struct clapgpu_bp (bp_object.h) is written and read in broadphase.hip and
+// bp_create.hip alone
 struct clapgpu_bp;
 // geoms_dev.h's scene_grid, for rays.hip and slide.hip: true when `bp` holds an index over exactly (n, aabb) (aabb == nullptr: any array of n boxes); fills *v
 __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp *bp, uint32_t n, const double *aabb, clapgpu::BpGridView *v);

@@ -1,0 +1,79 @@
+// bp_statics.h -- the static boxes of a clapgpu_bp binned on the host, at create time: host arithmetic only, no HIP call
+// (bp_create.hip uploads the result; tests/c/test_bp_statics.cpp checks it alone).
+#pragma once
+#include <math.h>
+#include <string.h>
+#include <utility>
+#include <vector>
+#include "bp_grid.h"
+
+namespace clapgpu {
+
+// Every block whose own bodies could touch the static (its AABB grown by half a cell), as a CSR over the block buckets;
+// statics that would enter more than 64 blocks go to the large list, which every body tests.
+struct __attribute__((visibility("hidden"))) StaticsImage {
+    std::vector<uint32_t> start;         // [buckets + 1]
+    std::vector<uint32_t> entries;       // static indices, ascending inside a bucket; one placeholder when none
+    std::vector<uint32_t> large;         // n_large static indices, ascending; one placeholder when none
+    std::vector<GridRec> recs, lrecs;    // entries / large with their boxes (placeholders: zero)
+    uint32_t n_large;
+    double bounds[6];                    // union of the registered (not large) boxes: min xyz, max xyz; min > max: none
+};
+
+__attribute__((visibility("hidden"))) inline StaticsImage bp_statics_image(uint32_t buckets, double cell, uint32_t n_static, const double *static_aabb)
+{
+    StaticsImage im;
+    im.start.assign(buckets + 1, 0);
+    std::vector<std::pair<uint32_t, uint32_t>> ins;                               // (bucket, static)
+    const double grow = cell * 0.5 * (1.0 + 1e-9);
+    for (int a = 0; a < 3; a++) { im.bounds[a] = INFINITY; im.bounds[3 + a] = -INFINITY; }
+    for (uint32_t s = 0; s < n_static; s++) {
+        const double *bb = static_aabb + 6 * (size_t)s;
+        int32_t lo[3], hi[3];
+        bool large = false;
+        unsigned long long blocks = 1;
+        for (int a = 0; a < 3; a++) {
+            lo[a] = cell_coord(bb[2 * a] - grow, cell) >> 2;
+            hi[a] = cell_coord(bb[2 * a + 1] + grow, cell) >> 2;
+            if (!(bb[2 * a] <= bb[2 * a + 1])) large = true;                      // NaN / inverted: keep it in the tested-by-all list
+            blocks *= (unsigned long long)(hi[a] - lo[a] + 1);
+            if (blocks > 64) large = true;
+        }
+        if (large) { im.large.push_back(s); continue; }
+        for (int a = 0; a < 3; a++) {
+            im.bounds[a] = fmin(im.bounds[a], bb[2 * a]);
+            im.bounds[3 + a] = fmax(im.bounds[3 + a], bb[2 * a + 1]);
+        }
+        const size_t first = ins.size();
+        for (int32_t z = lo[2]; z <= hi[2]; z++)
+            for (int32_t y = lo[1]; y <= hi[1]; y++)
+                for (int32_t x = lo[0]; x <= hi[0]; x++) {
+                    const uint32_t h = block_hash(x, y, z, buckets - 1);
+                    bool dup = false;
+                    for (size_t e = first; e < ins.size(); e++) dup |= ins[e].first == h;
+                    if (!dup) ins.push_back({ h, s });
+                }
+    }
+    for (auto &e : ins) im.start[e.first + 1]++;
+    for (uint32_t b = 0; b < buckets; b++) im.start[b + 1] += im.start[b];
+    im.entries.resize(ins.size() ? ins.size() : 1);
+    {
+        std::vector<uint32_t> cur(im.start.begin(), im.start.end() - 1);
+        for (auto &e : ins) im.entries[cur[e.first]++] = e.second;                // ascending static index inside a bucket
+    }
+    im.n_large = (uint32_t)im.large.size();
+    im.recs.resize(im.entries.size());
+    im.lrecs.resize(im.large.size() ? im.large.size() : 1);
+    auto fill_rec = [&](GridRec &r, uint32_t sidx) {
+        memset(&r, 0, sizeof(r));
+        if (n_static) memcpy(r.bb, static_aabb + 6 * (size_t)sidx, sizeof(r.bb));
+        r.idx = sidx;
+    };
+    for (size_t e = 0; e < ins.size(); e++) fill_rec(im.recs[e], im.entries[e]);
+    for (size_t e = 0; e < im.large.size(); e++) fill_rec(im.lrecs[e], im.large[e]);
+    if (ins.empty()) memset(&im.recs[0], 0, sizeof(GridRec));
+    if (im.large.empty()) { memset(&im.lrecs[0], 0, sizeof(GridRec)); im.large.push_back(0); }
+    return im;
+}
+
+} // namespace clapgpu

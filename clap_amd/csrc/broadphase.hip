@@ -1,12 +1,9 @@
 // broadphase.hip -- the broadphase over explicit AABBs, for gfx950: dSpaceCollide2(ground, bodies) + dSpaceCollide(bodies)
 // (physics.c:751-753) as ascending candidate-pair lists, and the same grid as an index for the ray cast (rays.hip).
-// struct clapgpu_bp lives here alone; other translation units go through the hidden accessors of bp_grid.h.
+// The six kernels and the entry points that launch them; the object itself is made in bp_create.hip (bp_object.h).
 // fp64 boxes.  ODE is an absent submodule of the reference: PARITY UNPINNED (oracle/physics2.c states what is restated).
-#include <string.h>
-#include <stdlib.h>
-#include <vector>
-#include "common.h"
-#include "bp_grid.h"
+#include "bp_object.h"
+#include "scan_dev.h"
 
 namespace clapgpu {
 
@@ -32,56 +29,16 @@ constexpr int PB = 256;
 // Two different cells of one 3x3x3 neighbourhood never share a slot (same position inside a block means at least four
 // cells apart), and a body from a far block that shares a slot cannot overlap (cell >= every edge), so candidates need
 // no cell check beyond the box test.
-constexpr int BP_LIST = 16;            // partners kept per body in its fixed slot
+// BP_LIST (partners kept per body in its fixed slot), BP_EMIT_TILE: bp_object.h
 constexpr int BP_TILE = 16;            // bodies per wavefront of the search
 constexpr int BP_WORK = 512;           // candidate entries listed per tile and round (256: spheres -2 us, capsules +5 us)
-constexpr int BP_EMIT_TILE = 1024;     // bodies per tile of the pair-offset scan (= emit block; 256: +3 us, four times the look-back words)
 #ifndef BP_SEARCH_IN_FLIGHT
 #define BP_SEARCH_IN_FLIGHT 1            // candidate records gathered per lane and round
 #endif
 
-// block_hash, cell_coord, cell_slot, box_cell, the record and the control words: bp_grid.h
-
-struct BpK {
-    uint32_t n;
-    double cell;
-    uint32_t mask;                       // block buckets - 1
-    const double *aabb;
-    uint32_t *cell_cnt;                  // [buckets * 64] the bin pass's counters, zero between frames
-    uint2    *cell_range;                // [buckets * 64] (first position in cell order, bodies) of every cell: one load per lookup
-    uint32_t *key, *rank;                // [n] cell slot and rank inside the cell
-    uint32_t *entries;                   // [n] body indices in cell order
-    GridRec *recs;                  // [n] the same with the boxes: what the search reads
-    uint32_t *cnt, *scnt;                // [n] partners (larger index) / statics per body: atomics in the search
-    uint32_t *partners, *spartners;      // [n][BP_LIST]
-    uint64_t *lb_body, *lb_static;       // [tiles] look-back words of the pair-offset scan (k_bp_emit)
-    uint64_t *lb_cells;                  // [buckets / 4] look-back words of the block-start scan (k_bp_cells)
-    uint32_t *ctrl;
-    uint32_t n_tiles;
-    // statics (binned on the host at create time)
-    const uint32_t *s_start;             // [buckets + 1]
-    const uint32_t *s_entries;
-    const double *s_aabb;
-    const uint32_t *s_large;
-    const GridRec *s_recs;          // s_entries with their boxes (what the search gathers)
-    const GridRec *s_lrecs;         // the large statics with their boxes
-    uint32_t n_large, n_static;
-    // outputs
-    uint32_t *pairs, capacity, *pair_total;
-    uint32_t *spairs, scapacity, *spair_total;
-};
-
-__device__ __forceinline__ void load_box(const double *aabb, uint32_t i, double (&bb)[6])
-{
-    const double2 *p = reinterpret_cast<const double2 *>(aabb + 6 * (size_t)i);
-    const double2 a = p[0], b = p[1], c = p[2];
-    bb[0] = a.x; bb[1] = a.y; bb[2] = b.x; bb[3] = b.y; bb[4] = c.x; bb[5] = c.y;
-}
-
-__device__ __forceinline__ bool boxes_overlap(const double (&a)[6], const double (&b)[6])
-{
-    return !(a[0] > b[1] || a[1] < b[0] || a[2] > b[3] || a[3] < b[2] || a[4] > b[5] || a[5] < b[4]);
-}
+// block_hash, cell_coord, cell_slot, box_cell, bin_body, the box helpers, the record and the control words: bp_grid.h
+// BpK and bin_of: bp_object.h.  The look-back scan of k_bp_cells and k_bp_emit: scan_dev.h
+constexpr uint32_t BP_STATUS_SCAN = 4u;  // CTRL_STATUS: a look-back word never arrived
 
 // Launch 1 (skipped when the step before it has binned the boxes it wrote: clapgpu_bodies_step_prebin)
 __global__ __launch_bounds__(PB)
@@ -92,59 +49,7 @@ void k_bp_bin(BpK k)
     if (i >= k.n) return;
     double bb[6];
     load_box(k.aabb, i, bb);
-    if (bb[1] - bb[0] > k.cell || bb[3] - bb[2] > k.cell || bb[5] - bb[4] > k.cell)
-        atomicOr(&k.ctrl[CTRL_STATUS], 1u);
-    int32_t cx, cy, cz;
-    box_cell(bb, k.cell, cx, cy, cz);
-    const uint32_t slot = cell_slot(cx, cy, cz, k.mask);
-    k.key[i] = slot;
-    k.rank[i] = atomicAdd(&k.cell_cnt[slot], 1u);
-}
-
-// Single-pass scans with decoupled look-back (the block starts in k_bp_cells, the pair offsets of the 256-body emit
-// tiles in k_bp_emit): a tile's offset = the sum of everything before it.  Tile b publishes (flag, epoch, value) as ONE 64-bit word -- its own sum first
-// (AGGREGATE), its inclusive prefix once known (PREFIX) -- and a wavefront walks back over its predecessors' words, 64 at
-// a time, until it meets a PREFIX.  Workgroups are dispatched in index order and wait only on lower indices, so the
-// walk always terminates; the frame's epoch in the word makes last frame's entries read as empty (no clearing pass).
-constexpr uint64_t LB_AGG = 1ull << 62, LB_PREFIX = 2ull << 62, LB_FLAGS = 3ull << 62;
-__device__ __forceinline__ uint64_t lb_word(uint64_t flag, uint32_t epoch, uint32_t value)
-{
-    return flag | ((uint64_t)(epoch & 0x3fffffffu) << 32) | value;
-}
-
-// exclusive prefix of tile `b` (called by one whole wavefront); publishes the tile's own words
-__device__ __forceinline__ uint32_t lb_exclusive(uint64_t *state, uint32_t b, uint32_t sum, uint32_t epoch, uint32_t *status)
-{
-    const int lane = lane_id();
-    if (b == 0) {
-        if (lane == 0) __hip_atomic_store(&state[0], lb_word(LB_PREFIX, epoch, sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return 0;
-    }
-    if (lane == 0) __hip_atomic_store(&state[b], lb_word(LB_AGG, epoch, sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t excl = 0;
-    for (int64_t top = (int64_t)b - 1; top >= 0; top -= WAVE) {         // window: tiles top, top-1, ..., top-63
-        const int64_t t = top - lane;
-        uint64_t w = 0;
-        if (t >= 0) {
-            uint32_t spins = 0;
-            do {
-                w = __hip_atomic_load(&state[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((w & LB_FLAGS) && (uint32_t)((w >> 32) & 0x3fffffffu) == (epoch & 0x3fffffffu)) break;
-                w = 0;
-                __builtin_amdgcn_s_sleep(1);
-            } while (++spins < (1u << 22));                               // a bound, not an expectation: see above
-            if (!w) atomicOr(status, 4u);
-        }
-        const uint64_t is_prefix = __ballot(t >= 0 && (w & LB_FLAGS) == LB_PREFIX);
-        const int stop = is_prefix ? __builtin_ctzll(is_prefix) : WAVE - 1;   // nearest predecessor that knows its prefix
-        uint32_t v = (t >= 0 && lane <= stop) ? (uint32_t)w : 0u;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        excl += v;
-        if (is_prefix) break;
-    }
-    if (lane == 0) __hip_atomic_store(&state[b], lb_word(LB_PREFIX, epoch, excl + sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return excl;
+    bin_body(bin_of(k), i, bb);
 }
 
 // Launch 2: wave w = block bucket w; a workgroup's BP_CELLS_BLOCK / 64 block totals enter the look-back scan as one tile
@@ -160,12 +65,7 @@ void k_bp_cells(BpK k)
     if (b <= k.mask) {
         c = k.cell_cnt[(size_t)b * 64 + lane];
         k.cell_cnt[(size_t)b * 64 + lane] = 0;                          // ready for the next frame
-        uint32_t incl = c;
-#pragma unroll
-        for (int o = 1; o < WAVE; o <<= 1) {
-            const uint32_t u = __shfl_up(incl, o);
-            if (lane >= o) incl += u;
-        }
+        const uint32_t incl = wave_prefix_sum(c);
         before = incl - c;
         block_total = __shfl(incl, WAVE - 1);
     }
@@ -175,7 +75,7 @@ void k_bp_cells(BpK k)
         uint32_t sum = 0;
 #pragma unroll
         for (int q = 0; q < BP_CELLS_BLOCK / WAVE; q++) sum += tot[q];
-        const uint32_t excl = lb_exclusive(k.lb_cells, blockIdx.x, sum, k.ctrl[CTRL_EPOCH], k.ctrl + CTRL_STATUS);
+        const uint32_t excl = lb_exclusive(k.lb_cells, blockIdx.x, sum, k.ctrl[CTRL_EPOCH], k.ctrl + CTRL_STATUS, BP_STATUS_SCAN);
         if (lane == 0) excl_s = excl;
     }
     __syncthreads();
@@ -309,7 +209,7 @@ void k_bp_search(BpK k)
         len[r] = is_cell[r] ? v_cr[r].y : is_stat[r] ? v_s1[r] - v_s0[r] : 0u;
         mylen += len[r];
     }
-    uint32_t incl = mylen;
+    uint32_t incl = mylen;                                              // wave_prefix_sum (common.h) restated: calling it moves this kernel's code
 #pragma unroll
     for (int o = 1; o < WAVE; o <<= 1) {
         const uint32_t up = __shfl_up(incl, o);
@@ -320,14 +220,14 @@ void k_bp_search(BpK k)
 
     // A hit on another body needs one returning atomic on the partner count of min(i, j), ~2 us under load: hits are
     // parked in LDS while the candidates are tested and their atomics issued together once per round.
+    auto append_partner = [&](uint32_t lo, uint32_t hi) {
+        const uint32_t at = atomicAdd(&k.cnt[lo], 1u);
+        if (at < BP_LIST) k.partners[(size_t)lo * BP_LIST + at] = hi;
+    };
     auto flush_hits = [&]() {
         wave_lds_fence();
         const uint32_t nh = nhits[wave] < HITS ? nhits[wave] : HITS;
-        for (uint32_t h = lane; h < nh; h += WAVE) {
-            const uint32_t lo = hits[wave][h][0], hi = hits[wave][h][1];
-            const uint32_t at = atomicAdd(&k.cnt[lo], 1u);
-            if (at < BP_LIST) k.partners[(size_t)lo * BP_LIST + at] = hi;
-        }
+        for (uint32_t h = lane; h < nh; h += WAVE) append_partner(hits[wave][h][0], hits[wave][h][1]);
         wave_lds_fence();
         if (lane == 0) nhits[wave] = 0;
         wave_lds_fence();
@@ -348,10 +248,7 @@ void k_bp_search(BpK k)
                 const uint32_t lo = i < j ? i : j, hi = i < j ? j : i;
                 const uint32_t h = atomicAdd(&nhits[wave], 1u);
                 if (h < HITS) { hits[wave][h][0] = lo; hits[wave][h][1] = hi; }
-                else {                                                   // list full (a pile-up): straight to memory
-                    const uint32_t at = atomicAdd(&k.cnt[lo], 1u);
-                    if (at < BP_LIST) k.partners[(size_t)lo * BP_LIST + at] = hi;
-                }
+                else append_partner(lo, hi);                             // list full (a pile-up): straight to memory
             }
         }
     };
@@ -421,7 +318,9 @@ void k_bp_search(BpK k)
 }
 
 // all partners of body i (larger index) in ascending order, for a body whose list did not fit its slot: one lane
-// walks its 27 cells
+// walks its 27 cells.  k_bp_emit's search over a body's statics restates the repeated minimum search with other
+// candidates: one helper for both moved k_bp_emit's code and did not stay inside the parent's timing spread
+// (profiles/bp_split/README.md).
 template <typename F>
 __device__ __forceinline__ void research_body(const BpK &k, uint32_t i, F &&emit_sorted)
 {
@@ -494,7 +393,7 @@ void k_bp_emit(BpK k)
         for (int qq = 0; qq < BP_EMIT_TILE / WAVE; qq++) sum += lds[wave][qq];
         uint32_t excl = 0;
         if (wave == 0 || with_statics)
-            excl = lb_exclusive(wave ? k.lb_static : k.lb_body, blockIdx.x, sum, k.ctrl[CTRL_EPOCH], k.ctrl + CTRL_STATUS);
+            excl = lb_exclusive(wave ? k.lb_static : k.lb_body, blockIdx.x, sum, k.ctrl[CTRL_EPOCH], k.ctrl + CTRL_STATUS, BP_STATUS_SCAN);
         if (lane == 0) {
             tile_excl[wave] = excl;
             if (blockIdx.x == gridDim.x - 1) {                           // the last tile's inclusive prefix is the total
@@ -543,7 +442,7 @@ void k_bp_emit(BpK k)
             const uint32_t ob = block_hash(cx >> 2, cy >> 2, cz >> 2, k.mask);
             const uint32_t s0 = k.s_start[ob], nloc = k.s_start[ob + 1] - s0;
             uint32_t w = 0;
-            int64_t last = -1;
+            int64_t last = -1;                                           // research_body's search, from "nothing emitted yet"
             for (;;) {
                 uint32_t best = 0xffffffffu;
                 for (uint32_t e = 0; e < nloc + k.n_large; e++) {
@@ -577,7 +476,7 @@ void k_bp_index_bounds(BpK k)
     for (uint32_t i = blockIdx.x * PB + threadIdx.x; i < k.n; i += gridDim.x * PB) {
         double bb[6];
         load_box(k.aabb, i, bb);
-        if (bb[1] - bb[0] > k.cell || bb[3] - bb[2] > k.cell || bb[5] - bb[4] > k.cell) over = 1;   // k_bp_bin's test
+        if (box_oversized(bb, k.cell)) over = 1;
         // finite coordinates only: a geom at infinity or NaN never hits (rays.hip), and the bounds stay finite
         for (int a = 0; a < 3; a++) {
             if (isfinite(bb[2 * a])) m[a] = fmin(m[a], bb[2 * a]);
@@ -616,23 +515,7 @@ void k_bp_index_bounds(BpK k)
 
 using namespace clapgpu;
 
-// ---------------------------------------------------------------------------------- broadphase object
-struct clapgpu_bp {
-    uint32_t n_max, buckets, n_static, n_large, n_tiles;
-    double cell;
-    void *dev;                     // one allocation
-    BpK k;                         // device pointers filled in
-    // clapgpu_bodies_step_prebin: the step that wrote these boxes has also binned them (key / rank / cell counters / epoch):
-    // the next clapgpu_bp_collide over the same array skips its first launch
-    const double *prebinned_aabb;
-    uint32_t prebinned_n;
-    // clapgpu_bp_index: the grid now describes these boxes (cleared by everything that bins again)
-    bool indexed;
-    const double *indexed_aabb;
-    uint32_t indexed_n;
-    double s_bounds[6];            // union of the statics registered per block (not the large list); min > max: none
-};
-
+// ---------------------------------------------------------------------------------- launches, and the bookkeeping of struct clapgpu_bp (bp_object.h) they keep
 // The boxes a step pre-binned were changed by somebody else (clapgpu_bodies_aabb, an upload, another body count): the cell
 // counters go back to zero -- what k_bp_cells leaves between frames -- and the next collide bins for itself.
 extern "C" int clapgpu_bp_invalidate(void *stream, clapgpu_bp *bp)
@@ -644,136 +527,6 @@ extern "C" int clapgpu_bp_invalidate(void *stream, clapgpu_bp *bp)
     CLAPGPU_HIP(hipMemsetAsync(bp->k.cell_cnt, 0, (size_t)bp->buckets * 64 * sizeof(uint32_t), as_stream(stream)));
     return CLAPGPU_OK;
 }
-
-static uint32_t buckets_for(uint32_t n)
-{
-    uint32_t b = 1024;                                                  // block buckets: 64 cell slots each, about two slots per body
-    while (b < n / 32 && b < (1u << 22)) b <<= 1;
-    return b;
-}
-
-static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-extern "C" int clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t n_static, const double *static_aabb)
-{
-    if (!out || !(cell > 0.0) || (n_static && !static_aabb) || n_max > (1u << 30))
-        return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    clapgpu_bp *bp = static_cast<clapgpu_bp *>(calloc(1, sizeof(*bp)));
-    if (!bp) return CLAPGPU_ERR_NOMEM;
-    const uint32_t n = n_max ? n_max : 1, nb = buckets_for(n);
-    bp->n_max = n_max; bp->buckets = nb; bp->cell = cell; bp->n_static = n_static;
-    bp->n_tiles = (n + BP_EMIT_TILE - 1) / BP_EMIT_TILE;
-
-    // statics: every block whose own bodies could touch the static (its AABB grown by half a cell), as a CSR over
-    // the same buckets; statics that would enter more than 64 blocks go to the large list
-    std::vector<uint32_t> s_count(nb + 1, 0), s_entries, s_large;
-    std::vector<std::pair<uint32_t, uint32_t>> ins;                               // (bucket, static)
-    const double grow = cell * 0.5 * (1.0 + 1e-9);
-    for (int a = 0; a < 3; a++) { bp->s_bounds[a] = INFINITY; bp->s_bounds[3 + a] = -INFINITY; }
-    for (uint32_t s = 0; s < n_static; s++) {
-        const double *bb = static_aabb + 6 * (size_t)s;
-        int32_t lo[3], hi[3];
-        bool large = false;
-        unsigned long long blocks = 1;
-        for (int a = 0; a < 3; a++) {
-            lo[a] = cell_coord(bb[2 * a] - grow, cell) >> 2;
-            hi[a] = cell_coord(bb[2 * a + 1] + grow, cell) >> 2;
-            if (!(bb[2 * a] <= bb[2 * a + 1])) large = true;                      // NaN / inverted: keep it in the tested-by-all list
-            blocks *= (unsigned long long)(hi[a] - lo[a] + 1);
-            if (blocks > 64) large = true;
-        }
-        if (large) { s_large.push_back(s); continue; }
-        for (int a = 0; a < 3; a++) {
-            bp->s_bounds[a] = fmin(bp->s_bounds[a], bb[2 * a]);
-            bp->s_bounds[3 + a] = fmax(bp->s_bounds[3 + a], bb[2 * a + 1]);
-        }
-        const size_t first = ins.size();
-        for (int32_t z = lo[2]; z <= hi[2]; z++)
-            for (int32_t y = lo[1]; y <= hi[1]; y++)
-                for (int32_t x = lo[0]; x <= hi[0]; x++) {
-                    const uint32_t h = block_hash(x, y, z, nb - 1);
-                    bool dup = false;
-                    for (size_t e = first; e < ins.size(); e++) dup |= ins[e].first == h;
-                    if (!dup) ins.push_back({ h, s });
-                }
-    }
-    for (auto &e : ins) s_count[e.first + 1]++;
-    for (uint32_t b = 0; b < nb; b++) s_count[b + 1] += s_count[b];
-    s_entries.resize(ins.size() ? ins.size() : 1);
-    {
-        std::vector<uint32_t> cur(s_count.begin(), s_count.end() - 1);
-        for (auto &e : ins) s_entries[cur[e.first]++] = e.second;                 // ascending static index inside a bucket
-    }
-    bp->n_large = (uint32_t)s_large.size();
-    std::vector<GridRec> s_recs(s_entries.size()), s_lrecs(s_large.size() ? s_large.size() : 1);
-    auto fill_rec = [&](GridRec &r, uint32_t sidx) {
-        memset(&r, 0, sizeof(r));
-        if (n_static) memcpy(r.bb, static_aabb + 6 * (size_t)sidx, sizeof(r.bb));
-        r.idx = sidx;
-    };
-    for (size_t e = 0; e < ins.size(); e++) fill_rec(s_recs[e], s_entries[e]);
-    for (size_t e = 0; e < s_large.size(); e++) fill_rec(s_lrecs[e], s_large[e]);
-    if (ins.empty()) memset(&s_recs[0], 0, sizeof(GridRec));
-    if (s_large.empty()) { memset(&s_lrecs[0], 0, sizeof(GridRec)); s_large.push_back(0); }
-
-    // one device allocation, carved
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
-    const size_t o_ccnt = take(4 * (size_t)nb * 64), o_crange = take(8 * (size_t)nb * 64);
-    const size_t o_key = take(4 * (size_t)n), o_ranks = take(4 * (size_t)n), o_entries = take(4 * (size_t)n), o_recs = take(64 * (size_t)n);
-    const size_t o_cnt = take(4 * (size_t)n), o_scnt = take(4 * (size_t)n);
-    const size_t o_part = take(4 * (size_t)BP_LIST * n), o_spart = take(4 * (size_t)BP_LIST * n);
-    const size_t o_lbb = take(8 * (size_t)bp->n_tiles), o_lbs = take(8 * (size_t)bp->n_tiles), o_lbc = take(8 * ((size_t)nb / 4 + 1));
-    const size_t o_ctrl = take(4 * 160);
-    const size_t o_sstart = take(4 * ((size_t)nb + 1)), o_sent = take(4 * s_entries.size()), o_slarge = take(4 * s_large.size());
-    const size_t o_saabb = take(48 * (size_t)(n_static ? n_static : 1));
-    const size_t o_srecs = take(sizeof(GridRec) * s_recs.size()), o_slrecs = take(sizeof(GridRec) * s_lrecs.size());
-    const size_t fixed = off;
-    if (hipMalloc(&bp->dev, fixed) != hipSuccess) {
-        (void)hipGetLastError();
-        free(bp);
-        return CLAPGPU_ERR_NOMEM;
-    }
-    char *d = static_cast<char *>(bp->dev);
-    if (hipMemset(d, 0, fixed) != hipSuccess ||
-        hipMemcpy(d + o_sstart, s_count.data(), 4 * ((size_t)nb + 1), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + o_sent, s_entries.data(), 4 * s_entries.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + o_slarge, s_large.data(), 4 * s_large.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + o_srecs, s_recs.data(), sizeof(GridRec) * s_recs.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + o_slrecs, s_lrecs.data(), sizeof(GridRec) * s_lrecs.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        (n_static && hipMemcpy(d + o_saabb, static_aabb, 48 * (size_t)n_static, hipMemcpyHostToDevice) != hipSuccess)) {
-        (void)hipGetLastError();
-        (void)hipFree(bp->dev);
-        free(bp);
-        return CLAPGPU_ERR_UNKNOWN;
-    }
-    BpK &k = bp->k;
-    memset(&k, 0, sizeof(k));
-    k.cell = cell; k.mask = nb - 1;
-    k.cell_cnt = reinterpret_cast<uint32_t *>(d + o_ccnt); k.cell_range = reinterpret_cast<uint2 *>(d + o_crange);
-    k.key = reinterpret_cast<uint32_t *>(d + o_key); k.rank = reinterpret_cast<uint32_t *>(d + o_ranks);
-    k.entries = reinterpret_cast<uint32_t *>(d + o_entries); k.recs = reinterpret_cast<GridRec *>(d + o_recs);
-    k.cnt = reinterpret_cast<uint32_t *>(d + o_cnt); k.scnt = reinterpret_cast<uint32_t *>(d + o_scnt);
-    k.partners = reinterpret_cast<uint32_t *>(d + o_part); k.spartners = reinterpret_cast<uint32_t *>(d + o_spart);
-    k.lb_body = reinterpret_cast<uint64_t *>(d + o_lbb); k.lb_static = reinterpret_cast<uint64_t *>(d + o_lbs);
-    k.lb_cells = reinterpret_cast<uint64_t *>(d + o_lbc);
-    k.ctrl = reinterpret_cast<uint32_t *>(d + o_ctrl);
-    k.s_start = reinterpret_cast<const uint32_t *>(d + o_sstart); k.s_entries = reinterpret_cast<const uint32_t *>(d + o_sent);
-    k.s_large = reinterpret_cast<const uint32_t *>(d + o_slarge); k.s_aabb = reinterpret_cast<const double *>(d + o_saabb);
-    k.s_recs = reinterpret_cast<const GridRec *>(d + o_srecs); k.s_lrecs = reinterpret_cast<const GridRec *>(d + o_slrecs);
-    k.n_large = bp->n_large; k.n_static = n_static;
-    *out = bp;
-    return CLAPGPU_OK;
-}
-
-extern "C" void clapgpu_bp_destroy(clapgpu_bp *bp)
-{
-    if (!bp) return;
-    if (bp->dev) (void)hipFree(bp->dev);
-    free(bp);
-}
-
-extern "C" const double *clapgpu_bp_static_aabb(const clapgpu_bp *bp) { return bp ? bp->k.s_aabb : nullptr; }
 
 // The object's kernel arguments for the n boxes of `aabb`
 static BpK grid_k(const clapgpu_bp *bp, uint32_t n, const double *aabb)
@@ -847,28 +600,13 @@ extern "C" int clapgpu_bp_collide(void *stream, clapgpu_bp *bp, uint32_t n, cons
 __attribute__((visibility("hidden"))) int clapgpu_bp_prebin(void *stream, clapgpu_bp *bp, uint32_t n, const double *aabb, BinK *bin)
 {
     if (n > bp->n_max) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    *bin = BinK{ bp->cell, bp->k.mask, bp->k.key, bp->k.rank, bp->k.cell_cnt, bp->k.ctrl };
+    *bin = bin_of(bp->k);
     if (n == 0) return CLAPGPU_OK;
     int rc = clapgpu_bp_invalidate(stream, bp);                  // the step moves the boxes and rebins: the index is stale; a step
     if (rc) return rc;                                           // binned already and no collide consumed it: start over
     bp->prebinned_aabb = aabb;
     bp->prebinned_n = n;
     return CLAPGPU_OK;
-}
-
-extern "C" int clapgpu_bp_status(void *stream, clapgpu_bp *bp, uint32_t *status)
-{
-    if (!bp || !status) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    CLAPGPU_HIP(hipMemcpyAsync(status, bp->k.ctrl + CTRL_STATUS, sizeof(uint32_t), hipMemcpyDeviceToHost, as_stream(stream)));
-    CLAPGPU_HIP(hipStreamSynchronize(as_stream(stream)));
-    return CLAPGPU_OK;
-}
-
-// contacts.hip's one-launch form keeps its ticket + counts in this object's control words
-__attribute__((visibility("hidden"))) unsigned long long *clapgpu_bp_contact_ticket(clapgpu_bp *bp)
-{
-    static_assert((CTRL_CONTACT_WORD * sizeof(uint32_t)) % 8 == 0, "the ticket word is a 64-bit atomic");
-    return reinterpret_cast<unsigned long long *>(bp->k.ctrl + CTRL_CONTACT_WORD);
 }
 
 // The first three launches of clapgpu_bp_collide (the grid of the current boxes in cell order) and the bounds of those
@@ -901,38 +639,5 @@ extern "C" int clapgpu_bp_index(void *stream, clapgpu_bp *bp, uint32_t n, const 
         if (rc) return rc;
     }
     bp->indexed = true; bp->indexed_aabb = aabb; bp->indexed_n = n;
-    return CLAPGPU_OK;
-}
-
-// rays.hip's view of an index (bp_grid.h)
-__attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp *bp, uint32_t n, const double *aabb,
-                                                                 BpGridView *v)
-{
-    if (!bp || !bp->indexed || bp->indexed_n != n || (aabb && bp->indexed_aabb != aabb)) return false;
-    v->n = n; v->n_static = bp->n_static; v->cell = bp->cell; v->mask = bp->k.mask; v->n_large = bp->n_large;
-    v->cell_range = bp->k.cell_range;
-    v->recs = bp->k.recs;
-    v->s_start = bp->k.s_start;
-    v->s_recs = bp->k.s_recs;
-    v->s_lrecs = bp->k.s_lrecs;
-    v->index = reinterpret_cast<const uint64_t *>(bp->k.ctrl + CTRL_INDEX_WORD);
-    v->ctrl = bp->k.ctrl;
-    memcpy(v->s_bounds, bp->s_bounds, sizeof(v->s_bounds));
-    return true;
-}
-
-extern "C" int clapgpu_bp_index_status(void *stream, clapgpu_bp *bp, uint32_t *status)
-{
-    if (!bp || !status || !bp->indexed) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    *status = 0;
-    if (!bp->indexed_n) return CLAPGPU_OK;
-    uint64_t w = 0;
-    uint32_t epochs[2] = { 0, 0 };
-    hipStream_t s = as_stream(stream);
-    CLAPGPU_HIP(hipMemcpyAsync(&w, bp->k.ctrl + CTRL_INDEX_WORD + 2 * INDEX_OVERSIZE, sizeof(w), hipMemcpyDeviceToHost, s));
-    CLAPGPU_HIP(hipMemcpyAsync(&epochs[0], bp->k.ctrl + CTRL_EPOCH, 4, hipMemcpyDeviceToHost, s));
-    CLAPGPU_HIP(hipMemcpyAsync(&epochs[1], bp->k.ctrl + CTRL_INDEX_EPOCH, 4, hipMemcpyDeviceToHost, s));
-    CLAPGPU_HIP(hipStreamSynchronize(s));
-    *status = (w != ~0ull ? 1u : 0u) | (epochs[0] != epochs[1] ? 2u : 0u);
     return CLAPGPU_OK;
 }

@@ -482,11 +482,7 @@ void k_mesh_contacts_scan(const uint32_t *pair_total, uint32_t capacity, uint32_
     uint32_t sum = 0;
     for (uint32_t i = b0; i < b1; i++) sum += wsum[i];
     const int lane = lane_id(), wv = threadIdx.x / WAVE;
-    uint32_t incl = sum;
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t u = __shfl_up(incl, o);
-        if (lane >= o) incl += u;
-    }
+    const uint32_t incl = wave_prefix_sum(sum);
     if (lane == WAVE - 1) part[wv] = incl;
     __syncthreads();
     uint32_t off = incl - sum;
@@ -512,7 +508,7 @@ void k_mesh_contacts_write(GeomsK A, GeomsK B, MeshSet M, const uint2 *pairs, co
     const uint32_t p = blockIdx.x * MC + lane;
     PairSel s;
     select_mesh_records(A, B, M, pairs, p, np, L, lane, s);
-    uint32_t incl = s.kept;
+    uint32_t incl = s.kept;                                              // wave_prefix_sum (common.h) restated: calling it moves this kernel's code
     for (int o = 1; o < WAVE; o <<= 1) {
         const uint32_t u = __shfl_up(incl, o);
         if (lane >= o) incl += u;

@@ -92,8 +92,8 @@ def test_broadphase_touching_and_negative_coordinates(cuda_device):
 
 
 def test_broadphase_dense_bodies_with_long_partner_lists(cuda_device):
-    """Crowded cells: most bodies have more partners than a body's fixed list slot holds, so their lists go
-    through the arena and the emit pass ranks them there."""
+    """Crowded cells: most bodies have more partners than a body's fixed list slot holds, so the emit pass searches
+    their cells again and writes their partners in ascending order by repeated minimum search."""
     from clap_amd import physics
     b = synth.sphere_bodies(3000, box=6.0, seed=6)
     exp = ob.broadphase_aabb_pairs(oracle_aabbs(b), max_pairs=1 << 22)
@@ -127,6 +127,33 @@ def test_pair_capacity_overflow_reports_total(cuda_device):
     world.broadphase()
     out = world.download()
     assert out["pair_total"] == len(exp) > 100          # total found is reported, only `capacity` written
+    per_body = np.bincount(exp[:100, 0], minlength=3000)
+    assert per_body.max() > 16                          # the written rows come from lists that overflow the slot
+    assert np.array_equal(out["pairs"], exp[:100]), "the written pairs are the head of the ascending list"
+
+
+def test_static_pair_capacity_cuts_through_a_long_static_list(cuda_device):
+    """The scene of test_static_pairs_with_more_hits_than_the_kept_list with room for half of the static pairs: the
+    total is still the full count, and what is written is the head of the ascending list, the capacity falling
+    inside the list of a body whose hits did not fit its slot (the bound inside the emit pass's second search)."""
+    from clap_amd import physics
+    b = synth.sphere_bodies(700, box=8.0, seed=9)
+    statics = synth.static_boxes(60, 8.0, seed=2)
+    for s_ in range(40):                                    # nested boxes around the low corner
+        statics[s_] = [-1.0, 3.0 + 0.05 * s_, -1.0, 3.0 + 0.05 * s_, -1.0, 3.0 + 0.05 * s_]
+    exp_s = ob.broadphase_aabb_static_pairs(statics, oracle_aabbs(b), max_pairs=1 << 20)
+    cap = len(exp_s) // 2
+    per_body = np.bincount(exp_s[:, 0], minlength=700)
+    first = np.cumsum(per_body) - per_body
+    assert ((per_body > 16) & (first < cap) & (first + per_body > cap)).any(), "no long list straddles the capacity"
+    world = physics.PhysWorld(b, statics, pair_capacity=1 << 16, static_pair_capacity=cap, device=cuda_device)
+    for _ in range(2):                                      # twice: the counters the kernels leave behind are clean
+        world.broadphase()
+    out = world.download()
+    assert out["static_pair_total"] == len(exp_s)
+    assert out["static_pairs"].shape == (cap, 2)
+    assert np.array_equal(out["static_pairs"], exp_s[:cap]), "the written static pairs are the head of the ascending list"
+    assert world.broadphase_status() == 0
 
 
 def test_broadphase_flags_a_body_larger_than_the_cell(cuda_device):

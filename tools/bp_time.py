@@ -1,5 +1,5 @@
-import sys, numpy as np, torch
-sys.path.insert(0,'/root/repo')
+import sys, os, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from clap_amd import _lib, physics, synth
 _lib.check(_lib.lib().clapgpu_init(0),"init")
 for kind in (sys.argv[1:] or ("spheres","capsules")):
