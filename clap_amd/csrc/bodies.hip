@@ -13,7 +13,8 @@
 //   k_phys_body_update, k_bodies_rotate_from_entities   body pose -> entity SoA (physics.c:789-812) and back
 //                     (physics.c:136-145)
 // and on the host: the fixed-step schedule, world defaults, and the masses and capsule geoms phys_body_new gives a body.
-// The broadphase is broadphase.hip, the narrowphase and the sweep contacts.hip.
+// The broadphase is broadphase.hip, the narrowphase and the sweep contacts.hip (spheres only: contacts_spheres.hip;
+// against meshes: mesh_contacts.hip).
 // fp64 throughout (the reference builds ODE with dDOUBLE, physics.h:5-9), no FMA contraction.
 // ODE is an absent submodule of the reference: PARITY UNPINNED (oracle/physics.c, oracle/physics2.c state what is restated).
 #include <string.h>

@@ -104,7 +104,7 @@ extern "C" int clapgpu_bp_status(void *stream, clapgpu_bp *bp, uint32_t *status)
     return CLAPGPU_OK;
 }
 
-// contacts.hip's one-launch form keeps its ticket + counts in this object's control words
+// contacts.hip's one-launch form (k_contacts_geoms_both) keeps its ticket + counts in this object's control words
 __attribute__((visibility("hidden"))) unsigned long long *clapgpu_bp_contact_ticket(clapgpu_bp *bp)
 {
     static_assert((CTRL_CONTACT_WORD * sizeof(uint32_t)) % 8 == 0, "the ticket word is a 64-bit atomic");

@@ -118,7 +118,7 @@ struct BpGridView {
 struct clapgpu_bp;
 // geoms_dev.h's scene_grid, for rays.hip and slide.hip: true when `bp` holds an index over exactly (n, aabb) (aabb == nullptr: any array of n boxes); fills *v
 __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp *bp, uint32_t n, const double *aabb, clapgpu::BpGridView *v);
-// contacts.hip: the one-launch form keeps its ticket + counts in the object's control words
+// contacts.hip (k_contacts_geoms_both): the one-launch form keeps its ticket + counts in the object's control words
 __attribute__((visibility("hidden"))) unsigned long long *clapgpu_bp_contact_ticket(clapgpu_bp *bp);
 // bodies.hip: the bin arrays for a step that is about to write and bin the n boxes of `aabb`, recorded as pre-binned
 // (an unconsumed prebin is undone first, an index dropped).  The caller launches that step or calls clapgpu_bp_invalidate.

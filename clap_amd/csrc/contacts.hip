@@ -1,17 +1,16 @@
-// contacts.hip -- narrowphase contact records and the capsule sweep, for gfx950 (a translation unit of its own so that
-// it alone is built with -mllvm -simplifycfg-sink-common=false, see the Makefile).
+// contacts.hip -- the geom narrowphase of the world step and the capsule sweep over candidate lists, for gfx950:
 //
-//   k_contacts_geoms[_both]  near_callback's dCollide + phys_contact_surface (physics.c:399-449, 291-330)
-//   k_contacts<BOX>          the same for sphere bodies against each other / against static boxes: 104-byte records
-//   k_sweep_capsules         phys_body_sweep_capsule (physics.c:559-670), one wavefront per sweep; <true>: candidates
-//                            that own a mesh of the mesh set collide through its triangles (tricontact_dev.h)
-//   k_mesh_contacts_count / _scan / _write   near_callback for (body, static) pairs whose static owns a mesh: the
-//                            triangles under the body's box, the rule of tricontact_dev.h, MAX_CONTACTS, canonical order
+//   k_contacts_geoms        near_callback's dCollide + phys_contact_surface (physics.c:399-449, 291-330) for candidate
+//                           pairs of any two colliders, 160-byte records; one list of pairs a launch
+//   k_contacts_geoms_both   both lists of a step (bodies x bodies, bodies x statics) in one launch, the totals through
+//                           one ticket word
+//   k_sweep_capsules<MESH>  phys_body_sweep_capsule (physics.c:559-670), one wavefront per sweep (the march: sweep_dev.h,
+//                           which slide.hip runs too); true: candidates that own a mesh of the mesh set collide through
+//                           its triangles (tricontact_dev.h).  It stays in this file: in a translation unit of its own
+//                           both instantiations compile to other code, and <true> was 1 % slower
+//                           (profiles/contacts_split/README.md)
 //
-// Why the flag: phd::collide() writes its (up to two) contacts through CGeom references.  After inlining, LLVM's
-// SimplifyCFG sinks the "same" stores of different call sites into one block that stores through a SELECTED pointer
-// (c0 or c1), which keeps both contacts addressable: 56 bytes (contacts) / 128 bytes (sweep) of scratch per lane, and
-// scratch is HBM traffic on gfx950.  Without the sinking SROA turns them into registers (private segment 0, +6 VGPRs).
+// Built without SimplifyCFG's common-code sinking: see phd::collide (phys_dev.h).
 // fp64 throughout, no FMA contraction.  ODE is an absent submodule of the reference: PARITY UNPINNED.
 #include <string.h>
 #include <stdlib.h>
@@ -22,34 +21,14 @@
 #include "trimesh_dev.h"
 #include "tricontact_dev.h"
 #include "sweep_dev.h"
+#include "contact_record_dev.h"
 
 namespace clapgpu {
 
 constexpr int PB = 256;
 
-// ================================================================================== narrowphase
-// GeomsK, load_geom, geoms_k: geoms_dev.h (shared with the ray cast)
-
-// phys_contact_surface (physics.c:291-330) for the two colliders' parameter rows (NULL: defaults), into either record
-// type; nc is the caller's
-template <typename Rec>
-__device__ __forceinline__ void contact_surface(Rec &c, const double *m1, const double *m2)
-{
-    double bounce = 0, bounce_vel = 0, mu = 0, soft_erp = 0.05, soft_cfm = 0.01;   // physics.c:293-294
-    if (m1 && m2) {
-        bounce = fmax(m1[0], m2[0]);
-        bounce_vel = (m1[1] + m2[1]) * 0.5;
-        mu = sqrt(m1[2] * m2[2]);
-        if (m1[3] > 0 && m2[3] > 0) soft_erp = fmin(m1[3], m2[3]);
-        else if (m1[3] > 0) soft_erp = m1[3];
-        else if (m2[3] > 0) soft_erp = m2[3];
-        if (m1[4] > 0 && m2[4] > 0) soft_cfm = fmax(m1[4], m2[4]);
-        else if (m1[4] > 0) soft_cfm = m1[4];
-        else if (m2[4] > 0) soft_cfm = m2[4];
-    }
-    c.mode = CLAPGPU_CONTACT_SOFT_CFM | CLAPGPU_CONTACT_SOFT_ERP | (bounce > 0 ? CLAPGPU_CONTACT_BOUNCE : 0);
-    c.mu = mu; c.bounce = bounce; c.bounce_vel = bounce_vel; c.soft_erp = soft_erp; c.soft_cfm = soft_cfm;
-}
+// GeomsK, load_geom, geoms_k: geoms_dev.h (shared with the ray cast); contact_surface, record_points, mark_has_joint,
+// clamped: contact_record_dev.h
 
 // one candidate pair -> its record; true if the pair produced contacts (or is flagged deep)
 __device__ __forceinline__ bool contact_of_pair(const GeomsK &A, const GeomsK &B, const uint2 pr, clapgpu_contact2 &c,
@@ -68,19 +47,13 @@ __device__ __forceinline__ bool contact_of_pair(const GeomsK &A, const GeomsK &B
             c.nc = CLAPGPU_CONTACT_DEEP;
             counted = true;
         } else if (nc > 0) {
-            for (int a = 0; a < 3; a++) { c.pos[a] = c0.pos[a]; c.normal[a] = c0.normal[a]; }
-            c.depth = c0.depth;
-            if (nc > 1) {
-                for (int a = 0; a < 3; a++) { c.pos2[a] = c1.pos[a]; c.normal2[a] = c1.normal[a]; }
-                c.depth2 = c1.depth;
-            }
+            record_points(c, nc > 1, c0, c1);
             contact_surface(c, (A.material && B.material) ? A.material + 5 * (size_t)pr.x : nullptr,
                             (A.material && B.material) ? B.material + 5 * (size_t)pr.y : nullptr);
             c.nc = (uint32_t)nc;
             counted = true;
-            // plain read-modify-write: every writer of this launch sets the same bit and nothing else changes the word
-            if (flags_a && !(flags_a[pr.x] & CLAPGPU_BODY_HAS_JOINT)) flags_a[pr.x] |= CLAPGPU_BODY_HAS_JOINT;
-            if (flags_b && !(flags_b[pr.y] & CLAPGPU_BODY_HAS_JOINT)) flags_b[pr.y] |= CLAPGPU_BODY_HAS_JOINT;
+            mark_has_joint(flags_a, pr.x);
+            mark_has_joint(flags_b, pr.y);
         }
     }
     return counted;
@@ -153,15 +126,11 @@ __device__ __forceinline__ uint32_t contact_from_inputs(const GeomsK &A, const G
     const int nc = phd::collide(in.ga, in.gb, c0, c1);
     if (nc < 0) { c.nc = CLAPGPU_CONTACT_DEEP; return 1; }
     if (nc == 0) return 0;
-    for (int a = 0; a < 3; a++) { c.pos[a] = c0.pos[a]; c.normal[a] = c0.normal[a]; }
-    c.depth = c0.depth;
-    if (nc > 1) {
-        for (int a = 0; a < 3; a++) { c.pos2[a] = c1.pos[a]; c.normal2[a] = c1.normal[a]; }
-        c.depth2 = c1.depth;
-    }
+    record_points(c, nc > 1, c0, c1);
     contact_surface(c, (A.material && B.material) ? A.material + 5 * (size_t)in.pr.x : nullptr,
                     (A.material && B.material) ? B.material + 5 * (size_t)in.pr.y : nullptr);
     c.nc = (uint32_t)nc;
+    // mark_has_joint (contact_record_dev.h) from the words load_pair_inputs asked for early
     if (flags_a && !(in.fa & CLAPGPU_BODY_HAS_JOINT)) flags_a[in.pr.x] = in.fa | CLAPGPU_BODY_HAS_JOINT;
     if (flags_b && !(in.fb & CLAPGPU_BODY_HAS_JOINT)) flags_b[in.pr.y] = in.fb | CLAPGPU_BODY_HAS_JOINT;
     return 1;
@@ -187,8 +156,7 @@ void k_contacts_geoms(GeomsK A, GeomsK B, const uint2 *pairs, const uint32_t *pa
     __shared__ uint4 tile[PB / WAVE][WAVE * CONTACT_ROW];
     if (threadIdx.x == 0) block_hits = 0;
     __syncthreads();
-    uint32_t np = *pair_total;
-    if (np > capacity) np = capacity;
+    const uint32_t np = clamped(pair_total, capacity);
     uint32_t mine = 0;
     const uint32_t wave = threadIdx.x / WAVE;
     for (uint32_t p0 = blockIdx.x * PB + wave * WAVE; p0 < np; p0 += gridDim.x * PB)      // wave-uniform
@@ -216,9 +184,7 @@ void k_contacts_geoms_both(GeomsK A, GeomsK B, const uint2 *pairs, const uint32_
     __shared__ uint4 tile[PB / WAVE][WAVE * CONTACT_ROW];
     if (threadIdx.x < 2) block_hits[threadIdx.x] = 0;
     __syncthreads();
-    uint32_t nb = *pair_total, ns = spair_total ? *spair_total : 0u;
-    if (nb > capacity) nb = capacity;
-    if (ns > scapacity) ns = scapacity;
+    const uint32_t nb = clamped(pair_total, capacity), ns = spair_total ? clamped(spair_total, scapacity) : 0u;
     uint32_t mine_b = 0, mine_s = 0;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));   // in an SGPR: what is selected by chunk is scalar
     const uint32_t cb = (nb + WAVE - 1) / WAVE, cs = (ns + WAVE - 1) / WAVE;   // 64-pair chunks: the bodies' list, then the statics'
@@ -261,88 +227,6 @@ void k_contacts_geoms_both(GeomsK A, GeomsK B, const uint2 *pairs, const uint32_
     }
 }
 
-// ---- sphere bodies, 104-byte records: near_callback's dCollide + phys_contact_surface (see include/clapgpu.h), one lane
-// per candidate pair, IEEE fp64 (sqrt, divide), no contraction.  BOX = false: (body, body) sphere pairs; BOX = true: (body,
-// static box) pairs, `other` = static_aabb, `other_material` = the static colliders' parameter rows.
-template <bool BOX>
-__global__ __launch_bounds__(PB)
-void k_contacts(const double *pos, const double *radius, uint32_t n_bodies, const double *other, uint32_t n_other,
-                const uint2 *pairs, const uint32_t *pair_total, uint32_t capacity, const double *material,
-                const double *other_material, clapgpu_contact *out, uint32_t *contact_total)
-{
-    __shared__ __attribute__((aligned(16))) double recs[PB / WAVE][WAVE * 13];
-    static_assert(sizeof(clapgpu_contact) == 13 * sizeof(double), "contact record layout");
-    const uint32_t n_pairs = *pair_total < capacity ? *pair_total : capacity;
-    const int lane = lane_id();
-    uint32_t found = 0;
-    // the pair count is only known on the device: a fixed grid strides over the pairs (a grid sized for
-    // the capacity spends 50 us launching empty workgroups)
-    for (uint32_t k = blockIdx.x * PB + threadIdx.x; k - lane < n_pairs; k += gridDim.x * PB) {
-    double *rec = recs[threadIdx.x / WAVE];
-    bool touch = false;
-    if (k < n_pairs) {
-        const uint2 pr = pairs[k];
-        clapgpu_contact c;
-        memset(&c, 0, sizeof(c));
-        if (pr.x < n_bodies && pr.y < (BOX ? n_other : n_bodies)) {
-            const double *p1 = pos + 3 * (size_t)pr.x;
-            const double c1[3] = { p1[0], p1[1], p1[2] };
-            phd::CGeom g;
-            const double *m1 = nullptr, *m2 = nullptr;
-            if (BOX) {
-                const double *o = other + 6 * (size_t)pr.y;
-                const double bb[6] = { o[0], o[1], o[2], o[3], o[4], o[5] };
-                touch = phd::collide_sphere_box(c1, radius[pr.x], bb, g) != 0;
-                if (material && other_material) { m1 = material + 5 * (size_t)pr.x; m2 = other_material + 5 * (size_t)pr.y; }
-            } else {
-                const double *o = pos + 3 * (size_t)pr.y;
-                const double c2[3] = { o[0], o[1], o[2] };
-                touch = phd::collide_spheres(c1, radius[pr.x], c2, radius[pr.y], g) != 0;
-                if (material) { m1 = material + 5 * (size_t)pr.x; m2 = material + 5 * (size_t)pr.y; }
-            }
-            if (touch || BOX) {                                              // collide_sphere_box leaves zeros without a contact
-                for (int a = 0; a < 3; a++) { c.pos[a] = g.pos[a]; c.normal[a] = g.normal[a]; }
-                c.depth = g.depth;
-            }
-            if (touch) {
-                contact_surface(c, m1, m2);
-                c.nc = 1;
-            }
-        }
-        // the 104-byte records of a wave are contiguous in memory: stage them in LDS and write the run as
-        // 16-byte pieces (a record per lane straight to memory is 13 scattered 8-byte stores per lane)
-        memcpy(rec + (size_t)lane * 13, &c, sizeof(c));
-    }
-    wave_lds_fence();
-    {
-        const uint32_t wave_first = k - lane;                       // first pair of this wave
-        const uint32_t n_here = wave_first < n_pairs ? (n_pairs - wave_first < WAVE ? n_pairs - wave_first : WAVE) : 0;
-        const uint32_t n16 = n_here * (uint32_t)(sizeof(clapgpu_contact) / 8) / 2;      // 16-byte pieces (104 * 64 % 16 == 0 only for even counts)
-        const double2 *src = reinterpret_cast<const double2 *>(rec);
-        double2 *dst = reinterpret_cast<double2 *>(out + wave_first);
-        if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-            for (uint32_t q = lane; q < n16; q += WAVE) dst[q] = src[q];
-            if ((n_here & 1) && lane == 0)                          // odd count: the last 8 bytes
-                reinterpret_cast<double *>(out + wave_first)[n_here * 13 - 1] = rec[n_here * 13 - 1];
-        } else {
-            for (uint32_t q = lane; q < n_here * 13; q += WAVE)
-                reinterpret_cast<double *>(out + wave_first)[q] = rec[q];
-        }
-    }
-    found += (uint32_t)__popcll(__ballot(touch));
-    wave_lds_fence();                                               // the staging tile is reused by the next trip
-    }
-    // one global atomic per workgroup: same-address atomics serialise at ~12 ns each (4096 of them were
-    // 50 us of this kernel)
-    __shared__ uint32_t block_found;
-    if (threadIdx.x == 0) block_found = 0;
-    __syncthreads();
-    if (lane == 0 && found) atomicAdd(&block_found, found);
-    __syncthreads();
-    if (contact_total && threadIdx.x == 0 && block_found)
-        atomicAdd(contact_total, block_found);
-}
-
 // segment_box, mesh_of, sweep_march: sweep_dev.h (shared with the slide)
 
 // phys_body_sweep_capsule: one wavefront per sweep, the candidates of a step spread over the lanes (sweep_march).  MESH:
@@ -378,174 +262,6 @@ void k_sweep_capsules(GeomsK A, GeomsK B, MeshSet M, uint32_t n_sweeps, const ui
         hit_out[sw] = best_hit;
     }
 }
-
-
-// ================================================================================== contacts against meshes
-// One lane per (body, static) pair, one wavefront per workgroup (the LDS below is per lane: [entry][lane] columns).  A
-// pair's records are kept in LDS as the 16 best by (deeper first, then lower triangle index) -- a pair keeps at most 16
-// contacts, so no record beyond those can be kept -- and the kept ones are that order's longest prefix whose contacts
-// fit in 16.  Both passes compute the same selection; the first counts, the scan places, the second writes.
-constexpr int MC = WAVE;
-constexpr int MC_KEEP = 16;                                              // MAX_CONTACTS, physics.c:150
-
-struct MeshLds {
-    uint32_t stk[TM_STACK * MC];
-    double dep[MC_KEEP * MC];                                            // a record's depth: the deeper of its contacts
-    uint32_t tri[MC_KEEP * MC];                                          // triangle of the mesh
-    uint32_t slot[MC_KEEP * MC];                                         // leaf slot | (nc - 1) << 31
-};
-
-struct PairSel { uint32_t body, stat, kept, found; double a[3], b[3], r; };
-
-// pair p's selection into the lane's LDS columns; false: the pair has no mesh contacts to look for
-__device__ __forceinline__ bool select_mesh_records(const GeomsK &A, const GeomsK &B, const MeshSet &M, const uint2 *pairs,
-                                                    uint32_t p, uint32_t np, MeshLds &L, int lane, PairSel &s)
-{
-    s.kept = s.found = 0;
-    if (p >= np) return false;
-    const uint2 pr = pairs[p];
-    s.body = pr.x; s.stat = pr.y;
-    if (pr.x >= A.n || pr.y >= B.n || mesh_of(M, pr.y) < 0) return false;
-    phd::Geom g;
-    load_geom(A, pr.x, g);
-    if (!phd::geom_segment(g, s.a, s.b)) return false;                   // boxes: no triangle collider here
-    s.r = g.radius;
-    double lo[3], hi[3];
-    segment_box(s.a, s.b, s.r, lo, hi);
-    uint32_t n = 0, found = 0;
-    box_walk(M, lo, hi, L.stk + lane, [&](uint32_t slot) {
-        const uint2 kt = M.key[slot];
-        if (kt.x != pr.y) return;                                        // another mesh's leaf
-        phd::CGeom c0, c1;
-        const int nc = phd::collide_segment_triangle(s.a, s.b, s.r, M.tri + 9 * (size_t)slot, c0, c1);
-        if (nc <= 0) return;
-        found++;
-        const double d = nc > 1 && c1.depth > c0.depth ? c1.depth : c0.depth;
-        auto before = [&](int k) {                                       // the new record goes before entry k
-            const double dk = L.dep[k * MC + lane];
-            return d > dk || (d == dk && kt.y < L.tri[k * MC + lane]);
-        };
-        if (n == MC_KEEP && !before(MC_KEEP - 1)) return;
-        int k = n < MC_KEEP ? (int)n : MC_KEEP;
-        while (k > 0 && before(k - 1)) {
-            if (k < MC_KEEP) {
-                L.dep[k * MC + lane] = L.dep[(k - 1) * MC + lane];
-                L.tri[k * MC + lane] = L.tri[(k - 1) * MC + lane];
-                L.slot[k * MC + lane] = L.slot[(k - 1) * MC + lane];
-            }
-            k--;
-        }
-        L.dep[k * MC + lane] = d;
-        L.tri[k * MC + lane] = kt.y;
-        L.slot[k * MC + lane] = slot | ((uint32_t)(nc - 1) << 31);
-        if (n < MC_KEEP) n++;
-    });
-    uint32_t used = 0, kept = 0;
-    for (; kept < n; kept++) {
-        const uint32_t nc = (L.slot[kept * MC + lane] >> 31) + 1;
-        if (used + nc > (uint32_t)MC_KEEP) break;
-        used += nc;
-    }
-    s.kept = kept;
-    s.found = found;
-    return true;
-}
-
-__global__ __launch_bounds__(MC)
-void k_mesh_contacts_count(GeomsK A, GeomsK B, MeshSet M, const uint2 *pairs, const uint32_t *pair_total, uint32_t capacity,
-                           uint32_t *wsum, uint32_t *capped)
-{
-    __shared__ MeshLds L;
-    const int lane = lane_id();
-    uint32_t np = *pair_total;
-    if (np > capacity) np = capacity;
-    PairSel s;
-    select_mesh_records(A, B, M, pairs, blockIdx.x * MC + lane, np, L, lane, s);
-    uint32_t kept = s.kept, cap = s.found > s.kept ? 1u : 0u;
-    for (int o = 32; o > 0; o >>= 1) { kept += __shfl_xor(kept, o); cap += __shfl_xor(cap, o); }
-    if (lane == 0) {
-        wsum[blockIdx.x] = kept;
-        if (cap && capped) atomicAdd(capped, cap);
-    }
-}
-
-// one workgroup: the exclusive scan of the wavefronts' record counts in place, and the total
-constexpr int MS = 1024;
-__global__ __launch_bounds__(MS)
-void k_mesh_contacts_scan(const uint32_t *pair_total, uint32_t capacity, uint32_t *wsum, uint32_t *total)
-{
-    __shared__ uint32_t part[MS / WAVE];
-    uint32_t np = *pair_total;
-    if (np > capacity) np = capacity;
-    const uint32_t nw = (np + MC - 1) / MC, per = (nw + MS - 1) / MS;
-    const uint32_t b0 = threadIdx.x * per, b1 = b0 + per < nw ? b0 + per : nw;
-    uint32_t sum = 0;
-    for (uint32_t i = b0; i < b1; i++) sum += wsum[i];
-    const int lane = lane_id(), wv = threadIdx.x / WAVE;
-    const uint32_t incl = wave_prefix_sum(sum);
-    if (lane == WAVE - 1) part[wv] = incl;
-    __syncthreads();
-    uint32_t off = incl - sum;
-    for (int k = 0; k < wv; k++) off += part[k];
-    for (uint32_t i = b0; i < b1; i++) { const uint32_t c = wsum[i]; wsum[i] = off; off += c; }
-    if (threadIdx.x == MS - 1) {
-        uint32_t t = 0;
-        for (int k = 0; k < MS / WAVE; k++) t += part[k];
-        if (total) *total = t;
-    }
-}
-
-__global__ __launch_bounds__(MC)
-void k_mesh_contacts_write(GeomsK A, GeomsK B, MeshSet M, const uint2 *pairs, const uint32_t *pair_total, uint32_t capacity,
-                           const uint32_t *wsum, uint32_t out_capacity, clapgpu_contact2 *out, uint32_t *mesh_ref,
-                           uint32_t *body_flags)
-{
-    __shared__ MeshLds L;
-    const int lane = lane_id();
-    uint32_t np = *pair_total;
-    if (np > capacity) np = capacity;
-    if (blockIdx.x * MC >= np) return;                                   // wave-uniform
-    const uint32_t p = blockIdx.x * MC + lane;
-    PairSel s;
-    select_mesh_records(A, B, M, pairs, p, np, L, lane, s);
-    uint32_t incl = s.kept;                                              // wave_prefix_sum (common.h) restated: calling it moves this kernel's code
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t u = __shfl_up(incl, o);
-        if (lane >= o) incl += u;
-    }
-    const uint32_t base = wsum[blockIdx.x] + incl - s.kept;
-    if (s.kept == 0) return;
-    const double *m1 = (A.material && B.material) ? A.material + 5 * (size_t)s.body : nullptr;
-    const double *m2 = (A.material && B.material) ? B.material + 5 * (size_t)s.stat : nullptr;
-    for (uint32_t k = 0; k < s.kept; k++) {
-        const uint32_t t = L.tri[k * MC + lane];
-        uint32_t rank = 0;                                               // ascending triangle index within the pair
-        for (uint32_t j = 0; j < s.kept; j++) rank += L.tri[j * MC + lane] < t ? 1u : 0u;
-        const uint32_t o = base + rank;
-        if (o >= out_capacity) continue;
-        const uint32_t slot = L.slot[k * MC + lane] & 0x7fffffffu;
-        phd::CGeom c0, c1;
-        memset(&c0, 0, sizeof(c0));
-        memset(&c1, 0, sizeof(c1));
-        const int nc = phd::collide_segment_triangle(s.a, s.b, s.r, M.tri + 9 * (size_t)slot, c0, c1);
-        clapgpu_contact2 c;
-        memset(&c, 0, sizeof(c));
-        for (int i = 0; i < 3; i++) { c.pos[i] = c0.pos[i]; c.normal[i] = c0.normal[i]; }
-        c.depth = c0.depth;
-        if (nc > 1) {
-            for (int i = 0; i < 3; i++) { c.pos2[i] = c1.pos[i]; c.normal2[i] = c1.normal[i]; }
-            c.depth2 = c1.depth;
-        }
-        contact_surface(c, m1, m2);
-        c.nc = (uint32_t)nc;
-        out[o] = c;
-        mesh_ref[2 * (size_t)o] = p;
-        mesh_ref[2 * (size_t)o + 1] = t;
-    }
-    // plain read-modify-write: every writer of this launch sets the same bit and nothing else changes the word
-    if (body_flags && !(body_flags[s.body] & CLAPGPU_BODY_HAS_JOINT)) body_flags[s.body] |= CLAPGPU_BODY_HAS_JOINT;
-}
-
 
 } // namespace clapgpu
 
@@ -627,50 +343,6 @@ extern "C" int clapgpu_contacts_geoms_both(void *stream, clapgpu_bp *bp, const c
     return CLAPGPU_OK;
 }
 
-extern "C" int clapgpu_contacts_spheres(void *stream, const clapgpu_bodies *b, const uint32_t *pairs,
-                                        const uint32_t *pair_total, uint32_t capacity, const double *material,
-                                        clapgpu_contact *contacts, uint32_t *contact_total)
-{
-    int rc = check_bodies(b);
-    if (rc) return rc;
-    if (!pair_total || (capacity && (!pairs || !contacts)))
-        return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    hipStream_t s = as_stream(stream);
-    if (contact_total)
-        CLAPGPU_HIP(hipMemsetAsync(contact_total, 0, sizeof(uint32_t), s));
-    if (capacity == 0 || b->n == 0)
-        return CLAPGPU_OK;
-    // the pair count lives on the device: launch for the capacity, lanes past the count retire at once
-    const uint32_t blocks = (capacity + PB - 1) / PB;
-    hipLaunchKernelGGL(k_contacts<false>, dim3(blocks < 512 ? blocks : 512), dim3(PB), 0, s,
-                       b->pos, b->radius, b->n, nullptr, 0u, reinterpret_cast<const uint2 *>(pairs), pair_total, capacity,
-                       material, nullptr, contacts, contact_total);
-    CLAPGPU_LAUNCH_CHECK("k_contacts<spheres>");
-    return CLAPGPU_OK;
-}
-
-extern "C" int clapgpu_contacts_sphere_box(void *stream, const clapgpu_bodies *b, uint32_t n_static,
-                                           const double *static_aabb, const uint32_t *pairs, const uint32_t *pair_total,
-                                           uint32_t capacity, const double *material, const double *static_material,
-                                           clapgpu_contact *contacts, uint32_t *contact_total)
-{
-    int rc = check_bodies(b);
-    if (rc) return rc;
-    if (!pair_total || (n_static && !static_aabb) || (capacity && (!pairs || !contacts)))
-        return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    hipStream_t s = as_stream(stream);
-    if (contact_total)
-        CLAPGPU_HIP(hipMemsetAsync(contact_total, 0, sizeof(uint32_t), s));
-    if (capacity == 0 || b->n == 0 || n_static == 0)
-        return CLAPGPU_OK;
-    const uint32_t blocks = (capacity + PB - 1) / PB;
-    hipLaunchKernelGGL(k_contacts<true>, dim3(blocks < 512 ? blocks : 512), dim3(PB), 0, s,
-                       b->pos, b->radius, b->n, static_aabb, n_static, reinterpret_cast<const uint2 *>(pairs), pair_total,
-                       capacity, material, static_material, contacts, contact_total);
-    CLAPGPU_LAUNCH_CHECK("k_contacts<sphere_box>");
-    return CLAPGPU_OK;
-}
-
 extern "C" int clapgpu_sweep_capsules_meshes(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B,
                                              const clapgpu_trimesh *meshes, uint32_t n_sweeps, const uint32_t *sweep_body,
                                              const float *delta, const uint32_t *cand_first, const uint32_t *cand, float *frac,
@@ -699,33 +371,4 @@ extern "C" int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, cons
                                       const uint32_t *cand, float *frac, float *normal, int32_t *hit)
 {
     return clapgpu_sweep_capsules_meshes(stream, A, B, nullptr, n_sweeps, sweep_body, delta, cand_first, cand, frac, normal, hit);
-}
-
-extern "C" int clapgpu_contacts_meshes(void *stream, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
-                                       const clapgpu_trimesh *meshes, const uint32_t *static_pairs,
-                                       const uint32_t *static_pair_total, uint32_t static_capacity, uint32_t *scratch,
-                                       uint32_t capacity, clapgpu_contact2 *contacts, uint32_t *mesh_ref,
-                                       uint32_t *contact_total, uint32_t *capped_pairs, uint32_t *body_flags)
-{
-    if (!bodies || !statics || !meshes || !static_pair_total || (static_capacity && (!static_pairs || !scratch)) ||
-        (capacity && (!contacts || !mesh_ref)))
-        return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (reinterpret_cast<uintptr_t>(contacts) & 15u) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (trimesh_set(meshes).n_statics != statics->n) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    hipStream_t s = as_stream(stream);
-    if (contact_total) CLAPGPU_HIP(hipMemsetAsync(contact_total, 0, sizeof(uint32_t), s));
-    if (capped_pairs) CLAPGPU_HIP(hipMemsetAsync(capped_pairs, 0, sizeof(uint32_t), s));
-    if (static_capacity == 0 || bodies->n == 0 || statics->n == 0) return CLAPGPU_OK;
-    const MeshSet M = trimesh_set(meshes);
-    const uint32_t waves = (static_capacity + MC - 1) / MC;
-    const uint2 *pairs = reinterpret_cast<const uint2 *>(static_pairs);
-    hipLaunchKernelGGL(k_mesh_contacts_count, dim3(waves), dim3(MC), 0, s, geoms_k(bodies), geoms_k(statics), M, pairs,
-                       static_pair_total, static_capacity, scratch, capped_pairs);
-    CLAPGPU_LAUNCH_CHECK("k_mesh_contacts_count");
-    hipLaunchKernelGGL(k_mesh_contacts_scan, dim3(1), dim3(MS), 0, s, static_pair_total, static_capacity, scratch, contact_total);
-    CLAPGPU_LAUNCH_CHECK("k_mesh_contacts_scan");
-    hipLaunchKernelGGL(k_mesh_contacts_write, dim3(waves), dim3(MC), 0, s, geoms_k(bodies), geoms_k(statics), M, pairs,
-                       static_pair_total, static_capacity, scratch, capacity, contacts, mesh_ref, body_flags);
-    CLAPGPU_LAUNCH_CHECK("k_mesh_contacts_write");
-    return CLAPGPU_OK;
 }

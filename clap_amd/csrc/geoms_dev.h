@@ -1,5 +1,6 @@
-// geoms_dev.h -- a clapgpu_geoms set as the narrowphase kernels read it (contacts.hip, rays.hip, slide.hip), and the
-// host's checks of the scene a device query reads: the bodies' geoms, the mesh set and the broadphase index.
+// geoms_dev.h -- a clapgpu_geoms set as the narrowphase kernels read it (contacts.hip, mesh_contacts.hip,
+// rays.hip, slide.hip), and the host's checks of the scene a device query reads: the bodies' geoms, the mesh set and the
+// broadphase index.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -392,6 +392,12 @@ struct Geom {
 
 // dCollide(o1 = a, o2 = b): the class pair's collider; swapped and reversed (normals negated) when only the
 // swapped one exists (collision_kernel.cpp).  Returns nc; -1 for the dBoxBox branch; 0 without a collider here.
+//
+// Why a translation unit whose kernels call a collider is built with -mllvm -simplifycfg-sink-common=false (the Makefile
+// lists them): the colliders write their (up to two) contacts through CGeom references.  After inlining, LLVM's
+// SimplifyCFG sinks the "same" stores of different call sites into one block that stores through a SELECTED pointer (c0
+// or c1), which keeps both contacts addressable: 56 bytes (contacts) / 128 bytes (sweep) of scratch per lane, and
+// scratch is HBM traffic on gfx950.  Without the sinking SROA turns them into registers (private segment 0, +6 VGPRs).
 PHD int collide(const Geom &a, const Geom &b, CGeom &c0, CGeom &c1)
 {
     int nc = 0;

@@ -2,7 +2,7 @@
 // contacts.hip (k_sweep_capsules: the candidates are a list of the host's) and slide.hip (the candidates are gathered
 // on the device, and the probe is a mover's running position).  Include it after phys_dev.h, geoms_dev.h,
 // trimesh_dev.h and tricontact_dev.h; a translation unit that uses it is built with -mllvm
-// -simplifycfg-sink-common=false (see contacts.hip's header and the Makefile).
+// -simplifycfg-sink-common=false (why: the comment on phd::collide, phys_dev.h; which: the Makefile).
 #pragma once
 #include <string.h>
 #include "common.h"

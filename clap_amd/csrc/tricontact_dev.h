@@ -1,5 +1,5 @@
 // tricontact_dev.h -- a sphere or capsule against one static triangle, shared by the mesh contact pass and the capsule
-// sweep against meshes (contacts.hip), and the triangle normal every mesh kernel uses (tri_normal; rays.hip too).
+// sweep against meshes (mesh_contacts.hip, contacts.hip), and the triangle normal every mesh kernel uses (tri_normal; rays.hip too).
 // fp64, no FMA contraction (the Makefile builds with -ffp-contract=off).
 //
 // The body geom is a segment a, b with radius r (a sphere: a == b); the triangle is (v0, v1, v2) as the mesh set bakes

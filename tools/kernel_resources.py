@@ -13,7 +13,7 @@ CSRC = os.path.join(ROOT, "clap_amd", "csrc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
          "-Wno-unused-function", "--cuda-device-only", "-S"]
 NO_SINK = ["-mllvm", "-simplifycfg-sink-common=false"]
-PER_FILE = {"contacts.hip": NO_SINK, "slide.hip": NO_SINK}                    # as in the Makefile
+PER_FILE = {f + ".hip": NO_SINK for f in "contacts contacts_spheres mesh_contacts slide".split()}   # as in the Makefile
 
 
 def main():
