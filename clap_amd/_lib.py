@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 OK = 0
 ERR_NOMEM = -1
@@ -184,6 +184,23 @@ class Slide(C.Structure):
                 ("first_frac", C.c_void_p), ("push_hit", C.c_void_p), ("flags", C.c_void_p)]
 
 
+class CharactersMove(C.Structure):
+    """clapgpu_move (include/clapgpu.h): a batch of movers for clapgpu_characters_move."""
+    _fields_ = [("n", C.c_uint32), ("body", C.c_void_p), ("ray_off", C.c_void_p), ("motion", C.c_void_p),
+                ("state", C.c_void_p), ("jump", C.c_void_p), ("jump_params", C.c_void_p), ("velocity", C.c_void_p),
+                ("normal", C.c_void_p), ("airborne", C.c_void_p), ("request", C.c_void_p), ("applied", C.c_void_p),
+                ("collision", C.c_void_p), ("first_frac", C.c_void_p), ("push_hit", C.c_void_p), ("flags", C.c_void_p),
+                ("entity", C.c_void_p), ("yaw_quat", C.c_void_p)]
+
+
+CS_START, CS_WAKING, CS_IDLE, CS_MOVING, CS_JUMP_START, CS_JUMPING, CS_FALLING, CS_NONE = 0, 1, 2, 3, 4, 5, 6, 0xff
+
+
+def characters_move_scratch_bytes(n_bodies, n):
+    """clapgpu_characters_move_scratch_bytes: bytes of device scratch clapgpu_characters_move takes (needs a device)."""
+    return int(lib().clapgpu_characters_move_scratch_bytes(int(n_bodies), int(n)))
+
+
 class Characters(C.Structure):
     """clapgpu_characters (include/clapgpu.h)."""
     _fields_ = [("n", C.c_uint32), ("limbo_height", C.c_float), ("entity", C.c_void_p), ("body", C.c_void_p),
@@ -238,6 +255,29 @@ class FrameDesc(Frame):
     its own fields out behind its base's, as the C struct has them."""
     _fields_ = [("solver", C.POINTER(Solver)), ("solve_scratch", C.c_void_p), ("solve_rows_capacity", C.c_uint32),
                 ("solve_status", C.c_void_p)]
+
+
+class FrameDescMove(FrameDesc):
+    """clapgpu_frame (include/clapgpu.h) of ABI 39, whole: FrameDesc's fields, then the move stage's.  FrameDesc keeps the
+    layout of ABI 38; _FrameArg hands the library either of them at the full length."""
+    _fields_ = [("move", C.POINTER(CharactersMove)), ("move_dt_sec", C.c_double), ("move_scratch", C.c_void_p)]
+
+
+class _FrameArg:
+    """The argument type of clapgpu_frame_issue: a FrameDescMove by reference as it is; a FrameDesc (the descriptor of ABI
+    38) copied into a FrameDescMove whose move fields are NULL, so the library never reads past what it was given.
+    Anything shorter (Frame) is refused."""
+
+    @classmethod
+    def from_param(cls, obj):
+        inner = getattr(obj, "_obj", obj)                   # byref(x)._obj is x
+        if isinstance(inner, FrameDescMove):
+            return C.byref(inner)
+        if isinstance(inner, FrameDesc):
+            whole = FrameDescMove()
+            C.memmove(C.byref(whole), C.byref(inner), C.sizeof(FrameDesc))
+            return C.byref(whole)
+        raise TypeError("clapgpu_frame_issue takes a FrameDesc or a FrameDescMove by reference")
 
 
 LIGHTS_MAX = 128
@@ -342,6 +382,9 @@ SYMBOLS = {
     "clapgpu_bodies_push_scratch_bytes": (C.c_size_t, [C.c_uint32]),
     "clapgpu_bodies_push": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.c_uint32, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_characters_move_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "clapgpu_characters_move": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.POINTER(Geoms),
+                                          C.c_void_p, C.POINTER(Entities), C.c_double, C.POINTER(CharactersMove), C.c_void_p]),
     "clapgpu_bodies_islands_scratch_bytes": (C.c_size_t, [C.c_uint32]),
     "clapgpu_bodies_islands": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.c_double, C.c_void_p, C.c_void_p,
                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -379,7 +422,7 @@ SYMBOLS = {
     "clapgpu_shard_bases": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "clapgpu_mat4_invert": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "clapgpu_mat4_from_quat": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
-    "clapgpu_frame_issue": (C.c_int, [C.c_void_p, C.POINTER(FrameDesc), C.c_double, C.c_uint32]),
+    "clapgpu_frame_issue": (C.c_int, [C.c_void_p, _FrameArg, C.c_double, C.c_uint32]),
     "clapgpu_particles_update": (C.c_int, [C.c_void_p, C.POINTER(Particles), C.POINTER(C.c_float)]),
     "clapgpu_characters_update": (C.c_int, [C.c_void_p, C.POINTER(Characters), C.POINTER(Entities),
                                             C.POINTER(Bodies)]),

@@ -215,3 +215,13 @@ __attribute__((visibility("hidden"))) int clapgpu_bodies_ground_apply(void *stre
 // bodies.hip: clapgpu_characters_slide's last launch (slide.hip sweeps and decides, this moves)
 __attribute__((visibility("hidden"))) int clapgpu_bodies_slide_apply(void *stream, const clapgpu_bodies *b, uint32_t n,
                                                                      const uint32_t *body, uint32_t *flags, const uint32_t *moved);
+// rays.hip: clapgpu_bodies_ground_collide_meshes with the mesh pass's [n] doubles given by the caller (NULL: allocated);
+// cleared: scratch[0 .. b->n) is zero already
+__attribute__((visibility("hidden"))) int clapgpu_bodies_ground_collide_on(void *stream, struct clapgpu_bp *bp,
+                                                                           const clapgpu_bodies *b, const clapgpu_geoms *statics,
+                                                                           const clapgpu_trimesh *meshes, uint32_t n,
+                                                                           const uint32_t *body, const double *ray_off,
+                                                                           const uint8_t *grounded, uint8_t *grounded_out,
+                                                                           float *normal, double *dist, int32_t *hit,
+                                                                           uint32_t *flags, uint32_t *scratch, double *other,
+                                                                           bool cleared);

@@ -1,5 +1,6 @@
 // frame.hip -- one display frame of the batched path as ONE C call: the sequence clap_frame() runs
-// (core/clap.c:551-665) -- phys_step (clap.c:604: per fixed substep the two broadphase passes, near_callback's
+// (core/clap.c:551-665) -- scene_characters_move (clap.c:589: clapgpu_characters_move, when asked for) -> phys_step
+// (clap.c:604: per fixed substep the two broadphase passes, near_callback's
 // contact records, the island pass and the contact solve when asked for, the world step) -> scene_update -> mq_update with every entity's hook in list order
 // (character_update in front of default_update: body read-back, rotation push to colliders, light hand-off, TRS
 // rebuild, animated_update; particles_update) -> light grid -> render-pass glue (visible list, LOD pick).
@@ -146,7 +147,13 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         FR(chain_c());
     }
 
-    // ---- chain A.  phys_step: per substep broadphase x2, contacts, dWorldQuickStep's body stage (physics.c:746-771) ----
+    // ---- chain A.  scene_characters_move (clap.c:589): ground ray, velocity, slide and push of the movers ----
+    if (f->move) {
+        if (!f->bodies || !f->world || !f->static_geoms) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+        FR(clapgpu_characters_move(stream, f->bp, f->bodies, f->world, f->static_geoms, f->meshes, f->move->entity ? e : nullptr,
+                                   f->move_dt_sec, f->move, f->move_scratch));
+    }
+    // ---- phys_step: per substep broadphase x2, contacts, dWorldQuickStep's body stage (physics.c:746-771) ----
     if (f->bodies && f->world) {
         for (uint32_t s = 0; s < substeps; s++) {
             if (f->bp) {

@@ -698,11 +698,17 @@ extern "C" int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geom
     return clapgpu_ray_cast_meshes(stream, bp, bodies, statics, nullptr, n_rays, ray, skip, dist, hit, contact, flags);
 }
 
-extern "C" int clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b,
-                                                    const clapgpu_geoms *statics, const clapgpu_trimesh *meshes, uint32_t n,
-                                                    const uint32_t *body, const double *ray_off, const uint8_t *grounded,
-                                                    uint8_t *grounded_out, float *normal, double *dist, int32_t *hit,
-                                                    uint32_t *flags, uint32_t *scratch)
+// clapgpu_bodies_ground_collide_meshes on the caller's memory (move.hip): other = [n] doubles for the mesh pass
+// (meshes != NULL), so the call allocates nothing; cleared: the caller's own launch has zeroed scratch[0 .. b->n), so the
+// call issues kernels only
+__attribute__((visibility("hidden"))) int clapgpu_bodies_ground_collide_on(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b,
+                                                                           const clapgpu_geoms *statics,
+                                                                           const clapgpu_trimesh *meshes, uint32_t n,
+                                                                           const uint32_t *body, const double *ray_off,
+                                                                           const uint8_t *grounded, uint8_t *grounded_out,
+                                                                           float *normal, double *dist, int32_t *hit,
+                                                                           uint32_t *flags, uint32_t *scratch, double *other,
+                                                                           bool cleared)
 {
     if (!b || !statics || !b->pos || !b->quat || !b->radius || !b->yoffset)
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
@@ -715,10 +721,13 @@ extern "C" int clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp
     if (rc) return rc;
     if (n == 0) return CLAPGPU_OK;
     hipStream_t s = as_stream(stream);
-    CLAPGPU_HIP(hipMemsetAsync(scratch, 0, (size_t)(b->n ? b->n : 1) * sizeof(uint32_t), s));
-    double *other;
-    rc = mesh_scratch(s, meshes, n, &other);
-    if (rc) return rc;
+    if (!cleared) CLAPGPU_HIP(hipMemsetAsync(scratch, 0, (size_t)(b->n ? b->n : 1) * sizeof(uint32_t), s));
+    const bool own = meshes && !other;                                       // stream-ordered, freed behind the mesh pass
+    if (own) {
+        rc = mesh_scratch(s, meshes, n, &other);
+        if (rc) return rc;
+    }
+    if (!meshes) other = nullptr;
     hipLaunchKernelGGL(k_ground_rays, dim3((n + RB / WAVE - 1) / (RB / WAVE)), dim3(RB), 0, s, k, n, b->pos, b->yoffset, body,
                        ray_off, grounded, grounded_out, normal, dist, hit, flags, scratch, other);
     const hipError_t le = launch_error();
@@ -731,12 +740,22 @@ extern "C" int clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp
         p.grounded_out = grounded_out; p.normal = normal; p.moved = scratch;
         rc = mesh_pass(s, meshes, p);
     }
-    rc = free_scratch(s, other, rc);
+    if (own) rc = free_scratch(s, other, rc);
     if (rc) return rc;
     rc = clapgpu_bodies_ground_apply(stream, b, n, body, ray_off, grounded, grounded_out, dist, hit, flags, scratch);
     if (rc) return rc;
     if (bp) return clapgpu_bp_invalidate(stream, bp);                        // the moved boxes: the index is stale
     return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b,
+                                                    const clapgpu_geoms *statics, const clapgpu_trimesh *meshes, uint32_t n,
+                                                    const uint32_t *body, const double *ray_off, const uint8_t *grounded,
+                                                    uint8_t *grounded_out, float *normal, double *dist, int32_t *hit,
+                                                    uint32_t *flags, uint32_t *scratch)
+{
+    return clapgpu_bodies_ground_collide_on(stream, bp, b, statics, meshes, n, body, ray_off, grounded, grounded_out, normal,
+                                            dist, hit, flags, scratch, nullptr, false);
 }
 
 extern "C" int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,

@@ -19,7 +19,8 @@ from . import entities as ent_mod
 
 class FrameLoop:
     def __init__(self, batch, cam, world=None, feed=None, body_links=None, lights=None, characters=None,
-                 particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False, solve=False):
+                 particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False, solve=False,
+                 move=None):
         """batch: EntityBatch.  world: PhysWorld (dynamic bodies write their entities through
         body_entity; character bodies have body_entity = -1).  feed: CharacterFeed.  body_links:
         (link_body, link_entity) of characters / static colliders whose rotation follows the entity.
@@ -31,8 +32,12 @@ class FrameLoop:
         (clapgpu_pose_batch.skip).  A model with (joint, path) pairs that have no channel keeps "trs": such a path's
         value lives there (model.c:1301).  islands: every substep wakes sleeping bodies by contact
         (clapgpu_bodies_islands between its contacts and its step; implies contacts).  solve: every substep's contacts
-        act on the bodies (clapgpu_bodies_solve between the island pass and the step; implies islands)."""
+        act on the bodies (clapgpu_bodies_solve between the island pass and the step; implies islands).  move: a
+        physics.CharacterMoves over `world`: character_move of those characters is the frame's first stage
+        (clapgpu_characters_move, scene_characters_move of clap.c:589) with the frame's dt as its raw frame delta; the
+        host updates its arrays (CharacterMoves.set) between frames and reads its outputs after them."""
         islands = islands or solve
+        self.move, self.move_dt = move, 0.0
         self.solve = solve
         self.batch, self.world, self.feed, self.lights = batch, world, feed, lights
         self.characters, self.particles = characters, particles
@@ -55,7 +60,7 @@ class FrameLoop:
         import ctypes as C
         from . import _lib
         b, w = self.batch, self.world
-        f = _lib.FrameDesc()
+        f = _lib.FrameDescMove()
         keep = []                                           # ctypes objects the descriptor points into
         f.entities = C.pointer(b._desc)
         if b.tiled:
@@ -102,6 +107,17 @@ class FrameLoop:
                 f.solver = C.pointer(w.solver)
                 f.solve_scratch, f.solve_rows_capacity = w.solve_scratch.data_ptr(), w.solve_rows_capacity
                 f.solve_status = w.solve_status.data_ptr()
+            if self.move is not None:
+                if w.facc is None or self.move.world is not w:
+                    raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "FrameLoop",
+                                            "move: a CharacterMoves over this world, and PhysWorld(forces=True)")
+                if not f.static_geoms:                          # (alone they add no launch to the physics block)
+                    sg = w.static_geoms()
+                    keep.append(sg)
+                    f.static_geoms = C.pointer(sg)
+                if w._meshes is not None:
+                    f.meshes = w._meshes
+                f.move, f.move_scratch = C.pointer(self.move._desc), self.move.scratch.data_ptr()
             if self.body_links is not None:
                 lb, le = w.upload_links(*self.body_links)
                 f.n_body_links, f.link_body, f.link_entity = len(self.body_links[0]), lb.data_ptr(), le.data_ptr()
@@ -166,6 +182,7 @@ class FrameLoop:
 
     def clap_frame(self, now, dt):
         steps = self.world.phys_step_begin(dt) if self.world is not None else 0
+        self.move_dt = float(dt)                             # character_move's frame delta (clap_get_fps_delta)
         self._issue(now, steps)
 
     def _issue(self, now, steps):
@@ -178,6 +195,7 @@ class FrameLoop:
         f.now_dev = self.characters.now_dev.data_ptr() if (now is None and self.characters is not None) else None
         # CLAPGPU_FRAME_OVERLAP: three chains on three streams (frame.hip); CLAPGPU_FRAME_PREBIN
         f.flags = (1 if getattr(self, "overlap", False) else 0) | (2 if self.prebin else 0)
+        f.move_dt_sec = self.move_dt
         rc = _lib.lib().clapgpu_frame_issue(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(f),
                                             0.0 if now is None else float(now), int(steps))
         _lib.check(rc, "clapgpu_frame_issue")

@@ -314,6 +314,20 @@ class PhysWorld:
         pushed = self.bodies_push(body_d[:nb], given[:nb] if nb else given, push, flags)
         return vel, first, push, flags, pushed
 
+    def characters_move(self, moves, dt_sec, grid=True, meshes=True):
+        """character_move for the movers of `moves` (a CharacterMoves over this world) as one call without a host round
+        trip (clapgpu_characters_move): ground ray, the airborne / jump / walking decision, slide and push, and the
+        rotation hand-off when `moves` has one.  dt_sec: the raw frame delta.  Returns moves.outputs(): device tensors."""
+        if self.facc is None:
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "characters_move", "no force accumulator: PhysWorld(forces=True)")
+        sg = self.static_geoms()
+        e = C.byref(moves.entity_batch._desc) if moves.entity_batch is not None else None
+        _lib.check(_lib.lib().clapgpu_characters_move(_stream(), self._bp if grid else None, C.byref(self._desc),
+                                                      C.byref(self.world), C.byref(sg), self._meshes if meshes else None, e,
+                                                      float(dt_sec), C.byref(moves._desc), _ptr(moves.scratch) if moves.n else None),
+                   "clapgpu_characters_move")
+        return moves.outputs()
+
     def islands(self, h, want_island=True, want_woken=True):
         """The island pass of dWorldQuickStep (clapgpu_bodies_islands) over the body-body pairs of the last broadphase()
         and the records of the last contacts_geoms(): the step's auto-disable bookkeeping, then every sleeping body in
@@ -634,3 +648,67 @@ class PhysWorld:
 
     def integrate_algorithmic_bytes(self):
         return 232 * self.n
+
+
+class CharacterMoves:
+    """The movers of clapgpu_characters_move (clapgpu_move): device arrays of the per-character state character_move reads
+    and writes, the outputs, the scratch and the descriptor.  bodies [n]: the characters' bodies, each once; ray_off [n];
+    jump_params [n, 2] (jump_forward, jump_upward).  entity [n] with entity_batch: the rotation hand-off (set yaw_quat
+    every frame).  velocity / normal / airborne persist on the device from call to call, as the reference keeps them in
+    struct character; set() uploads what the host changed."""
+
+    _IN = dict(motion=(np.float32, 2), state=(np.uint8, 0), jump=(np.uint8, 0), jump_params=(np.float32, 2),
+               velocity=(np.float32, 3), normal=(np.float32, 3), airborne=(np.uint8, 0), yaw_quat=(np.float32, 4))
+
+    def __init__(self, world, bodies, ray_off, jump_params=None, entity=None, entity_batch=None, **state):
+        if (entity is None) != (entity_batch is None):
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "CharacterMoves", "entity and entity_batch: both or neither")
+        self.world, self.entity_batch = world, entity_batch
+        self.device = dev = world.device
+        self.n = n = len(bodies)
+        n1 = max(n, 1)
+        up = lambda a, dt, view=None: torch.from_numpy(np.ascontiguousarray(a, dt).view(view or dt)).to(dev)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        self.body = up(np.asarray(bodies, np.uint32), np.uint32, np.int32) if n else z(1, torch.int32)
+        self.ray_off = up(np.asarray(ray_off, np.float64).reshape(-1), np.float64) if n else z(1, torch.float64)
+        self.motion, self.jump_params = z((n1, 2), torch.float32), z((n1, 2), torch.float32)
+        self.state, self.jump, self.airborne = z(n1, torch.uint8), z(n1, torch.uint8), z(n1, torch.uint8)
+        self.velocity, self.normal = z((n1, 3), torch.float32), z((n1, 3), torch.float32)
+        self.request, self.applied = z(n1, torch.uint8), z(n1, torch.uint8)
+        self.collision = torch.full((n1,), -1, dtype=torch.int32, device=dev)
+        self.first_frac = torch.ones((n1, 2), dtype=torch.float32, device=dev)
+        self.push_hit = torch.full((n1, 6), -1, dtype=torch.int32, device=dev)
+        self.flags = z(n1, torch.int32)
+        self.entity = self.yaw_quat = None
+        if entity is not None:
+            self.entity = up(np.asarray(entity, np.uint32), np.uint32, np.int32) if n else z(1, torch.int32)
+            self.yaw_quat = z((n1, 4), torch.float32)
+            self.yaw_quat[:, 3] = 1.0
+        need = _lib.characters_move_scratch_bytes(world.n, n) if n else 0
+        self.scratch = torch.zeros(max(need, 256), dtype=torch.uint8, device=dev)
+        self._desc = _lib.CharactersMove(n, *[_ptr(getattr(self, k)) for k in
+                                              ("body", "ray_off", "motion", "state", "jump", "jump_params", "velocity",
+                                               "normal", "airborne", "request", "applied", "collision", "first_frac",
+                                               "push_hit", "flags", "entity", "yaw_quat")])
+        if jump_params is not None:
+            state["jump_params"] = jump_params
+        self.set(**state)
+
+    def set(self, **arrays):
+        """Upload motion [n, 2], state [n], jump [n], jump_params [n, 2], velocity [n, 3], normal [n, 3], airborne [n],
+        yaw_quat [n, 4] (x, y, z, w): those given, into the arrays the descriptor points at."""
+        for k, a in arrays.items():
+            dt, width = self._IN[k]
+            a = np.asarray(a)
+            if dt == np.uint8 and a.dtype != np.uint8:
+                a = a != 0 if k != "state" else a
+            a = np.ascontiguousarray(a, dt).reshape((-1, width) if width else (-1,))
+            if self.n:
+                getattr(self, k)[:self.n].copy_(torch.from_numpy(a).to(self.device))
+
+    def outputs(self):
+        """dict of device tensors: velocity, normal, airborne (in / out), request, applied, collision, first_frac,
+        push_hit, flags (ray flags | slide flags << 8)."""
+        n = self.n
+        return {k: getattr(self, k)[:n] for k in ("velocity", "normal", "airborne", "request", "applied", "collision",
+                                                   "first_frac", "push_hit", "flags")}

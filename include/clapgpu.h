@@ -1382,6 +1382,91 @@ int clapgpu_characters_update(void *stream, const clapgpu_characters *c, const c
 int clapgpu_characters_update_clock(void *stream, const clapgpu_characters *c, const clapgpu_entities *e, const clapgpu_bodies *b,
                                     const clapgpu_anim_clock *clk, double now, const double *now_dev);
 
+/*
+ * clapgpu_characters_move: character_move (character.c:450-537) for a batch of characters that have a body, as one call
+ * without host synchronisation: the ground ray (:454), the airborne / jump / walking decision (:464-532) and the
+ * ENTITY3D_HAS_PHYSICS branch of character_apply_velocity with its pushes.  It is scene_characters_move's body
+ * (clap.c:589), which runs before phys_step.  What stays with the host, from the outputs: the animation side of
+ * character_set_state and ch->state itself (request), connect / disconnect (collision), character_set_moved (applied),
+ * character_debug, dash and input handling, characters without a body (transform_move).  PARITY UNPINNED (ODE absent):
+ * the rule below is the library's own contract; tests/moveref.py restates it.
+ *
+ * Mover k, all arithmetic in float exactly as character.c writes it, no FMA, linmath's loops in their own order:
+ *   1. Ground ray.  grounded[k] = !airborne[k]; the ray is clapgpu_bodies_ground_collide_meshes' and snaps the body as
+ *      that call does.  normal[k] is written only on a hit, collision[k] = the hit (body i, -2 - s) or -1 on a miss,
+ *      airborne[k] = !grounded_out.  A ray flagged CLAPGPU_RAY_INVALID or CLAPGPU_RAY_UNRESOLVED ends the mover here:
+ *      velocity, normal and airborne unchanged, request 0xff, applied 0, first_frac 1, push_hit -1; the host redoes it.
+ *      CLAPGPU_RAY_MOVED_TARGET is reported and the mover goes on.
+ *   2. Jump protection (:464): state == JUMPING && velocity[1] > 0 sets airborne = 1.
+ *   3. Airborne (:467-488): when the raw dt_sec > 1e-6, velocity[1] = (float)((double)velocity[1] +
+ *      (double)(float)w->gravity[1] * dt_sec) and the mover slides (applied = 1); either way request = FALLING.
+ *   4. Grounded.  jump[k] set (:501, :437-447): velocity = (dx * jump_forward, jump_upward, dz * jump_forward),
+ *      request = JUMP_START, airborne = 1 when state == MOVING (:388), no slide.  Else vec3_len(motion) != 0 (:504):
+ *      when vec3_len(normal) > 0, newz = cross((1, 0, 0), normal) and newx = cross(normal, newz) as vec3_mul_cross
+ *      writes them (the products by 0 and 1 are made), each normalised by k = (float)(1.0 / (double)len) with the
+ *      scaling in float (vec3_norm, vec3_scale); coef = 1 if state == MOVING else 0.3f; velocity[i] = newx[i] * (dx *
+ *      coef) + newz[i] * (dz * coef) (:526).  Whatever the normal, request = MOVING; the mover slides (applied = 1) only
+ *      when state >= IDLE (character_set_state's early return, :319-326).  Else request = IDLE.
+ *   5. Slide and push.  The sliding movers go through clapgpu_characters_slide's own launches (dt_sec clamped there);
+ *      the others stand in its list under the body index 0xffffffff, which the slide leaves alone, and the
+ *      CLAPGPU_SLIDE_INVALID it gives such an entry is cleared.  The pushes go through clapgpu_bodies_push with the
+ *      velocity of steps 3 and 4, from before the slide zeroed velocity[1].  A raw dt_sec < 1e-6 issues no slide or push
+ *      launch; applied stays 1 for the grounded walkers (the reference still rotates them, :259-260, :312-313).
+ *   6. Rotation hand-off (entity and yaw_quat given, both or neither): for every mover with applied == 1,
+ *      e->rot[entity[k]] = yaw_quat[k] and e->flags[entity[k]] |= CLAPGPU_E_DIRTY (entity3d_rotate, :313).
+ * One batch: every ground ray sees the poses from before the call, every slide the poses after all ground snaps.  The
+ * reference moves one character at a time: flags[k] = the ray's CLAPGPU_RAY_* | the slide's CLAPGPU_SLIDE_* << 8, and
+ * the MOVED_TARGET bit of either stage marks the movers to redo in list order.  A body listed more than once is INVALID
+ * in both stages and stays (its normal[k] may hold its ray's).
+ * Launches: the index (bp given), a launch that writes grounded[], the ground rays (+ the mesh pass) and their apply,
+ * k_move_decide, the index again, the slide's, the push's, k_move_finish.  No allocation, no host synchronisation: a
+ * captured graph can hold the call, dt_sec baked in as for the slide.  n == 0 returns CLAPGPU_OK and launches nothing.
+ * CLAPGPU_ERR_INVALID_ARGUMENTS before any HIP call: a NULL m, b, w or statics; with n > 0 a missing array of m, only
+ * one of entity / yaw_quat, the pair without e (or e without rot / flags), a missing b->facc or any other array of b the
+ * three stages ask for, bp without b->aabb, a scratch that is NULL or not 256-byte aligned.
+ * bp: NULL, or created with statics->n statics; the call indexes it itself and leaves it cleared.  meshes: NULL, or
+ * created with n_statics == statics->n.  scratch: clapgpu_characters_move_scratch_bytes(b->n, n) bytes of device memory,
+ * 256-byte aligned, overwritten: the [b->n] words the ray and the slide use one after the other, the slide's body list
+ * and flags, the velocities given to the push, the grounded bytes in and out, the ray's distance and its mesh pass's
+ * word, the push's scratch (the helper needs clapgpu_init, and returns 0 when it cannot tell or for n == 0).
+ */
+typedef struct clapgpu_move {
+    uint32_t        n;
+    const uint32_t *body;          /* [n] index into the bodies, each at most once */
+    const double   *ray_off;       /* [n] phys_body.ray_off, as clapgpu_bodies_ground_collide takes it */
+    const float    *motion;        /* [n][2] mctl dx, dz of this frame (ch->motion = {dx, 0, dz}) */
+    const uint8_t  *state;         /* [n] ch->state, CS_* of character.h:10-19 (0 START, 1 WAKING, 2 IDLE, 3 MOVING,
+                                      4 JUMP_START, 5 JUMPING, 6 FALLING) */
+    const uint8_t  *jump;          /* [n] ch->jump && ch->can_jump */
+    const float    *jump_params;   /* [n][2] jump_forward, jump_upward */
+    float          *velocity;      /* [n][3] in/out ch->velocity */
+    float          *normal;        /* [n][3] in/out ch->normal (kept on a ray miss) */
+    uint8_t        *airborne;      /* [n] in/out ch->airborne */
+    /* out */
+    uint8_t        *request;       /* [n] the state character_move asks character_set_state for, or 0xff: none */
+    uint8_t        *applied;       /* [n] 1: character_apply_velocity ran (host: character_set_moved, entity3d_rotate) */
+    int32_t        *collision;     /* [n] ch->collision: body i, -2 - s, or -1 */
+    float          *first_frac;    /* [n][2] as clapgpu_slide */
+    int32_t        *push_hit;      /* [n][6] as clapgpu_slide */
+    uint32_t       *flags;         /* [n] ray flags | slide flags << 8 */
+    /* optional rotation hand-off, both or neither */
+    const uint32_t *entity;        /* [n] slot in the entity SoA */
+    const float    *yaw_quat;      /* [n][4] the host's quat for entity3d_rotate(e, 0, atan2f(dx, dz), 0), 16-byte aligned */
+} clapgpu_move;
+#define CLAPGPU_CS_START      0u   /* character_state, character.h:10-19 */
+#define CLAPGPU_CS_WAKING     1u
+#define CLAPGPU_CS_IDLE       2u
+#define CLAPGPU_CS_MOVING     3u
+#define CLAPGPU_CS_JUMP_START 4u
+#define CLAPGPU_CS_JUMPING    5u
+#define CLAPGPU_CS_FALLING    6u
+#define CLAPGPU_CS_NONE       0xffu
+size_t clapgpu_characters_move_scratch_bytes(uint32_t n_bodies, uint32_t n);
+int    clapgpu_characters_move(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_world *w,
+                               const clapgpu_geoms *statics, const clapgpu_trimesh *meshes,
+                               const clapgpu_entities *e /* NULL without the hand-off */,
+                               double dt_sec /* raw frame delta */, const clapgpu_move *m, void *scratch);
+
 /* ======================================================================== */
 /* Clustered lighting: lights x screen tiles bitmask (core/light.c)           */
 /* ======================================================================== */
@@ -1434,7 +1519,7 @@ int clapgpu_lights_from_entities(void *stream, const clapgpu_entities *e, uint32
 
 /*
  * Everything clap_frame() does on the batched path, as one C call that issues the launches in the reference's
- * order on `stream` -- phys_step's substeps (broadphase x2, contact records, world step), character hooks, body
+ * order on `stream` -- scene_characters_move (when `move` is set), phys_step's substeps (broadphase x2, contact records, world step), character hooks, body
  * read-back + rotation push + light hand-off, the entity update with the main view's cull, animation clock + pose +
  * skinning, particles, the light grid, the ordered visible list + LOD pick -- without reading anything back.
  * Every pointer except `entities` may be NULL: that part of the frame is skipped.  The descriptor holds no state: a
@@ -1494,6 +1579,14 @@ typedef struct clapgpu_frame {
     void     *solve_scratch;                   /* clapgpu_bodies_solve_scratch_bytes(bodies->n, solve_rows_capacity), 256-byte aligned */
     uint32_t  solve_rows_capacity;
     uint32_t *solve_status;
+    /* scene_characters_move (clap.c:589, before phys_step): clapgpu_characters_move as the frame's first stage, on the
+     * physics chain under CLAPGPU_FRAME_OVERLAP, over bodies, world, bp, static_geoms and meshes of this descriptor and,
+     * for the rotation hand-off, entities.  move NULL: none, the frame issues the launches it issued before these fields
+     * existed.  clapgpu_characters.airborne may alias move->airborne when both lists are in the same order: the hooks
+     * then see what this frame's move left */
+    const clapgpu_move *move;
+    double    move_dt_sec;                     /* the raw frame delta, as clapgpu_characters_move takes it */
+    void     *move_scratch;                    /* clapgpu_characters_move_scratch_bytes(bodies->n, move->n), 256-byte aligned */
 } clapgpu_frame;
 
 /* Default (0): everything on the caller's stream in the reference's order.  CLAPGPU_FRAME_OVERLAP: the frame's three
