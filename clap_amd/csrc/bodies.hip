@@ -8,7 +8,7 @@
 //                     <.., true>: ... with the force accumulator (dxBody::facc) and kinematic bodies; the gravity-only
 //                     instantiations are what ran before the accumulator existed, instruction for instruction
 //   k_bodies_aabb     the geoms alone
-//   k_ground_apply    phys_body_ground_collide's moves (the rays and the decision: rays.hip)
+//   k_ground_apply    phys_body_ground_collide's moves (the rays and the decision: rays.hip, ray_trimesh.hip)
 //   k_slide_apply     character_apply_velocity's moves (the sweeps and the decision: slide.hip)
 //   k_phys_body_update, k_bodies_rotate_from_entities   body pose -> entity SoA (physics.c:789-812) and back
 //                     (physics.c:136-145)
@@ -229,9 +229,9 @@ void k_bodies_step(BodiesK b, clapgpu_world w, double h, BinK bin, double *facc)
         write_geom(b, i, p, q);
 }
 
-// clapgpu_bodies_ground_collide's second launch (rays.hip casts, this moves): phys_body_move of every body whose ray
-// said so, through a vec3 (float), then the geom as clapgpu_bodies_aabb writes it.  A ray whose hit body moved here is
-// flagged: it saw that body where it was before the call.
+// clapgpu_bodies_ground_collide's second launch (rays.hip and ray_trimesh.hip cast, this moves): phys_body_move of every
+// body whose ray said so, through a vec3 (float), then the geom as clapgpu_bodies_aabb writes it.  A ray whose hit body
+// moved here is flagged: it saw that body where it was before the call.
 __global__ __launch_bounds__(PB)
 void k_ground_apply(BodiesK b, const double *yoffset, uint32_t n, const uint32_t *body, const double *ray_off,
                     const uint8_t *grounded, uint8_t *grounded_out, const double *dist, const int32_t *hit, uint32_t *flags,

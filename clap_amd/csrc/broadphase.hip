@@ -477,7 +477,7 @@ void k_bp_index_bounds(BpK k)
         double bb[6];
         load_box(k.aabb, i, bb);
         if (box_oversized(bb, k.cell)) over = 1;
-        // finite coordinates only: a geom at infinity or NaN never hits (rays.hip), and the bounds stay finite
+        // finite coordinates only: a geom at infinity or NaN never hits (ray_colliders_dev.h), and the bounds stay finite
         for (int a = 0; a < 3; a++) {
             if (isfinite(bb[2 * a])) m[a] = fmin(m[a], bb[2 * a]);
             if (isfinite(bb[2 * a + 1])) m[3 + a] = fmax(m[3 + a], bb[2 * a + 1]);

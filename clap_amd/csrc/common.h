@@ -36,6 +36,25 @@ __attribute__((visibility("hidden"))) int current_device_cus(int *dev, int *n_cu
 // bodies.hip: what every entry point that takes a clapgpu_bodies asks of it (include/clapgpu.h)
 __attribute__((visibility("hidden"))) int check_bodies(const clapgpu_bodies *b);
 
+// ---------------------------------------------------------------- the scratch carve (host)
+// A call's device scratch is cut into parts that each start on a 256-byte boundary (the caller's pointer is 256-byte
+// aligned).  The rule is stated here alone: a call that nests another's scratch in its own (move.hip: the push's) stays
+// inside the bytes its *_scratch_bytes asks for because both sums are this one.
+static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct Carve {
+    size_t at = 0;
+    size_t take(size_t bytes) { const size_t was = at; at += align256(bytes); return was; }   // the part's offset
+    size_t bytes() const { return at; }                                                       // of every part so far
+};
+
+static inline uint32_t bits_of(uint32_t v)              // bits that hold every value 0 .. v (a radix sort's key width)
+{
+    uint32_t b = 1;
+    while (b < 32 && (v >> b)) b++;
+    return b;
+}
+
 // ---------------------------------------------------------------- device side
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 
@@ -206,7 +225,7 @@ __device__ __forceinline__ uint32_t wave_byte_sum(const uint8_t *bytes, uint32_t
 
 } // namespace clapgpu
 
-// bodies.hip: clapgpu_bodies_ground_collide's second launch (rays.hip casts and decides, this moves)
+// bodies.hip: clapgpu_bodies_ground_collide's second launch (rays.hip casts, rays.hip or ray_trimesh.hip decides, this moves)
 __attribute__((visibility("hidden"))) int clapgpu_bodies_ground_apply(void *stream, const clapgpu_bodies *b, uint32_t n,
                                                                       const uint32_t *body, const double *ray_off,
                                                                       const uint8_t *grounded, uint8_t *grounded_out,

@@ -53,7 +53,7 @@ static inline clapgpu::GeomsK geoms_k(const clapgpu_geoms *g)
     return k;
 }
 
-// ---- the scene checks the device queries share (rays.hip, slide.hip)
+// ---- the scene checks the device queries share (rays.hip's cast_scene, slide.hip)
 // the bodies' geoms, as PhysWorld.body_geoms; false: capsules need their axis
 static inline bool body_geoms(const clapgpu_bodies *b, clapgpu_geoms *g)
 {

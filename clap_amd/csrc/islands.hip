@@ -139,16 +139,27 @@ void k_islands_wake(uint32_t n, uint32_t *bflags, const uint32_t *awake, const u
     if (threadIdx.x == 0 && count) atomicAdd(woken_total, count);
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// the scratch: parent [n] | awake [n] | root [n] (the last unused when the caller takes `island`)
+struct IslandsLayout { size_t parent, awake, root, total; };
+
+static IslandsLayout islands_layout(uint32_t n)
+{
+    IslandsLayout l;
+    Carve c;
+    l.parent = c.take((size_t)n * sizeof(uint32_t));
+    l.awake = c.take((size_t)n * sizeof(uint32_t));
+    l.root = c.take((size_t)n * sizeof(uint32_t));
+    l.total = c.bytes();
+    return l;
+}
 
 } // namespace clapgpu
 
 using namespace clapgpu;
 
-// the scratch: parent [n] | awake [n] | root [n] (the last unused when the caller takes `island`)
 extern "C" size_t clapgpu_bodies_islands_scratch_bytes(uint32_t n)
 {
-    return 3 * align256((size_t)n * sizeof(uint32_t));
+    return islands_layout(n).total;
 }
 
 extern "C" int clapgpu_bodies_islands(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, double h,
@@ -166,9 +177,10 @@ extern "C" int clapgpu_bodies_islands(void *stream, const clapgpu_bodies *b, con
     if (n == 0) return CLAPGPU_OK;
     if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 255u)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     hipStream_t s = as_stream(stream);
-    const size_t words = align256((size_t)n * sizeof(uint32_t)) / sizeof(uint32_t);
-    uint32_t *parent = static_cast<uint32_t *>(scratch), *awake = parent + words;
-    uint32_t *root = island ? island : awake + words;
+    const IslandsLayout l = islands_layout(n);
+    uint8_t *base = static_cast<uint8_t *>(scratch);
+    uint32_t *parent = reinterpret_cast<uint32_t *>(base + l.parent), *awake = reinterpret_cast<uint32_t *>(base + l.awake);
+    uint32_t *root = island ? island : reinterpret_cast<uint32_t *>(base + l.root);
 
     IslandsK k;
     k.n = n; k.samples = b->adis_average_samples;

@@ -1,9 +1,9 @@
 // move.hip -- character_move (character.c:450-537) for a batch of characters with a body, for gfx950: the stage of
 // clap_frame() in front of phys_step (scene_characters_move, clap.c:589) as one call without a host round trip.
 //
-// Every physics call the function makes is a batched call of its own already: the ground ray (rays.hip, bodies.hip's
-// k_ground_apply), the sweep-and-slide (slide.hip, k_slide_apply) and the pushes (push.hip).  This file is what the host
-// did between them:
+// Every physics call the function makes is a batched call of its own already: the ground ray (rays.hip, ray_trimesh.hip,
+// bodies.hip's k_ground_apply), the sweep-and-slide (slide.hip, k_slide_apply) and the pushes (push.hip).  This file is
+// what the host did between them:
 //   k_move_begin    grounded[k] = !airborne[k], what phys_body_ground_collide is given (:454); also clears the per-body
 //                   words of the ray stage, so that the whole call is kernel launches (a captured graph holds no
 //                   memset node of this file's making)
@@ -147,9 +147,7 @@ void k_move_finish(uint32_t n, const uint32_t *slide_body, const uint32_t *slide
     }
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// the scratch, every part 256-byte aligned
+// the scratch, every part 256-byte aligned (Carve, common.h); the last is the push's own, by its own count
 struct MoveScratch {
     size_t words, slide_body, slide_flags, given, dist, other, grounded, grounded_out, push, bytes;
 };
@@ -157,18 +155,17 @@ struct MoveScratch {
 static MoveScratch move_layout(uint32_t n_bodies, uint32_t n, size_t push_bytes)
 {
     MoveScratch l;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t here = at; at += align256(bytes); return here; };
-    l.words = take((size_t)(n_bodies ? n_bodies : 1) * sizeof(uint32_t));
-    l.slide_body = take((size_t)n * sizeof(uint32_t));
-    l.slide_flags = take((size_t)n * sizeof(uint32_t));
-    l.given = take((size_t)n * 3 * sizeof(float));
-    l.dist = take((size_t)n * sizeof(double));
-    l.other = take((size_t)n * sizeof(double));
-    l.grounded = take(n);
-    l.grounded_out = take(n);
-    l.push = take(push_bytes);
-    l.bytes = at;
+    Carve c;
+    l.words = c.take((size_t)(n_bodies ? n_bodies : 1) * sizeof(uint32_t));
+    l.slide_body = c.take((size_t)n * sizeof(uint32_t));
+    l.slide_flags = c.take((size_t)n * sizeof(uint32_t));
+    l.given = c.take((size_t)n * 3 * sizeof(float));
+    l.dist = c.take((size_t)n * sizeof(double));
+    l.other = c.take((size_t)n * sizeof(double));
+    l.grounded = c.take(n);
+    l.grounded_out = c.take(n);
+    l.push = c.take(push_bytes);
+    l.bytes = c.bytes();
     return l;
 }
 

@@ -82,22 +82,20 @@ void k_push_apply(PushK p, const uint64_t *keys)
     if (p.pushed) p.pushed[t] = count;
 }
 
-static uint32_t bits_of(uint32_t v)                     // bits that hold every value 0 .. v
-{
-    uint32_t b = 1;
-    while (b < 32 && (v >> b)) b++;
-    return b;
-}
-
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the scratch: keys [6 n] | keys [6 n] | the sort's work space, sized for every key bit (the most it asks for)
-static hipError_t push_layout(uint32_t n_slots, hipStream_t s, size_t &key_bytes, size_t &sort_bytes)
+struct PushLayout { size_t keys0, keys1, sort, sort_bytes, total; };
+
+static hipError_t push_layout(uint32_t n_slots, hipStream_t s, PushLayout &l)
 {
-    key_bytes = align256((size_t)n_slots * sizeof(uint64_t));
+    Carve c;
+    l.keys0 = c.take((size_t)n_slots * sizeof(uint64_t));
+    l.keys1 = c.take((size_t)n_slots * sizeof(uint64_t));
     rocprim::double_buffer<uint64_t> none(nullptr, nullptr);
-    sort_bytes = 0;
-    return rocprim::radix_sort_keys(nullptr, sort_bytes, none, (size_t)n_slots, 0, 64, s);
+    l.sort_bytes = 0;
+    const hipError_t err = rocprim::radix_sort_keys(nullptr, l.sort_bytes, none, (size_t)n_slots, 0, 64, s);
+    l.sort = c.take(l.sort_bytes);
+    l.total = c.bytes();
+    return err;
 }
 
 } // namespace clapgpu
@@ -107,12 +105,12 @@ using namespace clapgpu;
 extern "C" size_t clapgpu_bodies_push_scratch_bytes(uint32_t n)
 {
     if (n == 0 || n > PUSH_MAX_MOVERS) return 0;
-    size_t key_bytes, sort_bytes;
-    if (push_layout(6 * n, nullptr, key_bytes, sort_bytes) != hipSuccess) {
+    PushLayout l;
+    if (push_layout(6 * n, nullptr, l) != hipSuccess) {
         (void)hipGetLastError();
         return 0;
     }
-    return 2 * key_bytes + align256(sort_bytes);
+    return l.total;
 }
 
 extern "C" int clapgpu_bodies_push(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, uint32_t n,
@@ -127,10 +125,11 @@ extern "C" int clapgpu_bodies_push(void *stream, const clapgpu_bodies *b, const 
     if (n > PUSH_MAX_MOVERS) return CLAPGPU_ERR_TOO_LARGE;
     hipStream_t s = as_stream(stream);
     const uint32_t n_slots = 6 * n;
-    size_t key_bytes, sort_bytes;
-    CLAPGPU_HIP(push_layout(n_slots, s, key_bytes, sort_bytes));
+    PushLayout l;
+    CLAPGPU_HIP(push_layout(n_slots, s, l));
     uint8_t *base = static_cast<uint8_t *>(scratch);
-    rocprim::double_buffer<uint64_t> keys(reinterpret_cast<uint64_t *>(base), reinterpret_cast<uint64_t *>(base + key_bytes));
+    rocprim::double_buffer<uint64_t> keys(reinterpret_cast<uint64_t *>(base + l.keys0),
+                                          reinterpret_cast<uint64_t *>(base + l.keys1));
 
     PushK p;
     p.n_slots = n_slots; p.n_bodies = b->n; p.shift = bits_of(n_slots - 1);
@@ -142,7 +141,7 @@ extern "C" int clapgpu_bodies_push(void *stream, const clapgpu_bodies *b, const 
     const uint32_t lanes = pushed && b->n > n_slots ? b->n : n_slots;
     hipLaunchKernelGGL(k_push_keys, dim3((lanes + UB - 1) / UB), dim3(UB), 0, s, p, keys.current());
     CLAPGPU_LAUNCH_CHECK("k_push_keys");
-    CLAPGPU_HIP(rocprim::radix_sort_keys(base + 2 * key_bytes, sort_bytes, keys, (size_t)n_slots, 0, p.shift + bits_of(b->n), s));
+    CLAPGPU_HIP(rocprim::radix_sort_keys(base + l.sort, l.sort_bytes, keys, (size_t)n_slots, 0, p.shift + bits_of(b->n), s));
     hipLaunchKernelGGL(k_push_apply, dim3((n_slots + UB - 1) / UB), dim3(UB), 0, s, p, keys.current());
     CLAPGPU_LAUNCH_CHECK("k_push_apply");
     return CLAPGPU_OK;

@@ -413,39 +413,29 @@ void k_solve_apply(uint32_t n, uint32_t rows_capacity, double h, const uint32_t 
     }
 }
 
-static uint32_t bits_of(uint32_t v)                     // bits that hold every value 0 .. v
-{
-    uint32_t b = 1;
-    while (b < 32 && (v >> b)) b++;
-    return b;
-}
-
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the scratch: ctl [64] | sums [SOLVE_BLOCKS_MAX] | a [n][6] | touched [n] | keys [rows] | keys [rows] | rows [rows] |
 // lambda [rows] | the sort's work space, sized for every key bit
 struct SolveLayout { size_t ctl, sums, a, touched, keys0, keys1, rows, lam, sort, sort_bytes, total; };
 
 static hipError_t solve_layout(uint32_t n, uint32_t rows_capacity, hipStream_t s, SolveLayout &l)
 {
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t was = at; at += align256(bytes); return was; };
-    l.ctl = take(64 * sizeof(uint32_t));
-    l.sums = take(SOLVE_BLOCKS_MAX * sizeof(uint32_t));
-    l.a = take((size_t)n * 6 * sizeof(double));
-    l.touched = take((size_t)n * sizeof(uint32_t));
-    l.keys0 = take((size_t)rows_capacity * sizeof(uint64_t));
-    l.keys1 = take((size_t)rows_capacity * sizeof(uint64_t));
-    l.rows = take((size_t)rows_capacity * sizeof(SolveRow));
-    l.lam = take((size_t)rows_capacity * sizeof(double));
+    Carve c;
+    l.ctl = c.take(64 * sizeof(uint32_t));
+    l.sums = c.take(SOLVE_BLOCKS_MAX * sizeof(uint32_t));
+    l.a = c.take((size_t)n * 6 * sizeof(double));
+    l.touched = c.take((size_t)n * sizeof(uint32_t));
+    l.keys0 = c.take((size_t)rows_capacity * sizeof(uint64_t));
+    l.keys1 = c.take((size_t)rows_capacity * sizeof(uint64_t));
+    l.rows = c.take((size_t)rows_capacity * sizeof(SolveRow));
+    l.lam = c.take((size_t)rows_capacity * sizeof(double));
     l.sort_bytes = 0;
     if (rows_capacity) {
         rocprim::double_buffer<uint64_t> none(nullptr, nullptr);
         const hipError_t err = rocprim::radix_sort_keys(nullptr, l.sort_bytes, none, (size_t)rows_capacity, 0, 64, s);
         if (err != hipSuccess) return err;
     }
-    l.sort = take(l.sort_bytes);
-    l.total = at;
+    l.sort = c.take(l.sort_bytes);
+    l.total = c.bytes();
     return hipSuccess;
 }
 

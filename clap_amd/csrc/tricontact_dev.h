@@ -1,5 +1,5 @@
 // tricontact_dev.h -- a sphere or capsule against one static triangle, shared by the mesh contact pass and the capsule
-// sweep against meshes (mesh_contacts.hip, contacts.hip), and the triangle normal every mesh kernel uses (tri_normal; rays.hip too).
+// sweep against meshes (mesh_contacts.hip, contacts.hip), and the triangle normal every mesh kernel uses (tri_normal; ray_trimesh.hip too).
 // fp64, no FMA contraction (the Makefile builds with -ffp-contract=off).
 //
 // The body geom is a segment a, b with radius r (a sphere: a == b); the triangle is (v0, v1, v2) as the mesh set bakes
@@ -28,7 +28,7 @@ PHD void cross3(const double (&x)[3], const double (&y)[3], double (&o)[3])
     o[2] = x[0] * y[1] - x[1] * y[0];
 }
 
-// n = (v1 - v0) x (v2 - v0) of a baked triangle v[9], not normalised: the one normal of the mesh rays (rays.hip) and of
+// n = (v1 - v0) x (v2 - v0) of a baked triangle v[9], not normalised: the one normal of the mesh rays (ray_trimesh.hip) and of
 // the rule above
 PHD void tri_normal(const double *v, double (&n)[3])
 {

@@ -1,5 +1,5 @@
 // trimesh.hip -- the triangle meshes of static trimesh geoms on the device, for gfx950: the mesh set, its bake and its
-// BVH.  The kernels that read the set are elsewhere: ray casts in rays.hip (k_ray_trimesh), contacts and the capsule
+// BVH.  The kernels that read the set are elsewhere: ray casts in ray_trimesh.hip (k_ray_trimesh), contacts and the capsule
 // sweep in contacts.hip, all through trimesh_dev.h (the node layout, the MeshSet view, the walk).
 //
 //   k_tm_check      the index check of clapgpu_trimesh_create: every vertex index below its mesh's vertex count, every

@@ -1,5 +1,5 @@
 // trimesh_dev.h -- the mesh set's BVH as kernels read it: the node layout, the device view of the set (filled by
-// trimesh.hip's trimesh_set alone) and the one walk of the tree.  The mesh ray pass (rays.hip) walks it with a pruned
+// trimesh.hip's trimesh_set alone) and the one walk of the tree.  The mesh ray pass (ray_trimesh.hip) walks it with a pruned
 // slab test, the mesh contacts (mesh_contacts.hip) and the capsule sweep against meshes (contacts.hip, slide.hip) with a box query.
 //
 // Tree (built by trimesh.hip): one BVH2 over every triangle of every mesh.  A node is 64 B: both children's boxes

@@ -29,6 +29,15 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
+def guarded_scratch(need, dev, guard=4096):
+    """(scratch, tail): a zeroed scratch tensor of exactly `need` bytes, 256-byte aligned, followed in the same allocation
+    by `guard` bytes of 0xA5 that a call given the scratch must leave alone"""
+    buf = torch.zeros(need + guard, dtype=torch.uint8, device=dev)
+    buf[need:] = 0xA5
+    assert need > 0 and buf.data_ptr() % 256 == 0
+    return buf[:need], buf[need:]
+
+
 def unit(v):
     v = np.asarray(v, float)
     return v / np.linalg.norm(v, axis=-1, keepdims=True)

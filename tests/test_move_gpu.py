@@ -12,7 +12,7 @@ import torch
 from clap_amd import _lib, physics, synth
 import moveref as mr
 import slideref as sr
-from meshscene import Scene, fetch, same_bits, rng
+from meshscene import Scene, fetch, guarded_scratch, same_bits, rng
 
 pytestmark = pytest.mark.gpu
 DT = 1.0 / 60.0
@@ -412,7 +412,28 @@ def test_move_in_a_captured_graph(scene_b):
         assert_same((out, body_state(w)), eager, ("replay", trial))
 
 
-# ------------------------------------------------------------------------------------------------- 6. behaviour
+# ------------------------------------------------------------------------------------------------- 6. the scratch
+@pytest.mark.parametrize("n", [1, 256, 257])
+def test_move_stays_inside_the_scratch_it_asks_for(scene_a, n):
+    """a scratch of exactly clapgpu_characters_move_scratch_bytes, 0xA5 behind it: the call leaves the tail alone and
+    gives the bytes it gives on the wrapper's own scratch.  n = 256 fills the byte-sized grounded arrays' 256-byte part,
+    257 starts the next; the push's scratch, sized by its own count, is the last part"""
+    w, b, before = scene_a
+    mv = movers(b, rng(8).choice(b["n"], n, replace=False), 17)
+    restore(w, before)
+    want = run_call(w, mv)
+    restore(w, before)
+    m = make(w, mv)
+    need = _lib.characters_move_scratch_bytes(w.n, n)
+    m.scratch, tail = guarded_scratch(need, w.device)
+    out = {k: t.cpu().numpy().copy() for k, t in w.characters_move(m, DT).items()}
+    out["flags"] = out["flags"].view(np.uint32)
+    got = (out, body_state(w))
+    assert (tail == 0xA5).all().item(), ("written past the scratch", need, torch.nonzero(tail != 0xA5)[:8].flatten().tolist())
+    assert_same(got, want, ("guarded scratch", n))
+
+
+# ------------------------------------------------------------------------------------------------- 7. behaviour
 def test_characters_land_and_walk_on_the_terrain(cuda_device):
     """64 characters dropped over scene B's terrain, 120 frames of one clapgpu_characters_move call each and the host's
     half of the state machine: all land, end grounded and walking, their feet (pos.y - yoffset) within a capsule radius

@@ -10,7 +10,7 @@ import torch
 from clap_amd import _lib, physics, synth
 from clap_amd.synth import box_mesh
 import meshscene
-from meshscene import C2, IDENT, rng, same_bits
+from meshscene import C2, IDENT, guarded_scratch, rng, same_bits
 import pushref as pr
 import solveref as sr
 
@@ -300,6 +300,57 @@ def test_a_sphere_rests_on_the_floor(cuda_device):
     assert int(w.solve_status.item()) == 0
     assert abs(depth - want) <= 1e-3 * want
     assert np.abs(d["lvel"][0]).max() <= 1e-6
+
+
+# ------------------------------------------------------------------------------------------------- the scratch
+def sunk_sphere():
+    """the resting sphere 0.01 into its floor: one contact, rows that fit"""
+    b, floor = resting_sphere()
+    b["pos"][:, 1] = 0.49
+    return b, floor, {}
+
+
+def sleeping_row():
+    """test_islands_gpu's row: 65 capsules in a floor slab and in each other, more rows than either capacity below holds"""
+    from test_islands_gpu import row_scene
+    b, statics = row_scene()
+    return b, statics, dict(pair_capacity=8192)
+
+
+@pytest.mark.parametrize("rows_capacity", [32, 33])
+@pytest.mark.parametrize("scene", [sunk_sphere, sleeping_row], ids=["fits", "overflows"])
+def test_solve_stays_inside_the_scratch_it_asks_for(cuda_device, scene, rows_capacity):
+    """a scratch of exactly clapgpu_bodies_solve_scratch_bytes, 0xA5 behind it: the call leaves the tail alone and gives
+    the bytes it gives on the wrapper's own scratch.  32 rows fill the 8-byte key arrays' 256-byte part, 33 start the
+    next.  Rows that fit run every launch; rows that do not (status bit 0) run the clamps at the arrays' ends"""
+    b, statics, kw = scene()
+    w = physics.PhysWorld(b, statics, device=cuda_device, **kw)
+    w.broadphase()
+    w.contacts_geoms_both()
+    w.islands(H)
+    snap = snapshot(w)
+
+    def result():
+        total, status, lam, key = w.solve(H, want_lambda=True)
+        torch.cuda.synchronize()
+        k = int(total.item()) if int(total.item()) <= rows_capacity else 0   # rows that do not fit: none is written
+        return dict(lvel=w.lvel.cpu().numpy().copy(), avel=w.avel.cpu().numpy().copy(), rows_total=int(total.item()),
+                    status=int(status.item()), row_lambda=lam.cpu().numpy()[:k].copy(), row_key=key.cpu().numpy()[:k].copy())
+    w.alloc_solve(rows_capacity)
+    want = result()
+    if scene is sunk_sphere:
+        assert want["status"] == 0 and 1 <= want["rows_total"] <= 32 and not same_bits(want["lvel"], snap["lvel"].cpu().numpy())
+    else:
+        assert want["status"] & 1 and want["rows_total"] > 33 and same_bits(want["lvel"], snap["lvel"].cpu().numpy())
+    restore(w, snap)
+    w.solve_status.zero_()
+    w.row_lambda.fill_(-1.0)
+    w.row_key.fill_(-1)
+    w.solve_scratch, tail = guarded_scratch(_lib.bodies_solve_scratch_bytes(w.n, rows_capacity), w.device)
+    got = result()
+    assert (tail == 0xA5).all().item(), ("written past the scratch", torch.nonzero(tail != 0xA5)[:8].flatten().tolist())
+    for k in want:
+        assert same_bits(got[k], want[k]) if isinstance(want[k], np.ndarray) else got[k] == want[k], k
 
 
 # ------------------------------------------------------------------------------------------------- the frame
