@@ -12,21 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else 0
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(a, device, dtype=None):
-    a = np.ascontiguousarray(a, dtype) if dtype is not None else np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return torch.from_numpy(a).to(device)
+from ._dev import ptr as _ptr, stream as _stream, upload
 
 
 def joint_depths(parent):
@@ -85,17 +71,17 @@ class SkinnedModel:
         self.nr_joints = J = int(sk["nr_joints"])
         self.depth_host = joint_depths(sk["parent"])
         self.n_levels = int(self.depth_host.max()) + 1
-        self.parent = _dev(sk["parent"], dev, np.int32)
-        self.depth = _dev(self.depth_host, dev, np.int32)
-        self.root_pose = _dev(sk["root_pose"], dev, np.float32)
-        self.invmx = _dev(sk["invmx"], dev, np.float32)
+        self.parent = upload(sk["parent"], np.int32, dev)
+        self.depth = upload(self.depth_host, np.int32, dev)
+        self.root_pose = upload(sk["root_pose"], np.float32, dev)
+        self.invmx = upload(sk["invmx"], np.float32, dev)
         if bind is None:
             bind = skeleton_bind(sk["invmx"])
-        self.bind = _dev(bind, dev, np.float32)
+        self.bind = upload(bind, np.float32, dev)
         self.anims_host = anims
         ct = channel_table(anims, J)
         self.time_end = [float(a["time_end"]) for a in anims]
-        self._ct = {k: _dev(v, dev) for k, v in ct.items()}
+        self._ct = {k: upload(v, v.dtype, dev) for k, v in ct.items()}
         self.skel_desc = _lib.Skeleton(J, self.n_levels, _ptr(self.parent), _ptr(self.depth),
                                        _ptr(self.root_pose), _ptr(self.invmx), _ptr(self.bind))
         self.anim_desc = _lib.Animations(len(anims), int(ct["times"].shape[0]), _ptr(self._ct["chan_table"]),
@@ -117,9 +103,9 @@ class SkinnedModel:
             self.anim_desc.packed_layout = layout.value
         self.mesh = None
         if mesh is not None:
-            self.mesh = dict(n_verts=int(mesh["n_verts"]), position=_dev(mesh["position"], dev, np.float32),
-                             normal=_dev(mesh["normal"], dev, np.float32), joints=_dev(mesh["joints"], dev, np.uint8),
-                             weights=_dev(mesh["weights"], dev, np.float32))
+            self.mesh = dict(n_verts=int(mesh["n_verts"]), position=upload(mesh["position"], np.float32, dev),
+                             normal=upload(mesh["normal"], np.float32, dev), joints=upload(mesh["joints"], np.uint8, dev),
+                             weights=upload(mesh["weights"], np.float32, dev))
 
 
 class CharacterBatch:
@@ -133,9 +119,9 @@ class CharacterBatch:
         trs0 = np.asarray(trs0, np.float32)
         if trs0.ndim == 2:
             trs0 = np.broadcast_to(trs0, (n, J, 10))
-        self.trs = _dev(trs0, dev, np.float32)
-        self.entity_mx = entity_mx if torch.is_tensor(entity_mx) else _dev(entity_mx, dev, np.float32)
-        self.entity_index = None if entity_index is None else _dev(entity_index, dev, np.uint32)
+        self.trs = upload(trs0, np.float32, dev)
+        self.entity_mx = entity_mx if torch.is_tensor(entity_mx) else upload(entity_mx, np.float32, dev)
+        self.entity_index = None if entity_index is None else upload(entity_index, np.uint32, dev)
         self.anim = torch.zeros(n, dtype=torch.int32, device=dev)
         self.frame_time = torch.zeros(n, dtype=torch.float32, device=dev)
         self.joint_transforms = torch.zeros((n, J, 16), dtype=torch.float32, device=dev)
@@ -144,6 +130,7 @@ class CharacterBatch:
         self.ani_time = np.zeros(n, np.float64)
         self.speed = np.ones(n, np.float64)
         self.anim_host = np.zeros(n, np.int32)
+        self._clock = None                                   # start_clock()
         self._pose_desc = _lib.PoseBatch(n, 0, _ptr(self.anim), _ptr(self.frame_time), _ptr(self.entity_index),
                                          _ptr(self.entity_mx), _ptr(self.trs), _ptr(self.joint_transforms),
                                          _ptr(self.joint_pos))
@@ -152,12 +139,12 @@ class CharacterBatch:
             if vert_first is None:                       # every character instances the whole mesh
                 vert_first = np.zeros(n, np.uint32)
                 vert_count = np.full(n, model.mesh["n_verts"], np.uint32)
-            self.vert_first = _dev(vert_first, dev, np.uint32)
+            self.vert_first = upload(vert_first, np.uint32, dev)
             self.vert_count_host = np.asarray(vert_count, np.uint32)
-            self.vert_count = _dev(self.vert_count_host, dev, np.uint32)
+            self.vert_count = upload(self.vert_count_host, np.uint32, dev)
             of = np.concatenate([[0], np.cumsum(self.vert_count_host.astype(np.int64))])
             self.out_first_host = of
-            self.out_first = _dev(of[:-1], dev, np.uint32)
+            self.out_first = upload(of[:-1], np.uint32, dev)
             total = int(of[-1])
             self.n_out_verts = total
             self.out_position = torch.zeros((total, 3), dtype=torch.float32, device=dev)
@@ -172,7 +159,7 @@ class CharacterBatch:
     # ---- animated_update (model.c:1563-1592) --------------------------------------------
     def set_frame_times(self, frame_time, anim=None):
         """Directly set each character's (float)frame_time (and animation id)."""
-        self.frame_time.copy_(torch.from_numpy(np.ascontiguousarray(frame_time, np.float32)))
+        self.frame_time.copy_(upload(frame_time, np.float32, "cpu"))
         if anim is not None:
             self.anim_host[:] = anim
             self.anim.copy_(torch.from_numpy(self.anim_host))
@@ -182,7 +169,7 @@ class CharacterBatch:
         (now, ani_time, speed) into the float frame times, flags `ended` and restarts repeating queue
         entries (animation_next -> animation_start: ani_time = now); then pose + palette.  The host
         only reads `ended` back when it has non-repeating entries or callbacks to serve."""
-        if getattr(self, "_clock", None) is None:
+        if self._clock is None:
             self.start_clock()
         if now is None:                                      # graph replay: the caller has written self.now_dev
             rc = _lib.lib().clapgpu_animation_time_dev(_stream(), C.byref(self._clock), _ptr(self.now_dev))
@@ -200,8 +187,7 @@ class CharacterBatch:
         if speed is not None:
             self.speed[:] = speed
         self.repeat_host = np.ones(n, np.uint8) if repeat is None else np.ascontiguousarray(repeat, np.uint8)
-        self.ani_time_dev = torch.from_numpy(np.ascontiguousarray(self.ani_time, np.float64)).to(dev)
-        self.speed_dev = torch.from_numpy(np.ascontiguousarray(self.speed, np.float32)).to(dev)
+        self.ani_time_dev, self.speed_dev = upload(self.ani_time, np.float64, dev), upload(self.speed, np.float32, dev)
         self.repeat_dev = torch.from_numpy(self.repeat_host).to(dev)
         self.ended = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
         self.now_dev = torch.zeros(1, dtype=torch.float64, device=dev)

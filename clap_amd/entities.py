@@ -11,14 +11,7 @@ import torch
 
 from . import _lib
 from . import synth
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._dev import ptr as _ptr, stream as _stream, upload
 
 
 def view_calc_frustum(cam):
@@ -136,9 +129,8 @@ class EntityBatch:
         a = np.ascontiguousarray(attach)
         assert np.all(np.diff(a["entity"].astype(np.int64)) > 0), "attach table must be sorted by entity"
         self._attach = torch.from_numpy(a.view(np.uint8).reshape(-1, 16).copy()).to(self.device)
-        self._jt_pool = jt_pool if torch.is_tensor(jt_pool) else torch.from_numpy(
-            np.ascontiguousarray(jt_pool, np.float32)).to(self.device)
-        self._bind_pool = torch.from_numpy(np.ascontiguousarray(bind_pool, np.float32)).to(self.device)
+        self._jt_pool = jt_pool if torch.is_tensor(jt_pool) else upload(jt_pool, np.float32, self.device)
+        self._bind_pool = upload(bind_pool, np.float32, self.device)
         idx = torch.from_numpy(a["entity"].astype(np.int64)).to(self.device)
         self.flags[idx] |= np.int32(_lib.E_JOINT_ATTACHED)
         self._desc.n_attach = a.shape[0]
@@ -215,7 +207,7 @@ class EntityBatch:
         updates cur_lod, fills draw_lod[:visible_count] (the draw list is (visible, draw_lod))."""
         self.alloc_lod()
         if force_lod is not None:
-            self.force_lod = torch.from_numpy(np.ascontiguousarray(force_lod, np.int32)).to(self.device)
+            self.force_lod = upload(force_lod, np.int32, self.device)
         cp = (C.c_float * 3)(*[float(v) for v in cam_pos])
         rc = _lib.lib().clapgpu_entities_lod(_stream(), C.byref(self._desc), _ptr(self.visible),
                                              _ptr(self.visible_count), 0, cp, _ptr(self.force_lod),
@@ -227,7 +219,7 @@ class EntityBatch:
         the LOD of every entry."""
         self.alloc_lod()
         if force_lod is not None:
-            self.force_lod = torch.from_numpy(np.ascontiguousarray(force_lod, np.int32)).to(self.device)
+            self.force_lod = upload(force_lod, np.int32, self.device)
         cp = (C.c_float * 3)(*[float(v) for v in cam_pos])
         rc = _lib.lib().clapgpu_visible_compact_lod(_stream(), C.byref(self._desc), index_base, cp, _ptr(self.force_lod),
                                                     _ptr(self.cur_lod), _ptr(self.visible), _ptr(self.visible_count),
@@ -243,8 +235,8 @@ class EntityBatch:
     def set_transforms(self, idx, pos_scale, rot):
         """entity3d_position/rotate/scale on a batch of entities: writes TRS, sets dirty."""
         idx_t = torch.as_tensor(np.asarray(idx, np.int64), device=self.device)
-        self.pos_scale[idx_t] = torch.from_numpy(np.ascontiguousarray(pos_scale, np.float32)).to(self.device)
-        self.rot[idx_t] = torch.from_numpy(np.ascontiguousarray(rot, np.float32)).to(self.device)
+        self.pos_scale[idx_t] = upload(pos_scale, np.float32, self.device)
+        self.rot[idx_t] = upload(rot, np.float32, self.device)
         self.flags[idx_t] |= np.int32(_lib.E_DIRTY)
 
     def download(self):

@@ -43,6 +43,7 @@ class FrameLoop:
         self.characters, self.particles = characters, particles
         self.body_links, self.contacts = body_links, contacts or islands
         self.islands = islands
+        self.overlap = False        # CLAPGPU_FRAME_OVERLAP: a caller may set it (three chains on three streams, frame.hip)
         self.prebin = prebin        # CLAPGPU_FRAME_PREBIN: the step bins its boxes for the next frame's broadphase (nothing else writes them)
         self._desc = None
         if characters is not None:
@@ -94,11 +95,7 @@ class FrameLoop:
                         f.mesh_contact_total, f.mesh_capped = w.mesh_contact_total.data_ptr(), w.mesh_capped.data_ptr()
                         f.mesh_scratch = w.mesh_scratch.data_ptr()
             if self.islands:
-                need = _lib.bodies_islands_scratch_bytes(w.n)
-                if getattr(w, "island_scratch", None) is None or w.island_scratch.numel() < need:
-                    w.island_scratch = torch.zeros(max(need, 256), dtype=torch.uint8, device=w.device)
-                    w.island = torch.zeros(max(w.n, 1), dtype=torch.int32, device=w.device)
-                    w.island_woken = torch.zeros(1, dtype=torch.int32, device=w.device)
+                w.alloc_islands()
                 f.island_scratch, f.island = w.island_scratch.data_ptr(), w.island.data_ptr()
                 f.island_woken = w.island_woken.data_ptr()
             if self.solve:
@@ -141,7 +138,7 @@ class FrameLoop:
                 f.light_width, f.light_height, f.light_cell, f.light_tiles = ls.width, ls.height, ls.cell, tiles.data_ptr()
         cb = self.characters
         if cb is not None:
-            if getattr(cb, "_clock", None) is None:
+            if cb._clock is None:
                 cb.start_clock()
             f.anim_clock = C.pointer(cb._clock)
             f.skeleton, f.animations = C.pointer(cb.model.skel_desc), C.pointer(cb.model.anim_desc)
@@ -194,7 +191,7 @@ class FrameLoop:
         # graph capture: the clock comes from a device double written before every replay
         f.now_dev = self.characters.now_dev.data_ptr() if (now is None and self.characters is not None) else None
         # CLAPGPU_FRAME_OVERLAP: three chains on three streams (frame.hip); CLAPGPU_FRAME_PREBIN
-        f.flags = (1 if getattr(self, "overlap", False) else 0) | (2 if self.prebin else 0)
+        f.flags = (1 if self.overlap else 0) | (2 if self.prebin else 0)
         f.move_dt_sec = self.move_dt
         rc = _lib.lib().clapgpu_frame_issue(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(f),
                                             0.0 if now is None else float(now), int(steps))

@@ -12,12 +12,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._dev import ptr as _ptr, stream as _stream, upload  # noqa: F401
 
 TILE_WIDTH = 64          # shader_constants.h:16
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _fp(a):
@@ -117,10 +114,8 @@ class LightSet:
     def set_carriers(self, entity, light, off):
         """Entities that carry a light slot (e->light_idx, e->light_off; scene.c:1586-1608), in entity order."""
         dev = self.device
-        self._carriers = (len(entity),
-                          torch.from_numpy(np.ascontiguousarray(entity, np.uint32).view(np.int32)).to(dev),
-                          torch.from_numpy(np.ascontiguousarray(light, np.int32)).to(dev),
-                          torch.from_numpy(np.ascontiguousarray(off, np.float32)).to(dev))
+        self._carriers = (len(entity), upload(entity, np.uint32, dev), upload(light, np.int32, dev),
+                          upload(off, np.float32, dev))
 
     def from_entities(self, batch, all_dirty=False):
         """model.c:1689-1694 for the carriers; run before batch.mq_update (which clears the dirty flags)."""

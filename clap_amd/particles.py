@@ -11,10 +11,7 @@ import torch
 
 from . import _lib
 from . import synth
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+from ._dev import ptr as _ptr, stream as _stream, upload  # noqa: F401
 
 
 class ParticleBatch:
@@ -27,9 +24,8 @@ class ParticleBatch:
         self.sys_host = np.ascontiguousarray(ps["sys"]).copy()
         self.n_sys = self.sys_host.shape[0]
         self.sys = torch.from_numpy(self.sys_host.view(np.uint8).reshape(self.n_sys, 64)).to(dev)
-        self.row_sys = torch.from_numpy(np.ascontiguousarray(ps["row_sys"]).view(np.int32)).to(dev)
-        self.pos = torch.from_numpy(np.ascontiguousarray(pos, np.float32)).to(dev)
-        self.vel = torch.from_numpy(np.ascontiguousarray(vel, np.float32)).to(dev)
+        self.row_sys = upload(ps["row_sys"], np.uint32, dev)
+        self.pos, self.vel = upload(pos, np.float32, dev), upload(vel, np.float32, dev)
         self.rng_state = torch.tensor([rng_state, rng_state], dtype=torch.int64, device=dev)
         self.billboard_mx = torch.zeros((self.n_sys, 16), dtype=torch.float32, device=dev)
         rows = n // 64
@@ -51,8 +47,7 @@ class ParticleBatch:
     def particles_update(self, view_mx):
         """particles_update for every system (mq order), one libc-compatible drand48 stream."""
         v = np.ascontiguousarray(view_mx, np.float32)
-        rc = _lib.lib().clapgpu_particles_update(C.c_void_p(torch.cuda.current_stream().cuda_stream),
-                                                 C.byref(self._desc), v.ctypes.data_as(C.POINTER(C.c_float)))
+        rc = _lib.lib().clapgpu_particles_update(_stream(), C.byref(self._desc), v.ctypes.data_as(C.POINTER(C.c_float)))
         _lib.check(rc, "clapgpu_particles_update")
 
     def particle_system_count(self, s):

@@ -12,14 +12,8 @@ import numpy as np
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else 0
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._dev import ptr as _ptr, stream as _stream, upload
+from .characters import CharacterMoves  # noqa: F401  (physics.CharacterMoves: the name callers know it by)
 
 
 class PhysWorld:
@@ -30,18 +24,17 @@ class PhysWorld:
         accumulator (clapgpu_bodies.facc, zeros or bodies["facc"]): the step consumes it, bodies_push adds to it."""
         self.device = dev = torch.device(device)
         self.n = n = int(bodies["n"])
-        t = lambda k, dt: torch.from_numpy(np.ascontiguousarray(bodies[k], dt)).to(dev)
+        t = lambda k, dt: upload(bodies[k], dt, dev)
         self.pos, self.quat = t("pos", np.float64), t("quat", np.float64)
         self.lvel, self.avel = t("lvel", np.float64), t("avel", np.float64)
         self.mass, self.radius, self.yoffset = t("mass", np.float64), t("radius", np.float64), t("yoffset", np.float64)
-        self.bflags = torch.from_numpy(np.ascontiguousarray(bodies["bflags"]).view(np.int32)).to(dev)
+        self.bflags = t("bflags", np.uint32)
         self.adis_steps_left = t("adis_steps_left", np.int32)
         self.adis_time_left = t("adis_time_left", np.float64)
         self.body_entity = t("body_entity", np.int32)
         self.length = t("length", np.float64) if "length" in bodies else None
         self.inertia = t("inertia", np.float64) if "inertia" in bodies else None
-        self.aabb = torch.zeros((max(n, 1), 6), dtype=torch.float64, device=dev)
-        self.axis = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=dev)
+        self.aabb, self.axis = self._out(n, (6,), torch.float64), self._out(n, (3,), torch.float64)
         self.cell = float(bodies["cell"])
         self.world = _lib.World()
         _lib.lib().clapgpu_world_defaults(C.byref(self.world))
@@ -49,8 +42,7 @@ class PhysWorld:
         samples = int(bodies.get("adis_average_samples", 1))
         self.adis_samples = self.adis_counter = None
         if samples > 1:
-            self.adis_samples = torch.zeros((max(n, 1), samples, 6), dtype=torch.float64, device=dev)
-            self.adis_counter = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+            self.adis_samples, self.adis_counter = self._out(n, (samples, 6), torch.float64), self._out(n, (), torch.int32)
         d = _lib.Bodies(n, samples, _ptr(self.pos), _ptr(self.quat), _ptr(self.lvel), _ptr(self.avel),
                         _ptr(self.mass), _ptr(self.radius), _ptr(self.yoffset), _ptr(self.bflags),
                         _ptr(self.adis_steps_left), _ptr(self.adis_time_left), _ptr(self.body_entity))
@@ -59,7 +51,7 @@ class PhysWorld:
         d.aabb, d.axis = _ptr(self.aabb), _ptr(self.axis)
         d.adis_samples, d.adis_counter = _ptr(self.adis_samples), _ptr(self.adis_counter)
         # the narrowphase's one-sector view of every body geom (clapgpu_bodies.geom_records), kept by the step / aabb kernels
-        self.geom_records = torch.zeros((max(n, 1), 8), dtype=torch.float64, device=dev) if geom_records else None
+        self.geom_records = self._out(n, (8,), torch.float64) if geom_records else None
         d.geom_records = _ptr(self.geom_records)
         self.facc = None
         self._desc = d
@@ -81,6 +73,20 @@ class PhysWorld:
         _lib.check(_lib.lib().clapgpu_bp_create(C.byref(self._bp), n, self.cell, self.n_static,
                                                 st.ctypes.data if st is not None else None), "clapgpu_bp_create")
         self.statics_ptr = _lib.lib().clapgpu_bp_static_aabb(self._bp)     # device copy owned by the broadphase object
+        # what the methods below allocate on demand (the alloc_* methods) or keep from their last call
+        self.material = self.static_material = None                        # set_materials / contacts_static, or assigned
+        self._static_geoms = self._static_keep = None                      # static_geoms / set_static_geoms
+        self._links_key = self._links = None                               # upload_links
+        self.contact_buf = self.contact_total = self.static_contact_buf = self.static_contact_total = None
+        self.contact2_buf = self.contact2_total = self.static_contact2_buf = self.static_contact2_total = None
+        self.island_scratch = self.island = self.island_woken = None
+        self.solver = self.solve_scratch = self.row_lambda = self.row_key = self.rows_total = self.solve_status = None
+        self.solve_rows_capacity = self.mesh_contact_capacity = 0
+        self.mesh_contact_buf = self.mesh_ref = self.mesh_contact_total = self.mesh_capped = self.mesh_scratch = None
+        self._meshes_keep = None                                           # set_static_meshes (beside _meshes)
+        self._slide_scratch = self._ground_scratch = self._push_scratch_buf = None
+        self._sweep_keep = self._sweep_grid_keep = self._slide_keep = self._push_keep = None
+        self._ray_keep = self._ground_keep = None
         self.bodies_aabb()
 
     def __del__(self):
@@ -98,10 +104,27 @@ class PhysWorld:
     def enable_forces(self, facc=None):
         """Give the bodies a force accumulator (clapgpu_bodies.facc; zeros, or facc [n, 3]): from now on the step is the
         force path -- it adds facc to gravity, honours BODY_KINEMATIC and clears what it consumed."""
-        self.facc = torch.zeros((max(self.n, 1), 3), dtype=torch.float64, device=self.device)
+        self.facc = self._out(self.n, (3,), torch.float64)
         if facc is not None and self.n:
-            self.facc[:self.n] = torch.from_numpy(np.ascontiguousarray(facc, np.float64).reshape(-1, 3)).to(self.device)
+            self.facc[:self.n] = upload(facc, np.float64, self.device, (-1, 3))
         self._desc.facc = _ptr(self.facc)
+
+    def _out(self, n, tail_shape, dtype, fill=0):
+        """A device array of n rows of tail_shape, every element `fill`; one row when n is 0, so that its address is
+        never null (callers hand out [:n])."""
+        shape = (max(n, 1), *tail_shape)
+        if fill == 0:
+            return torch.zeros(shape, dtype=dtype, device=self.device)
+        return torch.full(shape, fill, dtype=dtype, device=self.device)
+
+    def _grown(self, name, need):
+        """The byte scratch kept in attribute `name`, allocated anew (zeroed, at least 256 bytes) only when it is missing
+        or smaller than `need`."""
+        have = vars(self)[name]
+        if have is None or have.numel() < need:
+            have = torch.zeros(max(need, 256), dtype=torch.uint8, device=self.device)
+            setattr(self, name, have)
+        return have
 
     # ---- __phys_step pieces -----------------------------------------------------------
     def bp_invalidate(self):
@@ -109,8 +132,8 @@ class PhysWorld:
         _lib.check(_lib.lib().clapgpu_bp_invalidate(_stream(), self._bp), "clapgpu_bp_invalidate")
 
     def bodies_aabb(self):
-        self.bp_invalidate()
         """Geom axis + AABB of every body from its pose (after the host moved bodies; world_step keeps them current)."""
+        self.bp_invalidate()
         _lib.check(_lib.lib().clapgpu_bodies_aabb(_stream(), C.byref(self._desc)), "clapgpu_bodies_aabb")
 
     def broadphase(self, side=None):
@@ -128,48 +151,51 @@ class PhysWorld:
         return st.value
 
     def body_geoms(self):
-        g = _lib.Geoms(self.n, 0, _ptr(self.pos), _ptr(self.axis), _ptr(self.radius), _ptr(self.length), 0, 0,
-                       _ptr(getattr(self, "material", None)), _ptr(self.geom_records))
-        return g
+        return _lib.Geoms(self.n, 0, _ptr(self.pos), _ptr(self.axis), _ptr(self.radius), _ptr(self.length), 0, 0,
+                          _ptr(self.material), _ptr(self.geom_records))
 
     def static_geoms(self):
         """The statics as axis-aligned boxes (their AABBs); static_geom_arrays overrides kind / pos / radius / ..."""
-        sg = getattr(self, "_static_geoms", None)
+        sg = self._static_geoms
         if sg is None:
-            kind = torch.full((max(self.n_static, 1),), _lib.GEOM_BOX, dtype=torch.uint8, device=self.device)
+            kind = self._out(self.n_static, (), torch.uint8, _lib.GEOM_BOX)
             self._static_keep = dict(kind=kind)
-            sg = _lib.Geoms(self.n_static, 0, 0, 0, 0, 0, _ptr(kind), self.statics_ptr,
-                            _ptr(getattr(self, "static_material", None)))
-            self._static_geoms = sg
-        sg.material = _ptr(getattr(self, "static_material", None))
+            sg = self._static_geoms = _lib.Geoms(self.n_static, 0, 0, 0, 0, 0, _ptr(kind), self.statics_ptr, 0)
+        sg.material = _ptr(self.static_material)
         return sg
 
     def set_static_geoms(self, kind, pos=None, axis=None, radius=None, length=None):
         """Narrowphase description of the statics (default: every static is its AABB as a box)."""
         dev = self.device
-        keep = dict(kind=torch.from_numpy(np.ascontiguousarray(kind, np.uint8)).to(dev))
+        keep = dict(kind=upload(kind, np.uint8, dev))
         for name, a in (("pos", pos), ("axis", axis), ("radius", radius), ("length", length)):
-            keep[name] = None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev)
+            keep[name] = None if a is None else upload(a, np.float64, dev)
         self._static_keep = keep
         self._static_geoms = _lib.Geoms(self.n_static, 0, _ptr(keep["pos"]), _ptr(keep["axis"]), _ptr(keep["radius"]),
                                         _ptr(keep["length"]), _ptr(keep["kind"]), self.statics_ptr,
-                                        _ptr(getattr(self, "static_material", None)))
+                                        _ptr(self.static_material))
 
     def alloc_contacts(self):
-        if getattr(self, "contact2_buf", None) is None:
+        if self.contact2_buf is None:
             self.contact2_buf = torch.zeros((self.capacity, 160), dtype=torch.uint8, device=self.device)
             self.contact2_total = torch.zeros(1, dtype=torch.int32, device=self.device)
             self.static_contact2_buf = torch.zeros((self.static_capacity if self.n_static else 1, 160), dtype=torch.uint8,
                                                    device=self.device)
             self.static_contact2_total = torch.zeros(1, dtype=torch.int32, device=self.device)
 
+    def alloc_islands(self):
+        """The island pass's scratch and outputs (island [n], island_woken [1])."""
+        have = self.island_scratch
+        if self._grown("island_scratch", _lib.bodies_islands_scratch_bytes(self.n)) is not have:
+            self.island = self._out(self.n, (), torch.int32)
+            self.island_woken = torch.zeros(1, dtype=torch.int32, device=self.device)
+
     def upload_links(self, link_body, link_entity):
         """Device copies of a (body, entity) link table, uploaded once per table."""
         key = (id(link_body), id(link_entity))
-        if getattr(self, "_links_key", None) != key:
+        if self._links_key != key:
             self._links_key = key
-            self._links = (torch.from_numpy(np.ascontiguousarray(link_body, np.uint32).view(np.int32)).to(self.device),
-                           torch.from_numpy(np.ascontiguousarray(link_entity, np.uint32).view(np.int32)).to(self.device))
+            self._links = (upload(link_body, np.uint32, self.device), upload(link_entity, np.uint32, self.device))
         return self._links
 
     def contacts_geoms(self, set_joint_flags=True):
@@ -216,11 +242,9 @@ class PhysWorld:
         meshes: candidate statics that own a mesh collide through its triangles once set_static_meshes ran."""
         dev = self.device
         ns = len(sweep_body)
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt).view(np.int32 if dt == np.uint32 else dt)).to(dev)
-        sb, dl, cf, cd = up(sweep_body, np.uint32), up(delta, np.float32), up(cand_first, np.uint32), up(cand, np.uint32)
-        frac = torch.zeros(max(ns, 1), dtype=torch.float32, device=dev)
-        normal = torch.zeros((max(ns, 1), 3), dtype=torch.float32, device=dev)
-        hit = torch.zeros(max(ns, 1), dtype=torch.int32, device=dev)
+        sb, dl = upload(sweep_body, np.uint32, dev), upload(delta, np.float32, dev)
+        cf, cd = upload(cand_first, np.uint32, dev), upload(cand, np.uint32, dev)
+        frac, normal, hit = self._out(ns, (), torch.float32), self._out(ns, (3,), torch.float32), self._out(ns, (), torch.int32)
         g, sg = self.body_geoms(), self.static_geoms()
         _lib.check(_lib.lib().clapgpu_sweep_capsules_meshes(_stream(), C.byref(g), C.byref(sg), self._meshes if meshes else None,
                                                             ns, _ptr(sb), _ptr(dl), _ptr(cf), _ptr(cd), _ptr(frac), _ptr(normal),
@@ -234,13 +258,9 @@ class PhysWorld:
         tensors (frac, normal [n, 3], hit, flags)."""
         dev = self.device
         ns = len(sweep_body)
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt).view(np.int32 if dt == np.uint32 else dt)).to(dev)
-        sb, dl = up(sweep_body, np.uint32), up(np.asarray(delta, np.float32).reshape(-1, 3), np.float32)
-        n1 = max(ns, 1)
-        frac = torch.zeros(n1, dtype=torch.float32, device=dev)
-        normal = torch.zeros((n1, 3), dtype=torch.float32, device=dev)
-        hit = torch.zeros(n1, dtype=torch.int32, device=dev)
-        flags = torch.zeros(n1, dtype=torch.int32, device=dev)
+        sb, dl = upload(sweep_body, np.uint32, dev), upload(delta, np.float32, dev, (-1, 3))
+        frac, normal = self._out(ns, (), torch.float32), self._out(ns, (3,), torch.float32)
+        hit, flags = self._out(ns, (), torch.int32), self._out(ns, (), torch.int32)
         sg = self.static_geoms()
         _lib.check(_lib.lib().clapgpu_sweep_capsules_grid(_stream(), self._bp if grid else None, C.byref(self._desc), C.byref(sg),
                                                           self._meshes if meshes else None, ns, _ptr(sb), _ptr(dl), _ptr(frac),
@@ -254,23 +274,18 @@ class PhysWorld:
         Returns device tensors (velocity [n, 3] float32, first_frac [n, 2], push_hit [n, 6], flags [n])."""
         dev = self.device
         nb = len(bodies)
-        up = lambda a, dt, view=None: torch.from_numpy(np.ascontiguousarray(a, dt).view(view or dt)).to(dev)
-        body_d = up(bodies, np.uint32, np.int32)
-        vel = up(np.asarray(velocity, np.float32).reshape(-1, 3), np.float32) if nb else \
-            torch.zeros((1, 3), dtype=torch.float32, device=dev)
-        air_d = up(np.asarray(airborne) != 0, np.uint8)
-        n1 = max(nb, 1)
-        first = torch.ones((n1, 2), dtype=torch.float32, device=dev)
-        push = torch.full((n1, 6), -1, dtype=torch.int32, device=dev)
-        flags = torch.zeros(n1, dtype=torch.int32, device=dev)
-        scratch = getattr(self, "_slide_scratch", None)          # [n] words of the call's own
-        if scratch is None:
-            scratch = self._slide_scratch = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dev)
+        body_d = upload(bodies, np.uint32, dev)
+        vel = upload(velocity, np.float32, dev, (-1, 3)) if nb else self._out(0, (3,), torch.float32)
+        air_d = upload(np.asarray(airborne) != 0, np.uint8, dev)
+        first, push = self._out(nb, (2,), torch.float32, 1), self._out(nb, (6,), torch.int32, -1)
+        flags = self._out(nb, (), torch.int32)
+        if self._slide_scratch is None:                          # [n] words of the call's own
+            self._slide_scratch = self._out(self.n, (), torch.int32)
         sg = self.static_geoms()
         s = _lib.Slide(nb, _ptr(body_d), _ptr(vel), _ptr(air_d), _ptr(first), _ptr(push), _ptr(flags))
         _lib.check(_lib.lib().clapgpu_characters_slide(_stream(), self._bp if grid else None, C.byref(self._desc), C.byref(sg),
                                                        self._meshes if meshes else None, float(dt_sec), C.byref(s),
-                                                       _ptr(scratch)), "clapgpu_characters_slide")
+                                                       _ptr(self._slide_scratch)), "clapgpu_characters_slide")
         self._slide_keep = (body_d, air_d, vel, first, push, flags)
         return vel[:nb], first[:nb], push[:nb], flags[:nb]
 
@@ -281,33 +296,20 @@ class PhysWorld:
         if self.facc is None:
             raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "bodies_push", "no force accumulator: PhysWorld(forces=True)")
         dev = self.device
-
-        def up(a, dt, view=None):
-            if isinstance(a, torch.Tensor):
-                return a.contiguous()
-            return torch.from_numpy(np.ascontiguousarray(a, dt).view(view or dt)).to(dev)
         n = len(pusher)
-        pu, ve, ph = up(pusher, np.uint32, np.int32), up(velocity, np.float32), up(push_hit, np.int32)
-        fl = None if flags is None else up(flags, np.uint32, np.int32)
-        pushed = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dev) if want_pushed else None
-        scratch = self._push_scratch(n)
+        pu, ve, ph = upload(pusher, np.uint32, dev), upload(velocity, np.float32, dev), upload(push_hit, np.int32, dev)
+        fl = None if flags is None else upload(flags, np.uint32, dev)
+        pushed = self._out(self.n, (), torch.int32) if want_pushed else None
+        scratch = self._grown("_push_scratch_buf", _lib.bodies_push_scratch_bytes(n) if n else 0)
         _lib.check(_lib.lib().clapgpu_bodies_push(_stream(), C.byref(self._desc), C.byref(self.world), n, _ptr(pu), _ptr(ve),
                                                   _ptr(ph), _ptr(fl), _ptr(pushed), _ptr(scratch)), "clapgpu_bodies_push")
         self._push_keep = (pu, ve, ph, fl, scratch)
         return None if pushed is None else pushed[:self.n]
 
-    def _push_scratch(self, n):
-        """the push's device scratch for n movers, kept between calls"""
-        need = _lib.bodies_push_scratch_bytes(n) if n else 0
-        have = getattr(self, "_push_scratch_buf", None)
-        if have is None or have.numel() < need:
-            have = self._push_scratch_buf = torch.zeros(max(need, 256), dtype=torch.uint8, device=self.device)
-        return have
-
     def slide_and_push(self, bodies, velocity, airborne, dt_sec, grid=True, meshes=True):
         """slide(), then the pushes of that batch (bodies_push) with the velocity the slide was given: the whole
         ENTITY3D_HAS_PHYSICS branch of character_apply_velocity.  Returns slide()'s tuple and pushed [self.n]."""
-        given = torch.from_numpy(np.ascontiguousarray(np.asarray(velocity, np.float32).reshape(-1, 3))).to(self.device)
+        given = upload(velocity, np.float32, self.device, (-1, 3))
         vel, first, push, flags = self.slide(bodies, velocity, airborne, dt_sec, grid=grid, meshes=meshes)
         body_d = self._slide_keep[0]
         nb = len(bodies)
@@ -335,12 +337,7 @@ class PhysWorld:
         world_step(h).  Returns device tensors (island [n]: the smallest body index of each body's component, woken [1]:
         the number of bodies enabled), None for what was not asked for."""
         self.alloc_contacts()
-        dev = self.device
-        need = _lib.bodies_islands_scratch_bytes(self.n)
-        if getattr(self, "island_scratch", None) is None or self.island_scratch.numel() < need:
-            self.island_scratch = torch.zeros(max(need, 256), dtype=torch.uint8, device=dev)
-            self.island = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dev)
-            self.island_woken = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.alloc_islands()
         island = self.island if want_island else None
         woken = self.island_woken if want_woken else None
         _lib.check(_lib.lib().clapgpu_bodies_islands(_stream(), C.byref(self._desc), C.byref(self.world), h, _ptr(self.pairs),
@@ -352,18 +349,15 @@ class PhysWorld:
     def alloc_solve(self, rows_capacity=None):
         """The solve's scratch, outputs and parameters (clapgpu_solver_defaults in self.solver).  rows_capacity: the most
         contact rows a substep may have (240 bytes of scratch each); by default 6 n + 1024."""
-        cap = int(rows_capacity if rows_capacity is not None else getattr(self, "solve_rows_capacity", None) or
-                  6 * self.n + 1024)
-        if getattr(self, "solve_scratch", None) is None or self.solve_rows_capacity != cap:
-            dev = self.device
+        cap = int(rows_capacity if rows_capacity is not None else self.solve_rows_capacity or 6 * self.n + 1024)
+        if self.solve_scratch is None or self.solve_rows_capacity != cap:
             self.solve_rows_capacity = cap
-            need = _lib.bodies_solve_scratch_bytes(self.n, cap)
-            self.solve_scratch = torch.zeros(max(need, 256), dtype=torch.uint8, device=dev)
-            self.row_lambda = torch.zeros(max(cap, 1), dtype=torch.float64, device=dev)
-            self.row_key = torch.zeros(max(cap, 1), dtype=torch.int64, device=dev)
-            self.rows_total = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.solve_status = torch.zeros(1, dtype=torch.int32, device=dev)
-        if getattr(self, "solver", None) is None:
+            self.solve_scratch = None                  # another capacity: all of it anew, zeroed
+            self._grown("solve_scratch", _lib.bodies_solve_scratch_bytes(self.n, cap))
+            self.row_lambda, self.row_key = self._out(cap, (), torch.float64), self._out(cap, (), torch.int64)
+            self.rows_total = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.solve_status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if self.solver is None:
             self.solver = _lib.Solver()
             _lib.lib().clapgpu_solver_defaults(C.byref(self.solver))
 
@@ -373,11 +367,11 @@ class PhysWorld:
         contact.  Run it between islands() and world_step(h).  Returns device tensors (rows_total [1], status [1]; bit 0:
         the rows did not fit and nothing was applied; the caller clears it) and, with want_lambda, (row_lambda
         [rows_capacity], row_key [rows_capacity]) in canonical row order."""
-        if getattr(self, "island", None) is None or getattr(self, "contact2_buf", None) is None:
+        if self.island is None or self.contact2_buf is None:
             raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "solve", "no islands: call contacts_geoms and islands first")
         self.alloc_solve(rows_capacity)
         st = bool(self.n_static)
-        mesh = st and self._meshes is not None and getattr(self, "mesh_contact_buf", None) is not None
+        mesh = st and self._meshes is not None and self.mesh_contact_buf is not None
         _lib.check(_lib.lib().clapgpu_bodies_solve(
             _stream(), C.byref(self._desc), C.byref(self.world), C.byref(self.solver), h, _ptr(self.island),
             _ptr(self.static_pairs) if st else None, _ptr(self.static_pair_total) if st else None,
@@ -394,13 +388,12 @@ class PhysWorld:
 
     def alloc_mesh_contacts(self, capacity=None):
         """The mesh contact list (clapgpu_contact2 records, mesh_ref [k][2]), its totals and scratch."""
-        cap = int(capacity if capacity is not None else getattr(self, "mesh_contact_capacity", None) or
+        cap = int(capacity if capacity is not None else self.mesh_contact_capacity or
                   max(min(self.static_capacity, 16 * self.n), 1024))
-        if getattr(self, "mesh_contact_buf", None) is None or self.mesh_contact_capacity != cap:
+        if self.mesh_contact_buf is None or self.mesh_contact_capacity != cap:
             dev = self.device
             self.mesh_contact_capacity = cap
-            self.mesh_contact_buf = torch.zeros((max(cap, 1), 160), dtype=torch.uint8, device=dev)
-            self.mesh_ref = torch.zeros((max(cap, 1), 2), dtype=torch.int32, device=dev)
+            self.mesh_contact_buf, self.mesh_ref = self._out(cap, (160,), torch.uint8), self._out(cap, (2,), torch.int32)
             self.mesh_contact_total = torch.zeros(1, dtype=torch.int32, device=dev)
             self.mesh_capped = torch.zeros(1, dtype=torch.int32, device=dev)
             self.mesh_scratch = torch.zeros(_lib.mesh_contact_scratch(self.static_capacity), dtype=torch.int32, device=dev)
@@ -452,14 +445,12 @@ class PhysWorld:
         ix = [np.asarray(i, np.uint16).reshape(-1, 3) for i in indices]
         vx_first = np.concatenate([[0], np.cumsum([len(v) for v in vx])]).astype(np.uint32)
         tri_first = np.concatenate([[0], np.cumsum([len(i) for i in ix])]).astype(np.uint32)
-        up = lambda a, dt, view=None: torch.from_numpy(np.ascontiguousarray(a, dt).view(view or dt)).to(dev)
-        keep = dict(static_index=up(np.asarray(static_index, np.uint32), np.uint32, np.int32),
-                    vx_first=up(vx_first, np.uint32, np.int32), tri_first=up(tri_first, np.uint32, np.int32),
-                    vx=up(np.concatenate(vx) if m else np.zeros((1, 3)), np.float32),
-                    idx=up(np.concatenate(ix) if m else np.zeros((1, 3)), np.uint16, np.int16),
-                    scale=up(np.asarray(scale, np.float32).reshape(-1), np.float32),
-                    pos=up(np.asarray(pos, np.float64).reshape(-1, 3), np.float64),
-                    quat=up(np.asarray(quat, np.float32).reshape(-1, 4), np.float32))
+        keep = dict(static_index=upload(static_index, np.uint32, dev),
+                    vx_first=upload(vx_first, np.uint32, dev), tri_first=upload(tri_first, np.uint32, dev),
+                    vx=upload(np.concatenate(vx) if m else np.zeros((1, 3)), np.float32, dev),
+                    idx=upload(np.concatenate(ix) if m else np.zeros((1, 3)), np.uint16, dev),
+                    scale=upload(scale, np.float32, dev, (-1,)), pos=upload(pos, np.float64, dev, (-1, 3)),
+                    quat=upload(quat, np.float32, dev, (-1, 4)))
         d = _lib.TrimeshDesc(m, self.n_static, *[(_ptr(keep[k]) if m else None) for k in
                                                   ("static_index", "vx_first", "tri_first", "vx", "idx", "scale", "pos", "quat")])
         out = C.c_void_p()
@@ -470,8 +461,7 @@ class PhysWorld:
     def pose_static_meshes(self, pos, quat):
         """New poses of every mesh (entity position, rotation x, y, z, w): re-bake and rebuild (clapgpu_trimesh_pose)."""
         dev = self.device
-        p = torch.from_numpy(np.ascontiguousarray(pos, np.float64).reshape(-1, 3)).to(dev)
-        q = torch.from_numpy(np.ascontiguousarray(quat, np.float32).reshape(-1, 4)).to(dev)
+        p, q = upload(pos, np.float64, dev, (-1, 3)), upload(quat, np.float32, dev, (-1, 4))
         _lib.check(_lib.lib().clapgpu_trimesh_pose(_stream(), self._meshes, _ptr(p), _ptr(q)), "clapgpu_trimesh_pose")
         torch.cuda.current_stream().synchronize()
 
@@ -489,23 +479,22 @@ class PhysWorld:
 
     def ray_cast(self, start, dir, length, skip=None, grid=True, meshes=True):
         """__phys_ray_cast for a batch: start / dir [n, 3], length [n]; skip [n] (body i, -2 - s, -1).  grid: through the
-        last bp_index().  meshes: through the static meshes once set_static_meshes ran.  Returns device tensors (dist [n] (NaN on a miss), hit [n], contact [n, 6], flags [n])."""
+        last bp_index().  meshes: through the static meshes once set_static_meshes ran.  Returns device tensors (dist [n]
+        (NaN on a miss), hit [n], contact [n, 6], flags [n])."""
         dev = self.device
         start, dir = np.asarray(start, np.float64).reshape(-1, 3), np.asarray(dir, np.float64).reshape(-1, 3)
         nr = start.shape[0]
         ray = np.zeros((max(nr, 1), 8))
         ray[:nr, 0:3], ray[:nr, 3:6], ray[:nr, 6] = start, dir, np.broadcast_to(np.asarray(length, np.float64), (nr,))
         ray_d = torch.from_numpy(ray).to(dev)
-        skip_d = None if skip is None else torch.from_numpy(np.ascontiguousarray(skip, np.int32)).to(dev)
-        dist = torch.full((max(nr, 1),), float("nan"), dtype=torch.float64, device=dev)
-        hit = torch.zeros(max(nr, 1), dtype=torch.int32, device=dev)
-        contact = torch.full((max(nr, 1), 6), float("nan"), dtype=torch.float64, device=dev)
-        flags = torch.zeros(max(nr, 1), dtype=torch.int32, device=dev)
+        skip_d = None if skip is None else upload(skip, np.int32, dev)
+        nan = float("nan")
+        dist, contact = self._out(nr, (), torch.float64, nan), self._out(nr, (6,), torch.float64, nan)
+        hit, flags = self._out(nr, (), torch.int32), self._out(nr, (), torch.int32)
         g, sg = self.body_geoms(), self.static_geoms()
         _lib.check(_lib.lib().clapgpu_ray_cast_meshes(_stream(), self._bp if grid else None, C.byref(g), C.byref(sg),
                                                       self._meshes if meshes else None, nr, _ptr(ray_d), _ptr(skip_d),
-                                                      _ptr(dist), _ptr(hit),
-                                                      _ptr(contact), _ptr(flags)),
+                                                      _ptr(dist), _ptr(hit), _ptr(contact), _ptr(flags)),
                    "clapgpu_ray_cast_meshes")
         self._ray_keep = (ray_d, skip_d)
         return dist[:nr], hit[:nr], contact[:nr], flags[:nr]
@@ -516,23 +505,19 @@ class PhysWorld:
         hit [n], flags [n])."""
         dev = self.device
         nb = len(bodies)
-        up = lambda a, dt, view=None: torch.from_numpy(np.ascontiguousarray(a, dt).view(view or dt)).to(dev)
-        body_d, off_d, gr_d = up(bodies, np.uint32, np.int32), up(ray_off, np.float64), up(np.asarray(grounded) != 0, np.uint8)
-        n1 = max(nb, 1)
-        out = torch.zeros(n1, dtype=torch.uint8, device=dev)
-        normal = torch.zeros((n1, 3), dtype=torch.float32, device=dev)
-        dist = torch.full((n1,), float("nan"), dtype=torch.float64, device=dev)
-        hit = torch.zeros(n1, dtype=torch.int32, device=dev)
-        flags = torch.zeros(n1, dtype=torch.int32, device=dev)
-        scratch = getattr(self, "_ground_scratch", None)
-        if scratch is None:
-            scratch = self._ground_scratch = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dev)
+        body_d, off_d = upload(bodies, np.uint32, dev), upload(ray_off, np.float64, dev)
+        gr_d = upload(np.asarray(grounded) != 0, np.uint8, dev)
+        out, normal = self._out(nb, (), torch.uint8), self._out(nb, (3,), torch.float32)
+        dist = self._out(nb, (), torch.float64, float("nan"))
+        hit, flags = self._out(nb, (), torch.int32), self._out(nb, (), torch.int32)
+        if self._ground_scratch is None:                         # [n] words of the call's own
+            self._ground_scratch = self._out(self.n, (), torch.int32)
         sg = self.static_geoms()
         _lib.check(_lib.lib().clapgpu_bodies_ground_collide_meshes(_stream(), self._bp if grid else None, C.byref(self._desc),
                                                                    C.byref(sg), self._meshes if meshes else None, nb,
-                                                                   _ptr(body_d), _ptr(off_d),
-                                                                   _ptr(gr_d), _ptr(out), _ptr(normal), _ptr(dist), _ptr(hit),
-                                                                   _ptr(flags), _ptr(scratch)),
+                                                                   _ptr(body_d), _ptr(off_d), _ptr(gr_d), _ptr(out),
+                                                                   _ptr(normal), _ptr(dist), _ptr(hit), _ptr(flags),
+                                                                   _ptr(self._ground_scratch)),
                    "clapgpu_bodies_ground_collide_meshes")
         self._ground_keep = (body_d, off_d, gr_d)
         return out[:nb], normal[:nb], dist[:nb], hit[:nb], flags[:nb]
@@ -548,33 +533,32 @@ class PhysWorld:
 
     def set_materials(self, material):
         """Per-body phys_body parameters (bounce, bounce_vel, mu, soft_erp, soft_cfm; physics.c:77-81)."""
-        self.material = torch.from_numpy(np.ascontiguousarray(material, np.float64)).to(self.device)
+        self.material = upload(material, np.float64, self.device)
 
     def contacts(self):
         """near_callback on the body x body candidate pairs of the last broadphase(): one contact record
         per pair (oracle.binding.CONTACT_DTYPE layout = clapgpu_contact) + the number of touching pairs."""
-        if getattr(self, "contact_buf", None) is None:
+        if self.contact_buf is None:
             self.contact_buf = torch.zeros((self.capacity, 104), dtype=torch.uint8, device=self.device)
             self.contact_total = torch.zeros(1, dtype=torch.int32, device=self.device)
-        mat = getattr(self, "material", None)
         _lib.check(_lib.lib().clapgpu_contacts_spheres(_stream(), C.byref(self._desc), _ptr(self.pairs),
-                                                       _ptr(self.pair_total), self.capacity, _ptr(mat),
+                                                       _ptr(self.pair_total), self.capacity, _ptr(self.material),
                                                        _ptr(self.contact_buf), _ptr(self.contact_total)),
                    "clapgpu_contacts_spheres")
 
     def contacts_static(self, static_material=None):
         """near_callback on the (body, static box) candidate pairs of the last broadphase(): ODE's
         dCollideSphereBox + phys_contact_surface, one record per pair."""
-        if getattr(self, "static_contact_buf", None) is None:
+        if self.static_contact_buf is None:
             self.static_contact_buf = torch.zeros((self.static_capacity, 104), dtype=torch.uint8, device=self.device)
             self.static_contact_total = torch.zeros(1, dtype=torch.int32, device=self.device)
         if static_material is not None:
-            self.static_material = torch.from_numpy(np.ascontiguousarray(static_material, np.float64)).to(self.device)
-        mat, smat = getattr(self, "material", None), getattr(self, "static_material", None)
+            self.static_material = upload(static_material, np.float64, self.device)
         _lib.check(_lib.lib().clapgpu_contacts_sphere_box(_stream(), C.byref(self._desc), self.n_static,
                                                           self.statics_ptr, _ptr(self.static_pairs),
-                                                          _ptr(self.static_pair_total), self.static_capacity, _ptr(mat),
-                                                          _ptr(smat), _ptr(self.static_contact_buf),
+                                                          _ptr(self.static_pair_total), self.static_capacity,
+                                                          _ptr(self.material), _ptr(self.static_material),
+                                                          _ptr(self.static_contact_buf),
                                                           _ptr(self.static_contact_total)),
                    "clapgpu_contacts_sphere_box")
 
@@ -649,66 +633,3 @@ class PhysWorld:
     def integrate_algorithmic_bytes(self):
         return 232 * self.n
 
-
-class CharacterMoves:
-    """The movers of clapgpu_characters_move (clapgpu_move): device arrays of the per-character state character_move reads
-    and writes, the outputs, the scratch and the descriptor.  bodies [n]: the characters' bodies, each once; ray_off [n];
-    jump_params [n, 2] (jump_forward, jump_upward).  entity [n] with entity_batch: the rotation hand-off (set yaw_quat
-    every frame).  velocity / normal / airborne persist on the device from call to call, as the reference keeps them in
-    struct character; set() uploads what the host changed."""
-
-    _IN = dict(motion=(np.float32, 2), state=(np.uint8, 0), jump=(np.uint8, 0), jump_params=(np.float32, 2),
-               velocity=(np.float32, 3), normal=(np.float32, 3), airborne=(np.uint8, 0), yaw_quat=(np.float32, 4))
-
-    def __init__(self, world, bodies, ray_off, jump_params=None, entity=None, entity_batch=None, **state):
-        if (entity is None) != (entity_batch is None):
-            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "CharacterMoves", "entity and entity_batch: both or neither")
-        self.world, self.entity_batch = world, entity_batch
-        self.device = dev = world.device
-        self.n = n = len(bodies)
-        n1 = max(n, 1)
-        up = lambda a, dt, view=None: torch.from_numpy(np.ascontiguousarray(a, dt).view(view or dt)).to(dev)
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        self.body = up(np.asarray(bodies, np.uint32), np.uint32, np.int32) if n else z(1, torch.int32)
-        self.ray_off = up(np.asarray(ray_off, np.float64).reshape(-1), np.float64) if n else z(1, torch.float64)
-        self.motion, self.jump_params = z((n1, 2), torch.float32), z((n1, 2), torch.float32)
-        self.state, self.jump, self.airborne = z(n1, torch.uint8), z(n1, torch.uint8), z(n1, torch.uint8)
-        self.velocity, self.normal = z((n1, 3), torch.float32), z((n1, 3), torch.float32)
-        self.request, self.applied = z(n1, torch.uint8), z(n1, torch.uint8)
-        self.collision = torch.full((n1,), -1, dtype=torch.int32, device=dev)
-        self.first_frac = torch.ones((n1, 2), dtype=torch.float32, device=dev)
-        self.push_hit = torch.full((n1, 6), -1, dtype=torch.int32, device=dev)
-        self.flags = z(n1, torch.int32)
-        self.entity = self.yaw_quat = None
-        if entity is not None:
-            self.entity = up(np.asarray(entity, np.uint32), np.uint32, np.int32) if n else z(1, torch.int32)
-            self.yaw_quat = z((n1, 4), torch.float32)
-            self.yaw_quat[:, 3] = 1.0
-        need = _lib.characters_move_scratch_bytes(world.n, n) if n else 0
-        self.scratch = torch.zeros(max(need, 256), dtype=torch.uint8, device=dev)
-        self._desc = _lib.CharactersMove(n, *[_ptr(getattr(self, k)) for k in
-                                              ("body", "ray_off", "motion", "state", "jump", "jump_params", "velocity",
-                                               "normal", "airborne", "request", "applied", "collision", "first_frac",
-                                               "push_hit", "flags", "entity", "yaw_quat")])
-        if jump_params is not None:
-            state["jump_params"] = jump_params
-        self.set(**state)
-
-    def set(self, **arrays):
-        """Upload motion [n, 2], state [n], jump [n], jump_params [n, 2], velocity [n, 3], normal [n, 3], airborne [n],
-        yaw_quat [n, 4] (x, y, z, w): those given, into the arrays the descriptor points at."""
-        for k, a in arrays.items():
-            dt, width = self._IN[k]
-            a = np.asarray(a)
-            if dt == np.uint8 and a.dtype != np.uint8:
-                a = a != 0 if k != "state" else a
-            a = np.ascontiguousarray(a, dt).reshape((-1, width) if width else (-1,))
-            if self.n:
-                getattr(self, k)[:self.n].copy_(torch.from_numpy(a).to(self.device))
-
-    def outputs(self):
-        """dict of device tensors: velocity, normal, airborne (in / out), request, applied, collision, first_frac,
-        push_hit, flags (ray flags | slide flags << 8)."""
-        n = self.n
-        return {k: getattr(self, k)[:n] for k in ("velocity", "normal", "airborne", "request", "applied", "collision",
-                                                   "first_frac", "push_hit", "flags")}
