@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 OK = 0
 ERR_NOMEM = -1
@@ -215,8 +215,9 @@ class Lights(C.Structure):
 
 
 class Solver(C.Structure):
-    """clapgpu_solver (include/clapgpu.h): quickstep's iteration count, SOR factor and global CFM."""
-    _fields_ = [("iterations", C.c_uint32), ("pad", C.c_uint32), ("sor_w", C.c_double), ("cfm", C.c_double)]
+    """clapgpu_solver (include/clapgpu.h): quickstep's iteration count, SOR factor and global CFM; wide_rows: the rows from
+    which an island is solved by a workgroup, level by level (0: never)."""
+    _fields_ = [("iterations", C.c_uint32), ("wide_rows", C.c_uint32), ("sor_w", C.c_double), ("cfm", C.c_double)]
 
 
 class Frame(C.Structure):
@@ -395,6 +396,13 @@ SYMBOLS = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_bodies_solve_wide": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.POINTER(Solver), C.c_double,
+                                            C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                            C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
     "clapgpu_visible_compact_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_characters_update_clock": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),

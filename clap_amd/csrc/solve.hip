@@ -1,5 +1,5 @@
-// solve.hip -- contact response for gfx950: dWorldQuickStep's constraint stage for contact joints, one sequential SOR
-// solve per island, islands in parallel.
+// solve.hip -- contact response for gfx950: dWorldQuickStep's constraint stage for contact joints, one SOR solve per
+// island, islands in parallel; a small island on one lane, a large one level by level on a workgroup.
 //
 // near_callback leaves penetration to "contact joints and ERP" (physics.c:433-438); the records of the three contact
 // lists become quickstep's rows (dxJointContact::getInfo2 of ODE 0.16 as physics.c:291-330 configures it) and are
@@ -8,34 +8,32 @@
 // tests/solveref.py and held to bit equality -- PARITY UNPINNED.
 //   k_solve_count   a fixed number of workgroups, each over one contiguous chunk of the record slots (static list, mesh
 //                   list, body list, by capacity): the rows of its chunk into sums[workgroup]; the same launch zeroes
-//                   a[], touched[] and fills the keys with the key that sorts last
+//                   a[], touched[], last_level[], row_level[] and fills the keys with the key that sorts last
 //   k_solve_rows    the same walk again, now with the prefix of sums[]: every active contact writes its rows' constants
-//                   (J, iMJ, rhs, Ad, cfm / h, lo, hi), lambda = 0 and the key (island << 32) | ordinal
+//                   (J, iMJ, rhs, Ad, cfm / h, lo, hi), its bodies (row_bodies: a dropped row keeps them), lambda = 0
+//                   and the key (island << 32) | ordinal
 //   (rocPRIM radix sort of the keys inside the caller's scratch: the keys are distinct)
-//   k_solve_sweep   one lane per sorted key; the lane at the head of an island's run walks it through all sweeps.
+//   k_solve_sweep   one lane per sorted key; the lane at the head of an island's run walks it through all sweeps, or,
+//                   when the run has wide_rows rows or more, appends (start, length) to the wide list and leaves.
 //                   lambda and a live in global scratch, each lane touching only its own island's words
+//   k_solve_sweep_wide (solve_wide.hip; not launched when wide_rows is 0) a fixed grid of workgroups over the wide list
 //   k_solve_apply   one lane per body: lvel += h a_lin, avel += h a_ang
-// Islands are disjoint in the bodies they write and statics have no state: no atomic on a double, no fence, no
-// hand-over inside a launch; launches hand over at kernel boundaries.  The row total is known on the device only: the
-// launches read it and apply nothing when it exceeds rows_capacity.
-// One lane per island is the price of the sequential sweep (as a body's run is in push.hip): a pile of thousands of
-// bodies costs that many dependent updates, 20 times over.
+// Islands are disjoint in the bodies they write and statics have no state: no atomic on a double and no hand-over
+// between workgroups inside a launch; launches hand over at kernel boundaries.  The row total is known on the device
+// only: the launches read it and apply nothing when it exceeds rows_capacity.
+// The sweep is sequential only between rows that share a body (as a body's run is in push.hip): the lane path pays every
+// row of its island as a dependent update, the wide path every LEVEL (solve_wide.hip); both run relax_row
+// (solve_dev.h), stated once.
 // fp64, no FMA contraction (the Makefile builds with -ffp-contract=off); every sum in the order of the header.
 #include <rocprim/device/device_radix_sort.hpp>
 #include "common.h"
 #include "phys_dev.h"
+#include "solve_dev.h"
 
 namespace clapgpu {
 
-constexpr int SB = 256;
 constexpr uint32_t SOLVE_BLOCKS_MAX = 1024;             // workgroups of the two counting walks (sums[] is this long)
-constexpr uint32_t NONE = 0xffffffffu;
-
-struct SolveRow {                                       // 240 bytes; b1 == NONE: dropped (d == 0)
-    double J[12], iMJ[12];
-    double rhs, Ad, cfmh, lo, hi;
-    uint32_t b1, b2;                                    // b2 == NONE: a static or a mesh on the other side
-};
+constexpr uint32_t SOLVE_WIDE_ROWS_DEFAULT = 64;        // clapgpu_solver_defaults' wide_rows: the measured crossover (profiles/solve)
 
 struct SolveLists {
     uint32_t n;                                         // bodies
@@ -112,29 +110,10 @@ __device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *lds)
     return t;
 }
 
-// exclusive prefix of v over the workgroup; total: the workgroup's sum
-__device__ __forceinline__ uint32_t block_prefix(uint32_t v, uint32_t *lds, uint32_t &total)
-{
-    const uint32_t incl = wave_prefix_sum(v);
-    const int wave = threadIdx.x / WAVE;
-    __syncthreads();
-    if (lane_id() == WAVE - 1) lds[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < SB / WAVE; k++) {
-        const uint32_t t = lds[k];
-        if (k < wave) base += t;
-        total += t;
-    }
-    return base + incl - v;
-}
-
 // launch 1: the rows of every chunk, and the fills
 __global__ __launch_bounds__(SB)
 void k_solve_count(SolveLists L, uint64_t slots, uint64_t chunk, uint32_t rows_capacity, uint32_t *sums, uint64_t *keys,
-                   double *a, uint32_t *touched)
+                   double *a, uint32_t *touched, uint32_t *last_level, uint32_t *ctl, uint32_t *row_level, uint32_t *wide_total)
 {
     __shared__ uint32_t lds[SB / WAVE];
     const uint64_t lanes = (uint64_t)gridDim.x * SB, lane = (uint64_t)blockIdx.x * SB + threadIdx.x;
@@ -142,7 +121,14 @@ void k_solve_count(SolveLists L, uint64_t slots, uint64_t chunk, uint32_t rows_c
 #pragma unroll
         for (int k = 0; k < 6; k++) a[6 * i + k] = 0.0;
         touched[i] = 0;
+        last_level[i] = 0;
     }
+    if (lane == 0) {                                                        // no wide island yet
+        ctl[1] = 0;
+        if (wide_total) *wide_total = 0;
+    }
+    if (row_level)
+        for (uint64_t i = lane; i < rows_capacity; i += lanes) row_level[i] = 0;
     const uint64_t last = (uint64_t)L.n << 32 | NONE;                       // island n: sorts behind every row
     for (uint64_t i = lane; i < rows_capacity; i += lanes) keys[i] = last;
     const uint64_t begin = blockIdx.x * chunk, end = begin + chunk < slots ? begin + chunk : slots;
@@ -274,7 +260,7 @@ __device__ __forceinline__ void write_row(SolveRow *out, const SolveK &k, const 
 // launch 2: the rows.  ctl[0] = the row total
 __global__ __launch_bounds__(SB)
 void k_solve_rows(SolveLists L, SolveK k, uint64_t slots, uint64_t chunk, uint32_t rows_capacity, const uint32_t *sums,
-                  uint32_t *ctl, uint64_t *keys, SolveRow *rows, double *lam, uint32_t *touched, uint64_t *row_key,
+                  uint32_t *ctl, uint64_t *keys, SolveRow *rows, uint2 *row_bodies, double *lam, uint32_t *touched, uint64_t *row_key,
                   uint32_t *rows_total, uint32_t *status)
 {
     __shared__ uint32_t lds[SB / WAVE];
@@ -342,6 +328,7 @@ void k_solve_rows(SolveLists L, SolveK k, uint64_t slots, uint64_t chunk, uint32
             for (uint32_t q = 0; q < per; q++) {
                 const uint64_t key = isl | (r + q);
                 keys[r + q] = key;
+                row_bodies[r + q] = make_uint2(b1, b2);
                 lam[r + q] = 0.0;
                 if (row_key) row_key[r + q] = key;
             }
@@ -350,50 +337,35 @@ void k_solve_rows(SolveLists L, SolveK k, uint64_t slots, uint64_t chunk, uint32
     }
 }
 
-// launch 4: the sweeps.  The head of an island's run of sorted keys walks the run `iterations` times.
+// launch 4: the sweeps.  The head of an island's run of sorted keys walks the run `iterations` times -- or hands a run of
+// wide_rows rows or more (wide_rows != 0) to the wide sweep: (start, length) into wide_list[ctl[1]++], in any order
 __global__ __launch_bounds__(SB)
-void k_solve_sweep(uint32_t n, uint32_t rows_capacity, uint32_t iterations, const uint32_t *ctl, const uint64_t *keys,
-                   const SolveRow *__restrict__ rows, double *lam, double *a)
+void k_solve_sweep(uint32_t n, uint32_t rows_capacity, uint32_t iterations, uint32_t wide_rows, uint32_t *ctl,
+                   const uint64_t *keys, const SolveRow *__restrict__ rows, double *lam, double *a, uint2 *wide_list)
 {
     const uint32_t i = blockIdx.x * SB + threadIdx.x;
     if (i >= rows_capacity || ctl[0] > rows_capacity) return;
     const uint32_t t = (uint32_t)(keys[i] >> 32);
     if (t >= n) return;                                                     // the unused keys sort last
     if (i > 0 && (uint32_t)(keys[i - 1] >> 32) == t) return;                // not the head of its island's run
+    const uint64_t far = (uint64_t)i + wide_rows - 1;                       // the run is sorted: wide when it reaches this far
+    if (wide_rows && far < rows_capacity && (uint32_t)(keys[far] >> 32) == t) {
+        uint32_t in = (uint32_t)far, out = rows_capacity;                   // keys[in] is the island's, keys[out] (or the end) is not
+        while (out - in > 1) {
+            const uint32_t mid = in + (out - in) / 2;
+            if ((uint32_t)(keys[mid] >> 32) == t) in = mid;
+            else out = mid;
+        }
+        const uint32_t at = atomicAdd(ctl + 1, 1u);
+        if (at < rows_capacity) wide_list[at] = make_uint2(i, out - i);     // (it is: an island has a row)
+        return;
+    }
     for (uint32_t it = 0; it < iterations; it++) {
         for (uint32_t j = i; j < rows_capacity; j++) {
             const uint64_t key = keys[j];
             if ((uint32_t)(key >> 32) != t) break;
             const uint32_t r = (uint32_t)key;
-            const SolveRow *R = rows + r;
-            const uint32_t b1 = R->b1, b2 = R->b2;
-            if (b1 == NONE) continue;                                       // dropped: lambda stays 0
-            double *a1 = a + 6 * (size_t)b1, *a2 = a + 6 * (size_t)(b2 == NONE ? b1 : b2);
-            double x[12], J[12], iMJ[12];
-#pragma unroll
-            for (int q = 0; q < 12; q++) { J[q] = R->J[q]; iMJ[q] = R->iMJ[q]; }
-#pragma unroll
-            for (int q = 0; q < 6; q++) { x[q] = a1[q]; x[6 + q] = a2[q]; }
-            double Ja = J[0] * x[0];
-#pragma unroll
-            for (int q = 1; q < 6; q++) Ja += J[q] * x[q];
-            if (b2 != NONE) {
-#pragma unroll
-                for (int q = 6; q < 12; q++) Ja += J[q] * x[q];
-            }
-            const double l = lam[r];
-            const double delta = R->Ad * ((R->rhs - R->cfmh * l) - Ja);
-            double nl = l + delta;
-            if (nl < R->lo) nl = R->lo;
-            if (nl > R->hi) nl = R->hi;
-            const double dl = nl - l;
-#pragma unroll
-            for (int q = 0; q < 6; q++) a1[q] = x[q] + iMJ[q] * dl;
-            if (b2 != NONE) {
-#pragma unroll
-                for (int q = 0; q < 6; q++) a2[q] = x[6 + q] + iMJ[6 + q] * dl;
-            }
-            lam[r] = nl;
+            relax_row(rows, r, lam, a);
         }
     }
 }
@@ -413,9 +385,14 @@ void k_solve_apply(uint32_t n, uint32_t rows_capacity, double h, const uint32_t 
     }
 }
 
-// the scratch: ctl [64] | sums [SOLVE_BLOCKS_MAX] | a [n][6] | touched [n] | keys [rows] | keys [rows] | rows [rows] |
-// lambda [rows] | the sort's work space, sized for every key bit
-struct SolveLayout { size_t ctl, sums, a, touched, keys0, keys1, rows, lam, sort, sort_bytes, total; };
+// the scratch: ctl [64] (0: the row total, 1: the wide islands) | sums [SOLVE_BLOCKS_MAX] | a [n][6] | touched [n] |
+// keys [rows] | keys [rows] | rows [rows] | lambda [rows] | the sort's work space, sized for every key bit | the wide
+// sweep's: row_bodies [rows][2] | list [rows][2] (every island may be wide: wide_rows == 1) | last_level [n] | level
+// [rows] | cursor [rows] | order [rows]
+struct SolveLayout {
+    size_t ctl, sums, a, touched, keys0, keys1, rows, lam, sort, sort_bytes, row_bodies, wide_list, last_level, level, cursor,
+           order, total;
+};
 
 static hipError_t solve_layout(uint32_t n, uint32_t rows_capacity, hipStream_t s, SolveLayout &l)
 {
@@ -435,6 +412,12 @@ static hipError_t solve_layout(uint32_t n, uint32_t rows_capacity, hipStream_t s
         if (err != hipSuccess) return err;
     }
     l.sort = c.take(l.sort_bytes);
+    l.row_bodies = c.take((size_t)rows_capacity * sizeof(uint2));
+    l.wide_list = c.take((size_t)rows_capacity * sizeof(uint2));
+    l.last_level = c.take((size_t)n * sizeof(uint32_t));
+    l.level = c.take((size_t)rows_capacity * sizeof(uint32_t));
+    l.cursor = c.take((size_t)rows_capacity * sizeof(uint32_t));
+    l.order = c.take((size_t)rows_capacity * sizeof(uint32_t));
     l.total = c.bytes();
     return hipSuccess;
 }
@@ -449,7 +432,7 @@ extern "C" void clapgpu_solver_defaults(clapgpu_solver *s)
 {
     if (!s) return;
     s->iterations = 20;                                 // dWorldSetQuickStepNumIterations' default
-    s->pad = 0;
+    s->wide_rows = SOLVE_WIDE_ROWS_DEFAULT;
     s->sor_w = 1.3;                                     // dWorldSetQuickStepW's default
     s->cfm = 1e-10;                                     // dWorldSetCFM's default under dDOUBLE
 }
@@ -465,16 +448,16 @@ extern "C" size_t clapgpu_bodies_solve_scratch_bytes(uint32_t n, uint32_t rows_c
     return l.total;
 }
 
-extern "C" int clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_solver *sv,
-                                    double h, const uint32_t *island,
-                                    const uint32_t *static_pairs, const uint32_t *static_pair_total, uint32_t static_capacity,
-                                    const clapgpu_contact2 *static_contacts,
-                                    const clapgpu_contact2 *mesh_contacts, const uint32_t *mesh_ref,
-                                    const uint32_t *mesh_contact_total, uint32_t mesh_capacity,
-                                    const uint32_t *pairs, const uint32_t *pair_total, uint32_t capacity,
-                                    const clapgpu_contact2 *contacts,
-                                    uint32_t rows_capacity, void *scratch, double *row_lambda, uint64_t *row_key,
-                                    uint32_t *rows_total, uint32_t *status)
+extern "C" int clapgpu_bodies_solve_wide(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_solver *sv,
+                                         double h, const uint32_t *island,
+                                         const uint32_t *static_pairs, const uint32_t *static_pair_total, uint32_t static_capacity,
+                                         const clapgpu_contact2 *static_contacts,
+                                         const clapgpu_contact2 *mesh_contacts, const uint32_t *mesh_ref,
+                                         const uint32_t *mesh_contact_total, uint32_t mesh_capacity,
+                                         const uint32_t *pairs, const uint32_t *pair_total, uint32_t capacity,
+                                         const clapgpu_contact2 *contacts,
+                                         uint32_t rows_capacity, void *scratch, double *row_lambda, uint64_t *row_key,
+                                         uint32_t *rows_total, uint32_t *status, uint32_t *row_level, uint32_t *wide_total)
 {
     int rc = check_bodies(b);
     if (rc) return rc;
@@ -493,7 +476,8 @@ extern "C" int clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const
         (reinterpret_cast<uintptr_t>(static_contacts) & 15u) || (reinterpret_cast<uintptr_t>(mesh_contacts) & 15u) ||
         (reinterpret_cast<uintptr_t>(row_lambda) & 7u) || (reinterpret_cast<uintptr_t>(row_key) & 7u) ||
         (reinterpret_cast<uintptr_t>(island) & 3u) || (reinterpret_cast<uintptr_t>(rows_total) & 3u) ||
-        (reinterpret_cast<uintptr_t>(status) & 3u))
+        (reinterpret_cast<uintptr_t>(status) & 3u) || (reinterpret_cast<uintptr_t>(row_level) & 3u) ||
+        (reinterpret_cast<uintptr_t>(wide_total) & 3u))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
     hipStream_t s = as_stream(stream);
 
@@ -513,6 +497,8 @@ extern "C" int clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const
     if (slots > 0xffffffffull / 6) return CLAPGPU_ERR_TOO_LARGE;            // six rows a record: the total stays inside 32 bits
     if (slots == 0) {                                                       // no list: no rows, nothing changes
         if (rows_total) CLAPGPU_HIP(hipMemsetAsync(rows_total, 0, sizeof(uint32_t), s));
+        if (wide_total) CLAPGPU_HIP(hipMemsetAsync(wide_total, 0, sizeof(uint32_t), s));
+        if (row_level && rows_capacity) CLAPGPU_HIP(hipMemsetAsync(row_level, 0, (size_t)rows_capacity * sizeof(uint32_t), s));
         return CLAPGPU_OK;
     }
     SolveLayout l;
@@ -524,6 +510,14 @@ extern "C" int clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const
     rocprim::double_buffer<uint64_t> keys(reinterpret_cast<uint64_t *>(base + l.keys0), reinterpret_cast<uint64_t *>(base + l.keys1));
     SolveRow *rows = reinterpret_cast<SolveRow *>(base + l.rows);
     double *lam = row_lambda ? row_lambda : reinterpret_cast<double *>(base + l.lam);
+    uint2 *row_bodies = reinterpret_cast<uint2 *>(base + l.row_bodies);
+    SolveWide wide;
+    wide.row_bodies = row_bodies;
+    wide.list = reinterpret_cast<uint2 *>(base + l.wide_list);
+    wide.last_level = reinterpret_cast<uint32_t *>(base + l.last_level);
+    wide.level = reinterpret_cast<uint32_t *>(base + l.level);
+    wide.cursor = reinterpret_cast<uint32_t *>(base + l.cursor);
+    wide.order = reinterpret_cast<uint32_t *>(base + l.order);
 
     SolveK k;
     k.pos = b->pos; k.quat = b->quat; k.lvel = b->lvel; k.avel = b->avel; k.mass = b->mass; k.inertia = b->inertia;
@@ -535,18 +529,37 @@ extern "C" int clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const
     const uint32_t blocks = tiles < SOLVE_BLOCKS_MAX ? (uint32_t)tiles : SOLVE_BLOCKS_MAX;
     const uint64_t chunk = ((tiles + blocks - 1) / blocks) * SB;            // whole tiles per workgroup
     hipLaunchKernelGGL(k_solve_count, dim3(blocks), dim3(SB), 0, s, L, slots, chunk, rows_capacity, sums, keys.current(), a,
-                       touched);
+                       touched, wide.last_level, ctl, row_level, wide_total);
     CLAPGPU_LAUNCH_CHECK("k_solve_count");
     hipLaunchKernelGGL(k_solve_rows, dim3(blocks), dim3(SB), 0, s, L, k, slots, chunk, rows_capacity, sums, ctl, keys.current(),
-                       rows, lam, touched, row_key, rows_total, status);
+                       rows, row_bodies, lam, touched, row_key, rows_total, status);
     CLAPGPU_LAUNCH_CHECK("k_solve_rows");
     if (rows_capacity == 0) return CLAPGPU_OK;                              // any row at all is one too many: status says so
     CLAPGPU_HIP(rocprim::radix_sort_keys(base + l.sort, l.sort_bytes, keys, (size_t)rows_capacity, 0, 32 + bits_of(n), s));
-    hipLaunchKernelGGL(k_solve_sweep, dim3((rows_capacity + SB - 1) / SB), dim3(SB), 0, s, n, rows_capacity, sv->iterations, ctl,
-                       keys.current(), rows, lam, a);
+    hipLaunchKernelGGL(k_solve_sweep, dim3((rows_capacity + SB - 1) / SB), dim3(SB), 0, s, n, rows_capacity, sv->iterations,
+                       sv->wide_rows, ctl, keys.current(), rows, lam, a, wide.list);
     CLAPGPU_LAUNCH_CHECK("k_solve_sweep");
+    if (sv->wide_rows)                                                      // 0: never, and not a launch more than before
+        CLAPGPU_HIP(solve_sweep_wide(s, rows_capacity, sv->iterations, ctl, keys.current(), rows, wide, lam, a, row_level,
+                                     wide_total));
     hipLaunchKernelGGL(k_solve_apply, dim3((n + SB - 1) / SB), dim3(SB), 0, s, n, rows_capacity, h, ctl, b->bflags, touched, a,
                        b->lvel, b->avel);
     CLAPGPU_LAUNCH_CHECK("k_solve_apply");
     return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_solver *sv,
+                                    double h, const uint32_t *island,
+                                    const uint32_t *static_pairs, const uint32_t *static_pair_total, uint32_t static_capacity,
+                                    const clapgpu_contact2 *static_contacts,
+                                    const clapgpu_contact2 *mesh_contacts, const uint32_t *mesh_ref,
+                                    const uint32_t *mesh_contact_total, uint32_t mesh_capacity,
+                                    const uint32_t *pairs, const uint32_t *pair_total, uint32_t capacity,
+                                    const clapgpu_contact2 *contacts,
+                                    uint32_t rows_capacity, void *scratch, double *row_lambda, uint64_t *row_key,
+                                    uint32_t *rows_total, uint32_t *status)
+{
+    return clapgpu_bodies_solve_wide(stream, b, w, sv, h, island, static_pairs, static_pair_total, static_capacity, static_contacts,
+                                     mesh_contacts, mesh_ref, mesh_contact_total, mesh_capacity, pairs, pair_total, capacity,
+                                     contacts, rows_capacity, scratch, row_lambda, row_key, rows_total, status, nullptr, nullptr);
 }

@@ -81,6 +81,7 @@ class PhysWorld:
         self.contact2_buf = self.contact2_total = self.static_contact2_buf = self.static_contact2_total = None
         self.island_scratch = self.island = self.island_woken = None
         self.solver = self.solve_scratch = self.row_lambda = self.row_key = self.rows_total = self.solve_status = None
+        self.row_level = self.wide_total = None
         self.solve_rows_capacity = self.mesh_contact_capacity = 0
         self.mesh_contact_buf = self.mesh_ref = self.mesh_contact_total = self.mesh_capped = self.mesh_scratch = None
         self._meshes_keep = None                                           # set_static_meshes (beside _meshes)
@@ -357,22 +358,26 @@ class PhysWorld:
             self.row_lambda, self.row_key = self._out(cap, (), torch.float64), self._out(cap, (), torch.int64)
             self.rows_total = torch.zeros(1, dtype=torch.int32, device=self.device)
             self.solve_status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.row_level = self._out(cap, (), torch.int32)
+            self.wide_total = torch.zeros(1, dtype=torch.int32, device=self.device)
         if self.solver is None:
             self.solver = _lib.Solver()
             _lib.lib().clapgpu_solver_defaults(C.byref(self.solver))
 
-    def solve(self, h, want_lambda=False, rows_capacity=None):
-        """Contact response (clapgpu_bodies_solve): the rows of the last contacts_geoms[_both]() / contacts_meshes() lists,
+    def solve(self, h, want_lambda=False, rows_capacity=None, want_levels=False):
+        """Contact response (clapgpu_bodies_solve_wide): the rows of the last contacts_geoms[_both]() / contacts_meshes() lists,
         solved island by island with the islands of the last islands(); changes lvel / avel of the enabled bodies in
         contact.  Run it between islands() and world_step(h).  Returns device tensors (rows_total [1], status [1]; bit 0:
         the rows did not fit and nothing was applied; the caller clears it) and, with want_lambda, (row_lambda
-        [rows_capacity], row_key [rows_capacity]) in canonical row order."""
+        [rows_capacity], row_key [rows_capacity]) in canonical row order; with want_levels, behind those, (row_level
+        [rows_capacity]: a row's level when a workgroup solved its island -- one of at least self.solver.wide_rows rows --
+        and 0 when one lane did, wide_total [1]: the islands a workgroup solved)."""
         if self.island is None or self.contact2_buf is None:
             raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "solve", "no islands: call contacts_geoms and islands first")
         self.alloc_solve(rows_capacity)
         st = bool(self.n_static)
         mesh = st and self._meshes is not None and self.mesh_contact_buf is not None
-        _lib.check(_lib.lib().clapgpu_bodies_solve(
+        _lib.check(_lib.lib().clapgpu_bodies_solve_wide(
             _stream(), C.byref(self._desc), C.byref(self.world), C.byref(self.solver), h, _ptr(self.island),
             _ptr(self.static_pairs) if st else None, _ptr(self.static_pair_total) if st else None,
             self.static_capacity if st else 0, _ptr(self.static_contact2_buf) if st else None,
@@ -381,10 +386,15 @@ class PhysWorld:
             _ptr(self.pairs), _ptr(self.pair_total), self.capacity, _ptr(self.contact2_buf),
             self.solve_rows_capacity, _ptr(self.solve_scratch),
             _ptr(self.row_lambda) if want_lambda else None, _ptr(self.row_key) if want_lambda else None,
-            _ptr(self.rows_total), _ptr(self.solve_status)), "clapgpu_bodies_solve")
+            _ptr(self.rows_total), _ptr(self.solve_status),
+            _ptr(self.row_level) if want_levels else None, _ptr(self.wide_total) if want_levels else None),
+            "clapgpu_bodies_solve_wide")
+        out = (self.rows_total, self.solve_status)
         if want_lambda:
-            return self.rows_total, self.solve_status, self.row_lambda, self.row_key
-        return self.rows_total, self.solve_status
+            out += (self.row_lambda, self.row_key)
+        if want_levels:
+            out += (self.row_level, self.wide_total)
+        return out
 
     def alloc_mesh_contacts(self, capacity=None):
         """The mesh contact list (clapgpu_contact2 records, mesh_ref [k][2]), its totals and scratch."""

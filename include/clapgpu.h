@@ -1261,8 +1261,8 @@ int  clapgpu_bodies_islands(void *stream, const clapgpu_bodies *b, const clapgpu
 /*
  * clapgpu_bodies_solve: contact response -- the constraint stage of dWorldQuickStep (physics.c:769) for the contact joints
  * near_callback creates ("rely on contact joints and ERP for penetration resolution", physics.c:433-438).  The records of a
- * substep's three contact lists become quickstep's contact rows and are relaxed by its SOR iteration, one sequential
- * solve per island, islands in parallel.  ODE 0.16 (joints/contact.cpp, quickstep.cpp) restated, with ONE deliberate
+ * substep's three contact lists become quickstep's contact rows and are relaxed by its SOR iteration, one solve per
+ * island, islands in parallel.  ODE 0.16 (joints/contact.cpp, quickstep.cpp) restated, with ONE deliberate
  * difference: ODE reorders its rows at random, here the row order is the canonical order of the lists.  The rule below is
  * this library's own contract, restated independently in tests/solveref.py and held to bit equality; PARITY UNPINNED (ODE
  * is absent from the reference).  fp64, no FMA contraction, every sum left to right in the order written.
@@ -1310,21 +1310,44 @@ int  clapgpu_bodies_islands(void *stream, const clapgpu_bodies *b, const clapgpu
  *   a += iMJ * (lambda' - lambda);  lambda = lambda'
  * After the sweeps lvel += h * a_lin and avel += h * a_ang for every enabled, non-kinematic body named by an active row.
  *
- * One lane walks an island: the price of the sequential sweep.  A pile of thousands of bodies in one island costs that
- * many dependent row updates, `iterations` times over, on one lane, while separate islands run side by side.
+ * Levels.  The row order matters only between rows that share a body: a row reads and writes the six a of its one or
+ * two bodies and its own lambda, nothing else.  Walking an island's rows in canonical order,
+ *   level(row) = 1 + max(level of the latest earlier row of the island naming body 1, the same for body 2)
+ * with 0 where no earlier row names the body; an absent body 2 (a static or a mesh contact) is no dependency, a KINEMATIC
+ * body is a body like any other, and a dropped row (d == 0) takes part with its bodies like any other row although it does
+ * nothing in the sweeps, so the levels depend on the lists alone and never on arithmetic.  Rows of one level name disjoint
+ * bodies.  Running every sweep as level 1, then level 2, ..., the rows of a level in any order or at once, gives each row
+ * the operands the sequential walk gives it: the same bits, no sum reordered.  tests/solvelevelref.py restates the rule.
+ *
+ * What is parallel.  Islands run side by side.  An island with fewer than s->wide_rows rows (every island when wide_rows
+ * is 0) is walked by one lane, row after row.  An island with at least wide_rows rows is walked by one 256-thread
+ * workgroup: its first wavefront takes the levels, 64 rows at a time; the workgroup buckets the rows by level and runs
+ * the sweeps level by level with a workgroup barrier behind each level.  CLAPGPU_SOLVE_WIDE_WORKGROUPS workgroups (fewer
+ * when rows_capacity is smaller) stride over the wide islands; no grid depends on a count only the device knows.
+ * What stays sequential.  The depth: an island costs as many dependent steps per sweep as it has levels, the longest
+ * chain of rows that share bodies.  A square grid of piled spheres whose pairs are listed by first index has about four levels per grid line
+ * (253 for 64 x 64 spheres and their 12 160 rows); a tower listed bottom-up, where every row shares a body with the row before, has one row per level and
+ * gains nothing -- it only pays the barriers.  The order of the pair list decides the depth, the result never.
  *
  * Each list may be absent (a NULL pointer or capacity 0); the mesh list needs static_pairs and static_pair_total.
  * rows_capacity: the most rows the call can hold.  When the rows do not fit, the launches -- which read the total on the
  * device, where alone it is known -- apply nothing and OR 1 into *status (the caller clears it).  row_lambda
  * [rows_capacity] and row_key [rows_capacity] (device, may be NULL) receive lambda and the key of every row at its
  * ordinal; *rows_total (device, may be NULL) the number of rows.
+ * clapgpu_bodies_solve_wide is the same call with two more outputs (device, may be NULL, 4-byte aligned): row_level
+ * [rows_capacity] receives at every row's ordinal its level (>= 1) when its island was solved by a workgroup and 0 when
+ * by one lane (all 0 when the rows do not fit); *wide_total the number of islands solved by a workgroup.
+ * clapgpu_bodies_solve is that call with both NULL.
  * scratch: clapgpu_bodies_solve_scratch_bytes(b->n, rows_capacity) bytes of device memory, 256-byte aligned, overwritten;
- * the caller need not clear it between calls.  Four launches and a rocPRIM radix sort of the row keys inside the scratch,
- * no allocation, no host synchronisation: a captured graph can hold the call.  b->n == 0 returns CLAPGPU_OK and launches
+ * the caller need not clear it between calls; its size does not depend on wide_rows.  Four launches (five when wide_rows
+ * is not 0) and a rocPRIM radix sort of the row keys inside the scratch, no allocation, no host synchronisation: a captured graph can hold the call.  b->n == 0 returns CLAPGPU_OK and launches
  * nothing; without any list nothing changes and *rows_total = 0.  Pairs 8-byte, records 16-byte aligned.
  */
-typedef struct clapgpu_solver { uint32_t iterations; uint32_t pad; double sor_w; double cfm; } clapgpu_solver;
-void   clapgpu_solver_defaults(clapgpu_solver *s);    /* 20, 1.3, 1e-10: ODE's dDOUBLE defaults, physics.c:1127-1128 leave them */
+#define CLAPGPU_SOLVE_WIDE_WORKGROUPS 1024u    /* the most workgroups the wide sweep launches */
+/* wide_rows: an island with at least this many rows is solved by a workgroup, level by level; 0: never */
+typedef struct clapgpu_solver { uint32_t iterations; uint32_t wide_rows; double sor_w; double cfm; } clapgpu_solver;
+/* 20, 1.3, 1e-10: ODE's dDOUBLE defaults, physics.c:1127-1128 leave them; wide_rows 64: the measured crossover (profiles/solve) */
+void   clapgpu_solver_defaults(clapgpu_solver *s);
 size_t clapgpu_bodies_solve_scratch_bytes(uint32_t n, uint32_t rows_capacity);
 int    clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_solver *s, double h,
                             const uint32_t *island,   /* required: clapgpu_bodies_islands' output of this substep */
@@ -1337,6 +1360,18 @@ int    clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const clapgpu
                             uint32_t rows_capacity, void *scratch,
                             double *row_lambda, uint64_t *row_key,
                             uint32_t *rows_total, uint32_t *status);
+int    clapgpu_bodies_solve_wide(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_solver *s, double h,
+                            const uint32_t *island,
+                            const uint32_t *static_pairs, const uint32_t *static_pair_total, uint32_t static_capacity,
+                            const clapgpu_contact2 *static_contacts,
+                            const clapgpu_contact2 *mesh_contacts, const uint32_t *mesh_ref,
+                            const uint32_t *mesh_contact_total, uint32_t mesh_capacity,
+                            const uint32_t *pairs, const uint32_t *pair_total, uint32_t capacity,
+                            const clapgpu_contact2 *contacts,
+                            uint32_t rows_capacity, void *scratch,
+                            double *row_lambda, uint64_t *row_key,
+                            uint32_t *rows_total, uint32_t *status,
+                            uint32_t *row_level, uint32_t *wide_total);
 
 /* ======================================================================== */
 /* Characters: the feeder in front of default_update (core/character.c)      */
