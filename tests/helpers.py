@@ -1,10 +1,33 @@
 """Shared helpers of the parity tests."""
+import os
+import subprocess
+
 import numpy as np
 
 from clap_amd import synth
 
 SCENE_KEYS = ("pos_scale", "rot", "parent", "model", "model_aabb", "model_skip", "flags", "level_start")
 CAM_KEYS = ("cam_pos", "cam_quat", "persp", "ndc_z_zero_one")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST = os.path.join(ROOT, "clap_amd", "host")
+LOADER_SRCS = [os.path.join(HOST, f) for f in ("clapgpu_load.c", "clapgpu_load_json.c", "clapgpu_load_gltf.c", "clapgpu_load_model.c",
+                                               "clapgpu_snapshot.c")]
+SANITIZE = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+
+
+def build_test_load(exe, sanitize):
+    """tests/c/test_load.c.  sanitize: with the loader's sources under AddressSanitizer + UBSan and without the GPU
+    part (host code only); otherwise against the built libraries and the oracle's, which the caller has built."""
+    cc = ["gcc", "-O1", "-std=gnu11", "-Wall", "-I", os.path.join(ROOT, "include")]
+    src = os.path.join(ROOT, "tests", "c", "test_load.c")
+    if sanitize:
+        cmd = cc + SANITIZE + ["-DTEST_LOAD_NO_GPU", src] + LOADER_SRCS + ["-o", exe, "-lm"]
+    else:
+        libdir, odir = os.path.join(ROOT, "clap_amd", "lib"), os.path.join(ROOT, "oracle", "_build")
+        cmd = cc + ["-I", os.path.join(ROOT, "oracle"), src, "-o", exe, "-L", libdir, "-lclapgpu_scene", "-lclapgpu",
+                    "-L", odir, "-lclap_oracle", "-lm", f"-Wl,-rpath,{libdir}", f"-Wl,-rpath,{odir}"]
+    subprocess.run(cmd, check=True)
 
 
 def bits_equal(a, b):

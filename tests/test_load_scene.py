@@ -15,11 +15,10 @@ import pytest
 
 from clap_amd import _lib, snapshot, synth
 from oracle import binding as ob
-from helpers import bits_equal
+from helpers import HOST, SANITIZE, bits_equal, build_test_load
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = os.path.join(ROOT, "tests", "golden", "scene_fixture")
-LIBDIR = os.path.join(ROOT, "clap_amd", "lib")
 
 E_VISIBLE, E_CHAR, E_PHYS, E_BODY, E_LIGHT, E_ARM, E_ANIM, E_SKIPCULL, E_DIRTY, E_ATTACHED, E_ALIVE = (
     1, 2, 1 << 4, 1 << 5, 1 << 8, 1 << 12, 1 << 13, 1 << 14, 1 << 16, 1 << 17, 1 << 31)
@@ -248,11 +247,19 @@ def test_loader_under_sanitizers(tmp_path):
     """The loader + snapshot writer built with AddressSanitizer + UBSan (host code), run over the fixture and over
     damaged copies of its files."""
     exe = str(tmp_path / "test_load_c")
-    subprocess.run(["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-DTEST_LOAD_NO_GPU", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "c", "test_load.c"),
-                    os.path.join(ROOT, "clap_amd", "host", "clapgpu_load.c"), os.path.join(ROOT, "clap_amd", "host", "clapgpu_snapshot.c"),
-                    "-o", exe, "-lm"], check=True)
+    build_test_load(exe, sanitize=True)
     r = subprocess.run([exe, FIX, str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "PASS" in r.stdout
+
+
+def test_json_module_alone_under_sanitizers(tmp_path):
+    """tests/c/test_json.c: the loader's JSON parser and getters, linked with nothing else, under AddressSanitizer +
+    UBSan: nesting limit, escapes, buffer growth, number literals, malformed structure, the typed getters."""
+    exe = str(tmp_path / "test_json")
+    subprocess.run(["gcc", "-O1", "-std=gnu11", "-Wall", "-Wextra"] + SANITIZE + ["-I", os.path.join(ROOT, "include"), "-I", HOST,
+                    os.path.join(ROOT, "tests", "c", "test_json.c"), os.path.join(HOST, "clapgpu_load_json.c"), "-o", exe, "-lm"], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "PASS" in r.stdout
 
@@ -312,10 +319,7 @@ def test_c_program_loads_and_replays_the_fixture(tmp_path, cuda_device):
     against the oracle) and the characters' pose / skinning through the flat ABI (equal values)."""
     ob.lib()                                                  # builds oracle/_build/libclap_oracle.so
     exe = str(tmp_path / "test_load")
-    odir = os.path.join(ROOT, "oracle", "_build")
-    subprocess.run(["gcc", "-O1", "-std=gnu11", "-Wall", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "oracle"),
-                    os.path.join(ROOT, "tests", "c", "test_load.c"), "-o", exe, "-L", LIBDIR, "-lclapgpu_scene", "-lclapgpu",
-                    "-L", odir, "-lclap_oracle", "-lm", f"-Wl,-rpath,{LIBDIR}", f"-Wl,-rpath,{odir}"], check=True)
+    build_test_load(exe, sanitize=False)
     r = subprocess.run([exe, FIX, str(tmp_path)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "PASS" in r.stdout

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from clap_amd import _lib, snapshot
+from helpers import build_test_load
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = os.path.join(ROOT, "tests", "golden", "scene_fixture")
@@ -124,10 +125,7 @@ def test_loader_writes_the_crate_collision_mesh(tmp_path):
 def test_loader_collision_meshes_under_sanitizers(tmp_path):
     """The loader built with AddressSanitizer + UBSan (host code) over the fixture, writing the collision keys."""
     exe = str(tmp_path / "test_load_c")
-    subprocess.run(["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-DTEST_LOAD_NO_GPU", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "c", "test_load.c"),
-                    os.path.join(ROOT, "clap_amd", "host", "clapgpu_load.c"), os.path.join(ROOT, "clap_amd", "host", "clapgpu_snapshot.c"),
-                    "-o", exe, "-lm"], check=True)
+    build_test_load(exe, sanitize=True)
     r = subprocess.run([exe, FIX, str(tmp_path)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "PASS" in r.stdout
