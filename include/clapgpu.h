@@ -1265,7 +1265,9 @@ int  clapgpu_bodies_islands(void *stream, const clapgpu_bodies *b, const clapgpu
  * island, islands in parallel.  ODE 0.16 (joints/contact.cpp, quickstep.cpp) restated, with ONE deliberate
  * difference: ODE reorders its rows at random, here the row order is the canonical order of the lists.  The rule below is
  * this library's own contract, restated independently in tests/solveref.py and held to bit equality; PARITY UNPINNED (ODE
- * is absent from the reference).  fp64, no FMA contraction, every sum left to right in the order written.
+ * is absent from the reference).  fp64, no FMA contraction, every sum left to right in the order written.  What the rule
+ * means -- the boxed LCP  A = J invM J^T + diag(cfm / h),  b = c / h - J (v / h + invM f_ext) -- is stated densely in
+ * tests/lcpref.py, and both the restatement (on the CPU) and these kernels (on the device) are held to its solution.
  *
  * Call it after clapgpu_bodies_islands and before clapgpu_bodies_step[_prebin] of the same substep.  It changes lvel and
  * avel of enabled, non-kinematic bodies that a row names, and nothing else of the bodies.

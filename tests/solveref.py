@@ -1,7 +1,8 @@
 """The contact solve of clapgpu_bodies_solve restated in numpy from the rule in include/clapgpu.h: quickstep's contact
 rows and its SOR iteration with the row order fixed to the canonical order of the contact lists, one solve per island.
 Plain loops over float64 scalars, one rounding per operation, every sum left to right as the header writes it; nothing
-here imports the device code.  What the device is compared with, bit for bit.
+here imports the device code.  What the device is compared with, bit for bit.  Whether the rule itself is right is not
+decided here: tests/lcpref.py states it as a dense boxed LCP, and tests/test_solve_lcp.py holds this module to that.
 
 ODE is absent from the reference: like the rest of the rigid-body block this is PARITY UNPINNED."""
 import numpy as np

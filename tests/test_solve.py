@@ -1,6 +1,8 @@
 """CPU: the contact-solve rule of include/clapgpu.h (tests/solveref.py) is physics, before the device is held to it bit
 for bit (tests/test_solve_gpu.py).  Contacts come from the float64 geometry of tests/geomref.py, the step from
-tests/pushref.py; nothing here touches the device."""
+tests/pushref.py; nothing here touches the device.  These are the easy corner (identity quaternions, contact points on
+the line of centres, one to three rows); the independent truth for the whole rule -- rotated anisotropic bodies, the
+angular half of a row, coupled rows -- is tests/lcpref.py, which tests/test_solve_lcp.py holds solveref to."""
 import numpy as np
 
 import geomref as gr
