@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 40
+ABI_VERSION = 41
 
 OK = 0
 ERR_NOMEM = -1
@@ -333,6 +333,9 @@ SYMBOLS = {
                                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "clapgpu_bodies_aabb": (C.c_int, [C.c_void_p, C.POINTER(Bodies)]),
     "clapgpu_bp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_double, C.c_uint32, C.c_void_p]),
+    "clapgpu_bp_create_levels": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_double, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "clapgpu_bp_levels": (C.c_uint32, [C.c_void_p]),
+    "clapgpu_bp_cell_slot": (C.c_uint32, [C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32]),
     "clapgpu_bp_destroy": (None, [C.c_void_p]),
     "clapgpu_bp_collide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                      C.c_void_p, C.c_uint32, C.c_void_p]),

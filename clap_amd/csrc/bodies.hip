@@ -494,6 +494,7 @@ extern "C" int clapgpu_bodies_step_prebin(void *stream, const clapgpu_bodies *b,
     BinK bin;
     rc = clapgpu_bp_prebin(stream, bp, b->n, b->aabb, &bin);
     if (rc || b->n == 0) return rc;
+    if (!bin.key) return clapgpu_bodies_step(stream, b, w, h);   // a leveled bp bins in its own collide: the plain step
     const dim3 grid((b->n + PB - 1) / PB);
     if (b->facc)
         hipLaunchKernelGGL((k_bodies_step<true, true>), grid, dim3(PB), 0, as_stream(stream), bodies_k(b), *w, h, bin, b->facc);

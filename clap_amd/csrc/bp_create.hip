@@ -54,17 +54,24 @@ static size_t carve(BpK &k, char *base, uint32_t n, uint32_t nb, uint32_t n_tile
     return ok ? off : 0;
 }
 
-extern "C" int clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t n_static, const double *static_aabb)
+// levels == 1: the one-level object of clapgpu_bp_create.  More: the same arrays (the level is part of a cell's slot), one
+// statics image per level laid end to end, and the level in four bits of a record's index: n_max <= 2^28.
+static int create(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t levels, uint32_t n_static, const double *static_aabb)
 {
-    if (!out || !(cell > 0.0) || (n_static && !static_aabb) || n_max > (1u << 30))
+    if (!out || !(cell > 0.0) || (n_static && !static_aabb) || n_max > (levels > 1 ? BPL_IDX + 1u : 1u << 30) ||
+        levels == 0 || levels > CLAPGPU_BP_LEVELS_MAX)
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
     clapgpu_bp *bp = static_cast<clapgpu_bp *>(calloc(1, sizeof(*bp)));
     if (!bp) return CLAPGPU_ERR_NOMEM;
     const uint32_t n = n_max ? n_max : 1, nb = buckets_for(n);
     bp->n_max = n_max; bp->buckets = nb; bp->cell = cell; bp->n_static = n_static;
     bp->n_tiles = (n + BP_EMIT_TILE - 1) / BP_EMIT_TILE;
-    const StaticsImage im = bp_statics_image(nb, cell, n_static, static_aabb);
+    bp->levels = levels;
+    std::vector<uint32_t> large_start{ 0u, 0u };
+    const StaticsImage im = levels == 1 ? bp_statics_image(nb, cell, n_static, static_aabb)
+                                        : bp_statics_concat(bp_statics_level_images(nb, cell, levels, n_static, static_aabb), &large_start);
     bp->n_large = im.n_large;
+    memcpy(bp->large_start, large_start.data(), large_start.size() * sizeof(uint32_t));
     memcpy(bp->s_bounds, im.bounds, sizeof(bp->s_bounds));
 
     BpK &k = bp->k;                                                      // zero: calloc
@@ -85,6 +92,25 @@ extern "C" int clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, 
     }
     *out = bp;
     return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t n_static, const double *static_aabb)
+{
+    return create(out, n_max, cell, 1, n_static, static_aabb);
+}
+
+extern "C" int clapgpu_bp_create_levels(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t levels, uint32_t n_static,
+                                        const double *static_aabb)
+{
+    return create(out, n_max, cell, levels, n_static, static_aabb);
+}
+
+extern "C" uint32_t clapgpu_bp_levels(const clapgpu_bp *bp) { return bp ? bp->levels : 0; }
+
+extern "C" uint32_t clapgpu_bp_cell_slot(const clapgpu_bp *bp, uint32_t level, int32_t cx, int32_t cy, int32_t cz)
+{
+    if (!bp || level >= bp->levels) return 0xffffffffu;
+    return bp->levels == 1 ? cell_slot(cx, cy, cz, bp->k.mask) : level_slot(level, cx, cy, cz, bp->k.mask);
 }
 
 extern "C" void clapgpu_bp_destroy(clapgpu_bp *bp)
@@ -115,7 +141,7 @@ __attribute__((visibility("hidden"))) unsigned long long *clapgpu_bp_contact_tic
 __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp *bp, uint32_t n, const double *aabb,
                                                                  BpGridView *v)
 {
-    if (!bp || !bp->indexed || bp->indexed_n != n || (aabb && bp->indexed_aabb != aabb)) return false;
+    if (!bp || bp->levels > 1 || !bp->indexed || bp->indexed_n != n || (aabb && bp->indexed_aabb != aabb)) return false;
     v->n = n; v->n_static = bp->n_static; v->cell = bp->cell; v->mask = bp->k.mask; v->n_large = bp->n_large;
     v->cell_range = bp->k.cell_range;
     v->recs = bp->k.recs;
@@ -131,8 +157,8 @@ __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp
 extern "C" int clapgpu_bp_index_status(void *stream, clapgpu_bp *bp, uint32_t *status)
 {
     if (!bp || !status || !bp->indexed) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    *status = 0;
-    if (!bp->indexed_n) return CLAPGPU_OK;
+    *status = bp->levels > 1 ? 4u : 0u;                                  // leveled: no index was built, queries scan every geom
+    if (!bp->indexed_n || bp->levels > 1) return CLAPGPU_OK;
     uint64_t w = 0;
     uint32_t epochs[2] = { 0, 0 };
     hipStream_t s = as_stream(stream);

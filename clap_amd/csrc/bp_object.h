@@ -1,9 +1,11 @@
-// bp_object.h -- struct clapgpu_bp and the kernel arguments made from it.  PRIVATE to the two broadphase translation
-// units: bp_create.hip makes and hands out the object, broadphase.hip runs its kernels and keeps its bookkeeping.
-// struct clapgpu_bp is written and read in those two files alone; others go through the hidden accessors of bp_grid.h.
+// bp_object.h -- struct clapgpu_bp and the kernel arguments made from it.  PRIVATE to the broadphase translation
+// units: bp_create.hip makes and hands out the object, broadphase.hip runs its kernels and keeps its bookkeeping,
+// bp_levels.hip holds the kernels of a leveled object (it sees the kernel arguments, never the object).
+// struct clapgpu_bp is written and read in the first two files alone; others go through the hidden accessors of bp_grid.h.
 #pragma once
 #include "common.h"
 #include "bp_grid.h"
+#include "bp_levels.h"
 
 namespace clapgpu {
 
@@ -42,10 +44,26 @@ struct BpK {
 // the words a bin pass works on: what k_bp_bin uses and what clapgpu_bp_prebin hands to the pre-binning body step
 __host__ __device__ __forceinline__ BinK bin_of(const BpK &k) { return BinK{ k.cell, k.mask, k.key, k.rank, k.cell_cnt, k.ctrl }; }
 
+// A leveled object's kernel arguments (bp_levels.hip): BpK with one statics CSR per level laid end to end -- level l's
+// starts are s_start[l * (buckets + 1) ..], already offset into the shared s_entries / s_recs -- and level l's large
+// statics at s_large / s_lrecs[large_start[l] .. large_start[l + 1]).  k.cell is level 0's cell.
+struct BplK {
+    BpK k;
+    uint32_t levels;
+    uint32_t large_start[CLAPGPU_BP_LEVELS_MAX + 1];
+};
+
 } // namespace clapgpu
+
+// bp_levels.hip, for clapgpu_bp_collide on a leveled object: launch 1 (bin), and launches 3 to 5 (scatter, search, emit);
+// launch 2 in between is broadphase.hip's k_bp_cells, which reads slots and knows no level
+__attribute__((visibility("hidden"))) int clapgpu_bpl_bin(hipStream_t s, const clapgpu::BplK &q);
+__attribute__((visibility("hidden"))) int clapgpu_bpl_pairs(hipStream_t s, const clapgpu::BplK &q);
 
 struct clapgpu_bp {
     uint32_t n_max, buckets, n_static, n_large, n_tiles;
+    uint32_t levels;               // 1: the one-level grid of broadphase.hip; more: bp_levels.hip's kernels
+    uint32_t large_start[CLAPGPU_BP_LEVELS_MAX + 1];
     double cell;
     void *dev;                     // one allocation
     clapgpu::BpK k;                // device pointers filled in

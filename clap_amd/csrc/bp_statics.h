@@ -76,4 +76,44 @@ __attribute__((visibility("hidden"))) inline StaticsImage bp_statics_image(uint3
     return im;
 }
 
+// A leveled object (bp_levels.h): one image per level, level l binned with the cell cell * 2^l -- a body tests the
+// registrations of its own level, whose blocks are sized for bodies of that level.
+__attribute__((visibility("hidden"))) inline std::vector<StaticsImage> bp_statics_level_images(uint32_t buckets, double cell, uint32_t levels,
+                                                                                             uint32_t n_static, const double *static_aabb)
+{
+    std::vector<StaticsImage> ims;
+    double c = cell;
+    for (uint32_t l = 0; l < levels; l++, c *= 2.0) ims.push_back(bp_statics_image(buckets, c, n_static, static_aabb));
+    return ims;
+}
+
+// ... laid end to end for one upload (bp_object.h's BplK): starts offset into the shared entries, the placeholders of
+// the single images dropped; large_start[l] .. [l + 1]: level l's part of the large list.
+__attribute__((visibility("hidden"))) inline StaticsImage bp_statics_concat(const std::vector<StaticsImage> &ims, std::vector<uint32_t> *large_start)
+{
+    StaticsImage all;
+    all.n_large = 0;
+    for (int a = 0; a < 3; a++) { all.bounds[a] = INFINITY; all.bounds[3 + a] = -INFINITY; }
+    large_start->assign(1, 0u);
+    for (const StaticsImage &im : ims) {
+        const uint32_t base = (uint32_t)all.entries.size(), n = im.start.back();
+        for (uint32_t s : im.start) all.start.push_back(base + s);
+        all.entries.insert(all.entries.end(), im.entries.begin(), im.entries.begin() + n);
+        all.recs.insert(all.recs.end(), im.recs.begin(), im.recs.begin() + n);
+        all.large.insert(all.large.end(), im.large.begin(), im.large.begin() + im.n_large);
+        all.lrecs.insert(all.lrecs.end(), im.lrecs.begin(), im.lrecs.begin() + im.n_large);
+        all.n_large += im.n_large;
+        large_start->push_back(all.n_large);
+        for (int a = 0; a < 3; a++) {
+            all.bounds[a] = fmin(all.bounds[a], im.bounds[a]);
+            all.bounds[3 + a] = fmax(all.bounds[3 + a], im.bounds[3 + a]);
+        }
+    }
+    GridRec zero;
+    memset(&zero, 0, sizeof(zero));
+    if (all.entries.empty()) { all.entries.push_back(0); all.recs.push_back(zero); }
+    if (all.large.empty()) { all.large.push_back(0); all.lrecs.push_back(zero); }
+    return all;
+}
+
 } // namespace clapgpu

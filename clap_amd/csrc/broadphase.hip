@@ -1,6 +1,7 @@
 // broadphase.hip -- the broadphase over explicit AABBs, for gfx950: dSpaceCollide2(ground, bodies) + dSpaceCollide(bodies)
 // (physics.c:751-753) as ascending candidate-pair lists, and the same grid as an index for the ray cast (rays.hip).
 // The six kernels and the entry points that launch them; the object itself is made in bp_create.hip (bp_object.h).
+// An object of more than one level (clapgpu_bp_create_levels) runs bp_levels.hip's kernels around k_bp_cells instead.
 // fp64 boxes.  ODE is an absent submodule of the reference: PARITY UNPINNED (oracle/physics2.c states what is restated).
 #include "bp_object.h"
 #include "scan_dev.h"
@@ -536,6 +537,14 @@ static BpK grid_k(const clapgpu_bp *bp, uint32_t n, const double *aabb)
     return k;
 }
 
+static BplK bpl_k(const clapgpu_bp *bp, const BpK &k)
+{
+    BplK q;
+    q.k = k; q.levels = bp->levels;
+    for (uint32_t l = 0; l <= CLAPGPU_BP_LEVELS_MAX; l++) q.large_start[l] = bp->large_start[l];
+    return q;
+}
+
 static int launch_bin(hipStream_t s, const BpK &k)
 {
     hipLaunchKernelGGL(k_bp_bin, dim3((k.n + PB - 1) / PB), dim3(PB), 0, s, k);
@@ -586,6 +595,13 @@ extern "C" int clapgpu_bp_collide(void *stream, clapgpu_bp *bp, uint32_t n, cons
     k.pairs = pairs; k.capacity = capacity; k.pair_total = pair_total;
     k.spairs = static_pairs; k.scapacity = static_capacity; k.spair_total = static_pair_total;
     if (!statics) { k.n_static = 0; k.n_large = 0; if (static_pair_total) CLAPGPU_HIP(hipMemsetAsync(static_pair_total, 0, 4, s)); }
+    if (bp->levels > 1) {                                        // bp_levels.hip's kernels around the shared k_bp_cells
+        int rc = clapgpu_bpl_bin(s, bpl_k(bp, k));
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_bp_cells, dim3((bp->buckets + BP_CELLS_BLOCK / WAVE - 1) / (BP_CELLS_BLOCK / WAVE)), dim3(BP_CELLS_BLOCK), 0, s, k);
+        CLAPGPU_LAUNCH_CHECK("k_bp_cells");
+        return clapgpu_bpl_pairs(s, bpl_k(bp, k));
+    }
     bool prebinned;
     int rc = build_grid(stream, bp, k, true, &prebinned);
     if (rc) return rc;
@@ -600,6 +616,10 @@ extern "C" int clapgpu_bp_collide(void *stream, clapgpu_bp *bp, uint32_t n, cons
 __attribute__((visibility("hidden"))) int clapgpu_bp_prebin(void *stream, clapgpu_bp *bp, uint32_t n, const double *aabb, BinK *bin)
 {
     if (n > bp->n_max) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (bp->levels > 1) {                                        // BinK bins one level: off, and no prebin recorded
+        *bin = BinK{};
+        return clapgpu_bp_invalidate(stream, bp);
+    }
     *bin = bin_of(bp->k);
     if (n == 0) return CLAPGPU_OK;
     int rc = clapgpu_bp_invalidate(stream, bp);                  // the step moves the boxes and rebins: the index is stale; a step
@@ -620,6 +640,10 @@ extern "C" int clapgpu_bp_index(void *stream, clapgpu_bp *bp, uint32_t n, const 
     if (!bp || (n && !aabb)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (n > bp->n_max) return CLAPGPU_ERR_TOO_LARGE;
     bp->indexed = false;
+    if (bp->levels > 1) {                                        // no leveled index yet: nothing is launched, queries scan
+        bp->indexed = true; bp->indexed_aabb = aabb; bp->indexed_n = n;       // (clapgpu_bp_index_status: bit 2)
+        return CLAPGPU_OK;
+    }
     hipStream_t s = as_stream(stream);
     const BpK k = grid_k(bp, n, aabb);
     CLAPGPU_HIP(hipMemsetAsync(k.ctrl + CTRL_INDEX_WORD, 0xff, INDEX_WORDS * sizeof(uint64_t), s));

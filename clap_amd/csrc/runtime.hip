@@ -9,9 +9,9 @@
 #include "lm_dev.h"
 
 #ifdef CLAPGPU_EXPERIMENT               // an A/B or sensitivity build (common.h): never loadable as the product
-#define CLAPGPU_ABI_VERSION (40u | 0x80000000u)
+#define CLAPGPU_ABI_VERSION (41u | 0x80000000u)
 #else
-#define CLAPGPU_ABI_VERSION 40u
+#define CLAPGPU_ABI_VERSION 41u
 #endif
 
 namespace clapgpu {

@@ -18,10 +18,12 @@ from .characters import CharacterMoves  # noqa: F401  (physics.CharacterMoves: t
 
 class PhysWorld:
     def __init__(self, bodies, statics=None, pair_capacity=None, device="cuda:0", static_pair_capacity=None, geom_records=True,
-                 forces=False):
+                 forces=False, bp_levels=1):
         """bodies: dict from synth.sphere_bodies() / synth.capsule_bodies(); statics: float64 [ns, 6]
         (minx,maxx,miny,maxy,minz,maxz), host array: binned once by clapgpu_bp_create.  forces: give the bodies a force
-        accumulator (clapgpu_bodies.facc, zeros or bodies["facc"]): the step consumes it, bodies_push adds to it."""
+        accumulator (clapgpu_bodies.facc, zeros or bodies["facc"]): the step consumes it, bodies_push adds to it.
+        bp_levels > 1: a multi-level broadphase grid (clapgpu_bp_create_levels) whose level-0 cell is bodies["cell"], for
+        bodies of mixed sizes: same pair lists; queries through it scan every geom."""
         self.device = dev = torch.device(device)
         self.n = n = int(bodies["n"])
         t = lambda k, dt: upload(bodies[k], dt, dev)
@@ -70,8 +72,13 @@ class PhysWorld:
             self.n_static = st.shape[0]
         self._statics_host = st
         self._bp = C.c_void_p()
-        _lib.check(_lib.lib().clapgpu_bp_create(C.byref(self._bp), n, self.cell, self.n_static,
-                                                st.ctypes.data if st is not None else None), "clapgpu_bp_create")
+        self.bp_levels = int(bp_levels)
+        st_ptr = st.ctypes.data if st is not None else None
+        if self.bp_levels > 1:
+            _lib.check(_lib.lib().clapgpu_bp_create_levels(C.byref(self._bp), n, self.cell, self.bp_levels, self.n_static, st_ptr),
+                       "clapgpu_bp_create_levels")
+        else:
+            _lib.check(_lib.lib().clapgpu_bp_create(C.byref(self._bp), n, self.cell, self.n_static, st_ptr), "clapgpu_bp_create")
         self.statics_ptr = _lib.lib().clapgpu_bp_static_aabb(self._bp)     # device copy owned by the broadphase object
         # what the methods below allocate on demand (the alloc_* methods) or keep from their last call
         self.material = self.static_material = None                        # set_materials / contacts_static, or assigned

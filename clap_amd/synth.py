@@ -465,6 +465,24 @@ def sphere_bodies(n=262_144, box=64.0, rmin=0.1, rmax=0.5, seed=4, entity_base=0
                 body_entity=(entity_base + np.arange(n)).astype(np.int32), cell=2.0 * rmax)
 
 
+def mixed_bodies(n=262_144, box=64.0, cell0=0.25, seed=4, entity_base=0, resting_frac=0.0):
+    """Sphere bodies of mixed sizes, for a multi-level broadphase (PhysWorld(bp_levels=...)): four size classes of radius
+    about 0.05 / 0.2 / 0.8 / 3.2 (each times U(0.5, 1.25)) with shares of about 70 / 20 / 9 / 1 %, and about a tenth of
+    the bodies given a diameter of exactly cell0 * 2^k, the cell of the level they then live on (their positions are multiples
+    of 2^-16, so that with cell0 a power of two their boxes have that edge exactly).  The dict of
+    sphere_bodies with cell = cell0: the level-0 cell, NOT the largest edge (max(2 * radius) is a one-level world's cell)."""
+    rng = _rng(seed)
+    cls = np.searchsorted(np.cumsum([0.70, 0.20, 0.09]), rng.uniform(0, 1, n))
+    radius = np.asarray([0.05, 0.2, 0.8, 3.2])[cls] * rng.uniform(0.5, 1.25, n)
+    exact = rng.uniform(0, 1, n) < 0.1
+    k = np.maximum(np.ceil(np.log2(2.0 * radius / cell0)), 0.0)
+    radius[exact] = (0.5 * cell0 * 2.0 ** k)[exact]
+    d = sphere_bodies(n, box=box, seed=seed + 1, entity_base=entity_base, resting_frac=resting_frac)
+    d["pos"][exact] = np.round(d["pos"][exact] * 65536.0) / 65536.0       # pos +- radius without rounding (cell0 a power of two)
+    d.update(radius=radius, yoffset=radius.copy(), mass=4.0 / 3.0 * math.pi * radius ** 3, cell=float(cell0))
+    return d
+
+
 def capsule_bodies(n=262_144, box=64.0, seed=4, sphere_frac=0.3, entity_base=0, resting_frac=0.0):
     """C4 with the reference's body geoms: every body goes through phys_geom_capsule_new (physics.c:814-873) on a
     random entity AABB -- upright capsules, "puppy" capsules along Z, and spheres where the capsule length comes

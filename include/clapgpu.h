@@ -868,9 +868,26 @@ int clapgpu_contacts_sphere_box(void *stream, const clapgpu_bodies *b, uint32_t 
  *                       *_total = number found (device uint32), at most `capacity` written (when a total
  *                       exceeds its capacity the written part is incomplete).  static outputs may be NULL.
  *   clapgpu_bp_status   host sync; bit 0: a body AABB edge exceeded `cell` (pairs may be missing)
+ *
+ * Bodies of mixed sizes (ABI 41): clapgpu_bp_create_levels makes a multi-level grid, as ODE's hash space is one.  Level l
+ * (0 .. levels - 1) has the cell size cell * 2^l; a body lives on the lowest level whose cell is not smaller than its
+ * largest AABB edge (an edge equal to cell * 2^l is level l; a NaN edge fits level 0) and is tested against its own and
+ * every coarser level.  An edge above the top level's cell sets status bit 0 with the meaning above.  Every call that
+ * takes a clapgpu_bp takes either kind, and the outputs of clapgpu_bp_collide keep their contract word for word.
+ * levels == 1 is the object of clapgpu_bp_create (which stays the call it is); levels == 0 or above
+ * CLAPGPU_BP_LEVELS_MAX, or levels > 1 with n_max > 2^28: CLAPGPU_ERR_INVALID_ARGUMENTS.  A leveled object is never
+ * pre-binned (clapgpu_bodies_step_prebin runs the plain step) and holds no index: see clapgpu_bp_index.
+ *   clapgpu_bp_levels     the levels of the object (0 for NULL)
+ *   clapgpu_bp_cell_slot  host only, no device work: the cell slot of cell (cx, cy, cz) of `level` in this object (for
+ *                         tests and tools); 0xffffffff for a level the object does not have
  */
+#define CLAPGPU_BP_LEVELS_MAX 16
 typedef struct clapgpu_bp clapgpu_bp;
 int  clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t n_static, const double *static_aabb_host);
+int      clapgpu_bp_create_levels(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t levels,
+                                  uint32_t n_static, const double *static_aabb_host);
+uint32_t clapgpu_bp_levels(const clapgpu_bp *bp);
+uint32_t clapgpu_bp_cell_slot(const clapgpu_bp *bp, uint32_t level, int32_t cx, int32_t cy, int32_t cz);
 void clapgpu_bp_destroy(clapgpu_bp *bp);
 int  clapgpu_bp_collide(void *stream, clapgpu_bp *bp, uint32_t n, const double *aabb,
                         uint32_t *pairs, uint32_t capacity, uint32_t *pair_total,
@@ -950,7 +967,9 @@ int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_g
  * index whose count has moved on scans every geom instead (same results, brute-force time) -- index after replays.
  * clapgpu_bp_index_status: host sync; bit 0: an indexed box's edge exceeds `cell` (this index only, unlike the sticky
  * bit 0 of clapgpu_bp_status); bit 1: the boxes were binned again since the index (a replayed collide or prebinning
- * step).  Either way rays through this index scan every geom.  CLAPGPU_ERR_INVALID_ARGUMENTS when not indexed.
+ * step); bit 2 (value 4): the object is leveled (clapgpu_bp_create_levels with levels > 1): clapgpu_bp_index launched
+ * nothing and every query through it scans every geom, as with bp == NULL.  In all three cases rays through this index
+ * scan every geom.  CLAPGPU_ERR_INVALID_ARGUMENTS when not indexed.
  *
  * clapgpu_ray_cast: ray k = ray[k][8] (start xyz, direction xyz of any length, normalised as dGeomRaySet does, length,
  * pad) against every body (a geom of `bodies`) and static (`statics`), as dCreateRay + dGeomRaySetClosestHit +
