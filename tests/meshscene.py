@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from clap_amd import _lib, synth
+from guards import Guards
 import meshcontactref as mc
 import trimeshref as tr
 
@@ -31,11 +32,12 @@ def same_bits(a, b):
 
 def guarded_scratch(need, dev, guard=4096):
     """(scratch, tail): a zeroed scratch tensor of exactly `need` bytes, 256-byte aligned, followed in the same allocation
-    by `guard` bytes of 0xA5 that a call given the scratch must leave alone"""
-    buf = torch.zeros(need + guard, dtype=torch.uint8, device=dev)
-    buf[need:] = 0xA5
-    assert need > 0 and buf.data_ptr() % 256 == 0
-    return buf[:need], buf[need:]
+    by `guard` bytes of 0xA5 that a call given the scratch must leave alone (guards.Guards.scratch)"""
+    assert need > 0
+    g = Guards(dev, band=guard)
+    scratch = g.scratch(need)
+    assert scratch.data_ptr() % 256 == 0
+    return scratch, g.bands()[1]
 
 
 def unit(v):
