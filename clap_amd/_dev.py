@@ -17,6 +17,24 @@ def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _new(shape, dtype, device, fill, contents):
+    """The one place a mirror's array on `device` is made: a copy of the host array `contents` when that is given (shape
+    and dtype are then its own), otherwise `shape` x `dtype` with every element `fill`, uninitialised for fill None.
+    device_array and upload look this name up when they are called, so the test suite's guard bands hook it here."""
+    if contents is not None:
+        return torch.from_numpy(contents).to(device)
+    if fill is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if fill == 0:
+        return torch.zeros(shape, dtype=dtype, device=device)
+    return torch.full(shape, fill, dtype=dtype, device=device)
+
+
+def device_array(shape, dtype, device, fill=0):
+    """A new array of `shape` x `dtype` on `device`, every element `fill`; fill=None leaves it uninitialised."""
+    return _new((int(shape),) if isinstance(shape, (int, np.integer)) else tuple(shape), dtype, device, fill, None)
+
+
 def upload(a, dtype, device, shape=None):
     """Contiguous copy of host array `a` on `device`, as `dtype` and, when given, reshaped to `shape`; uint32 / uint16
     arrive as the signed type of the same width with the same bits.  A tensor is taken as it is, made contiguous."""
@@ -25,4 +43,4 @@ def upload(a, dtype, device, shape=None):
     a = np.ascontiguousarray(a, dtype)
     if shape is not None:
         a = a.reshape(shape)
-    return torch.from_numpy(a.view(_SIGNED.get(a.dtype, a.dtype))).to(device)
+    return _new(None, None, device, None, a.view(_SIGNED.get(a.dtype, a.dtype)))

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._dev import ptr as _ptr, stream as _stream, upload
+from ._dev import device_array, ptr as _ptr, stream as _stream, upload
 
 
 def joint_depths(parent):
@@ -94,7 +94,7 @@ class SkinnedModel:
         max_keys = max(max_keys, 1)                       # animations without a single key: every path keeps its value
         if J <= 256 and len(anims):
             nbytes = int(_lib.lib().clapgpu_animations_packed_bytes(len(anims), max_keys, J))
-            self.packed = torch.zeros((nbytes + 15) // 16 * 4, dtype=torch.float32, device=dev)
+            self.packed = device_array((nbytes + 15) // 16 * 4, torch.float32, dev)
             layout = C.c_uint32(0)
             _lib.check(_lib.lib().clapgpu_animations_pack(_stream(), C.byref(self.anim_desc), J, max_keys, _ptr(self.packed),
                                                           C.byref(layout)), "clapgpu_animations_pack")
@@ -122,10 +122,10 @@ class CharacterBatch:
         self.trs = upload(trs0, np.float32, dev)
         self.entity_mx = entity_mx if torch.is_tensor(entity_mx) else upload(entity_mx, np.float32, dev)
         self.entity_index = None if entity_index is None else upload(entity_index, np.uint32, dev)
-        self.anim = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.frame_time = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.joint_transforms = torch.zeros((n, J, 16), dtype=torch.float32, device=dev)
-        self.joint_pos = torch.zeros((n, J, 4), dtype=torch.float32, device=dev)
+        self.anim = device_array(n, torch.int32, dev)
+        self.frame_time = device_array(n, torch.float32, dev)
+        self.joint_transforms = device_array((n, J, 16), torch.float32, dev)
+        self.joint_pos = device_array((n, J, 4), torch.float32, dev)
         # host animation state of animated_update(): start time, speed, current animation
         self.ani_time = np.zeros(n, np.float64)
         self.speed = np.ones(n, np.float64)
@@ -147,8 +147,8 @@ class CharacterBatch:
             self.out_first = upload(of[:-1], np.uint32, dev)
             total = int(of[-1])
             self.n_out_verts = total
-            self.out_position = torch.zeros((total, 3), dtype=torch.float32, device=dev)
-            self.out_normal = torch.zeros((total, 3), dtype=torch.float32, device=dev)
+            self.out_position = device_array((total, 3), torch.float32, dev)
+            self.out_normal = device_array((total, 3), torch.float32, dev)
             m = model.mesh
             self._skin_desc = _lib.SkinBatch(n, J, _ptr(self.vert_first), _ptr(self.vert_count), _ptr(self.out_first),
                                              _ptr(m["position"]), _ptr(m["normal"]), _ptr(m["joints"]),
@@ -188,10 +188,10 @@ class CharacterBatch:
             self.speed[:] = speed
         self.repeat_host = np.ones(n, np.uint8) if repeat is None else np.ascontiguousarray(repeat, np.uint8)
         self.ani_time_dev, self.speed_dev = upload(self.ani_time, np.float64, dev), upload(self.speed, np.float32, dev)
-        self.repeat_dev = torch.from_numpy(self.repeat_host).to(dev)
-        self.ended = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
-        self.now_dev = torch.zeros(1, dtype=torch.float64, device=dev)
-        self.time_end_dev = torch.from_numpy(np.asarray(self.model.time_end, np.float32)).to(dev)
+        self.repeat_dev = upload(self.repeat_host, np.uint8, dev)
+        self.ended = device_array(max(n, 1), torch.uint8, dev)
+        self.now_dev = device_array(1, torch.float64, dev)
+        self.time_end_dev = upload(self.model.time_end, np.float32, dev)
         self._clock = _lib.AnimClock(n, len(self.model.time_end), _ptr(self.anim), _ptr(self.time_end_dev),
                                      _ptr(self.ani_time_dev), _ptr(self.speed_dev), _ptr(self.repeat_dev),
                                      _ptr(self.frame_time), _ptr(self.ended))
@@ -228,7 +228,7 @@ class CharacterBatch:
     def set_skin_w(self, on=True):
         """Also write total_local_pos.w per vertex (clapgpu_skin_batch.out_w; model.vert:36-38,44)."""
         if on and self.out_w is None:
-            self.out_w = torch.zeros(self.n_out_verts, dtype=torch.float32, device=self.device)
+            self.out_w = device_array(self.n_out_verts, torch.float32, self.device)
         self._skin_desc.out_w = _ptr(self.out_w) if on else None
 
     def skin(self):

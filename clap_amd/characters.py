@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._dev import ptr as _ptr, stream as _stream, upload
+from ._dev import device_array, ptr as _ptr, stream as _stream, upload
 
 
 class CharacterFeed:
@@ -28,7 +28,7 @@ class CharacterFeed:
         self.hist_head = t(feed["hist_head"], np.uint32)
         self.hist_wrapped = t(feed["hist_wrapped"], np.uint8)
         self.airborne = t(feed["airborne"], np.uint8)
-        self.moved = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        self.moved = device_array(max(n, 1), torch.uint8, dev)
         self.limbo_height = float(feed["limbo_height"])
         self._desc = _lib.Characters(n, self.limbo_height, self.entity.data_ptr(), self.body.data_ptr(),
                                      self.hist_pos.data_ptr(), self.hist_head.data_ptr(),
@@ -83,7 +83,7 @@ class CharacterMoves:
             self.yaw_quat = out((4,), torch.float32)
             self.yaw_quat[:, 3] = 1.0
         need = _lib.characters_move_scratch_bytes(world.n, n) if n else 0
-        self.scratch = torch.zeros(max(need, 256), dtype=torch.uint8, device=dev)
+        self.scratch = device_array(max(need, 256), torch.uint8, dev)
         self._desc = _lib.CharactersMove(n, *[_ptr(getattr(self, k)) for k in
                                               ("body", "ray_off", "motion", "state", "jump", "jump_params", "velocity",
                                                "normal", "airborne", "request", "applied", "collision", "first_frac",
@@ -100,9 +100,8 @@ class CharacterMoves:
             a = np.asarray(a)
             if dt == np.uint8 and a.dtype != np.uint8:
                 a = a != 0 if k != "state" else a
-            a = np.ascontiguousarray(a, dt).reshape((-1, width) if width else (-1,))
             if self.n:
-                getattr(self, k)[:self.n].copy_(torch.from_numpy(a).to(self.device))
+                getattr(self, k)[:self.n].copy_(upload(a, dt, self.device, (-1, width) if width else (-1,)))
 
     def outputs(self):
         """dict of device tensors: velocity, normal, airborne (in / out), request, applied, collision, first_frac,

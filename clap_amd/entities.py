@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from . import synth
-from ._dev import ptr as _ptr, stream as _stream, upload
+from ._dev import device_array, ptr as _ptr, stream as _stream, upload
 
 
 def view_calc_frustum(cam):
@@ -56,7 +56,7 @@ class EntityBatch:
             if int(trs[-1]) * 64 != self.n:
                 raise ValueError("tile_row_start does not cover the scene")
             self.n_tiles = len(trs) - 1
-            self.tile_row_start = torch.from_numpy(trs.view(np.int32)).to(dev)
+            self.tile_row_start = upload(trs, np.uint32, dev)                  # its bits, as int32
             self.level_start, self.n_levels = None, 0
         else:               # level-major layout (synth.pad_levels): one launch per level
             ls = np.asarray(scene["level_start"], np.uint32)
@@ -66,23 +66,20 @@ class EntityBatch:
             self.n_levels = len(ls) - 1
             self._ls_ptr = self.level_start.ctypes.data_as(C.POINTER(C.c_uint32))
         for k in self.IN_KEYS:
-            a = scene[k]
-            if a.dtype == np.uint32:
-                a = a.view(np.int32)
-            setattr(self, k, torch.from_numpy(np.ascontiguousarray(a)).to(dev))
-        self.model_table = torch.from_numpy(synth.model_table(scene)).to(dev)
+            setattr(self, k, upload(scene[k], scene[k].dtype, dev))            # uint32 as int32 bits
+        self.model_table = upload(synth.model_table(scene), np.float32, dev)
         n = self.n
-        self.mx = torch.zeros((n, 16), dtype=torch.float32, device=dev)
-        self.inv_mx = torch.zeros((n, 16), dtype=torch.float32, device=dev)
-        self.aabb = torch.zeros((n, 6), dtype=torch.float32, device=dev)
-        self.center = torch.zeros((n, 3), dtype=torch.float32, device=dev)
-        self.vis_mask = torch.zeros(((n + 63) // 64 or 1,), dtype=torch.int64, device=dev)
+        self.mx = device_array((n, 16), torch.float32, dev)
+        self.inv_mx = device_array((n, 16), torch.float32, dev)
+        self.aabb = device_array((n, 6), torch.float32, dev)
+        self.center = device_array((n, 3), torch.float32, dev)
+        self.vis_mask = device_array(((n + 63) // 64 or 1,), torch.int64, dev)
         n_rows = (n + 63) // 64
-        self.vis_row_pop = torch.zeros(((n_rows + 15) // 16 * 16 or 16,), dtype=torch.uint8, device=dev)
-        self.visible = torch.zeros((max(n, 1),), dtype=torch.int32, device=dev)
-        self.visible_count = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.vis_row_pop = device_array(((n_rows + 15) // 16 * 16 or 16,), torch.uint8, dev)
+        self.visible = device_array((max(n, 1),), torch.int32, dev)
+        self.visible_count = device_array((1,), torch.int32, dev)
         nscratch = _lib.lib().clapgpu_visible_scratch_bytes(n)
-        self.scratch = torch.zeros((nscratch // 4 or 1,), dtype=torch.int32, device=dev)
+        self.scratch = device_array((nscratch // 4 or 1,), torch.int32, dev)
         self._desc = _lib.Entities(
             n=n, n_models=self.model_table.shape[0],
             pos_scale=self.pos_scale.data_ptr(), rot=self.rot.data_ptr(), parent=self.parent.data_ptr(),
@@ -110,8 +107,8 @@ class EntityBatch:
         self.view_masks, self.view_row_pops = [], []
         for v, fr in enumerate(frusta[:_lib.EXTRA_VIEWS_MAX]):
             C.memmove(C.byref(self._views.frustum[v]), C.byref(fr), C.sizeof(_lib.Frustum))
-            m = torch.zeros((n_rows or 1,), dtype=torch.int64, device=dev)
-            p = torch.zeros(((n_rows + 15) // 16 * 16 or 16,), dtype=torch.uint8, device=dev)
+            m = device_array((n_rows or 1,), torch.int64, dev)
+            p = device_array(((n_rows + 15) // 16 * 16 or 16,), torch.uint8, dev)
             self.view_masks.append(m); self.view_row_pops.append(p)
             self._views.vis_mask[v] = m.data_ptr(); self._views.vis_row_pop[v] = p.data_ptr()
         self._desc.views = C.pointer(self._views) if frusta else None
@@ -128,21 +125,21 @@ class EntityBatch:
         bind_pool: mat4 array.  Flags the entities CLAPGPU_E_JOINT_ATTACHED."""
         a = np.ascontiguousarray(attach)
         assert np.all(np.diff(a["entity"].astype(np.int64)) > 0), "attach table must be sorted by entity"
-        self._attach = torch.from_numpy(a.view(np.uint8).reshape(-1, 16).copy()).to(self.device)
+        self._attach = upload(a.view(np.uint8), np.uint8, self.device, (-1, 16))
         self._jt_pool = jt_pool if torch.is_tensor(jt_pool) else upload(jt_pool, np.float32, self.device)
         self._bind_pool = upload(bind_pool, np.float32, self.device)
-        idx = torch.from_numpy(a["entity"].astype(np.int64)).to(self.device)
+        idx = upload(a["entity"], np.int64, self.device)
         self.flags[idx] |= np.int32(_lib.E_JOINT_ATTACHED)
         self._desc.n_attach = a.shape[0]
         self._desc.attach = self._attach.data_ptr()
         self._desc.jt_pool = self._jt_pool.data_ptr()
         self._desc.bind_pool = self._bind_pool.data_ptr()
-        self._attach_local = torch.zeros((a.shape[0], 16), dtype=torch.float32, device=self.device)
+        self._attach_local = device_array((a.shape[0], 16), torch.float32, self.device)
         self._desc.attach_local = self._attach_local.data_ptr()
 
     def set_bv_query(self, cam_pos, ctl_pos=None, ctl_entity=0):
         """Ask the next updates for default_update's camera bounding-volume pick."""
-        self.bv_result = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.bv_result = device_array(1, torch.int64, self.device)
         q = _lib.BvQuery()
         q.cam_pos[:] = [float(v) for v in cam_pos]
         q.has_ctl = 0 if ctl_pos is None else 1
@@ -198,8 +195,8 @@ class EntityBatch:
 
     def alloc_lod(self):
         if not hasattr(self, "cur_lod"):
-            self.cur_lod = torch.zeros(max(self.n, 1), dtype=torch.int32, device=self.device)
-            self.draw_lod = torch.zeros(max(self.n, 1), dtype=torch.int32, device=self.device)
+            self.cur_lod = device_array(max(self.n, 1), torch.int32, self.device)
+            self.draw_lod = device_array(max(self.n, 1), torch.int32, self.device)
             self.force_lod = None
 
     def select_lod(self, cam_pos, force_lod=None):
@@ -234,7 +231,7 @@ class EntityBatch:
     # ---- host access ----------------------------------------------------------------
     def set_transforms(self, idx, pos_scale, rot):
         """entity3d_position/rotate/scale on a batch of entities: writes TRS, sets dirty."""
-        idx_t = torch.as_tensor(np.asarray(idx, np.int64), device=self.device)
+        idx_t = upload(idx, np.int64, self.device)
         self.pos_scale[idx_t] = upload(pos_scale, np.float32, self.device)
         self.rot[idx_t] = upload(rot, np.float32, self.device)
         self.flags[idx_t] |= np.int32(_lib.E_DIRTY)

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._dev import ptr as _ptr, stream as _stream, upload  # noqa: F401
+from ._dev import device_array, ptr as _ptr, stream as _stream, upload  # noqa: F401
 
 TILE_WIDTH = 64          # shader_constants.h:16
 
@@ -39,11 +39,8 @@ class LightSet:
         self.active = np.zeros(M, np.uint32)
         self.nr_lights = 0
         self.width, self.height, self.cell = int(width), int(height), int(cell)
-        self._d = dict(pos=torch.zeros((M, 3), dtype=torch.float32, device=dev),
-                       color=torch.zeros((M, 3), dtype=torch.float32, device=dev),
-                       attenuation=torch.zeros((M, 3), dtype=torch.float32, device=dev),
-                       is_dir=torch.zeros(M, dtype=torch.int32, device=dev),
-                       active=torch.zeros(M, dtype=torch.int32, device=dev))
+        self._d = {k: device_array((M, 3), torch.float32, dev) for k in ("pos", "color", "attenuation")}
+        self._d.update({k: device_array(M, torch.int32, dev) for k in ("is_dir", "active")})
         self._dirty = set(self._d)
         self.tiles = None
         self._carriers = None
@@ -142,7 +139,7 @@ class LightSet:
         if not tw or not th:
             return None
         if self.tiles is None or self.tiles.shape[:2] != (th, tw):
-            self.tiles = torch.zeros((th, tw, 4), dtype=torch.int32, device=self.device)
+            self.tiles = device_array((th, tw, 4), torch.int32, self.device)
         return self.tiles
 
     def grid_compute(self, view_mx, proj_mx):

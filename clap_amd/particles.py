@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from . import synth
-from ._dev import ptr as _ptr, stream as _stream, upload  # noqa: F401
+from ._dev import device_array, ptr as _ptr, stream as _stream, upload  # noqa: F401
 
 
 class ParticleBatch:
@@ -23,19 +23,18 @@ class ParticleBatch:
         self.n_real = int(ps["n_real"])
         self.sys_host = np.ascontiguousarray(ps["sys"]).copy()
         self.n_sys = self.sys_host.shape[0]
-        self.sys = torch.from_numpy(self.sys_host.view(np.uint8).reshape(self.n_sys, 64)).to(dev)
+        self.sys = upload(self.sys_host.view(np.uint8), np.uint8, dev, (self.n_sys, 64))
         self.row_sys = upload(ps["row_sys"], np.uint32, dev)
         self.pos, self.vel = upload(pos, np.float32, dev), upload(vel, np.float32, dev)
-        self.rng_state = torch.tensor([rng_state, rng_state], dtype=torch.int64, device=dev)
-        self.billboard_mx = torch.zeros((self.n_sys, 16), dtype=torch.float32, device=dev)
+        self.rng_state = upload([rng_state, rng_state], np.int64, dev)
+        self.billboard_mx = device_array((self.n_sys, 16), torch.float32, dev)
         rows = n // 64
-        self.respawn_mask = torch.zeros((max(rows, 1),), dtype=torch.int64, device=dev)
-        self.respawn_row_pop = torch.zeros(((rows + 15) // 16 * 16 or 16,), dtype=torch.uint8, device=dev)
-        self.respawn_list = torch.zeros((max(n, 1),), dtype=torch.int32, device=dev)
-        self.respawn_count = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self.scratch = torch.zeros((_lib.lib().clapgpu_visible_scratch_bytes(n) // 4 or 1,), dtype=torch.int32,
-                                   device=dev)
-        self.respawn_groups = torch.zeros((132,), dtype=torch.int32, device=dev)    # CLAPGPU_RESPAWN_GROUP_WORDS
+        self.respawn_mask = device_array((max(rows, 1),), torch.int64, dev)
+        self.respawn_row_pop = device_array(((rows + 15) // 16 * 16 or 16,), torch.uint8, dev)
+        self.respawn_list = device_array((max(n, 1),), torch.int32, dev)
+        self.respawn_count = device_array((1,), torch.int32, dev)
+        self.scratch = device_array((_lib.lib().clapgpu_visible_scratch_bytes(n) // 4 or 1,), torch.int32, dev)
+        self.respawn_groups = device_array((132,), torch.int32, dev)    # CLAPGPU_RESPAWN_GROUP_WORDS
         self._desc = _lib.Particles(
             n=n, n_sys=self.n_sys, sys=self.sys.data_ptr(), row_sys=self.row_sys.data_ptr(),
             pos=self.pos.data_ptr(), vel=self.vel.data_ptr(), rng_state=self.rng_state.data_ptr(),
@@ -65,7 +64,7 @@ class ParticleBatch:
         old = self.sys_host["center"][s].copy()
         delta = center - old
         if attached and float(np.dot(delta, delta)) != 0.0:
-            self.pos_array(s).add_(torch.from_numpy(delta).to(self.device))
+            self.pos_array(s).add_(upload(delta, np.float32, self.device))
         self.sys_host["center"][s] = center
         self.sys[s].copy_(torch.from_numpy(self.sys_host[s:s + 1].view(np.uint8).reshape(64)))
 

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._dev import ptr as _ptr, stream as _stream, upload
+from ._dev import device_array, ptr as _ptr, stream as _stream, upload
 from .characters import CharacterMoves  # noqa: F401  (physics.CharacterMoves: the name callers know it by)
 
 
@@ -61,10 +61,10 @@ class PhysWorld:
             self.enable_forces(bodies.get("facc"))
         self.capacity = int(pair_capacity if pair_capacity is not None else max(8 * n, 1024))
         self.static_capacity = int(static_pair_capacity if static_pair_capacity is not None else self.capacity)
-        self.pairs = torch.zeros((self.capacity, 2), dtype=torch.int32, device=dev)
-        self.pair_total = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.static_pairs = torch.zeros((self.static_capacity, 2), dtype=torch.int32, device=dev)
-        self.static_pair_total = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.pairs = device_array((self.capacity, 2), torch.int32, dev)
+        self.pair_total = device_array(1, torch.int32, dev)
+        self.static_pairs = device_array((self.static_capacity, 2), torch.int32, dev)
+        self.static_pair_total = device_array(1, torch.int32, dev)
         self.n_static = 0
         st = None
         if statics is not None and len(statics):
@@ -120,17 +120,14 @@ class PhysWorld:
     def _out(self, n, tail_shape, dtype, fill=0):
         """A device array of n rows of tail_shape, every element `fill`; one row when n is 0, so that its address is
         never null (callers hand out [:n])."""
-        shape = (max(n, 1), *tail_shape)
-        if fill == 0:
-            return torch.zeros(shape, dtype=dtype, device=self.device)
-        return torch.full(shape, fill, dtype=dtype, device=self.device)
+        return device_array((max(n, 1), *tail_shape), dtype, self.device, fill)
 
     def _grown(self, name, need):
         """The byte scratch kept in attribute `name`, allocated anew (zeroed, at least 256 bytes) only when it is missing
         or smaller than `need`."""
         have = vars(self)[name]
         if have is None or have.numel() < need:
-            have = torch.zeros(max(need, 256), dtype=torch.uint8, device=self.device)
+            have = device_array(max(need, 256), torch.uint8, self.device)
             setattr(self, name, have)
         return have
 
@@ -185,18 +182,18 @@ class PhysWorld:
 
     def alloc_contacts(self):
         if self.contact2_buf is None:
-            self.contact2_buf = torch.zeros((self.capacity, 160), dtype=torch.uint8, device=self.device)
-            self.contact2_total = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self.static_contact2_buf = torch.zeros((self.static_capacity if self.n_static else 1, 160), dtype=torch.uint8,
-                                                   device=self.device)
-            self.static_contact2_total = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.contact2_buf = device_array((self.capacity, 160), torch.uint8, self.device)
+            self.contact2_total = device_array(1, torch.int32, self.device)
+            self.static_contact2_buf = device_array((self.static_capacity if self.n_static else 1, 160), torch.uint8,
+                                                    self.device)
+            self.static_contact2_total = device_array(1, torch.int32, self.device)
 
     def alloc_islands(self):
         """The island pass's scratch and outputs (island [n], island_woken [1])."""
         have = self.island_scratch
         if self._grown("island_scratch", _lib.bodies_islands_scratch_bytes(self.n)) is not have:
             self.island = self._out(self.n, (), torch.int32)
-            self.island_woken = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.island_woken = device_array(1, torch.int32, self.device)
 
     def upload_links(self, link_body, link_entity):
         """Device copies of a (body, entity) link table, uploaded once per table."""
@@ -363,10 +360,10 @@ class PhysWorld:
             self.solve_scratch = None                  # another capacity: all of it anew, zeroed
             self._grown("solve_scratch", _lib.bodies_solve_scratch_bytes(self.n, cap))
             self.row_lambda, self.row_key = self._out(cap, (), torch.float64), self._out(cap, (), torch.int64)
-            self.rows_total = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self.solve_status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.rows_total = device_array(1, torch.int32, self.device)
+            self.solve_status = device_array(1, torch.int32, self.device)
             self.row_level = self._out(cap, (), torch.int32)
-            self.wide_total = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.wide_total = device_array(1, torch.int32, self.device)
         if self.solver is None:
             self.solver = _lib.Solver()
             _lib.lib().clapgpu_solver_defaults(C.byref(self.solver))
@@ -411,9 +408,9 @@ class PhysWorld:
             dev = self.device
             self.mesh_contact_capacity = cap
             self.mesh_contact_buf, self.mesh_ref = self._out(cap, (160,), torch.uint8), self._out(cap, (2,), torch.int32)
-            self.mesh_contact_total = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.mesh_capped = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.mesh_scratch = torch.zeros(_lib.mesh_contact_scratch(self.static_capacity), dtype=torch.int32, device=dev)
+            self.mesh_contact_total = device_array(1, torch.int32, dev)
+            self.mesh_capped = device_array(1, torch.int32, dev)
+            self.mesh_scratch = device_array(_lib.mesh_contact_scratch(self.static_capacity), torch.int32, dev)
 
     def contacts_meshes(self, set_joint_flags=True, capacity=None):
         """near_callback for the (body, static) pairs of the last broadphase() whose static owns a mesh of
@@ -503,7 +500,7 @@ class PhysWorld:
         nr = start.shape[0]
         ray = np.zeros((max(nr, 1), 8))
         ray[:nr, 0:3], ray[:nr, 3:6], ray[:nr, 6] = start, dir, np.broadcast_to(np.asarray(length, np.float64), (nr,))
-        ray_d = torch.from_numpy(ray).to(dev)
+        ray_d = upload(ray, np.float64, dev)
         skip_d = None if skip is None else upload(skip, np.int32, dev)
         nan = float("nan")
         dist, contact = self._out(nr, (), torch.float64, nan), self._out(nr, (6,), torch.float64, nan)
@@ -556,8 +553,8 @@ class PhysWorld:
         """near_callback on the body x body candidate pairs of the last broadphase(): one contact record
         per pair (oracle.binding.CONTACT_DTYPE layout = clapgpu_contact) + the number of touching pairs."""
         if self.contact_buf is None:
-            self.contact_buf = torch.zeros((self.capacity, 104), dtype=torch.uint8, device=self.device)
-            self.contact_total = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.contact_buf = device_array((self.capacity, 104), torch.uint8, self.device)
+            self.contact_total = device_array(1, torch.int32, self.device)
         _lib.check(_lib.lib().clapgpu_contacts_spheres(_stream(), C.byref(self._desc), _ptr(self.pairs),
                                                        _ptr(self.pair_total), self.capacity, _ptr(self.material),
                                                        _ptr(self.contact_buf), _ptr(self.contact_total)),
@@ -567,8 +564,8 @@ class PhysWorld:
         """near_callback on the (body, static box) candidate pairs of the last broadphase(): ODE's
         dCollideSphereBox + phys_contact_surface, one record per pair."""
         if self.static_contact_buf is None:
-            self.static_contact_buf = torch.zeros((self.static_capacity, 104), dtype=torch.uint8, device=self.device)
-            self.static_contact_total = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.static_contact_buf = device_array((self.static_capacity, 104), torch.uint8, self.device)
+            self.static_contact_total = device_array(1, torch.int32, self.device)
         if static_material is not None:
             self.static_material = upload(static_material, np.float64, self.device)
         _lib.check(_lib.lib().clapgpu_contacts_sphere_box(_stream(), C.byref(self._desc), self.n_static,

@@ -10,6 +10,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from ._dev import device_array, upload
+
 
 def shard_tile_ranges(rows_per_tile, world):
     """Split tiles into `world` contiguous ranges of (nearly) equal row count (clapgpu_shard_tile_range, the C
@@ -60,13 +62,13 @@ def allgather_visible(visible, count, world, counts_buf=None, gather_buf=None, p
     gathered[r, :counts[r]].  One small and one payload allgather; the payload is padded to the
     largest count (RCCL has no allgatherv), rounded up to `pad_to`."""
     if counts_buf is None:
-        counts_buf = torch.empty(world, dtype=count.dtype, device=count.device)
+        counts_buf = device_array(world, count.dtype, count.device, fill=None)
     dist.all_gather_into_tensor(counts_buf, count, group=group)
     cap = int(counts_buf.max().item())
     cap = max((cap + pad_to - 1) // pad_to * pad_to, pad_to)
     cap = min(cap, visible.shape[0])
     if gather_buf is None or gather_buf.numel() < world * cap:
-        gather_buf = torch.empty(world * cap, dtype=visible.dtype, device=visible.device)
+        gather_buf = device_array(world * cap, visible.dtype, visible.device, fill=None)
     out = gather_buf[:world * cap]
     dist.all_gather_into_tensor(out, visible[:cap].contiguous(), group=group)
     return counts_buf, out.view(world, cap)
@@ -81,7 +83,7 @@ def allgather_visible_mask(vis_mask, world, out=None, group=None):
     global id list."""
     n_words = vis_mask.numel()
     if out is None:
-        out = torch.empty(world * n_words, dtype=vis_mask.dtype, device=vis_mask.device)
+        out = device_array(world * n_words, vis_mask.dtype, vis_mask.device, fill=None)
     dist.all_gather_into_tensor(out[:world * n_words], vis_mask, group=group)
     return out
 
@@ -108,7 +110,7 @@ class VisibleExchange:
         self.n_pad = batch.n
         # shards need not be equal (clapgpu_shard_tile_range cuts whole tiles; a rank may be empty): every rank's padded
         # size, its first scene-global id (ascending ranges in rank order) and the common capacity the collective carries
-        sizes = torch.zeros(world, dtype=torch.int64, device=device)
+        sizes = device_array(world, torch.int64, device)
         sizes[rank] = self.n_pad
         dist.all_reduce(sizes)
         self.n_pad_all = np.ascontiguousarray(sizes.cpu().numpy(), np.uint32)
@@ -120,15 +122,16 @@ class VisibleExchange:
         own = batch.vis_mask.numel()
 
         def mask_buf():                                      # cap_pad / 64 words, zero beyond this rank's own
-            return torch.zeros(n_words, dtype=batch.vis_mask.dtype, device=device)
+            return device_array(n_words, batch.vis_mask.dtype, device)
         self.masks = [mask_buf(), mask_buf()]
         self.masks[0][:own].copy_(batch.vis_mask)
-        self.pops = [batch.vis_row_pop, torch.zeros_like(batch.vis_row_pop)]
-        self.g_mask = [torch.zeros(world * n_words, dtype=torch.int64, device=device) for _ in range(2)]
-        self.g_vis = [torch.zeros(world * self.cap_pad, dtype=torch.int32, device=device) for _ in range(2)]
-        self.g_cnt = [torch.zeros(1, dtype=torch.int32, device=device) for _ in range(2)]
+        pop = batch.vis_row_pop
+        self.pops = [pop, device_array(pop.shape, pop.dtype, pop.device)]
+        self.g_mask = [device_array(world * n_words, torch.int64, device) for _ in range(2)]
+        self.g_vis = [device_array(world * self.cap_pad, torch.int32, device) for _ in range(2)]
+        self.g_cnt = [device_array(1, torch.int32, device) for _ in range(2)]
         nscratch = _lib.lib().clapgpu_visible_scratch_bytes(world * self.cap_pad)
-        self.g_scratch = torch.zeros(nscratch // 4 + 4, dtype=torch.int32, device=device)
+        self.g_scratch = device_array(nscratch // 4 + 4, torch.int32, device)
         self.comm = torch.cuda.Stream(device=device)
         self.ev_upd = [torch.cuda.Event() for _ in range(2)]
         self.ev_comm = [torch.cuda.Event() for _ in range(2)]
@@ -146,7 +149,7 @@ class VisibleExchange:
                 L.clapgpu_exchange_set_library(path.encode())
             # clapgpu_exchange_create is collective (ncclCommInitRank): ranks first agree that ALL of them can open RCCL
             # -- a rank that cannot would otherwise leave the others blocked inside the call -- and only then create it
-            can = torch.tensor([int(L.clapgpu_exchange_available())], dtype=torch.int32, device=device)
+            can = upload([int(L.clapgpu_exchange_available())], np.int32, device)
             dist.all_reduce(can, op=dist.ReduceOp.MIN)
             if int(can.item()) == 1:
                 try:
@@ -154,7 +157,7 @@ class VisibleExchange:
                 except Exception as exc:                    # keep the run alive: c10d does the same exchange
                     print(f"[clap_amd.shard] clapgpu_exchange unavailable ({exc}); using torch.distributed", file=sys.stderr)
                 # and the same route afterwards: one rank falling back alone would deadlock the others
-                ok = torch.tensor([1 if self.direct is not None else 0], dtype=torch.int32, device=device)
+                ok = upload([1 if self.direct is not None else 0], np.int32, device)
                 dist.all_reduce(ok, op=dist.ReduceOp.MIN)
                 if int(ok.item()) == 0 and self.direct is not None:
                     L.clapgpu_exchange_destroy(self.direct)
@@ -170,7 +173,7 @@ class VisibleExchange:
         uid = (C.c_uint8 * 128)()
         if rank == 0 and L.clapgpu_exchange_unique_id(uid) != 0:
             uid = (C.c_uint8 * 128)()                        # all zero = "no id": every rank then takes the fallback together
-        t = torch.frombuffer(bytearray(bytes(uid)), dtype=torch.uint8).to(device)
+        t = upload(np.frombuffer(bytearray(bytes(uid)), np.uint8), np.uint8, device)
         dist.broadcast(t, src=0)                             # rank 0 always takes part, whatever happened above
         raw = (C.c_uint8 * 128).from_buffer_copy(bytes(t.cpu().numpy().tobytes()))
         if not any(raw):

@@ -10,12 +10,11 @@ allocation; check() asserts that every band of every array it handed out is stil
   ... run kernels ...
   g.check("after the update")
 
-install(monkeypatch, g) makes the host mirrors allocate through g without editing them: in the namespaces of
-clap_amd.{physics, entities, animation, particles, lights, characters, frame, shard} the name `torch` becomes a proxy that
-forwards every attribute to the real torch except the factory functions (zeros / full / empty / ones and their *_like
-forms), which allocate through g.array when the target device is a GPU (a keyword besides dtype and device is refused
-there, so that no site leaves the guard silently) and fall through otherwise; `upload` in those
-namespaces is wrapped the same way, so inputs get bands too.  torch itself is not patched.
+install(monkeypatch, g) makes the host mirrors allocate through g: every device array of clap_amd.{physics, entities,
+animation, particles, lights, characters, shard} is made by clap_amd._dev.device_array or upload, and both end in
+_dev._new, which install replaces: a GPU target is served by g.array (outputs, scratch and uploaded inputs alike), every
+other target by the real function.  test_guards.py holds the mirrors to that one path by their source.  A label names the
+mirror's module:line that asked for the array.
 
 What this proves and what it does not.  A band is a condition, not a measurement: 4096 bytes is many times the largest
 record any kernel writes (160 bytes), so a one-record overrun in either direction stays inside memory the test owns and
@@ -24,8 +23,9 @@ that jumps over a whole band is not seen.  READ overruns cannot be proven absent
 guarded input reads 0xA5A5... (as a float -2.9e-16, as an index above 2^31), which the value comparison next to the
 guard check has a chance to notice and no more; nothing is claimed about reads.
 
-What the proxy does not reach: tensors made by .clone(), .to(), .contiguous() or torch.from_numpy(...).to(device), tensors
-a test builds itself and anything the library allocates for itself.  guard_like(g, t) re-homes such a tensor by hand.
+What the hook does not reach: tensors a test builds itself (guard_like(g, t) re-homes one by hand), .clone() snapshots,
+upload of what is already a tensor (it is taken as it is), and what the library allocates for itself: broadphase
+objects, mesh sets, the stream-ordered array between the two ray passes.
 """
 import collections
 import os
@@ -36,7 +36,6 @@ import torch as _torch
 
 POISON = 0xA5
 ALIGN = 256
-MIRRORS = ("physics", "entities", "animation", "particles", "lights", "characters", "frame", "shard")
 _HERE = os.path.abspath(__file__).rstrip("c")
 # one guarded array: its label, the whole allocation, where the leading band starts in it, the array's bytes, the array and
 # what it was filled with (None once it was given contents: an uploaded input)
@@ -44,9 +43,10 @@ Entry = collections.namedtuple("Entry", "label buf off nbytes view fill")
 
 
 def _site():
-    """module:line of the nearest caller outside this file"""
+    """module:line of the nearest caller outside this file and clap_amd._dev"""
     f = sys._getframe(1)
-    while f is not None and os.path.abspath(f.f_code.co_filename).rstrip("c") == _HERE:
+    while f is not None and (os.path.abspath(f.f_code.co_filename).rstrip("c") == _HERE
+                             or f.f_globals.get("__name__") == "clap_amd._dev"):
         f = f.f_back
     if f is None:
         return "?"
@@ -134,102 +134,37 @@ class Guards:
                     out.append(e.label)
         return out
 
+    def owns(self, t):
+        """Tensor `t` starts where a registered array starts and is no longer than it."""
+        at, nbytes = t.data_ptr(), t.numel() * t.element_size()
+        return any(e.view.data_ptr() == at and e.nbytes >= nbytes for e in self.entries)
+
     def __len__(self):
         return len(self.entries)
 
 
 def guard_like(g, t, label=None):
-    """A guarded copy of tensor `t` (for tensors the proxy does not reach); the caller re-points whatever held `t`."""
+    """A guarded copy of tensor `t` (for tensors the hook does not reach); the caller re-points whatever held `t`."""
     return g.array(t.shape, t.dtype, 0, label, contents=t)
 
 
-# ------------------------------------------------------------------------------------------------------ the proxy
-_KW = {"dtype", "device"}
-
-
+# ------------------------------------------------------------------------------------------------------ the hook
 def _on_gpu(device):
     return device is not None and _torch.device(device).type == "cuda"
 
 
-def _fill_dtype(fill):
-    if isinstance(fill, bool):
-        return _torch.bool
-    if isinstance(fill, (int, np.integer)):
-        return _torch.int64
-    return _torch.get_default_dtype()
-
-
-class TorchProxy:
-    """Stands for the name `torch` in a mirror's namespace: the factory functions allocate under guard when the target is a
-    GPU; every other attribute is the real torch's."""
-
-    def __init__(self, g):
-        self.__dict__["_g"] = g
-
-    def __getattr__(self, name):
-        return getattr(_torch, name)
-
-    def _make(self, real, args, kw, size, fill, dtype):
-        if not _on_gpu(kw.get("device")):
-            return real(*args, **kw)
-        assert not set(kw) - _KW, f"a GPU allocation the proxy cannot guard: keywords {sorted(set(kw) - _KW)}"
-        return self._g.array(size, kw.get("dtype") or dtype, fill)
-
-    @staticmethod
-    def _size(args):
-        return args[0] if len(args) == 1 and not isinstance(args[0], (int, np.integer)) else args
-
-    def zeros(self, *size, **kw):
-        return self._make(_torch.zeros, size, kw, self._size(size), 0, _torch.get_default_dtype())
-
-    def empty(self, *size, **kw):
-        return self._make(_torch.empty, size, kw, self._size(size), 0, _torch.get_default_dtype())
-
-    def ones(self, *size, **kw):
-        return self._make(_torch.ones, size, kw, self._size(size), 1, _torch.get_default_dtype())
-
-    def full(self, size, fill_value, **kw):
-        return self._make(_torch.full, (size, fill_value), kw, size, fill_value, _fill_dtype(fill_value))
-
-    def _like(self, real, t, fill, kw, *extra):
-        if not _on_gpu(kw.get("device", t.device)):
-            return real(t, *extra, **kw)
-        assert not set(kw) - _KW, f"a GPU allocation the proxy cannot guard: keywords {sorted(set(kw) - _KW)}"
-        return self._g.array(t.shape, kw.get("dtype") or t.dtype, fill)
-
-    def zeros_like(self, t, **kw):
-        return self._like(_torch.zeros_like, t, 0, kw)
-
-    def empty_like(self, t, **kw):
-        return self._like(_torch.empty_like, t, 0, kw)
-
-    def ones_like(self, t, **kw):
-        return self._like(_torch.ones_like, t, 1, kw)
-
-    def full_like(self, t, fill_value, **kw):
-        return self._like(_torch.full_like, t, fill_value, kw, fill_value)
-
-
-def _guarded_upload(real, g):
-    def upload(a, dtype, device, shape=None):
-        if isinstance(a, _torch.Tensor) or not _on_gpu(device):
-            return real(a, dtype, device, shape)
-        host = real(a, dtype, "cpu", shape)
-        return g.array(host.shape, host.dtype, contents=host)
-    return upload
-
-
 def install(monkeypatch, g):
-    """Guard what the mirrors allocate from here on, until monkeypatch undoes it.  Returns the proxy."""
-    import importlib
-    proxy = TorchProxy(g)
-    for name in MIRRORS:
-        mod = importlib.import_module("clap_amd." + name)
-        assert mod.torch is _torch or isinstance(mod.torch, TorchProxy), name
-        monkeypatch.setattr(mod, "torch", proxy)
-        if hasattr(mod, "upload"):
-            real = getattr(mod.upload, "real", mod.upload)               # installing twice does not wrap twice
-            wrapped = _guarded_upload(real, g)
-            wrapped.real = real
-            monkeypatch.setattr(mod, "upload", wrapped)
-    return proxy
+    """Guard what the mirrors allocate from here on, until monkeypatch undoes it: clap_amd._dev._new, the one function
+    that makes a mirror's device array, serves GPU targets from g and passes everything else on."""
+    from clap_amd import _dev
+    real = getattr(_dev._new, "real", _dev._new)                         # installing twice does not wrap twice
+
+    def _new(shape, dtype, device, fill, contents):
+        if not _on_gpu(device):
+            return real(shape, dtype, device, fill, contents)
+        if contents is None:
+            return g.array(shape, dtype, 0 if fill is None else fill)   # uninitialised: any fill will do
+        host = _torch.from_numpy(contents)
+        return g.array(host.shape, host.dtype, contents=host)
+    _new.real = real
+    monkeypatch.setattr(_dev, "_new", _new)

@@ -2,9 +2,9 @@
 statics are some boxes or geoms, then one OTHER static per triangle mesh, with the meshes set.  The mesh generators
 themselves are clap_amd.synth's."""
 import numpy as np
-import torch
 
 from clap_amd import _lib, synth
+from clap_amd._dev import upload
 from guards import Guards
 import meshcontactref as mc
 import trimeshref as tr
@@ -87,7 +87,7 @@ class Scene:
         if material is not None:
             w.set_materials(material)
         if static_material is not None:
-            w.static_material = torch.from_numpy(np.ascontiguousarray(static_material, np.float64)).to(w.device)
+            w.static_material = upload(static_material, np.float64, w.device)
         self.mesh_static = self.base + np.arange(len(meshes))
         self.ref = tr.Meshes.from_list([(self.base + k, t) for k, t in enumerate(self.tris)])
         if meshes:

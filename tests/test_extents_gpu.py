@@ -1,12 +1,13 @@
-"""GPU: WHERE every kernel family writes.  Each test installs tests/guards.py's proxy, so that every device array the
+"""GPU: WHERE every kernel family writes.  Each test installs tests/guards.py's hook, so that every device array the
 host mirrors allocate (outputs, scratch and uploaded inputs) sits between two 4096-byte bands of 0xA5, builds its scene
 at the counts where tails go wrong (1, 63, 65, 257: around a wavefront and a 256-thread workgroup; list capacities total,
 total - 1 and 0), runs the calls, and asserts both what the family's own test asserts about the values (same oracle,
 same strictness, imported from that test, not restated) and that no band was touched.
 
-What the proxy does not reach is re-homed by hand (rehome): tensors a mirror makes with torch.from_numpy(...).to() or
-torch.tensor().  Not covered: the .clone() snapshots of the imported helpers (host comparison only) and the arrays the
-library allocates for itself (broadphase objects, mesh sets).
+Where a descriptor was once re-pointed by hand, held() asserts that the mirror's array is under guard and that the
+descriptor holds its address.  Not covered: tensors a test builds itself unless it guards them (guard_like), the .clone()
+snapshots of the imported helpers (host comparison only), upload of what is already a tensor, and the arrays the library
+allocates for itself (broadphase objects, mesh sets, the stream-ordered array between the two ray passes).
 One test, and only one, passes a wrong extent on purpose, to show that the instrument sees one pair past the end."""
 import ctypes as C
 
@@ -15,7 +16,8 @@ import pytest
 import torch
 
 import guards
-from clap_amd import _lib, synth, tiler
+from clap_amd import _lib, entities, synth, tiler
+from clap_amd._dev import upload
 from oracle import binding as ob
 from helpers import apply_frame, assert_bits_equal
 
@@ -26,29 +28,31 @@ COUNTS = [1, 63, 65, 257]
 
 @pytest.fixture
 def g(cuda_device, monkeypatch):
-    """The registry of the test, with the proxy installed over the mirrors."""
+    """The registry of the test, with the hook installed under the mirrors."""
     reg = guards.Guards(cuda_device)
     guards.install(monkeypatch, reg)
     return reg
 
 
-def rehome(g, obj, names, desc=None, desc_names=None):
-    """Move obj.<name> (a tensor the proxy did not reach) under guard and point desc.<field> at the copy.  The field must
-    be one of the descriptor's: a ctypes structure takes any attribute name without a word.  The old tensor lives until
-    the descriptor points at the new one."""
+def held(g, obj, names, desc=None, desc_names=None):
+    """obj.<name> is an array under guard and desc.<field> holds its address.  The field must be one of the descriptor's:
+    a ctypes structure takes any attribute name without a word.  Returns obj."""
     fields = None if desc is None else {f[0] for f in type(desc)._fields_}
     for k, name in enumerate(names):
-        old = getattr(obj, name)
-        if old is None:
+        t = getattr(obj, name)
+        if t is None:
             continue
-        new = guards.guard_like(g, old, f"{type(obj).__name__}.{name}")
+        assert g.owns(t), f"{type(obj).__name__}.{name} is not under guard"
         if desc is not None:
             field = (desc_names or names)[k]
             assert field in fields, f"{type(desc).__name__} has no field {field!r}"
-            assert getattr(desc, field) == old.data_ptr(), f"{type(desc).__name__}.{field} does not hold {name}"
-            setattr(desc, field, new.data_ptr())
-        setattr(obj, name, new)
-        del old
+            assert getattr(desc, field) == t.data_ptr(), f"{type(desc).__name__}.{field} does not hold {name}"
+    return obj
+
+
+def held_entities(g, batch):
+    """held() for an EntityBatch's inputs."""
+    return held(g, held(g, batch, batch.IN_KEYS + ("model_table",), batch._desc), ("tile_row_start",) if batch.tiled else ())
 
 
 def untouched(t, fill, what):
@@ -63,20 +67,10 @@ ENTITY_SCENES = {"rows1": lambda: synth.entities_flat(1, 5), "rows2": lambda: sy
                  "rows5": lambda: synth.entities_flat(257, 8), "rows5_deep": lambda: synth.entities_chains(13, 5, 9)}
 
 
-def guarded_entities(g, scene, dev):
-    from clap_amd import entities
-    batch = entities.EntityBatch(scene, dev)
-    rehome(g, batch, batch.IN_KEYS + ("model_table",), batch._desc)
-    if batch.tiled:
-        rehome(g, batch, ("tile_row_start",))
-    return batch
-
-
 @pytest.mark.parametrize("n_extra", [1, 4], ids=["views1", "views4"])
 @pytest.mark.parametrize("layout", ["levels", "tiles"])
 @pytest.mark.parametrize("name", list(ENTITY_SCENES))
 def test_entity_update_cull_compact_and_lod(name, layout, n_extra, g, cuda_device):
-    from clap_amd import entities
     scene = lay_out(ENTITY_SCENES[name](), layout)
     scene["model_lod"] = np.tile(np.asarray([[0, 3]], np.uint8), (int(scene["model"].max()) + 1, 1))
     n = scene["n"]
@@ -87,7 +81,7 @@ def test_entity_update_cull_compact_and_lod(name, layout, n_extra, g, cuda_devic
     fr_o = ob.frustum_from_camera(cam)[0]
     frs_o = [ob.frustum_from_camera(c)[0] for c in cams]
     st = ob.entity_state(scene)
-    batch = guarded_entities(g, scene, cuda_device)
+    batch = held_entities(g, entities.EntityBatch(scene, cuda_device))
     batch.set_views([entities.view_calc_frustum(c)[0] for c in cams])
     alive = np.flatnonzero(scene["flags"] & synth.E_ALIVE)
     last_row = alive[alive >= (alive.max() // 64) * 64]
@@ -213,7 +207,7 @@ def test_animation_clock(n, g, cuda_device):
     start = np.linspace(0, 1, n)
     speed = np.full(n, 1.25, np.float32)
     batch.start_clock(ani_time=start, speed=speed, repeat=repeat)
-    rehome(g, batch, ("repeat_dev", "time_end_dev"), batch._clock, ("restart", "time_end"))
+    held(g, batch, ("repeat_dev", "time_end_dev"), batch._clock, ("restart", "time_end"))
     ani = start.copy()
     te = np.asarray(model.time_end, np.float32)
     trs = np.tile(ch["trs0"], (n, 1, 1))
@@ -242,7 +236,7 @@ def test_particles(kw, groups, g, cuda_device):
     pos, vel, st = ob.particles_spawn(ps, 0x00C0FFEE1234)
     view = np.asarray(ob.frustum_from_camera(synth.camera(pos=(4, 5, 6)))[1])
     batch = particles.ParticleBatch(ps, pos, vel, st, cuda_device)
-    rehome(g, batch, ("sys", "rng_state"), batch._desc)
+    held(g, batch, ("sys", "rng_state"), batch._desc)
     if not groups:
         batch._desc.respawn_groups = None
     total = 0
@@ -295,7 +289,7 @@ def test_lights_from_entities(nc, g, cuda_device):
     scene["flags"] = scene["flags"].copy()
     scene["flags"][roots[::3]] &= ~np.uint32(_lib.E_DIRTY)
     dirty = ((scene["flags"] & _lib.E_DIRTY) != 0).astype(np.uint8)
-    batch = guarded_entities(g, scene, cuda_device)
+    batch = held_entities(g, entities.EntityBatch(scene, cuda_device))
     ls = gl.LightSet(cuda_device, 640, 360, 64)
     ls.set_carriers(carriers["entity"], carriers["light"], carriers["off"])
     for all_dirty in (False, True):
@@ -458,7 +452,8 @@ def test_contacts_geoms_records_at_the_three_capacities(k, both, g, cuda_device,
     for cap in capacities(k):
         world = physics.PhysWorld(b, statics, pair_capacity=cap, static_pair_capacity=cap, device=cuda_device)
         world.set_materials(mat)
-        world.static_material = guards.guard_like(g, torch.from_numpy(smat).to(cuda_device), "static_material")
+        world.static_material = upload(smat, np.float64, cuda_device)
+        held(g, world, ("static_material",))
         write_pairs(world, pairs[:k], spairs[:k])
         world.alloc_contacts()
         assert world.contact2_buf.shape == (cap, 160)
@@ -603,7 +598,7 @@ def test_solve_on_the_lane_and_the_workgroup_path(n, g, cuda_device):
     """n spheres in a square on the floor, each touching its neighbours: one island; rows_capacity = rows and rows - 1"""
     side = int(np.ceil(np.sqrt(n)))
     w = tsw.spheres(tsw.grid_positions(n, side), cuda_device)
-    rehome(g, w, ("static_material",))
+    held(g, w, ("static_material",))
     case = tsw.Case(w)
     k = case.rows
     assert len(case.per_island) == 1 and k >= 3 * n
@@ -638,7 +633,7 @@ def test_body_step_and_read_back(n, forces, g, cuda_device):
     if forces and n > 4:
         b["bflags"][3] |= pr.KINEMATIC
     w = physics.PhysWorld(b, None, device=cuda_device, forces=forces)
-    batch = guarded_entities(g, scene, cuda_device)
+    batch = held_entities(g, entities.EntityBatch(scene, cuda_device))
     moving = g.array((max(n, 1),), torch.uint8, 0xEE, "moving")
     joint = torch.from_numpy(np.arange(n) % 2 == 0).to(cuda_device)
     if forces:
@@ -692,7 +687,7 @@ def test_rotate_from_entities(n, g, cuda_device):
     m = n - n // 5
     link_entity = np.concatenate([roots[:m], kids[:n - m]]).astype(np.uint32)
     link_body = tig.rng(2).permutation(n).astype(np.uint32)                  # every body linked, each once
-    batch = guarded_entities(g, scene, cuda_device)
+    batch = held_entities(g, entities.EntityBatch(scene, cuda_device))
     world = physics.PhysWorld(b, None, device=cuda_device)
     dirty = ((scene["flags"] & _lib.E_DIRTY) != 0).astype(np.uint8)
     for all_dirty in (False, True):
@@ -878,7 +873,7 @@ def test_calls_with_nothing_to_do_write_nothing(g, cuda_device):
         assert same_bits(getattr(w, k).cpu().numpy(), t.cpu().numpy()), k
     # zero carriers, through the C entry point (the mirror does not make this call)
     from clap_amd import lights as gl
-    batch = guarded_entities(g, synth.pad_levels(synth.entities_flat(5, 1)), cuda_device)
+    batch = held_entities(g, entities.EntityBatch(synth.pad_levels(synth.entities_flat(5, 1)), cuda_device))
     ls = gl.LightSet(cuda_device, 64, 64, 64)
     ls.load(synth.lights(4, seed=3, inactive_frac=0.0))
     ls._upload()
@@ -902,7 +897,7 @@ def test_characters_update(n, with_bodies, g, cuda_device):
     from clap_amd import characters, physics
     feed = synth.character_feed(n, seed=21, with_bodies=with_bodies)
     scene = _entity_scene(n, feed["pos"])
-    batch = guarded_entities(g, scene, cuda_device)
+    batch = held_entities(g, entities.EntityBatch(scene, cuda_device))
     cf = characters.CharacterFeed(feed, cuda_device)
     world, bodies = None, None
     if with_bodies:
@@ -962,7 +957,7 @@ def test_characters_update_with_the_clock_in_the_same_launch(n, n_clock, with_bo
     from clap_amd import characters, physics
     feed = synth.character_feed(n, seed=21, with_bodies=with_bodies)
     scene = _entity_scene(n, feed["pos"])
-    batch = guarded_entities(g, scene, cuda_device)
+    batch = held_entities(g, entities.EntityBatch(scene, cuda_device))
     cf = characters.CharacterFeed(feed, cuda_device)
     world, bodies = None, None
     if with_bodies:
@@ -1035,7 +1030,7 @@ def test_entry_points_with_no_body_or_no_character_write_nothing(g, cuda_device)
                                      level.data_ptr(), wide.data_ptr())
     assert rc == _lib.OK
     # no character, no clocked character
-    batch = guarded_entities(g, synth.pad_levels(synth.entities_flat(5, 1)), cuda_device)
+    batch = held_entities(g, entities.EntityBatch(synth.pad_levels(synth.entities_flat(5, 1)), cuda_device))
     before = {k: getattr(batch, k).clone() for k in ("pos_scale", "flags")}
     u8 = lambda what: g.array((1,), torch.uint8, 0xEE, what)
     ent, body, head = i32("entity", 0), i32("body", 0), i32("hist_head")
@@ -1064,13 +1059,13 @@ def whole_frame(g, dev):
     """A FrameLoop with every stage on, at the 65-sized scenes: 65 bodies (40 drive entities, 25 belong to characters that
     are fed, moved and linked) among static boxes and one static mesh, 65 posed and skinned characters, 3 x 65 particles,
     lights with carriers, contacts, islands, solve and the pre-binning step."""
-    from clap_amd import animation, characters, entities, frame, lights, particles
+    from clap_amd import animation, characters, frame, lights, particles
     from clap_amd.synth import box_mesh
     raw = synth.entities_flat(257, seed=5)
     scene, tl = tiler.tiled_scene(raw)
     roots = tl["slot_of"][np.flatnonzero(raw["parent"] < 0)]
     scene["model_lod"] = np.asarray([[0, 3]], np.uint8)
-    batch = guarded_entities(g, scene, dev)
+    batch = held_entities(g, entities.EntityBatch(scene, dev))
     nb, nd, J, vpc = N_WORLD, 40, 24, 65
     nc = nb - nd
     b = synth.capsule_bodies(nb, box=4.0, seed=19)
@@ -1081,7 +1076,7 @@ def whole_frame(g, dev):
     sc = mcg.meshscene.Scene(dev, b, [(bv, bi, 2.0, [2.0, 1.0, 2.0], mcg.IDENT)], bb=synth.static_boxes(6, 4.0),
                              material=_materials(nb, 4), static_material=_materials(7, 5), cap=(2048, 2048), grow=1e-6)
     w = sc.w
-    rehome(g, w, ("static_material",))
+    held(g, w, ("static_material",))
     w.enable_forces()
     char_bodies = np.arange(nd, nb).astype(np.uint32)
     char_e = roots[nd:nb].astype(np.uint32)
@@ -1100,11 +1095,11 @@ def whole_frame(g, dev):
     cb = animation.CharacterBatch(model, N_WORLD, ch["trs0"], batch.mx, entity_index=roots[100:100 + N_WORLD].astype(np.uint32),
                                   vert_first=np.zeros(N_WORLD, np.uint32), vert_count=np.full(N_WORLD, vpc, np.uint32))
     cb.start_clock(ani_time=np.zeros(N_WORLD), speed=np.ones(N_WORLD, np.float32))
-    rehome(g, cb, ("repeat_dev", "time_end_dev"), cb._clock, ("restart", "time_end"))
+    held(g, cb, ("repeat_dev", "time_end_dev"), cb._clock, ("restart", "time_end"))
     ps = synth.particle_systems(n_sys=3, count=65, radius=2.0, velocity=0.5, seed=5)
     ppos, pvel, pst = ob.particles_spawn(ps, 0x1234ABCD330E)
     pb = particles.ParticleBatch(ps, ppos, pvel, pst, dev)
-    rehome(g, pb, ("sys", "rng_state"), pb._desc)
+    held(g, pb, ("sys", "rng_state"), pb._desc)
     return frame.FrameLoop(batch, synth.camera(pos=(0, 10, 60)), world=w, feed=cf, body_links=(char_bodies, char_e), lights=ls,
                            characters=cb, particles=pb, contacts=True, prebin=True, islands=True, solve=True, move=m)
 
@@ -1169,10 +1164,10 @@ from test_exchange_gpu import _oracle_visible                                   
 @pytest.mark.parametrize("route", ["rccl", "c10d"])
 @pytest.mark.parametrize("n", [65, 257])
 def test_shard_world_1(n, route, g, cuda_device, process_group):
-    from clap_amd import entities, shard
+    from clap_amd import shard
     scene, _tl = tiler.tiled_scene(synth.entities_flat(n, seed=77))
     cams = [synth.camera(pos=(0, 5, 60)), synth.camera(pos=(30, 0, -20))]
-    batch = guarded_entities(g, scene, cuda_device)
+    batch = held_entities(g, entities.EntityBatch(scene, cuda_device))
     xch = shard.VisibleExchange(batch, 0, 1, cuda_device, route=route)
     assert (xch.direct is not None) == (route == "rccl")
     assert xch.g_vis[0].shape == (scene["n"],) and xch.g_mask[0].shape == (scene["n"] // 64,)

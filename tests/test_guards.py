@@ -1,5 +1,5 @@
 """tests/guards.py, the guard-band instrument of test_extents_gpu.py, on the CPU: what it hands out, what it reports, and
-that the proxy changes nothing but where GPU factories allocate."""
+that the hook changes nothing but where GPU arrays are allocated; and the source rule that keeps the mirrors on that path."""
 import numpy as np
 import pytest
 import torch
@@ -109,56 +109,116 @@ def test_writing_the_poison_value_is_the_one_blind_spot():
     g.check("0xA5 over 0xA5 is invisible: the reason the value is not 0")
 
 
-def test_proxy_leaves_cpu_factories_and_everything_else_alone(monkeypatch):
-    from clap_amd import _dev, entities, physics, shard, frame
+def test_hook_leaves_cpu_targets_and_everything_else_alone(monkeypatch):
+    from clap_amd import _dev, physics, shard
     g = Guards("cpu")
-    real_upload = physics.upload
-    proxy = guards.install(monkeypatch, g)
-    for mod in (entities, physics, shard, frame):
-        assert mod.torch is proxy and mod.torch is not torch
-    import clap_amd.animation as animation
-    assert animation.torch is proxy and _dev.torch is torch              # _dev is not a mirror; torch itself is untouched
-    z = physics.torch.zeros((3, 2), dtype=torch.int32, device="cpu")
-    assert torch.equal(z, torch.zeros((3, 2), dtype=torch.int32)) and len(g) == 0
-    assert torch.equal(physics.torch.zeros(2, 3), torch.zeros(2, 3))
-    assert torch.equal(physics.torch.full((2,), 7, dtype=torch.int64, device=torch.device("cpu")), torch.full((2,), 7))
-    assert physics.torch.empty(4, dtype=torch.uint8).shape == (4,)
-    assert torch.equal(physics.torch.ones(2, dtype=torch.float64), torch.ones(2, dtype=torch.float64))
-    assert torch.equal(shard.torch.zeros_like(z), z) and torch.equal(shard.torch.full_like(z, 3), torch.full_like(z, 3))
-    assert torch.equal(shard.torch.ones_like(z), torch.ones_like(z)) and shard.torch.empty_like(z).shape == z.shape
-    assert frame.torch.zeros(1, dtype=torch.float64, pin_memory=False).dtype == torch.float64
-    assert len(g) == 0, "nothing on the CPU goes through the registry"
-    for name in ("Tensor", "float32", "from_numpy", "cuda", "device", "is_tensor", "as_tensor", "uint8", "distributed", "cat"):
-        assert getattr(entities.torch, name) is getattr(torch, name), name
+    real_new = _dev._new
+    guards.install(monkeypatch, g)
+    assert _dev._new is not real_new and _dev._new.real is real_new
+    guards.install(monkeypatch, g)
+    assert _dev._new.real is real_new, "installing twice wraps once"
+    assert physics.device_array is _dev.device_array and shard.upload is _dev.upload      # the mirrors' names are not patched
+    z = physics.device_array((3, 2), torch.int32, "cpu")
+    assert torch.equal(z, torch.zeros((3, 2), dtype=torch.int32))
+    assert torch.equal(shard.device_array((2,), torch.int64, torch.device("cpu"), 7), torch.full((2,), 7))
+    assert shard.device_array(4, torch.uint8, "cpu", fill=None).shape == (4,)
     up = physics.upload(np.arange(6, dtype=np.uint32), np.uint32, "cpu", (3, 2))
-    assert up.dtype == torch.int32 and up.shape == (3, 2) and len(g) == 0
-    assert physics.upload is not real_upload and physics.upload(z, np.int32, "cpu") is z
+    assert up.dtype == torch.int32 and up.shape == (3, 2) and physics.upload(z, np.int32, "cpu") is z
+    assert len(g) == 0, "nothing on the CPU goes through the registry"
     monkeypatch.undo()
-    assert physics.torch is torch and physics.upload is real_upload
+    assert _dev._new is real_new
 
 
-def test_proxy_routes_a_gpu_target_through_the_registry(monkeypatch):
-    """Without a GPU: the registry stands on the CPU and the proxy is told that "cuda" targets are its own."""
-    from clap_amd import physics, shard
+def test_hook_routes_a_gpu_target_through_the_registry(monkeypatch):
+    """Without a GPU: the registry stands on the CPU and the hook is told that every target is its own."""
+    from clap_amd import _dev, physics, shard
     g = Guards("cpu")
     guards.install(monkeypatch, g)
     monkeypatch.setattr(guards, "_on_gpu", lambda device: device is not None)
-    a = physics.torch.zeros((65, 2), dtype=torch.int32, device="cuda:0")
-    b = physics.torch.full((3,), -1.0, dtype=torch.float64, device="cuda:0")
-    c = shard.torch.zeros_like(a)
-    d = physics.upload(np.arange(5, dtype=np.uint16), np.uint16, "cuda:0")
-    e = physics.torch.zeros(0, dtype=torch.float32, device="cuda:0")
-    assert len(g) == 5 and a.shape == (65, 2) and not a.any() and (b == -1).all() and c.shape == a.shape and c.dtype == a.dtype
-    assert d.dtype == torch.int16 and d.tolist() == [0, 1, 2, 3, 4] and e.shape == (0,)
-    assert g.entries[0].label.startswith("test_guards:") and all(t.data_ptr() % 256 == 0 for t in (a, b, c, d))
+    made = []
+
+    def once(t):                                             # each call lands in the registry exactly once
+        made.append(t)
+        assert len(g) == len(made) and g.owns(t) and g.entries[-1].view.data_ptr() == t.data_ptr()
+        return t
+    a = once(physics.device_array((65, 2), torch.int32, "cuda:0"))
+    b = once(physics.device_array((3,), torch.float64, "cuda:0", -1.0))
+    c = once(shard.device_array(a.shape, torch.uint8, "cuda:0", fill=None))
+    d = once(physics.upload(np.arange(6, dtype=np.uint16) + 0xFFFD, np.uint16, "cuda:0", (3, 2)))
+    e = once(physics.device_array(0, torch.float32, "cuda:0"))
+    assert a.shape == (65, 2) and a.dtype == torch.int32 and not a.any()
+    assert b.shape == (3,) and b.dtype == torch.float64 and (b == -1).all()
+    assert c.shape == (65, 2) and c.dtype == torch.uint8
+    assert d.shape == (3, 2) and d.dtype == torch.int16 and d.tolist() == [[-3, -2], [-1, 0], [1, 2]]      # the same bits
+    assert e.shape == (0,) and e.dtype == torch.float32
+    assert g.entries[0].label.startswith("test_guards:") and g.entries[3].label.startswith("test_guards:")
+    assert all(t.data_ptr() % 256 == 0 for t in (a, b, c, d))
+    assert not g.owns(a[1:]) and not g.owns(torch.zeros(3))
     g.check("fresh")
-    with pytest.raises(AssertionError, match="pin_memory"):  # a GPU site the proxy could not guard is refused, not passed on
-        physics.torch.zeros(4, dtype=torch.int32, device="cuda:0", pin_memory=False)
-    with pytest.raises(AssertionError, match="requires_grad"):
-        shard.torch.zeros_like(a, requires_grad=False)
     whole, first, nbytes = bigger_view(g, 3)
     whole[first + nbytes] = 0
     assert [(s, at) for _l, s, at in g.dirty()] == [("after", [0])]
+    monkeypatch.undo()
+    assert getattr(_dev._new, "real", None) is None
+
+
+# ------------------------------------------------------------------------------------------------------ the source rule
+MIRRORS = ("physics", "entities", "animation", "particles", "lights", "characters", "frame", "shard")
+FACTORIES = {f + like for f in ("zeros", "empty", "ones", "full") for like in ("", "_like")} | {
+    "tensor", "as_tensor", "from_numpy", "frombuffer", "arange"}
+
+
+def off_the_path(source, module):
+    """["line: what"] for every place in a mirror's source that could make a device array without clap_amd._dev: a
+    reference to a torch factory, or a call of a method .to() / .cuda().  Two things are let through, because they make
+    nothing on a device:
+      frame      torch.zeros(...).pin_memory(): the pinned host word the frame's clock is read from
+      any module torch.from_numpy(...) directly as the argument of x.copy_(...): a host view copied into an existing array"""
+    import ast
+    tree = ast.parse(source)
+    parent = {child: node for node in ast.walk(tree) for child in ast.iter_child_nodes(node)}
+    out = []
+    for node in ast.walk(tree):
+        if isinstance(node, ast.ImportFrom) and node.module == "torch":
+            out += [f"{node.lineno}: from torch import {a.name}" for a in node.names if a.name in FACTORIES]
+        if not isinstance(node, ast.Attribute):
+            continue
+        call = parent.get(node)
+        called = isinstance(call, ast.Call) and call.func is node
+        if isinstance(node.value, ast.Name) and node.value.id == "torch" and node.attr in FACTORIES:
+            user = parent.get(call) if called else None
+            pinned = (module == "frame" and node.attr == "zeros" and isinstance(user, ast.Attribute)
+                      and user.attr == "pin_memory" and user.value is call)
+            copied = (node.attr == "from_numpy" and isinstance(user, ast.Call) and call in user.args
+                      and isinstance(user.func, ast.Attribute) and user.func.attr == "copy_")
+            if not (pinned or copied):
+                out.append(f"{node.lineno}: torch.{node.attr}")
+        elif called and node.attr in ("to", "cuda"):
+            out.append(f"{node.lineno}: .{node.attr}()")
+    return out
+
+
+def test_the_rule_sees_what_it_is_for():
+    dev = "def f(dev, a, t):\n    return "
+    for bad in ("torch.zeros(3, dtype=torch.int32, device=dev)", "torch.full_like(t, 1)", "torch.from_numpy(a).to(dev)",
+                "t.cuda()", "torch.tensor([1], device=dev)", "torch.as_tensor(a, device=dev)", "make(torch.empty)",
+                "torch.zeros(1).pin_memory()", "t.add_(torch.from_numpy(a))", "t.copy_(torch.from_numpy(a).to(dev))"):
+        assert off_the_path(dev + bad, "physics"), bad
+    assert off_the_path("from torch import zeros, float32", "physics") == ["1: from torch import zeros"]
+    assert len(off_the_path(dev + "torch.from_numpy(a).to(dev)", "physics")) == 2
+    for fine, module in (("torch.zeros(1, dtype=torch.float64).pin_memory()", "frame"), ("t.copy_(torch.from_numpy(a))", "lights"),
+                         ("device_array(3, torch.int32, dev)", "physics"), ("upload(a, np.int32, dev)", "shard"),
+                         ("t.cpu().numpy().tolist()", "physics"), ("torch.cat([t, t])", "shard")):
+        assert off_the_path(dev + fine, module) == [], fine
+
+
+@pytest.mark.parametrize("module", MIRRORS)
+def test_mirrors_make_device_arrays_through_dev_only(module):
+    """What keeps a future allocation site from leaving the guard silently: the mirrors have no other way to a device."""
+    import os
+    import clap_amd
+    with open(os.path.join(os.path.dirname(clap_amd.__file__), module + ".py")) as f:
+        assert off_the_path(f.read(), module) == [], f"clap_amd/{module}.py makes a tensor past _dev.device_array / upload"
 
 
 def test_guarded_scratch_of_the_older_tests_is_the_same_instrument():

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from clap_amd import _lib, physics, synth
+from clap_amd._dev import upload
 from meshscene import C2, guarded_scratch, same_bits
 import solvelevelref as lr
 import solveref as sr
@@ -118,7 +119,7 @@ def spheres(pos, dev, mu=0.5):
     w = physics.PhysWorld(b, FLOOR, device=dev)
     mat = lambda k: np.tile([0.0, 0.0, mu, 0.0, 0.0], (k, 1))
     w.set_materials(mat(n))
-    w.static_material = torch.from_numpy(mat(1)).to(w.device)
+    w.static_material = upload(mat(1), np.float64, w.device)
     return w
 
 
