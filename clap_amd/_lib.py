@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 41
+ABI_VERSION = 42
 
 OK = 0
 ERR_NOMEM = -1
@@ -220,9 +220,8 @@ class Solver(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("wide_rows", C.c_uint32), ("sor_w", C.c_double), ("cfm", C.c_double)]
 
 
-class Frame(C.Structure):
-    """The fields of clapgpu_frame (include/clapgpu.h) up to ABI 37.  The whole descriptor is FrameDesc, which appends what
-    later versions appended; clapgpu_frame_issue takes nothing shorter."""
+class FrameDesc(C.Structure):
+    """clapgpu_frame (include/clapgpu.h)."""
     _fields_ = [("entities", C.POINTER(Entities)), ("tile_row_start", C.c_void_p), ("n_tiles", C.c_uint32),
                 ("level_start", C.c_void_p), ("n_levels", C.c_uint32), ("frustum", C.POINTER(Frustum)),
                 ("bodies", C.POINTER(Bodies)), ("world", C.POINTER(World)), ("bp", C.c_void_p),
@@ -248,40 +247,23 @@ class Frame(C.Structure):
                 ("meshes", C.c_void_p), ("mesh_contacts", C.c_void_p), ("mesh_ref", C.c_void_p),
                 ("mesh_contact_capacity", C.c_uint32), ("mesh_contact_total", C.c_void_p), ("mesh_capped", C.c_void_p),
                 ("mesh_scratch", C.c_void_p),
-                ("island_scratch", C.c_void_p), ("island", C.c_void_p), ("island_woken", C.c_void_p)]
-
-
-class FrameDesc(Frame):
-    """clapgpu_frame (include/clapgpu.h), whole: Frame's fields, then the contact solve's (ABI 38).  A ctypes subclass lays
-    its own fields out behind its base's, as the C struct has them."""
-    _fields_ = [("solver", C.POINTER(Solver)), ("solve_scratch", C.c_void_p), ("solve_rows_capacity", C.c_uint32),
-                ("solve_status", C.c_void_p)]
-
-
-class FrameDescMove(FrameDesc):
-    """clapgpu_frame (include/clapgpu.h) of ABI 39, whole: FrameDesc's fields, then the move stage's.  FrameDesc keeps the
-    layout of ABI 38; _FrameArg hands the library either of them at the full length."""
-    _fields_ = [("move", C.POINTER(CharactersMove)), ("move_dt_sec", C.c_double), ("move_scratch", C.c_void_p)]
-
-
-class _FrameArg:
-    """The argument type of clapgpu_frame_issue: a FrameDescMove by reference as it is; a FrameDesc (the descriptor of ABI
-    38) copied into a FrameDescMove whose move fields are NULL, so the library never reads past what it was given.
-    Anything shorter (Frame) is refused."""
-
-    @classmethod
-    def from_param(cls, obj):
-        inner = getattr(obj, "_obj", obj)                   # byref(x)._obj is x
-        if isinstance(inner, FrameDescMove):
-            return C.byref(inner)
-        if isinstance(inner, FrameDesc):
-            whole = FrameDescMove()
-            C.memmove(C.byref(whole), C.byref(inner), C.sizeof(FrameDesc))
-            return C.byref(whole)
-        raise TypeError("clapgpu_frame_issue takes a FrameDesc or a FrameDescMove by reference")
+                ("island_scratch", C.c_void_p), ("island", C.c_void_p), ("island_woken", C.c_void_p),
+                ("solver", C.POINTER(Solver)), ("solve_scratch", C.c_void_p), ("solve_rows_capacity", C.c_uint32),
+                ("solve_status", C.c_void_p),
+                ("move", C.POINTER(CharactersMove)), ("move_dt_sec", C.c_double), ("move_scratch", C.c_void_p)]
 
 
 LIGHTS_MAX = 128
+
+# every struct of include/clapgpu.h the binding mirrors: header name -> ctypes class (tests/test_cabi.py holds each to gcc's layout)
+STRUCTS = {
+    "clapgpu_frustum": Frustum, "clapgpu_bv_query": BvQuery, "clapgpu_views": Views, "clapgpu_entities": Entities,
+    "clapgpu_particles": Particles, "clapgpu_anim_clock": AnimClock, "clapgpu_skeleton": Skeleton,
+    "clapgpu_animations": Animations, "clapgpu_pose_batch": PoseBatch, "clapgpu_skin_batch": SkinBatch,
+    "clapgpu_world": World, "clapgpu_bodies": Bodies, "clapgpu_geoms": Geoms, "clapgpu_trimesh_desc": TrimeshDesc,
+    "clapgpu_slide": Slide, "clapgpu_move": CharactersMove, "clapgpu_characters": Characters, "clapgpu_lights": Lights,
+    "clapgpu_solver": Solver, "clapgpu_frame": FrameDesc,
+}
 
 
 # every symbol include/clapgpu.h declares: name -> (restype, argtypes)
@@ -346,8 +328,8 @@ SYMBOLS = {
     "clapgpu_contacts_geoms_both": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_void_p, C.c_void_p,
                                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
-    "clapgpu_sweep_capsules": (C.c_int, [C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_uint32, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_sweep_capsules": (C.c_int, [C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_void_p, C.c_uint32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_bodies_rotate_from_entities": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(Entities), C.c_uint32,
                                                       C.c_uint32, C.c_void_p, C.c_void_p]),
     "clapgpu_contacts_spheres": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.c_void_p, C.c_void_p, C.c_uint32,
@@ -360,25 +342,18 @@ SYMBOLS = {
     "clapgpu_bp_invalidate": (C.c_int, [C.c_void_p, C.c_void_p]),
     "clapgpu_bp_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "clapgpu_bp_index_status": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
-    "clapgpu_ray_cast": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_uint32, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "clapgpu_bodies_ground_collide": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_uint32,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_ray_cast": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_void_p, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_bodies_ground_collide": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_void_p,
+                                                C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_trimesh_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(TrimeshDesc)]),
     "clapgpu_trimesh_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_trimesh_status": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "clapgpu_trimesh_destroy": (None, [C.c_void_p]),
-    "clapgpu_ray_cast_meshes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_void_p, C.c_uint32,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "clapgpu_bodies_ground_collide_meshes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_void_p,
-                                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_contacts_meshes": (C.c_int, [C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
-    "clapgpu_sweep_capsules_meshes": (C.c_int, [C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_void_p, C.c_uint32, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_sweep_capsules_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_void_p, C.c_uint32,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_characters_slide": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_void_p, C.c_double,
@@ -398,14 +373,8 @@ SYMBOLS = {
                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
-                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "clapgpu_bodies_solve_wide": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.POINTER(Solver), C.c_double,
-                                            C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
-                                            C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
-                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p]),
+                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
     "clapgpu_visible_compact_lod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_characters_update_clock": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
@@ -433,7 +402,7 @@ SYMBOLS = {
     "clapgpu_shard_bases": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "clapgpu_mat4_invert": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "clapgpu_mat4_from_quat": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
-    "clapgpu_frame_issue": (C.c_int, [C.c_void_p, _FrameArg, C.c_double, C.c_uint32]),
+    "clapgpu_frame_issue": (C.c_int, [C.c_void_p, C.POINTER(FrameDesc), C.c_double, C.c_uint32]),
     "clapgpu_particles_update": (C.c_int, [C.c_void_p, C.POINTER(Particles), C.POINTER(C.c_float)]),
     "clapgpu_characters_update": (C.c_int, [C.c_void_p, C.POINTER(Characters), C.POINTER(Entities),
                                             C.POINTER(Bodies)]),

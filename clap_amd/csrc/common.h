@@ -112,7 +112,7 @@ __device__ __forceinline__ void unstage_mat4(const float4 *tile, float4 (&v)[4],
 // kernels out or change their store policy; some of them produce WRONG results on purpose.  None of them can reach a
 // release build by a stray EXTRA= flag: every such macro requires -DCLAPGPU_EXPERIMENT, and an experiment build
 // reports an ABI version with the top bit set (runtime.hip), which clap_amd/_lib.py and any caller checking
-// clapgpu_abi_version() against its header refuse to load.
+// clapgpu_abi_version() against its header's CLAPGPU_ABI_VERSION refuse to load.
 #if defined(CLAPGPU_EXP_NO_INVERT) || defined(CLAPGPU_EXP_NO_AABB) || defined(CLAPGPU_PLAIN_STORES) || defined(BP_SEARCH_IN_FLIGHT)
 #  ifndef CLAPGPU_EXPERIMENT
 #    error "CLAPGPU_EXP_* / CLAPGPU_PLAIN_STORES / BP_SEARCH_IN_FLIGHT are experiment switches: add -DCLAPGPU_EXPERIMENT (the library then reports an experiment ABI version)"
@@ -234,7 +234,7 @@ __attribute__((visibility("hidden"))) int clapgpu_bodies_ground_apply(void *stre
 // bodies.hip: clapgpu_characters_slide's last launch (slide.hip sweeps and decides, this moves)
 __attribute__((visibility("hidden"))) int clapgpu_bodies_slide_apply(void *stream, const clapgpu_bodies *b, uint32_t n,
                                                                      const uint32_t *body, uint32_t *flags, const uint32_t *moved);
-// rays.hip: clapgpu_bodies_ground_collide_meshes with the mesh pass's [n] doubles given by the caller (NULL: allocated);
+// rays.hip: clapgpu_bodies_ground_collide with the mesh pass's [n] doubles given by the caller (NULL: allocated);
 // cleared: scratch[0 .. b->n) is zero already
 __attribute__((visibility("hidden"))) int clapgpu_bodies_ground_collide_on(void *stream, struct clapgpu_bp *bp,
                                                                            const clapgpu_bodies *b, const clapgpu_geoms *statics,

@@ -343,10 +343,10 @@ extern "C" int clapgpu_contacts_geoms_both(void *stream, clapgpu_bp *bp, const c
     return CLAPGPU_OK;
 }
 
-extern "C" int clapgpu_sweep_capsules_meshes(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B,
-                                             const clapgpu_trimesh *meshes, uint32_t n_sweeps, const uint32_t *sweep_body,
-                                             const float *delta, const uint32_t *cand_first, const uint32_t *cand, float *frac,
-                                             float *normal, int32_t *hit)
+extern "C" int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B,
+                                      const clapgpu_trimesh *meshes, uint32_t n_sweeps, const uint32_t *sweep_body,
+                                      const float *delta, const uint32_t *cand_first, const uint32_t *cand, float *frac,
+                                      float *normal, int32_t *hit)
 {
     if (!A || !B || (n_sweeps && (!sweep_body || !delta || !cand_first || !frac || !normal || !hit)))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
@@ -364,11 +364,4 @@ extern "C" int clapgpu_sweep_capsules_meshes(void *stream, const clapgpu_geoms *
     }
     CLAPGPU_LAUNCH_CHECK("k_sweep_capsules");
     return CLAPGPU_OK;
-}
-
-extern "C" int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B, uint32_t n_sweeps,
-                                      const uint32_t *sweep_body, const float *delta, const uint32_t *cand_first,
-                                      const uint32_t *cand, float *frac, float *normal, int32_t *hit)
-{
-    return clapgpu_sweep_capsules_meshes(stream, A, B, nullptr, n_sweeps, sweep_body, delta, cand_first, cand, frac, normal, hit);
 }

@@ -197,7 +197,7 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
                                         meshes ? f->mesh_contacts : nullptr, meshes ? f->mesh_ref : nullptr,
                                         meshes ? f->mesh_contact_total : nullptr, meshes ? f->mesh_contact_capacity : 0,
                                         f->pairs, f->pair_total, f->pair_capacity, f->contacts, f->solve_rows_capacity,
-                                        f->solve_scratch, nullptr, nullptr, nullptr, f->solve_status));
+                                        f->solve_scratch, nullptr, nullptr, nullptr, f->solve_status, nullptr, nullptr));
             }
             if ((f->flags & CLAPGPU_FRAME_PREBIN) && f->bp && f->bodies->aabb)
                 FR(clapgpu_bodies_step_prebin(stream, f->bodies, f->world, 1.0 / 120.0, f->bp));

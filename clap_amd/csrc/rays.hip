@@ -278,9 +278,9 @@ static int second_pass(hipStream_t s, const clapgpu_trimesh *meshes, const char 
     return rc;
 }
 
-extern "C" int clapgpu_ray_cast_meshes(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
-                                       const clapgpu_trimesh *meshes, uint32_t n_rays, const double *ray, const int32_t *skip,
-                                       double *dist, int32_t *hit, double *contact, uint32_t *flags)
+extern "C" int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
+                                const clapgpu_trimesh *meshes, uint32_t n_rays, const double *ray, const int32_t *skip,
+                                double *dist, int32_t *hit, double *contact, uint32_t *flags)
 {
     if (!bodies || !statics || (n_rays && (!ray || !dist || !hit))) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     CastK k;
@@ -299,14 +299,7 @@ extern "C" int clapgpu_ray_cast_meshes(void *stream, clapgpu_bp *bp, const clapg
     return second_pass(s, meshes, "k_ray_cast", p, b);
 }
 
-extern "C" int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
-                                uint32_t n_rays, const double *ray, const int32_t *skip, double *dist, int32_t *hit,
-                                double *contact, uint32_t *flags)
-{
-    return clapgpu_ray_cast_meshes(stream, bp, bodies, statics, nullptr, n_rays, ray, skip, dist, hit, contact, flags);
-}
-
-// clapgpu_bodies_ground_collide_meshes on the caller's memory (move.hip): other = [n] doubles for the mesh pass
+// clapgpu_bodies_ground_collide on the caller's memory (move.hip): other = [n] doubles for the mesh pass
 // (meshes != NULL), so the call allocates nothing; cleared: the caller's own launch has zeroed scratch[0 .. b->n), so the
 // call issues kernels only
 __attribute__((visibility("hidden"))) int clapgpu_bodies_ground_collide_on(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b,
@@ -348,21 +341,11 @@ __attribute__((visibility("hidden"))) int clapgpu_bodies_ground_collide_on(void 
     return CLAPGPU_OK;
 }
 
-extern "C" int clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b,
-                                                    const clapgpu_geoms *statics, const clapgpu_trimesh *meshes, uint32_t n,
-                                                    const uint32_t *body, const double *ray_off, const uint8_t *grounded,
-                                                    uint8_t *grounded_out, float *normal, double *dist, int32_t *hit,
-                                                    uint32_t *flags, uint32_t *scratch)
+extern "C" int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,
+                                             const clapgpu_trimesh *meshes, uint32_t n, const uint32_t *body,
+                                             const double *ray_off, const uint8_t *grounded, uint8_t *grounded_out, float *normal,
+                                             double *dist, int32_t *hit, uint32_t *flags, uint32_t *scratch)
 {
     return clapgpu_bodies_ground_collide_on(stream, bp, b, statics, meshes, n, body, ray_off, grounded, grounded_out, normal,
                                             dist, hit, flags, scratch, nullptr, false);
-}
-
-extern "C" int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,
-                                             uint32_t n, const uint32_t *body, const double *ray_off, const uint8_t *grounded,
-                                             uint8_t *grounded_out, float *normal, double *dist, int32_t *hit, uint32_t *flags,
-                                             uint32_t *scratch)
-{
-    return clapgpu_bodies_ground_collide_meshes(stream, bp, b, statics, nullptr, n, body, ray_off, grounded, grounded_out, normal,
-                                                dist, hit, flags, scratch);
 }

@@ -9,9 +9,9 @@
 #include "lm_dev.h"
 
 #ifdef CLAPGPU_EXPERIMENT               // an A/B or sensitivity build (common.h): never loadable as the product
-#define CLAPGPU_ABI_VERSION (41u | 0x80000000u)
+#define ABI_EXPERIMENT_BIT 0x80000000u
 #else
-#define CLAPGPU_ABI_VERSION 41u
+#define ABI_EXPERIMENT_BIT 0u
 #endif
 
 namespace clapgpu {
@@ -69,7 +69,7 @@ extern "C" void clapgpu_test_fail_after(int launches)
     if (armed || launches < 0) g_fail_after.store(launches, std::memory_order_relaxed);
 }
 
-extern "C" uint32_t clapgpu_abi_version(void) { return CLAPGPU_ABI_VERSION; }
+extern "C" uint32_t clapgpu_abi_version(void) { return CLAPGPU_ABI_VERSION | ABI_EXPERIMENT_BIT; }
 
 extern "C" const char *clapgpu_last_error(void) { return g_last_error.c_str(); }
 

@@ -448,16 +448,16 @@ extern "C" size_t clapgpu_bodies_solve_scratch_bytes(uint32_t n, uint32_t rows_c
     return l.total;
 }
 
-extern "C" int clapgpu_bodies_solve_wide(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_solver *sv,
-                                         double h, const uint32_t *island,
-                                         const uint32_t *static_pairs, const uint32_t *static_pair_total, uint32_t static_capacity,
-                                         const clapgpu_contact2 *static_contacts,
-                                         const clapgpu_contact2 *mesh_contacts, const uint32_t *mesh_ref,
-                                         const uint32_t *mesh_contact_total, uint32_t mesh_capacity,
-                                         const uint32_t *pairs, const uint32_t *pair_total, uint32_t capacity,
-                                         const clapgpu_contact2 *contacts,
-                                         uint32_t rows_capacity, void *scratch, double *row_lambda, uint64_t *row_key,
-                                         uint32_t *rows_total, uint32_t *status, uint32_t *row_level, uint32_t *wide_total)
+extern "C" int clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_solver *sv,
+                                    double h, const uint32_t *island,
+                                    const uint32_t *static_pairs, const uint32_t *static_pair_total, uint32_t static_capacity,
+                                    const clapgpu_contact2 *static_contacts,
+                                    const clapgpu_contact2 *mesh_contacts, const uint32_t *mesh_ref,
+                                    const uint32_t *mesh_contact_total, uint32_t mesh_capacity,
+                                    const uint32_t *pairs, const uint32_t *pair_total, uint32_t capacity,
+                                    const clapgpu_contact2 *contacts,
+                                    uint32_t rows_capacity, void *scratch, double *row_lambda, uint64_t *row_key,
+                                    uint32_t *rows_total, uint32_t *status, uint32_t *row_level, uint32_t *wide_total)
 {
     int rc = check_bodies(b);
     if (rc) return rc;
@@ -546,20 +546,4 @@ extern "C" int clapgpu_bodies_solve_wide(void *stream, const clapgpu_bodies *b, 
                        b->lvel, b->avel);
     CLAPGPU_LAUNCH_CHECK("k_solve_apply");
     return CLAPGPU_OK;
-}
-
-extern "C" int clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_solver *sv,
-                                    double h, const uint32_t *island,
-                                    const uint32_t *static_pairs, const uint32_t *static_pair_total, uint32_t static_capacity,
-                                    const clapgpu_contact2 *static_contacts,
-                                    const clapgpu_contact2 *mesh_contacts, const uint32_t *mesh_ref,
-                                    const uint32_t *mesh_contact_total, uint32_t mesh_capacity,
-                                    const uint32_t *pairs, const uint32_t *pair_total, uint32_t capacity,
-                                    const clapgpu_contact2 *contacts,
-                                    uint32_t rows_capacity, void *scratch, double *row_lambda, uint64_t *row_key,
-                                    uint32_t *rows_total, uint32_t *status)
-{
-    return clapgpu_bodies_solve_wide(stream, b, w, sv, h, island, static_pairs, static_pair_total, static_capacity, static_contacts,
-                                     mesh_contacts, mesh_ref, mesh_contact_total, mesh_capacity, pairs, pair_total, capacity,
-                                     contacts, rows_capacity, scratch, row_lambda, row_key, rows_total, status, nullptr, nullptr);
 }

@@ -61,7 +61,7 @@ class FrameLoop:
         import ctypes as C
         from . import _lib
         b, w = self.batch, self.world
-        f = _lib.FrameDescMove()
+        f = _lib.FrameDesc()
         keep = []                                           # ctypes objects the descriptor points into
         f.entities = C.pointer(b._desc)
         if b.tiled:

@@ -251,9 +251,9 @@ class PhysWorld:
         cf, cd = upload(cand_first, np.uint32, dev), upload(cand, np.uint32, dev)
         frac, normal, hit = self._out(ns, (), torch.float32), self._out(ns, (3,), torch.float32), self._out(ns, (), torch.int32)
         g, sg = self.body_geoms(), self.static_geoms()
-        _lib.check(_lib.lib().clapgpu_sweep_capsules_meshes(_stream(), C.byref(g), C.byref(sg), self._meshes if meshes else None,
-                                                            ns, _ptr(sb), _ptr(dl), _ptr(cf), _ptr(cd), _ptr(frac), _ptr(normal),
-                                                            _ptr(hit)), "clapgpu_sweep_capsules_meshes")
+        _lib.check(_lib.lib().clapgpu_sweep_capsules(_stream(), C.byref(g), C.byref(sg), self._meshes if meshes else None,
+                                                     ns, _ptr(sb), _ptr(dl), _ptr(cf), _ptr(cd), _ptr(frac), _ptr(normal),
+                                                     _ptr(hit)), "clapgpu_sweep_capsules")
         self._sweep_keep = (sb, dl, cf, cd)
         return frac[:ns], normal[:ns], hit[:ns]
 
@@ -369,7 +369,7 @@ class PhysWorld:
             _lib.lib().clapgpu_solver_defaults(C.byref(self.solver))
 
     def solve(self, h, want_lambda=False, rows_capacity=None, want_levels=False):
-        """Contact response (clapgpu_bodies_solve_wide): the rows of the last contacts_geoms[_both]() / contacts_meshes() lists,
+        """Contact response (clapgpu_bodies_solve): the rows of the last contacts_geoms[_both]() / contacts_meshes() lists,
         solved island by island with the islands of the last islands(); changes lvel / avel of the enabled bodies in
         contact.  Run it between islands() and world_step(h).  Returns device tensors (rows_total [1], status [1]; bit 0:
         the rows did not fit and nothing was applied; the caller clears it) and, with want_lambda, (row_lambda
@@ -381,7 +381,7 @@ class PhysWorld:
         self.alloc_solve(rows_capacity)
         st = bool(self.n_static)
         mesh = st and self._meshes is not None and self.mesh_contact_buf is not None
-        _lib.check(_lib.lib().clapgpu_bodies_solve_wide(
+        _lib.check(_lib.lib().clapgpu_bodies_solve(
             _stream(), C.byref(self._desc), C.byref(self.world), C.byref(self.solver), h, _ptr(self.island),
             _ptr(self.static_pairs) if st else None, _ptr(self.static_pair_total) if st else None,
             self.static_capacity if st else 0, _ptr(self.static_contact2_buf) if st else None,
@@ -392,7 +392,7 @@ class PhysWorld:
             _ptr(self.row_lambda) if want_lambda else None, _ptr(self.row_key) if want_lambda else None,
             _ptr(self.rows_total), _ptr(self.solve_status),
             _ptr(self.row_level) if want_levels else None, _ptr(self.wide_total) if want_levels else None),
-            "clapgpu_bodies_solve_wide")
+            "clapgpu_bodies_solve")
         out = (self.rows_total, self.solve_status)
         if want_lambda:
             out += (self.row_lambda, self.row_key)
@@ -506,10 +506,10 @@ class PhysWorld:
         dist, contact = self._out(nr, (), torch.float64, nan), self._out(nr, (6,), torch.float64, nan)
         hit, flags = self._out(nr, (), torch.int32), self._out(nr, (), torch.int32)
         g, sg = self.body_geoms(), self.static_geoms()
-        _lib.check(_lib.lib().clapgpu_ray_cast_meshes(_stream(), self._bp if grid else None, C.byref(g), C.byref(sg),
-                                                      self._meshes if meshes else None, nr, _ptr(ray_d), _ptr(skip_d),
-                                                      _ptr(dist), _ptr(hit), _ptr(contact), _ptr(flags)),
-                   "clapgpu_ray_cast_meshes")
+        _lib.check(_lib.lib().clapgpu_ray_cast(_stream(), self._bp if grid else None, C.byref(g), C.byref(sg),
+                                               self._meshes if meshes else None, nr, _ptr(ray_d), _ptr(skip_d),
+                                               _ptr(dist), _ptr(hit), _ptr(contact), _ptr(flags)),
+                   "clapgpu_ray_cast")
         self._ray_keep = (ray_d, skip_d)
         return dist[:nr], hit[:nr], contact[:nr], flags[:nr]
 
@@ -527,12 +527,12 @@ class PhysWorld:
         if self._ground_scratch is None:                         # [n] words of the call's own
             self._ground_scratch = self._out(self.n, (), torch.int32)
         sg = self.static_geoms()
-        _lib.check(_lib.lib().clapgpu_bodies_ground_collide_meshes(_stream(), self._bp if grid else None, C.byref(self._desc),
-                                                                   C.byref(sg), self._meshes if meshes else None, nb,
-                                                                   _ptr(body_d), _ptr(off_d), _ptr(gr_d), _ptr(out),
-                                                                   _ptr(normal), _ptr(dist), _ptr(hit), _ptr(flags),
-                                                                   _ptr(self._ground_scratch)),
-                   "clapgpu_bodies_ground_collide_meshes")
+        _lib.check(_lib.lib().clapgpu_bodies_ground_collide(_stream(), self._bp if grid else None, C.byref(self._desc),
+                                                            C.byref(sg), self._meshes if meshes else None, nb,
+                                                            _ptr(body_d), _ptr(off_d), _ptr(gr_d), _ptr(out),
+                                                            _ptr(normal), _ptr(dist), _ptr(hit), _ptr(flags),
+                                                            _ptr(self._ground_scratch)),
+                   "clapgpu_bodies_ground_collide")
         self._ground_keep = (body_d, off_d, gr_d)
         return out[:nb], normal[:nb], dist[:nb], hit[:nb], flags[:nb]
 

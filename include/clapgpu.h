@@ -55,7 +55,10 @@ const char *clapgpu_last_error(void);
  * the entry point returns CLAPGPU_ERR_UNKNOWN with clapgpu_last_error() set).  < 0 turns it off (the default).  Armed only
  * in a process started with CLAPGPU_TEST_HOOKS in its environment: anywhere else the call does nothing. */
 void clapgpu_test_fail_after(int launches);
-/* ABI version: bumped whenever a signature or struct below changes. */
+/* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
+ * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
+ * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
+#define CLAPGPU_ABI_VERSION 42u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -699,7 +702,7 @@ typedef struct clapgpu_world {
 #define CLAPGPU_GEOM_CAPSULE 1
 #define CLAPGPU_GEOM_BOX     2                 /* an axis-aligned box given by its AABB (stand-in for any static geom) */
 #define CLAPGPU_GEOM_OTHER   3                 /* trimesh etc.: broadphase only, no narrowphase here (with a mesh set:
-                                                  clapgpu_contacts_meshes / clapgpu_sweep_capsules_meshes) */
+                                                  clapgpu_contacts_meshes / clapgpu_sweep_capsules) */
 
 /*
  * Bodies of the character_space, fp64 like the reference's dDOUBLE ODE (physics.h:5-9): capsules
@@ -883,6 +886,7 @@ int clapgpu_contacts_sphere_box(void *stream, const clapgpu_bodies *b, uint32_t 
  */
 #define CLAPGPU_BP_LEVELS_MAX 16
 typedef struct clapgpu_bp clapgpu_bp;
+typedef struct clapgpu_trimesh clapgpu_trimesh;                        /* a set of static triangle meshes: clapgpu_trimesh_create */
 int  clapgpu_bp_create(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t n_static, const double *static_aabb_host);
 int      clapgpu_bp_create_levels(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t levels,
                                   uint32_t n_static, const double *static_aabb_host);
@@ -946,10 +950,15 @@ int clapgpu_contacts_geoms_both(void *stream, clapgpu_bp *bp, const clapgpu_geom
  * every step with its candidate geoms cand[cand_first[k] .. cand_first[k + 1]): an index into B (statics) or,
  * with bit 31 set, into A (other bodies; the body itself is skipped).  Out per sweep: frac (best_frac),
  * normal[3], hit (body index, -2 - static index, or -1).  Contacts are taken in candidate order, 16 per
- * step at most (MAX_CONTACTS).  One wavefront per sweep.  Against static meshes: clapgpu_sweep_capsules_meshes.
+ * step at most (MAX_CONTACTS).  One wavefront per sweep.
+ * meshes (may be NULL: no mesh set; else created with n_statics == B->n): a candidate static that owns a mesh of the
+ * set is collided through that mesh's triangles alone, by the triangle rule stated at clapgpu_contacts_meshes (the mesh
+ * replaces its collider, as in the ray casts), queried with the probe's box at every step.  Within a mesh candidate
+ * the contacts are taken in ascending triangle index; the cap of 16 per step applies.  hit = -2 - s for the mesh's
+ * static s.
  */
-int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B, uint32_t n_sweeps,
-                           const uint32_t *sweep_body, const float *delta, const uint32_t *cand_first,
+int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B, const clapgpu_trimesh *meshes,
+                           uint32_t n_sweeps, const uint32_t *sweep_body, const float *delta, const uint32_t *cand_first,
                            const uint32_t *cand, float *frac, float *normal, int32_t *hit);
 
 /*
@@ -989,10 +998,22 @@ int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_g
  *            capsule: the exit point, normal flipped
  *   box      dCollideRayBox on the static's AABB: the entry face, its outward axis normal; an edge or corner takes the
  *            first axis (x, y, z) whose slab is entered last; a start inside: the exit face, normal flipped
- *   other    (CLAPGPU_GEOM_OTHER, trimesh): not intersected; see CLAPGPU_RAY_UNRESOLVED.  With a mesh set
- *            (clapgpu_ray_cast_meshes) a static that owns a mesh is intersected through its triangles instead
+ *   other    (CLAPGPU_GEOM_OTHER, trimesh): not intersected; see CLAPGPU_RAY_UNRESOLVED.  With a mesh set (`meshes`) a
+ *            static that owns a mesh is intersected through its triangles instead
  * Deviations: the hit kept is the smallest depth, ties to bodies before statics and then to the lower index (ODE keeps
  * the first in its hash-space order); NaN geometry never hits.
+ * meshes (may be NULL: no mesh set; else a set of clapgpu_trimesh_create, below, created with n_statics == statics->n,
+ * CLAPGPU_ERR_INVALID_ARGUMENTS otherwise): the statics that own a mesh of the set are intersected through their
+ * triangles (one more launch, one lane per ray).  Such statics raise no CLAPGPU_RAY_UNRESOLVED; OTHER statics without a
+ * mesh still do.  With meshes the call takes 8 bytes per ray of stream-ordered scratch (hipMallocAsync) when flags are
+ * written.
+ * The triangle test (BackfaceCull, ClosestHit: physics.c:485-487): a triangle is hit from its front only,
+ * u . n < 0 for the unit direction u and n = (v1 - v0) x (v2 - v0); n == 0 and a ray parallel to the plane never hit;
+ * a start inside a closed mesh sees back faces only and misses it.  Contact pos = start + depth * u, normal = n / |n|
+ * (towards the start); hit = -2 - s for the mesh's static s; skip = -2 - s skips the whole mesh.
+ * Deviation: ODE tests the triangles in float (OPCODE); here in fp64 with the watertight test of Woop, Benthin and Wald
+ * (2013), so a ray through a shared edge or vertex of front faces always hits one of them.  Ties extend the rule above:
+ * the smallest depth, bodies before statics, the lower static index, the lower triangle index of the mesh.
  */
 #define CLAPGPU_RAY_INVALID      1u   /* zero / NaN / infinite direction, NaN start, negative or NaN length: a miss */
 #define CLAPGPU_RAY_UNRESOLVED   2u   /* the segment enters an OTHER static's AABB before the hit (or there is no hit):
@@ -1000,8 +1021,9 @@ int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_g
 #define CLAPGPU_RAY_MOVED_TARGET 4u   /* clapgpu_bodies_ground_collide: the hit body was itself moved by this batch */
 int clapgpu_bp_index(void *stream, clapgpu_bp *bp, uint32_t n, const double *aabb);
 int clapgpu_bp_index_status(void *stream, clapgpu_bp *bp, uint32_t *status);
-int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics, uint32_t n_rays,
-                     const double *ray, const int32_t *skip, double *dist, int32_t *hit, double *contact, uint32_t *flags);
+int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
+                     const clapgpu_trimesh *meshes, uint32_t n_rays, const double *ray, const int32_t *skip,
+                     double *dist, int32_t *hit, double *contact, uint32_t *flags);
 /*
  * phys_body_ground_collide (physics.c:695-744, called from character_move, character.c:454) for bodies body[k]
  * (each once; see below), ray_off[k] = phys_body.ray_off, grounded[k] = !ch->airborne.  The ray starts at the body position less
@@ -1014,14 +1036,17 @@ int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, 
  * body moved in this call -- redo those in list order.  INVALID and UNRESOLVED rays move nothing (grounded_out 0).
  * A body listed more than once: all its rays get CLAPGPU_RAY_INVALID and grounded_out 0, and it does not move.
  * scratch: [b->n] uint32 of device memory, overwritten.  bp: NULL or an index over (b->n, b->aabb); cleared on return.
+ * meshes (may be NULL): as clapgpu_ray_cast takes it, by the same triangle test, with the same launch more and the same
+ * 8 bytes per ray of stream-ordered scratch; the decision and the move see the merged hit.
  */
 int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,
-                                  uint32_t n, const uint32_t *body, const double *ray_off, const uint8_t *grounded,
-                                  uint8_t *grounded_out, float *normal, double *dist, int32_t *hit, uint32_t *flags,
-                                  uint32_t *scratch);
+                                  const clapgpu_trimesh *meshes, uint32_t n, const uint32_t *body, const double *ray_off,
+                                  const uint8_t *grounded, uint8_t *grounded_out, float *normal, double *dist, int32_t *hit,
+                                  uint32_t *flags, uint32_t *scratch);
 
 /*
- * The triangle meshes of static trimesh geoms (phys_geom_trimesh_new, physics.c:882-930), for the ray casts above.
+ * The triangle meshes of static trimesh geoms (phys_geom_trimesh_new, physics.c:882-930): the `meshes` of the ray casts
+ * and the sweep above and of the mesh contacts below.
  * clapgpu_trimesh_desc holds DEVICE arrays for mesh m of n_meshes:
  *   static_index[m]       the static (of a statics set of n_statics) the mesh belongs to, meant to be a
  *                         CLAPGPU_GEOM_OTHER static.  The kind is not checked: a sphere, capsule or box static that owns
@@ -1044,22 +1069,7 @@ int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bo
  * 0 without triangles), *n_tris = the triangles of all meshes.
  * A static's broadphase AABB (clapgpu_bp_create) must hold its posed mesh: the mesh contacts below only see pairs the
  * broadphase found.
- *
- * clapgpu_ray_cast_meshes / clapgpu_bodies_ground_collide_meshes: clapgpu_ray_cast / clapgpu_bodies_ground_collide with
- * the statics that own a mesh of `meshes` intersected through their triangles (one more launch, one lane per ray; the
- * ground-collide decision and move see the merged hit).  Such statics raise no CLAPGPU_RAY_UNRESOLVED; OTHER statics
- * without a mesh still do.  meshes == NULL: exactly clapgpu_ray_cast / clapgpu_bodies_ground_collide, which are these
- * calls with NULL.  meshes must have been created with n_statics == statics->n (CLAPGPU_ERR_INVALID_ARGUMENTS otherwise).
- * With meshes the call takes 8 bytes per ray of stream-ordered scratch (hipMallocAsync) when flags are written.
- * The triangle test (BackfaceCull, ClosestHit: physics.c:485-487): a triangle is hit from its front only,
- * u . n < 0 for the unit direction u and n = (v1 - v0) x (v2 - v0); n == 0 and a ray parallel to the plane never hit;
- * a start inside a closed mesh sees back faces only and misses it.  Contact pos = start + depth * u, normal = n / |n|
- * (towards the start); hit = -2 - s for the mesh's static s; skip = -2 - s skips the whole mesh.
- * Deviation: ODE tests the triangles in float (OPCODE); here in fp64 with the watertight test of Woop, Benthin and Wald
- * (2013), so a ray through a shared edge or vertex of front faces always hits one of them.  Ties extend the rule above:
- * the smallest depth, bodies before statics, the lower static index, the lower triangle index of the mesh.
  */
-typedef struct clapgpu_trimesh clapgpu_trimesh;
 typedef struct clapgpu_trimesh_desc {
     uint32_t        n_meshes, n_statics;
     const uint32_t *static_index;
@@ -1074,18 +1084,11 @@ int  clapgpu_trimesh_create(void *stream, clapgpu_trimesh **out, const clapgpu_t
 int  clapgpu_trimesh_pose(void *stream, clapgpu_trimesh *mesh, const double *pos, const float *quat);
 int  clapgpu_trimesh_status(void *stream, const clapgpu_trimesh *mesh, uint32_t *depth, uint32_t *n_tris);
 void clapgpu_trimesh_destroy(clapgpu_trimesh *mesh);
-int  clapgpu_ray_cast_meshes(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
-                             const clapgpu_trimesh *meshes, uint32_t n_rays, const double *ray, const int32_t *skip,
-                             double *dist, int32_t *hit, double *contact, uint32_t *flags);
-int  clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_geoms *statics,
-                                          const clapgpu_trimesh *meshes, uint32_t n, const uint32_t *body,
-                                          const double *ray_off, const uint8_t *grounded, uint8_t *grounded_out, float *normal,
-                                          double *dist, int32_t *hit, uint32_t *flags, uint32_t *scratch);
 
 /*
  * Contacts against the mesh set: near_callback's dCollide for (body, static) pairs whose static owns a mesh, and the
- * capsule sweep against meshes.  ODE's trimesh colliders (dCollideSTL, dCollideCCTL, OPCODE) are an absent submodule of
- * the reference: the rule below is this project's own, PARITY UNPINNED.
+ * capsule sweep against meshes (clapgpu_sweep_capsules with a mesh set).  ODE's trimesh colliders (dCollideSTL,
+ * dCollideCCTL, OPCODE) are an absent submodule of the reference: the rule below is this project's own, PARITY UNPINNED.
  *
  * Sphere / capsule against one triangle (tricontact_dev.h).  The body geom is a segment a, b with radius r: a capsule's
  * ends pos + axis * length / 2 and pos - axis * length / 2, a sphere's centre twice (a capsule of length 0).  The
@@ -1124,26 +1127,17 @@ int  clapgpu_bodies_ground_collide_meshes(void *stream, clapgpu_bp *bp, const cl
  * The list is additive: clapgpu_contacts_geoms[_both] are unchanged, and a meshed OTHER static still gets nc = 0
  * there.  A mesh given to a sphere, capsule or box static adds mesh contacts on top of that static's own record (the
  * loader meshes only trimesh statics).
- *
- * clapgpu_sweep_capsules_meshes: clapgpu_sweep_capsules with a candidate static that owns a mesh collided through that
- * mesh's triangles alone (the mesh replaces its collider, as in the ray casts), queried with the probe's box at every
- * step.  Contacts are taken in candidate order, and within a mesh candidate in ascending triangle index; the cap of 16
- * per step applies.  hit = -2 - s for the mesh's static s.  meshes == NULL: exactly clapgpu_sweep_capsules, which is this
- * call with NULL.  meshes must have been created with n_statics == B->n.
  */
 #define CLAPGPU_MESH_CONTACT_SCRATCH(static_capacity) (((static_capacity) + 63u) / 64u + 1u)
 int  clapgpu_contacts_meshes(void *stream, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
                              const clapgpu_trimesh *meshes, const uint32_t *static_pairs, const uint32_t *static_pair_total,
                              uint32_t static_capacity, uint32_t *scratch, uint32_t capacity, clapgpu_contact2 *contacts,
                              uint32_t *mesh_ref, uint32_t *contact_total, uint32_t *capped_pairs, uint32_t *body_flags);
-int  clapgpu_sweep_capsules_meshes(void *stream, const clapgpu_geoms *A, const clapgpu_geoms *B, const clapgpu_trimesh *meshes,
-                                   uint32_t n_sweeps, const uint32_t *sweep_body, const float *delta, const uint32_t *cand_first,
-                                   const uint32_t *cand, float *frac, float *normal, int32_t *hit);
 
 /*
- * clapgpu_sweep_capsules_grid: clapgpu_sweep_capsules_meshes without candidate lists from the host, as
+ * clapgpu_sweep_capsules_grid: clapgpu_sweep_capsules without candidate lists from the host, as
  * phys_body_sweep_capsule takes none (it collides the probe with phys->space, physics.c:559-670).  Sweep k behaves as
- * clapgpu_sweep_capsules_meshes would with this list: every static, then every body (bit 31 set), in ascending index,
+ * clapgpu_sweep_capsules would with this list: every static, then every body (bit 31 set), in ascending index,
  * whose AABB (statics->aabb, b->aabb) meets the probe's swept box -- the union of b->aabb[sweep_body[k]] and the same
  * box moved by delta[k], closed overlap.
  *   - Contacts are taken in candidate order, 16 a step, and a candidate that does not touch contributes none: any
@@ -1354,11 +1348,10 @@ int  clapgpu_bodies_islands(void *stream, const clapgpu_bodies *b, const clapgpu
  * rows_capacity: the most rows the call can hold.  When the rows do not fit, the launches -- which read the total on the
  * device, where alone it is known -- apply nothing and OR 1 into *status (the caller clears it).  row_lambda
  * [rows_capacity] and row_key [rows_capacity] (device, may be NULL) receive lambda and the key of every row at its
- * ordinal; *rows_total (device, may be NULL) the number of rows.
- * clapgpu_bodies_solve_wide is the same call with two more outputs (device, may be NULL, 4-byte aligned): row_level
- * [rows_capacity] receives at every row's ordinal its level (>= 1) when its island was solved by a workgroup and 0 when
- * by one lane (all 0 when the rows do not fit); *wide_total the number of islands solved by a workgroup.
- * clapgpu_bodies_solve is that call with both NULL.
+ * ordinal; *rows_total (device, may be NULL) the number of rows.  row_level [rows_capacity] (device, may be NULL, 4-byte
+ * aligned) receives at every row's ordinal its level (>= 1) when its island was solved by a workgroup and 0 when by one
+ * lane (all 0 when the rows do not fit); *wide_total (device, may be NULL, 4-byte aligned) the number of islands solved by
+ * a workgroup.
  * scratch: clapgpu_bodies_solve_scratch_bytes(b->n, rows_capacity) bytes of device memory, 256-byte aligned, overwritten;
  * the caller need not clear it between calls; its size does not depend on wide_rows.  Four launches (five when wide_rows
  * is not 0) and a rocPRIM radix sort of the row keys inside the scratch, no allocation, no host synchronisation: a captured graph can hold the call.  b->n == 0 returns CLAPGPU_OK and launches
@@ -1372,17 +1365,6 @@ void   clapgpu_solver_defaults(clapgpu_solver *s);
 size_t clapgpu_bodies_solve_scratch_bytes(uint32_t n, uint32_t rows_capacity);
 int    clapgpu_bodies_solve(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_solver *s, double h,
                             const uint32_t *island,   /* required: clapgpu_bodies_islands' output of this substep */
-                            const uint32_t *static_pairs, const uint32_t *static_pair_total, uint32_t static_capacity,
-                            const clapgpu_contact2 *static_contacts,
-                            const clapgpu_contact2 *mesh_contacts, const uint32_t *mesh_ref,
-                            const uint32_t *mesh_contact_total, uint32_t mesh_capacity,
-                            const uint32_t *pairs, const uint32_t *pair_total, uint32_t capacity,
-                            const clapgpu_contact2 *contacts,
-                            uint32_t rows_capacity, void *scratch,
-                            double *row_lambda, uint64_t *row_key,
-                            uint32_t *rows_total, uint32_t *status);
-int    clapgpu_bodies_solve_wide(void *stream, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_solver *s, double h,
-                            const uint32_t *island,
                             const uint32_t *static_pairs, const uint32_t *static_pair_total, uint32_t static_capacity,
                             const clapgpu_contact2 *static_contacts,
                             const clapgpu_contact2 *mesh_contacts, const uint32_t *mesh_ref,
@@ -1448,7 +1430,7 @@ int clapgpu_characters_update_clock(void *stream, const clapgpu_characters *c, c
  * the rule below is the library's own contract; tests/moveref.py restates it.
  *
  * Mover k, all arithmetic in float exactly as character.c writes it, no FMA, linmath's loops in their own order:
- *   1. Ground ray.  grounded[k] = !airborne[k]; the ray is clapgpu_bodies_ground_collide_meshes' and snaps the body as
+ *   1. Ground ray.  grounded[k] = !airborne[k]; the ray is clapgpu_bodies_ground_collide's and snaps the body as
  *      that call does.  normal[k] is written only on a hit, collision[k] = the hit (body i, -2 - s) or -1 on a miss,
  *      airborne[k] = !grounded_out.  A ray flagged CLAPGPU_RAY_INVALID or CLAPGPU_RAY_UNRESOLVED ends the mover here:
  *      velocity, normal and airborne unchanged, request 0xff, applied 0, first_frac 1, push_hit -1; the host redoes it.
@@ -1624,22 +1606,21 @@ typedef struct clapgpu_frame {
     uint32_t *mesh_contact_total, *mesh_capped;
     uint32_t *mesh_scratch;                    /* CLAPGPU_MESH_CONTACT_SCRATCH(static_pair_capacity) uint32 */
     /* waking by contact (clapgpu_bodies_islands) in every substep, after its last contact launch and before its step;
-     * island_scratch NULL: none, the frame issues the launches it issued before these fields existed.  Needs pairs,
-     * pair_total, contacts and body_geoms; island / island_woken may be NULL */
+     * island_scratch NULL: this stage is skipped.  Needs pairs, pair_total, contacts and body_geoms; island / island_woken
+     * may be NULL */
     void     *island_scratch;                  /* clapgpu_bodies_islands_scratch_bytes(bodies->n) bytes, 256-byte aligned */
     uint32_t *island, *island_woken;
     /* contact response (clapgpu_bodies_solve) in every substep, between its island pass and its step; solve_scratch NULL:
-     * none, the frame issues the launches it issued before these fields existed.  Needs island_scratch and island;
-     * solver NULL: clapgpu_solver_defaults.  solve_status (may be NULL) as *status of clapgpu_bodies_solve */
+     * this stage is skipped.  Needs island_scratch and island; solver NULL: clapgpu_solver_defaults.  solve_status (may be
+     * NULL) as *status of clapgpu_bodies_solve; its other outputs are not asked for */
     const clapgpu_solver *solver;
     void     *solve_scratch;                   /* clapgpu_bodies_solve_scratch_bytes(bodies->n, solve_rows_capacity), 256-byte aligned */
     uint32_t  solve_rows_capacity;
     uint32_t *solve_status;
     /* scene_characters_move (clap.c:589, before phys_step): clapgpu_characters_move as the frame's first stage, on the
      * physics chain under CLAPGPU_FRAME_OVERLAP, over bodies, world, bp, static_geoms and meshes of this descriptor and,
-     * for the rotation hand-off, entities.  move NULL: none, the frame issues the launches it issued before these fields
-     * existed.  clapgpu_characters.airborne may alias move->airborne when both lists are in the same order: the hooks
-     * then see what this frame's move left */
+     * for the rotation hand-off, entities.  move NULL: this stage is skipped.  clapgpu_characters.airborne may alias
+     * move->airborne when both lists are in the same order: the hooks then see what this frame's move left */
     const clapgpu_move *move;
     double    move_dt_sec;                     /* the raw frame delta, as clapgpu_characters_move takes it */
     void     *move_scratch;                    /* clapgpu_characters_move_scratch_bytes(bodies->n, move->n), 256-byte aligned */

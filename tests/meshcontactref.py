@@ -1,5 +1,5 @@
 """Independent truth for contacts of spheres and capsules against static triangles (clapgpu_contacts_meshes,
-clapgpu_sweep_capsules_meshes).  It shares no formula with the kernel (tricontact_dev.h, which uses edge functions for
+clapgpu_sweep_capsules).  It shares no formula with the kernel (tricontact_dev.h, which uses edge functions for
 "inside", the crossing point of the plane and ODE's dClosestLineSegmentPoints):
 
 * "projects into the closed triangle": barycentric coordinates from the Gram system of the two edges;

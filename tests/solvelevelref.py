@@ -1,4 +1,4 @@
-"""The level rule of clapgpu_bodies_solve_wide restated in numpy from include/clapgpu.h: which rows of an island may run
+"""The level rule of clapgpu_bodies_solve restated in numpy from include/clapgpu.h: which rows of an island may run
 side by side without changing a bit of the sequential sweep.  The contacts are enumerated here anew from the lists (not
 taken from solveref's solve); solveref supplies the record layout, the row constants and the sequential answer this
 module's level-by-level execution is compared with.  Nothing here imports the device code."""

@@ -1,5 +1,7 @@
-"""CPU: libclapgpu.so loads and exports exactly what include/clapgpu.h declares.
+"""CPU: libclapgpu.so loads and exports exactly what include/clapgpu.h declares, and clap_amd/_lib.py mirrors that header
+whole: every struct's layout as gcc makes it, every prototype's argument classes, every constant.
 No compute call is made (there is no GPU here)."""
+import ctypes as C
 import os
 import re
 import subprocess
@@ -42,6 +44,99 @@ def test_exports_are_c_abi(built_lib):
 
 def test_abi_version(built_lib):
     assert built_lib.clapgpu_abi_version() == _lib.ABI_VERSION
+
+
+def constants():
+    return {k: v for k, v in vars(_lib).items() if k.isupper() and type(v) is int}
+
+
+@pytest.fixture(scope="module")
+def gcc_says(tmp_path_factory):
+    """What gcc makes of the header: sizeof of every struct of _lib.STRUCTS, offsetof and sizeof of every field the binding
+    names (a field the header lacks does not compile), the value of CLAPGPU_<NAME> for every constant NAME of the binding."""
+    out = []
+    for cname, cls in _lib.STRUCTS.items():
+        out.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
+        out += [f'printf("{cname}.{f} %zu %zu\\n", offsetof({cname}, {f}), sizeof((({cname} *)0)->{f}));' for f, _t in cls._fields_]
+    out += [f'printf("{k} %lld\\n", (long long)(CLAPGPU_{k}));' for k in constants()]
+    d = tmp_path_factory.mktemp("cabi")
+    src, exe = d / "abi.c", d / "abi"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "clapgpu.h"\nint main(void)\n{\n    ' + "\n    ".join(out) +
+                   "\n    return 0;\n}\n")
+    p = subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Werror", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
+    return {l.split()[0]: [int(x) for x in l.split()[1:]] for l in lines}
+
+
+def test_every_struct_of_the_binding_is_laid_out_as_the_header(gcc_says):
+    own = [v for v in vars(_lib).values() if isinstance(v, type) and issubclass(v, C.Structure) and v.__module__ == _lib.__name__]
+    assert sorted(own, key=id) == sorted(_lib.STRUCTS.values(), key=id), "every Structure of _lib stands in STRUCTS, once"
+    for cname, cls in _lib.STRUCTS.items():
+        end = 0
+        for f, t in cls._fields_:
+            d = getattr(cls, f)
+            assert gcc_says[f"{cname}.{f}"] == [d.offset, d.size], f"{cname}.{f}"
+            # the fields cover the struct: between two of them only what the next one's alignment asks for
+            assert d.offset - end == -end % C.alignment(t), f"{cname}: the header has a field in front of {f}"
+            end = d.offset + d.size
+        assert gcc_says[cname][0] - end == -end % C.alignment(cls), f"{cname}: the header has a field behind {f}"
+        assert gcc_says[cname] == [C.sizeof(cls)], cname
+
+
+def test_constants_and_version_match_the_header(gcc_says):
+    assert len(constants()) >= 45 and "ABI_VERSION" in constants()
+    for k, v in constants().items():
+        assert gcc_says[k] == [v], k
+
+
+SCALARS = {"int": "int", "int32_t": "int", "uint32_t": "uint32_t", "size_t": "size_t", "double": "double", "float": "float",
+           "void": "void"}
+CTYPES = {C.c_int32: "int", C.c_uint32: "uint32_t", C.c_size_t: "size_t", C.c_double: "double", C.c_float: "float", None: "void"}
+
+
+def c_class(decl, named):
+    """(class, struct pointed at) of a C parameter (named) or return type: "pointer" (arrays too) or the scalar's class"""
+    if "*" in decl or "[" in decl:
+        s = re.search(r"\bclapgpu_\w+", decl.split("[")[0].rsplit("*", 1)[0])
+        return "pointer", s.group(0) if s else None
+    words = [w for w in decl.split() if w != "const"]
+    return SCALARS[" ".join(words[:-1] if named else words)], None
+
+
+def ctypes_class(t):
+    if isinstance(t, type) and issubclass(t, C._Pointer):
+        return "pointer", t._type_ if issubclass(t._type_, C.Structure) else None
+    return ("pointer" if t in (C.c_void_p, C.c_char_p) else CTYPES[t]), None
+
+
+def prototypes():
+    """name -> (return type, [parameter declarations]) of every function the comment-stripped header declares"""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    src = re.sub(r"\{[^{}]*\}", "", src)                                    # struct bodies
+    found = {}
+    for stmt in src.split(";"):
+        m = re.search(r"([^{}]*?)\b(clapgpu_[a-z0-9_]+)\s*\((.*)\)\s*$", " ".join(stmt.split()))
+        if m:
+            args = [a.strip() for a in m.group(3).split(",")]
+            found[m.group(2)] = (m.group(1).strip(), [] if args == ["void"] else args)
+    return found
+
+
+def test_every_prototype_of_the_header_is_bound_with_its_argument_classes():
+    protos = prototypes()
+    assert sorted(protos) == declared_functions()
+    name_of = {cls: cname for cname, cls in _lib.STRUCTS.items()}
+    for name, (ret, args) in protos.items():
+        res, argtypes = _lib.SYMBOLS[name]
+        assert c_class(ret, False)[0] == ctypes_class(res)[0], f"{name}: the return type"
+        assert len(args) == len(argtypes), f"{name}: {len(args)} arguments in the header, {len(argtypes)} in SYMBOLS"
+        for i, (a, t) in enumerate(zip(args, argtypes)):
+            (want, struct), (got, cls) = c_class(a, True), ctypes_class(t)
+            assert want == got, f"{name}: argument {i} ({a}) is bound as {got}"
+            assert cls is None or name_of[cls] == struct, f"{name}: argument {i} ({a}) is bound as a {name_of[cls]}"
 
 
 def test_code_object_is_gfx950_only():

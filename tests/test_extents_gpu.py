@@ -1002,7 +1002,7 @@ def test_characters_update_with_the_clock_in_the_same_launch(n, n_clock, with_bo
 
 
 def test_entry_points_with_no_body_or_no_character_write_nothing(g, cuda_device):
-    """b->n == 0 for clapgpu_bodies_islands and clapgpu_bodies_solve_wide (the header: "returns CLAPGPU_OK and launches
+    """b->n == 0 for clapgpu_bodies_islands and clapgpu_bodies_solve (the header: "returns CLAPGPU_OK and launches
     nothing"), c->n == 0 for clapgpu_characters_update and n_chars == 0 for clapgpu_animation_time and for both parts of
     clapgpu_characters_update_clock: through the C entry points, every array one guarded row that keeps its fill."""
     from clap_amd import physics
@@ -1024,10 +1024,10 @@ def test_entry_points_with_no_body_or_no_character_write_nothing(g, cuda_device)
     assert rc == _lib.OK
     lam, key = g.array((1,), torch.float64, -1.0, "row_lambda"), g.array((1,), torch.int64, -1, "row_key")
     rows, status, level, wide = i32("rows_total"), i32("status"), i32("row_level"), i32("wide_total")
-    rc = L.clapgpu_bodies_solve_wide(physics._stream(), C.byref(nobody), C.byref(w.world), C.byref(w.solver), H, island.data_ptr(),
-                                     None, None, 0, None, None, None, None, 0, pairs.data_ptr(), total.data_ptr(), 1, rec.data_ptr(),
-                                     1, scratch.data_ptr(), lam.data_ptr(), key.data_ptr(), rows.data_ptr(), status.data_ptr(),
-                                     level.data_ptr(), wide.data_ptr())
+    rc = L.clapgpu_bodies_solve(physics._stream(), C.byref(nobody), C.byref(w.world), C.byref(w.solver), H, island.data_ptr(),
+                                None, None, 0, None, None, None, None, 0, pairs.data_ptr(), total.data_ptr(), 1, rec.data_ptr(),
+                                1, scratch.data_ptr(), lam.data_ptr(), key.data_ptr(), rows.data_ptr(), status.data_ptr(),
+                                level.data_ptr(), wide.data_ptr())
     assert rc == _lib.OK
     # no character, no clocked character
     batch = held_entities(g, entities.EntityBatch(synth.pad_levels(synth.entities_flat(5, 1)), cuda_device))

@@ -1,5 +1,5 @@
 """GPU: contacts of sphere and capsule bodies against static triangle meshes (clapgpu_contacts_meshes), the capsule sweep
-against meshes (clapgpu_sweep_capsules_meshes) and the frame's mesh contact pass, against the truth of
+against meshes (clapgpu_sweep_capsules) and the frame's mesh contact pass, against the truth of
 tests/meshcontactref.py.  Depth and normal must agree within TOL (relative to the scene's scale); pos must lie on the
 closest set; a decision the truth flags as within the rounding margin may go either way."""
 import os
@@ -253,7 +253,7 @@ def test_existing_lists_and_sweep_unchanged(cuda_device):
     pairs = w.download()["static_pairs"]
     meshed = pairs[:, 1] >= sc.base
     assert meshed.sum() > 100 and np.all(st["nc"][meshed] == 0)
-    # the sweep with a NULL mesh set is clapgpu_sweep_capsules, bit for bit
+    # the sweep with a NULL mesh set, through the raw call and through the wrapper
     R = rng(62)
     ns = 256
     sb = R.choice(w.n, ns, replace=False).astype(np.uint32)
@@ -263,23 +263,17 @@ def test_existing_lists_and_sweep_unchanged(cuda_device):
     import ctypes as C
     from clap_amd import physics
     up = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x).view(dt)).to(w.device)
-    outs = []
-    for fn in ("old", "null"):
-        frac = torch.zeros(ns, dtype=torch.float32, device=w.device)
-        nrm = torch.zeros((ns, 3), dtype=torch.float32, device=w.device)
-        hit = torch.zeros(ns, dtype=torch.int32, device=w.device)
-        g, sg = w.body_geoms(), w.static_geoms()
-        args = [C.byref(g), C.byref(sg)] + ([] if fn == "old" else [None]) + [
-            ns, up(sb, np.int32).data_ptr(), up(delta, np.float32).data_ptr(), up(cf, np.int32).data_ptr(),
-            up(cand.reshape(-1), np.int32).data_ptr(), frac.data_ptr(), nrm.data_ptr(), hit.data_ptr()]
-        f = _lib.lib().clapgpu_sweep_capsules if fn == "old" else _lib.lib().clapgpu_sweep_capsules_meshes
-        _lib.check(f(physics._stream(), *args), fn)
-        torch.cuda.synchronize()
-        outs.append([x.cpu().numpy() for x in (frac, nrm, hit)])
-    for x, y in zip(*outs):
-        assert np.array_equal(x.view(np.uint8), y.view(np.uint8))
+    frac = torch.zeros(ns, dtype=torch.float32, device=w.device)
+    nrm = torch.zeros((ns, 3), dtype=torch.float32, device=w.device)
+    hit = torch.zeros(ns, dtype=torch.int32, device=w.device)
+    g, sg = w.body_geoms(), w.static_geoms()
+    args = [C.byref(g), C.byref(sg), None, ns, up(sb, np.int32).data_ptr(), up(delta, np.float32).data_ptr(),
+            up(cf, np.int32).data_ptr(), up(cand.reshape(-1), np.int32).data_ptr(), frac.data_ptr(), nrm.data_ptr(), hit.data_ptr()]
+    _lib.check(_lib.lib().clapgpu_sweep_capsules(physics._stream(), *args), "clapgpu_sweep_capsules")
+    torch.cuda.synchronize()
+    raw = [x.cpu().numpy() for x in (frac, nrm, hit)]
     f0, _n0, h0 = (x.cpu().numpy() for x in w.sweep_capsules(sb, delta, cf, cand.reshape(-1), meshes=False))
-    assert np.array_equal(f0, outs[0][0]) and np.array_equal(h0, outs[0][2])
+    assert np.array_equal(f0, raw[0]) and np.array_equal(h0, raw[2])
 
 
 def test_sweep_onto_the_terrain(cuda_device):

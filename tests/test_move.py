@@ -1,10 +1,9 @@
-"""CPU: the restatement of character_move's decision (tests/moveref.py) on a table of hand cases, one per branch; the
-binding's descriptors against the header as gcc lays it out; clapgpu_characters_move refuses bad arguments before any
-HIP call.  (The device side: test_move_gpu.py.)"""
+"""CPU: the restatement of character_move's decision (tests/moveref.py) on a table of hand cases, one per branch; its
+character states against the binding's; clapgpu_characters_move refuses bad arguments before any HIP call.  (The device
+side: test_move_gpu.py; the binding's descriptors against the header: test_cabi.py.)"""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -147,60 +146,10 @@ def test_batch_is_the_single_rule_per_mover():
 
 
 # ------------------------------------------------------------------------------------------------- the binding
-PROGRAM = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "clapgpu.h"
-#define M(f) printf("move.%s %zu\n", #f, offsetof(clapgpu_move, f))
-#define F(f) printf("frame.%s %zu\n", #f, offsetof(clapgpu_frame, f))
-int main(void)
-{
-    printf("move %zu\nframe %zu\n", sizeof(clapgpu_move), sizeof(clapgpu_frame));
-    M(n); M(body); M(ray_off); M(motion); M(state); M(jump); M(jump_params); M(velocity); M(normal); M(airborne);
-    M(request); M(applied); M(collision); M(first_frac); M(push_hit); M(flags); M(entity); M(yaw_quat);
-    F(entities); F(bodies); F(flags); F(meshes); F(island_woken); F(solver); F(solve_scratch); F(solve_rows_capacity);
-    F(solve_status); F(move); F(move_dt_sec); F(move_scratch);
-    printf("cs %u %u %u %u %u %u %u %u\n", CLAPGPU_CS_START, CLAPGPU_CS_WAKING, CLAPGPU_CS_IDLE, CLAPGPU_CS_MOVING,
-           CLAPGPU_CS_JUMP_START, CLAPGPU_CS_JUMPING, CLAPGPU_CS_FALLING, CLAPGPU_CS_NONE);
-    return 0;
-}
-"""
-
-
-def test_descriptors_match_the_header_as_gcc_lays_it_out(tmp_path):
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(PROGRAM)
-    subprocess.run(["gcc", "-O1", "-std=gnu11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
-                   check=True)
-    lines = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split("\n")
-    got = {l.split()[0]: [int(x) for x in l.split()[1:]] for l in lines if l.strip()}
-    assert got["move"] == [C.sizeof(_lib.CharactersMove)] and got["frame"] == [C.sizeof(_lib.FrameDescMove)]
-    names = [f[0] for f in _lib.CharactersMove._fields_]
-    assert sorted(k[5:] for k in got if k.startswith("move.")) == sorted(names)
-    for name in names:
-        assert got["move." + name] == [getattr(_lib.CharactersMove, name).offset], name
-    for name in (k[6:] for k in got if k.startswith("frame.")):
-        assert got["frame." + name] == [getattr(_lib.FrameDescMove, name).offset], name
-    # appended: FrameDesc is the descriptor of ABI 38, a prefix of the whole one
-    assert [f[0] for f in _lib.FrameDescMove._fields_] == ["move", "move_dt_sec", "move_scratch"]
-    assert issubclass(_lib.FrameDescMove, _lib.FrameDesc) and _lib.FrameDescMove.move.offset == C.sizeof(_lib.FrameDesc)
-    assert got["cs"] == [mr.CS_START, mr.CS_WAKING, mr.CS_IDLE, mr.CS_MOVING, mr.CS_JUMP_START, mr.CS_JUMPING, mr.CS_FALLING,
-                         mr.CS_NONE]
-    assert got["cs"] == [_lib.CS_START, _lib.CS_WAKING, _lib.CS_IDLE, _lib.CS_MOVING, _lib.CS_JUMP_START, _lib.CS_JUMPING,
-                         _lib.CS_FALLING, _lib.CS_NONE]
-
-
-def test_frame_call_takes_the_whole_descriptor_and_extends_the_one_before():
-    arg = _lib.SYMBOLS["clapgpu_frame_issue"][1][1]
-    whole = _lib.FrameDescMove()
-    assert arg.from_param(C.byref(whole))._obj is whole
-    short = _lib.FrameDesc()
-    short.solve_rows_capacity = 77
-    ext = arg.from_param(C.byref(short))._obj                              # a copy at the full length, move fields NULL
-    assert isinstance(ext, _lib.FrameDescMove) and ext.solve_rows_capacity == 77
-    assert not ext.move and ext.move_scratch is None and ext.move_dt_sec == 0.0
-    with pytest.raises(TypeError):
-        arg.from_param(C.byref(_lib.Frame()))
+def test_restatement_and_binding_name_the_same_character_states():
+    """tests/test_cabi.py holds _lib's CS_* to the header's CLAPGPU_CS_*; this holds the restatement's to _lib's"""
+    names = ("CS_START", "CS_WAKING", "CS_IDLE", "CS_MOVING", "CS_JUMP_START", "CS_JUMPING", "CS_FALLING", "CS_NONE")
+    assert [getattr(mr, k) for k in names] == [getattr(_lib, k) for k in names]
 
 
 @pytest.fixture(scope="module")
@@ -254,7 +203,7 @@ def test_move_refuses_bad_arguments_before_any_hip_call(L):
 
 
 def test_frame_refuses_a_move_without_its_world(L):
-    f = _lib.FrameDescMove()
+    f = _lib.FrameDesc()
     ent = _lib.Entities()
     f.entities = C.pointer(ent)
     m = _lib.CharactersMove(0)

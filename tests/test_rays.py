@@ -30,13 +30,13 @@ def test_ray_cast_refuses_null_descriptors_and_arrays(L):
     g, s = geoms(), geoms()
     buf = (C.c_double * 64)()
     ptr = C.cast(buf, C.c_void_p)
-    assert L.clapgpu_ray_cast(None, None, None, C.byref(s), 1, ptr, None, ptr, ptr, None, None) == _lib.ERR_INVALID_ARGUMENTS
-    assert L.clapgpu_ray_cast(None, None, C.byref(g), None, 1, ptr, None, ptr, ptr, None, None) == _lib.ERR_INVALID_ARGUMENTS
+    assert L.clapgpu_ray_cast(None, None, None, C.byref(s), None, 1, ptr, None, ptr, ptr, None, None) == _lib.ERR_INVALID_ARGUMENTS
+    assert L.clapgpu_ray_cast(None, None, C.byref(g), None, None, 1, ptr, None, ptr, ptr, None, None) == _lib.ERR_INVALID_ARGUMENTS
     for ray, dist, hit in ((None, ptr, ptr), (ptr, None, ptr), (ptr, ptr, None)):
-        assert L.clapgpu_ray_cast(None, None, C.byref(g), C.byref(s), 2, ray, None, dist, hit, None, None) == \
+        assert L.clapgpu_ray_cast(None, None, C.byref(g), C.byref(s), None, 2, ray, None, dist, hit, None, None) == \
             _lib.ERR_INVALID_ARGUMENTS
     # nothing to do: no launch, OK
-    assert L.clapgpu_ray_cast(None, None, C.byref(g), C.byref(s), 0, None, None, None, None, None, None) == _lib.OK
+    assert L.clapgpu_ray_cast(None, None, C.byref(g), C.byref(s), None, 0, None, None, None, None, None, None) == _lib.OK
 
 
 def test_ground_collide_refuses_null_descriptors_and_arrays(L):
@@ -45,12 +45,12 @@ def test_ground_collide_refuses_null_descriptors_and_arrays(L):
     ptr = C.cast(buf, C.c_void_p)
     b = _lib.Bodies(4, 1, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr)
     args = [ptr] * 9                       # body, ray_off, grounded, grounded_out, normal, dist, hit, flags, scratch
-    assert L.clapgpu_bodies_ground_collide(None, None, None, C.byref(s), 1, *args) == _lib.ERR_INVALID_ARGUMENTS
-    assert L.clapgpu_bodies_ground_collide(None, None, C.byref(b), None, 1, *args) == _lib.ERR_INVALID_ARGUMENTS
+    assert L.clapgpu_bodies_ground_collide(None, None, None, C.byref(s), None, 1, *args) == _lib.ERR_INVALID_ARGUMENTS
+    assert L.clapgpu_bodies_ground_collide(None, None, C.byref(b), None, None, 1, *args) == _lib.ERR_INVALID_ARGUMENTS
     for k in range(9):
         a = list(args)
         a[k] = None
-        assert L.clapgpu_bodies_ground_collide(None, None, C.byref(b), C.byref(s), 2, *a) == _lib.ERR_INVALID_ARGUMENTS, k
+        assert L.clapgpu_bodies_ground_collide(None, None, C.byref(b), C.byref(s), None, 2, *a) == _lib.ERR_INVALID_ARGUMENTS, k
 
 
 def test_ray_flags_match_header():

@@ -161,20 +161,3 @@ def test_the_row_order_matters_and_is_fixed():
     assert a["lvel"].tobytes() != b["lvel"].tobytes() or a["avel"].tobytes() != b["avel"].tobytes()
     assert np.abs(a["lvel"] - b["lvel"]).max() < 1e-3                     # the same physics, other roundings and sweeps
     assert [int(k) & 0xffffffff for k in a["row_key"]] == list(range(6)) and not (a["row_key"] >> np.uint64(32)).any()
-
-
-def test_frame_descriptor_ends_with_the_solve_fields():
-    """_lib.Frame stays the descriptor of ABI 37; FrameDesc is clapgpu_frame whole, and the only one the frame call takes"""
-    import ctypes as C
-    import pytest
-    own = [f[0] for f in _lib.FrameDesc._fields_]
-    assert own == ["solver", "solve_scratch", "solve_rows_capacity", "solve_status"]
-    assert issubclass(_lib.FrameDesc, _lib.Frame)
-    assert _lib.FrameDesc.solver.offset == C.sizeof(_lib.Frame)                # appended: nothing before them moved
-    assert C.sizeof(_lib.FrameDesc) == C.sizeof(_lib.Frame) + 4 * C.sizeof(C.c_void_p)
-    assert _lib.FrameDesc.island_woken.offset == _lib.Frame.island_woken.offset
-    assert C.sizeof(_lib.Solver) == 24
-    argtype = _lib.SYMBOLS["clapgpu_frame_issue"][1][1]
-    assert argtype.from_param(C.byref(_lib.FrameDesc())) is not None
-    with pytest.raises(TypeError):
-        argtype.from_param(C.byref(_lib.Frame()))                              # too short for the library to read

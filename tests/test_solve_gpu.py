@@ -253,7 +253,7 @@ def test_capacity_and_absent_lists(solved):
         rc = _lib.lib().clapgpu_bodies_solve(physics._stream(), C.byref(w._desc), C.byref(w.world), C.byref(w.solver), H,
                                              w.island.data_ptr(), None, None, 0, None, None, None, None, 0, None, None, 0, None,
                                              w.solve_rows_capacity, w.solve_scratch.data_ptr(), None, None,
-                                             w.rows_total.data_ptr(), w.solve_status.data_ptr())
+                                             w.rows_total.data_ptr(), w.solve_status.data_ptr(), None, None)
         torch.cuda.synchronize()
         assert rc == _lib.OK and int(w.rows_total.item()) == 0 and int(w.solve_status.item()) == 0
         assert same_bits(w.lvel.cpu().numpy(), snap["lvel"].cpu().numpy())
@@ -261,7 +261,7 @@ def test_capacity_and_absent_lists(solved):
         L = _lib.lib()                                                      # argument checks
         args = [physics._stream(), C.byref(w._desc), C.byref(w.world), C.byref(w.solver), H, w.island.data_ptr(), None, None, 0,
                 None, None, None, None, 0, w.pairs.data_ptr(), w.pair_total.data_ptr(), w.capacity, w.contact2_buf.data_ptr(),
-                w.solve_rows_capacity, w.solve_scratch.data_ptr(), None, None, None, None]
+                w.solve_rows_capacity, w.solve_scratch.data_ptr(), None, None, None, None, None, None]
         bad = lambda i, v: args[:i] + [v] + args[i + 1:]
         assert L.clapgpu_bodies_solve(*bad(5, None)) == _lib.ERR_INVALID_ARGUMENTS            # island
         assert L.clapgpu_bodies_solve(*bad(19, None)) == _lib.ERR_INVALID_ARGUMENTS           # scratch

@@ -1,6 +1,6 @@
-"""CPU: the level schedule of clapgpu_bodies_solve_wide (include/clapgpu.h, tests/solvelevelref.py) is exact -- executing
-solveref's rows level after level, the rows inside a level in reversed order, gives the bits of the sequential sweep --
-and the interface is there.  Nothing here touches the device (tests/test_solve_wide_gpu.py does)."""
+"""CPU: the level schedule of clapgpu_bodies_solve's wide path (include/clapgpu.h, tests/solvelevelref.py) is exact --
+executing solveref's rows level after level, the rows inside a level in reversed order, gives the bits of the sequential
+sweep -- and the interface is there.  Nothing here touches the device (tests/test_solve_wide_gpu.py does)."""
 import ctypes as C
 import os
 
@@ -23,13 +23,11 @@ def built_lib():
 
 def test_abi_and_symbol():
     assert _lib.ABI_VERSION >= 40
-    assert "clapgpu_bodies_solve_wide" in _lib.SYMBOLS
-    plain, wide = _lib.SYMBOLS["clapgpu_bodies_solve"], _lib.SYMBOLS["clapgpu_bodies_solve_wide"]
-    assert wide[0] is plain[0] and wide[1] == plain[1] + [C.c_void_p, C.c_void_p]      # the same call, two outputs more
+    assert "clapgpu_bodies_solve" in _lib.SYMBOLS and "wide_rows" in [f[0] for f in _lib.Solver._fields_]
 
 
 def test_symbol_is_bound(built_lib):
-    assert built_lib.clapgpu_bodies_solve_wide.argtypes == _lib.SYMBOLS["clapgpu_bodies_solve_wide"][1]
+    assert built_lib.clapgpu_bodies_solve.argtypes == _lib.SYMBOLS["clapgpu_bodies_solve"][1]
 
 
 def test_solver_layout():

@@ -1,4 +1,4 @@
-"""GPU: clapgpu_bodies_solve_wide -- a large island walked level by level on a workgroup -- against tests/solveref.py
+"""GPU: clapgpu_bodies_solve's wide path -- a large island walked level by level on a workgroup -- against tests/solveref.py
 (the sequential sweep) and tests/solvelevelref.py (the levels).  The device makes its own contact lists; every
 comparison is == on bit patterns, and the wide path must give the bits of the lane path."""
 import ctypes as C
@@ -204,8 +204,8 @@ def test_rows_that_do_not_fit_and_absent_lists(stack):
     lists = [w.static_pairs.data_ptr(), w.static_pair_total.data_ptr(), w.static_capacity, w.static_contact2_buf.data_ptr(),
              None, None, None, 0, w.pairs.data_ptr(), w.pair_total.data_ptr(), w.capacity, w.contact2_buf.data_ptr()]
     head = [physics._stream(), C.byref(w._desc), C.byref(w.world), C.byref(w.solver), H, w.island.data_ptr()]
-    rc = _lib.lib().clapgpu_bodies_solve_wide(*head, *lists, 0, w.solve_scratch.data_ptr(), None, None, w.rows_total.data_ptr(),
-                                              w.solve_status.data_ptr(), w.row_level.data_ptr(), w.wide_total.data_ptr())
+    rc = _lib.lib().clapgpu_bodies_solve(*head, *lists, 0, w.solve_scratch.data_ptr(), None, None, w.rows_total.data_ptr(),
+                                         w.solve_status.data_ptr(), w.row_level.data_ptr(), w.wide_total.data_ptr())
     torch.cuda.synchronize()
     assert rc == _lib.OK and int(w.solve_status.item()) & 1 and int(w.rows_total.item()) == k and int(w.wide_total.item()) == 0
     assert same_bits(w.lvel.cpu().numpy(), before["lvel"].cpu().numpy()) and same_bits(w.avel.cpu().numpy(), before["avel"].cpu().numpy())
@@ -220,15 +220,15 @@ def test_rows_that_do_not_fit_and_absent_lists(stack):
             None, None, None, None, 0, None, None, 0, None, w.solve_rows_capacity, w.solve_scratch.data_ptr(), None, None,
             w.rows_total.data_ptr(), w.solve_status.data_ptr(), w.row_level.data_ptr(), w.wide_total.data_ptr()]
     L = _lib.lib()
-    assert L.clapgpu_bodies_solve_wide(*args) == _lib.OK
+    assert L.clapgpu_bodies_solve(*args) == _lib.OK
     torch.cuda.synchronize()
     assert int(w.rows_total.item()) == 0 and int(w.wide_total.item()) == 0 and int(w.solve_status.item()) == 0
     assert not w.row_level[:w.solve_rows_capacity].any().item()
     assert same_bits(w.lvel.cpu().numpy(), before["lvel"].cpu().numpy()) and same_bits(w.avel.cpu().numpy(), before["avel"].cpu().numpy())
     bad = lambda i, v: args[:i] + [v] + args[i + 1:]
-    assert L.clapgpu_bodies_solve_wide(*bad(24, w.row_level.data_ptr() + 2)) == _lib.ERR_INVALID_ARGUMENTS
-    assert L.clapgpu_bodies_solve_wide(*bad(25, w.wide_total.data_ptr() + 1)) == _lib.ERR_INVALID_ARGUMENTS
-    assert L.clapgpu_bodies_solve_wide(*bad(19, None)) == _lib.ERR_INVALID_ARGUMENTS              # scratch
+    assert L.clapgpu_bodies_solve(*bad(24, w.row_level.data_ptr() + 2)) == _lib.ERR_INVALID_ARGUMENTS
+    assert L.clapgpu_bodies_solve(*bad(25, w.wide_total.data_ptr() + 1)) == _lib.ERR_INVALID_ARGUMENTS
+    assert L.clapgpu_bodies_solve(*bad(19, None)) == _lib.ERR_INVALID_ARGUMENTS              # scratch
     # the scratch grows with the rows, the wide path's 28 bytes a row and 4 a body in it, whatever wide_rows is
     sizes = [_lib.bodies_solve_scratch_bytes(1000, r) for r in (0, 1, 33, 1000, 4096, 100_000, 1 << 20)]
     assert all(sizes) and sizes == sorted(sizes)

@@ -1,5 +1,5 @@
-"""CPU: the static-mesh entry points (clapgpu_trimesh_*, clapgpu_ray_cast_meshes, clapgpu_bodies_ground_collide_meshes)
-exist and refuse bad arguments before any HIP call; the loader writes the collision meshes of trimesh bodies."""
+"""CPU: the static-mesh entry points (clapgpu_trimesh_*) exist and refuse bad arguments before any HIP call (the ray casts
+that take the set: tests/test_rays.py); the loader writes the collision meshes of trimesh bodies."""
 import base64
 import ctypes as C
 import json
@@ -21,10 +21,6 @@ def L():
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
     return _lib.lib()
-
-
-def geoms(n=4):
-    return _lib.Geoms(n, 0, 0, 0, 0, 0, 0, 0, 0)
 
 
 def test_trimesh_create_refuses_bad_descriptors(L):
@@ -54,33 +50,6 @@ def test_trimesh_pose_and_status_refuse_null(L):
     assert L.clapgpu_trimesh_pose(None, None, ptr, ptr) == _lib.ERR_INVALID_ARGUMENTS
     assert L.clapgpu_trimesh_status(None, None, C.byref(dep), C.byref(nt)) == _lib.ERR_INVALID_ARGUMENTS
     L.clapgpu_trimesh_destroy(None)                          # a no-op
-
-
-def test_ray_cast_meshes_refuses_like_ray_cast(L):
-    g, s = geoms(), geoms()
-    buf = (C.c_double * 64)()
-    ptr = C.cast(buf, C.c_void_p)
-    rc = L.clapgpu_ray_cast_meshes
-    assert rc(None, None, None, C.byref(s), None, 1, ptr, None, ptr, ptr, None, None) == _lib.ERR_INVALID_ARGUMENTS
-    assert rc(None, None, C.byref(g), None, None, 1, ptr, None, ptr, ptr, None, None) == _lib.ERR_INVALID_ARGUMENTS
-    for ray, dist, hit in ((None, ptr, ptr), (ptr, None, ptr), (ptr, ptr, None)):
-        assert rc(None, None, C.byref(g), C.byref(s), None, 2, ray, None, dist, hit, None, None) == _lib.ERR_INVALID_ARGUMENTS
-    assert rc(None, None, C.byref(g), C.byref(s), None, 0, None, None, None, None, None, None) == _lib.OK
-
-
-def test_ground_collide_meshes_refuses_like_ground_collide(L):
-    s = geoms()
-    buf = (C.c_double * 64)()
-    ptr = C.cast(buf, C.c_void_p)
-    b = _lib.Bodies(4, 1, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr)
-    args = [ptr] * 9
-    gc = L.clapgpu_bodies_ground_collide_meshes
-    assert gc(None, None, None, C.byref(s), None, 1, *args) == _lib.ERR_INVALID_ARGUMENTS
-    assert gc(None, None, C.byref(b), None, None, 1, *args) == _lib.ERR_INVALID_ARGUMENTS
-    for k in range(9):
-        a = list(args)
-        a[k] = None
-        assert gc(None, None, C.byref(b), C.byref(s), None, 2, *a) == _lib.ERR_INVALID_ARGUMENTS, k
 
 
 def gltf_accessor(g, i, dtype, comps):

@@ -1,5 +1,5 @@
-"""GPU: ray casts against static triangle meshes (clapgpu_trimesh_* / clapgpu_ray_cast_meshes /
-clapgpu_bodies_ground_collide_meshes) against the exact truth of tests/trimeshref.py: a heightfield terrain under the
+"""GPU: ray casts against static triangle meshes (clapgpu_trimesh_* / clapgpu_ray_cast /
+clapgpu_bodies_ground_collide with a mesh set) against the exact truth of tests/trimeshref.py: a heightfield terrain under the
 ray-time body scene, watertightness on shared edges and vertices, culling and degenerate cases, tie order, flags, poses,
 ground collide, degenerate trees and a loaded scene."""
 import ctypes as C
@@ -322,18 +322,16 @@ def test_null_mesh_set_equals_ray_cast_bit_for_bit(cuda_device):
     ray = np.zeros((n, 8))
     ray[:, 0:3], ray[:, 3:6], ray[:, 6] = R.uniform(-5, 65, (n, 3)), R.normal(size=(n, 3)), R.choice([2.0, 20.0, 1e6], n)
     rd = torch.from_numpy(ray).cuda()
-    outs = []
-    for fn in ("clapgpu_ray_cast", "clapgpu_ray_cast_meshes"):
-        o = [torch.full((n,), float("nan"), dtype=torch.float64, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda"),
-             torch.full((n, 6), float("nan"), dtype=torch.float64, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda")]
-        g, sg = w.body_geoms(), w.static_geoms()
-        args = [physics._stream(), None, C.byref(g), C.byref(sg)] + ([None] if fn.endswith("meshes") else []) + \
-               [n, rd.data_ptr(), None] + [t.data_ptr() for t in o]
-        _lib.check(getattr(_lib.lib(), fn)(*args), fn)
-        outs.append([t.cpu().numpy() for t in o])
-    for a, c in zip(*outs):
-        assert same_bits(a, c)
-    assert (outs[0][3] & _lib.RAY_UNRESOLVED).any()
+    o = [torch.full((n,), float("nan"), dtype=torch.float64, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda"),
+         torch.full((n, 6), float("nan"), dtype=torch.float64, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda")]
+    g, sg = w.body_geoms(), w.static_geoms()
+    _lib.check(_lib.lib().clapgpu_ray_cast(physics._stream(), None, C.byref(g), C.byref(sg), None, n, rd.data_ptr(), None,
+                                           *[t.data_ptr() for t in o]), "clapgpu_ray_cast")
+    raw = [t.cpu().numpy() for t in o]
+    wrapped = w.ray_cast(ray[:, 0:3], ray[:, 3:6], ray[:, 6], grid=False, meshes=False)
+    for a, c in zip(raw, wrapped):
+        assert same_bits(a, c.cpu().numpy())
+    assert (raw[3] & _lib.RAY_UNRESOLVED).any()
 
 
 # ------------------------------------------------------------------------------------------- 6. pose

@@ -1,4 +1,4 @@
-"""Independent truth for ray casts against static triangle meshes (clapgpu_ray_cast_meshes): no formula shared with the
+"""Independent truth for ray casts against static triangle meshes (clapgpu_ray_cast with a mesh set): no formula shared with the
 kernel (which shears the ray onto its dominant axis and takes three 2-D edge functions).
 
 A ray p(t) = s + t u crosses triangle (v0, v1, v2) inside or on its boundary when the three signed volumes

@@ -77,7 +77,7 @@ def main():
         m = len(s)
         outs = [torch.empty(m, dtype=torch.float64, device="cuda"), torch.empty(m, dtype=torch.int32, device="cuda"),
                 torch.empty((m, 6), dtype=torch.float64, device="cuda"), torch.empty(m, dtype=torch.int32, device="cuda")]
-        return lambda: _lib.check(lib.clapgpu_ray_cast(st, w._bp if grid else None, C.byref(g), C.byref(sg), m, rd.data_ptr(),
+        return lambda: _lib.check(lib.clapgpu_ray_cast(st, w._bp if grid else None, C.byref(g), C.byref(sg), None, m, rd.data_ptr(),
                                                        None if sk is None else sk.data_ptr(), *[o.data_ptr() for o in outs]),
                                   "clapgpu_ray_cast")
 
@@ -102,14 +102,14 @@ def main():
     scratch = torch.empty(w.n, dtype=torch.int32, device="cuda")
 
     def gc():
-        _lib.check(lib.clapgpu_bodies_ground_collide(st, w._bp, C.byref(w._desc), C.byref(sg), n, body_d.data_ptr(),
+        _lib.check(lib.clapgpu_bodies_ground_collide(st, w._bp, C.byref(w._desc), C.byref(sg), None, n, body_d.data_ptr(),
                                                      off_d.data_ptr(), gr_d.data_ptr(), o8.data_ptr(), nrm.data_ptr(),
                                                      dd.data_ptr(), hh.data_ptr(), ff.data_ptr(), scratch.data_ptr()),
                    "clapgpu_bodies_ground_collide")
 
     res["index_plus_ground_collide_65536_us"] = timed(lambda: (w.bp_index(), gc()), a.reps)
     res["ground_collide_65536_brute_us"] = timed(lambda: _lib.check(lib.clapgpu_bodies_ground_collide(
-        st, None, C.byref(w._desc), C.byref(sg), n, body_d.data_ptr(), off_d.data_ptr(), gr_d.data_ptr(), o8.data_ptr(),
+        st, None, C.byref(w._desc), C.byref(sg), None, n, body_d.data_ptr(), off_d.data_ptr(), gr_d.data_ptr(), o8.data_ptr(),
         nrm.data_ptr(), dd.data_ptr(), hh.data_ptr(), ff.data_ptr(), scratch.data_ptr()), "ground"), 1)
     print(json.dumps(res))
 

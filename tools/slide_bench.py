@@ -194,9 +194,9 @@ def run(workload, a):
     res["sweep_grid_us"] = event_us(lambda: grid_sweep(w._bp), a.k, a.runs)
     res["sweep_brute_us"] = event_us(lambda: grid_sweep(None), 1, 3)
     res["sweep_host_lists_terrain_only_us"] = event_us(
-        lambda: _lib.check(L.clapgpu_sweep_capsules_meshes(physics._stream(), C.byref(g), C.byref(sg), w._meshes, n, sb_d.data_ptr(),
-                                                           dl_d.data_ptr(), cf_d.data_ptr(), cd_d.data_ptr(), frac.data_ptr(),
-                                                           nrm.data_ptr(), hit.data_ptr()), "lists"), a.k, a.runs)
+        lambda: _lib.check(L.clapgpu_sweep_capsules(physics._stream(), C.byref(g), C.byref(sg), w._meshes, n, sb_d.data_ptr(),
+                                                    dl_d.data_ptr(), cf_d.data_ptr(), cd_d.data_ptr(), frac.data_ptr(),
+                                                    nrm.data_ptr(), hit.data_ptr()), "lists"), a.k, a.runs)
     return res
 
 

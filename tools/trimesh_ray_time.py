@@ -1,8 +1,8 @@
 """Times ray casts against static triangle meshes at the full physics scene of tools/ray_time.py (262 144 bodies, 5 000
 statics) plus (A) a 256 x 256 heightfield terrain (130 050 triangles) or (B) that terrain and 2 048 more meshes of 512
 triangles each, and prints one JSON line per workload: clapgpu_trimesh_create and _pose (rebuild), the tree height,
-and grid clapgpu_ray_cast_meshes for 65 536 ground rays, 4 camera rays and 1 024 rays 10^6 long with and without the mesh
-set, and clapgpu_bodies_ground_collide_meshes for 65 536 bodies.  Medians of --reps runs (CUDA events), microseconds.
+and grid clapgpu_ray_cast for 65 536 ground rays, 4 camera rays and 1 024 rays 10^6 long with and without the mesh
+set, and clapgpu_bodies_ground_collide with the mesh set for 65 536 bodies.  Medians of --reps runs (CUDA events), microseconds.
     python tools/trimesh_ray_time.py [--reps 20] [--workload A|B|both]"""
 import argparse
 import ctypes as C
@@ -78,9 +78,9 @@ def run(workload, reps):
         m = len(s)
         outs = [torch.empty(m, dtype=torch.float64, device="cuda"), torch.empty(m, dtype=torch.int32, device="cuda"),
                 torch.empty((m, 6), dtype=torch.float64, device="cuda"), torch.empty(m, dtype=torch.int32, device="cuda")]
-        return lambda: _lib.check(lib.clapgpu_ray_cast_meshes(st, w._bp, C.byref(g), C.byref(sg), w._meshes if meshes else None,
-                                                              m, rd.data_ptr(), None if sk is None else sk.data_ptr(),
-                                                              *[o.data_ptr() for o in outs]), "ray_cast_meshes")
+        return lambda: _lib.check(lib.clapgpu_ray_cast(st, w._bp, C.byref(g), C.byref(sg), w._meshes if meshes else None,
+                                                       m, rd.data_ptr(), None if sk is None else sk.data_ptr(),
+                                                       *[o.data_ptr() for o in outs]), "clapgpu_ray_cast")
 
     skip = sel.astype(np.int32)
     for name, (s, d, ln), sk in (("ground_65536", ground, skip), ("camera_4", cam, None), ("down_1e6_1024", down, None)):
@@ -94,10 +94,10 @@ def run(workload, reps):
     scratch = torch.empty(w.n, dtype=torch.int32, device="cuda")
 
     def gc():
-        _lib.check(lib.clapgpu_bodies_ground_collide_meshes(st, w._bp, C.byref(w._desc), C.byref(sg), w._meshes, n,
-                                                            body_d.data_ptr(), off_d.data_ptr(), gr_d.data_ptr(), o8.data_ptr(),
-                                                            nrm.data_ptr(), dd.data_ptr(), hh.data_ptr(), ff.data_ptr(),
-                                                            scratch.data_ptr()), "ground_collide_meshes")
+        _lib.check(lib.clapgpu_bodies_ground_collide(st, w._bp, C.byref(w._desc), C.byref(sg), w._meshes, n,
+                                                     body_d.data_ptr(), off_d.data_ptr(), gr_d.data_ptr(), o8.data_ptr(),
+                                                     nrm.data_ptr(), dd.data_ptr(), hh.data_ptr(), ff.data_ptr(),
+                                                     scratch.data_ptr()), "clapgpu_bodies_ground_collide")
 
     res["index_plus_ground_collide_meshes_65536_us"] = timed(lambda: (w.bp_index(), gc()), reps)
     res["index_us"] = timed(w.bp_index, reps)
