@@ -166,9 +166,20 @@ LMD void mul_vec4(float (&o)[4], const float (&m)[16], const float (&v)[4])
 LMD float tmin(float a, float b) { return a < b ? a : b; }
 LMD float tmax(float a, float b) { return a > b ? a : b; }
 
-// model.c:1200-1234 (corner order 1207-1216) + util.h:104-109 aabb_center
-LMD void world_aabb(float (&bb)[6], float (&ctr)[3], const float (&m)[16],
-                    float lx, float ly, float lz, float hx, float hy, float hz)
+// util.h:104-109 aabb_center: three separate operations
+LMD void box_center(float (&ctr)[3], const float (&bb)[6])
+{
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        float d = bb[3 + k] - bb[k];
+        d = d * 0.5f;
+        ctr[k] = d + bb[k];
+    }
+}
+
+// model.c:1200-1234 (corner order 1207-1216): all eight corners through mul_point3 and a compare-and-keep chain
+LMD void world_box_literal(float (&bb)[6], const float (&m)[16],
+                           float lx, float ly, float lz, float hx, float hy, float hz)
 {
     bb[0] = bb[1] = bb[2] = INFINITY;
     bb[3] = bb[4] = bb[5] = -INFINITY;
@@ -183,12 +194,63 @@ LMD void world_aabb(float (&bb)[6], float (&ctr)[3], const float (&m)[16],
         bb[1] = tmin(vy, bb[1]);  bb[4] = tmax(vy, bb[4]);
         bb[2] = tmin(vz, bb[2]);  bb[5] = tmax(vz, bb[5]);
     }
+}
+
+LMD void world_aabb_literal(float (&bb)[6], float (&ctr)[3], const float (&m)[16],
+                            float lx, float ly, float lz, float hx, float hy, float hz)
+{
+    world_box_literal(bb, m, lx, ly, lz, hx, hy, hz);
+    box_center(ctr, bb);
+}
+
+// The finiteness of many values in one register: v * 0 is +-0 for a finite v and NaN for an infinity or a NaN, and a sum
+// keeps a NaN, so `acc` is +-0 while every value fed to it was finite (fabsf(v) <= FLT_MAX) and NaN after the first that
+// was not.  Each value is tested on its own (fmaxf over the magnitudes would drop a NaN) at one instruction a value; as a
+// chain of compares the compiler assembled a bit mask, four instructions a value.  An explicit fma: -ffp-contract=off
+// is about a * b + c written apart.
+LMD float nan_unless_finite(float acc, float v) { return __builtin_fmaf(v, 0.0f, acc); }
+
+// The same box from its two extreme corners per axis instead of all eight.  A corner's world coordinate a is the fp32
+// chain ((m0a x + m1a y) + m2a z) + m3a 1 (mul_point3).  Rounding is monotone, so the chain is non-decreasing in each of
+// its three products: the largest of the eight values is the chain over max(m0a lx, m0a hx), max(m1a ly, m1a hy),
+// max(m2a lz, m2a hz), the smallest the chain over the three minima -- the operations and operands of one of the eight
+// corners, hence its bits.  Which of two equal values the literal chain keeps shows only in the sign of a zero, and a
+// zero result can be -0 only where the translation term m3a is -0 (exact cancellation gives +0, and +-0 + +0 is +0).
+// A non-finite product or translation breaks monotonicity (inf - inf).  Returns false, with bb unspecified, for those
+// two cases: the caller takes the literal chain then.
+LMD bool world_box_extremes(float (&bb)[6], const float (&m)[16],
+                            float lx, float ly, float lz, float hx, float hy, float hz)
+{
+    float finite = 0.0f;
+    uint32_t not_neg0 = 0xffffffffu;
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float d = bb[3 + k] - bb[k];
-        d = d * 0.5f;
-        ctr[k] = d + bb[k];
+    for (int a = 0; a < 3; a++) {
+        const float ax = E_(m,0,a) * lx, bx = E_(m,0,a) * hx;
+        const float ay = E_(m,1,a) * ly, by = E_(m,1,a) * hy;
+        const float az = E_(m,2,a) * lz, bz = E_(m,2,a) * hz;
+        const float d = E_(m,3,a) * 1.0f;
+        // (one chain for the three axes: a chain each cost k_entities_tiles<true> a wavefront per SIMD in registers)
+        finite = nan_unless_finite(nan_unless_finite(finite, ax), bx);
+        finite = nan_unless_finite(nan_unless_finite(finite, ay), by);
+        finite = nan_unless_finite(nan_unless_finite(finite, az), bz);
+        finite = nan_unless_finite(finite, d);
+        const uint32_t d_flipped = __builtin_bit_cast(uint32_t, d) ^ 0x80000000u;      // 0 for -0.0 alone
+        not_neg0 = d_flipped < not_neg0 ? d_flipped : not_neg0;
+        float h = fmaxf(ax, bx) + fmaxf(ay, by);  h = h + fmaxf(az, bz);  h = h + d;
+        float l = fminf(ax, bx) + fminf(ay, by);  l = l + fminf(az, bz);  l = l + d;
+        bb[a] = l;  bb[3 + a] = h;
     }
+    return finite == 0.0f && not_neg0 != 0u;
+}
+
+// entity3d_aabb_update: world box and centre, bit for bit world_aabb_literal's.  The fallback branch holds arithmetic
+// only -- no load, no store: entities.hip's straight-line row counts its memory operations.
+LMD void world_aabb(float (&bb)[6], float (&ctr)[3], const float (&m)[16],
+                    float lx, float ly, float lz, float hx, float hy, float hz)
+{
+    if (!world_box_extremes(bb, m, lx, ly, lz, hx, hy, hz))
+        world_box_literal(bb, m, lx, ly, lz, hx, hy, hz);
+    box_center(ctr, bb);
 }
 
 struct Frustum {
