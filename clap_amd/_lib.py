@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 OK = 0
 ERR_NOMEM = -1
@@ -201,6 +201,16 @@ def characters_move_scratch_bytes(n_bodies, n):
     return int(lib().clapgpu_characters_move_scratch_bytes(int(n_bodies), int(n)))
 
 
+def characters_order_scratch_bytes(n, pair_capacity):
+    """clapgpu_characters_order_scratch_bytes: bytes of device scratch clapgpu_characters_order takes."""
+    return int(lib().clapgpu_characters_order_scratch_bytes(int(n), int(pair_capacity)))
+
+
+def characters_move_ordered_scratch_bytes(n_bodies, n, pair_capacity):
+    """clapgpu_characters_move_ordered_scratch_bytes: bytes of device scratch the ordered move takes (needs a device)."""
+    return int(lib().clapgpu_characters_move_ordered_scratch_bytes(int(n_bodies), int(n), int(pair_capacity)))
+
+
 class Characters(C.Structure):
     """clapgpu_characters (include/clapgpu.h)."""
     _fields_ = [("n", C.c_uint32), ("limbo_height", C.c_float), ("entity", C.c_void_p), ("body", C.c_void_p),
@@ -364,6 +374,15 @@ SYMBOLS = {
     "clapgpu_characters_move_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
     "clapgpu_characters_move": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.POINTER(Geoms),
                                           C.c_void_p, C.POINTER(Entities), C.c_double, C.POINTER(CharactersMove), C.c_void_p]),
+    "clapgpu_characters_order_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "clapgpu_characters_order": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.c_double,
+                                           C.POINTER(CharactersMove), C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_uint32), C.c_void_p]),
+    "clapgpu_characters_move_ordered_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "clapgpu_characters_move_ordered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(World),
+                                                  C.POINTER(Geoms), C.c_void_p, C.POINTER(Entities), C.c_double,
+                                                  C.POINTER(CharactersMove), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32),
+                                                  C.c_void_p]),
     "clapgpu_bodies_islands_scratch_bytes": (C.c_size_t, [C.c_uint32]),
     "clapgpu_bodies_islands": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.c_double, C.c_void_p, C.c_void_p,
                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -14,9 +14,13 @@
 //                   is given
 //   k_move_finish   flags = the ray's | the slide's << 8 (the CLAPGPU_SLIDE_INVALID of a 0xffffffff entry dropped), and
 //                   entity3d_rotate's hand-off to the entity SoA (:313)
+// The host side issues the stages through move_slice (stages 1 to 5 over a contiguous slice of the movers, with or without
+// the push) and move_finish (move_dev.h): clapgpu_characters_move runs them over all movers at once, order.hip's
+// clapgpu_characters_move_ordered over one slice per conflict level.
 // float arithmetic as character.c and linmath.h write it, no FMA contraction.  No collider is called here.
 // ODE is absent from the reference: PARITY UNPINNED.  The rule is in include/clapgpu.h, restated in tests/moveref.py.
 #include "common.h"
+#include "move_dev.h"
 
 namespace clapgpu {
 
@@ -180,9 +184,8 @@ extern "C" size_t clapgpu_characters_move_scratch_bytes(uint32_t n_bodies, uint3
     return move_layout(n_bodies, n, push_bytes).bytes;
 }
 
-extern "C" int clapgpu_characters_move(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_world *w,
-                                       const clapgpu_geoms *statics, const clapgpu_trimesh *meshes, const clapgpu_entities *e,
-                                       double dt_sec, const clapgpu_move *m, void *scratch)
+int clapgpu::move_check(clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_geoms *statics,
+                        const clapgpu_entities *e, const clapgpu_move *m)
 {
     if (!m || !b || !w || !statics) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     // what the three stages ask of the bodies, asked before anything is issued
@@ -196,35 +199,53 @@ extern "C" int clapgpu_characters_move(void *stream, clapgpu_bp *bp, const clapg
     if (!m->entity != !m->yaw_quat) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (m->entity && (!e || !e->rot || !e->flags || (reinterpret_cast<uintptr_t>(m->yaw_quat) & 15u)))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 255u)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    const uint32_t n = m->n;
+    return CLAPGPU_OK;
+}
+
+int clapgpu::move_parts(void *scratch, uint32_t n_bodies, uint32_t n, MoveParts *p)
+{
     const size_t push_bytes = clapgpu_bodies_push_scratch_bytes(n);          // asks the sort, launches nothing
     if (!push_bytes) return n > (1u << 28) ? CLAPGPU_ERR_TOO_LARGE : CLAPGPU_ERR_UNKNOWN;
-    const MoveScratch l = move_layout(b->n, n, push_bytes);
+    const MoveScratch l = move_layout(n_bodies, n, push_bytes);
     uint8_t *base = static_cast<uint8_t *>(scratch);
-    uint32_t *words = reinterpret_cast<uint32_t *>(base + l.words);
-    uint32_t *slide_body = reinterpret_cast<uint32_t *>(base + l.slide_body);
-    uint32_t *slide_flags = reinterpret_cast<uint32_t *>(base + l.slide_flags);
-    float *given = reinterpret_cast<float *>(base + l.given);
-    double *dist = reinterpret_cast<double *>(base + l.dist), *other = reinterpret_cast<double *>(base + l.other);
-    uint8_t *grounded = base + l.grounded, *grounded_out = base + l.grounded_out;
+    p->words = reinterpret_cast<uint32_t *>(base + l.words);
+    p->slide_body = reinterpret_cast<uint32_t *>(base + l.slide_body);
+    p->slide_flags = reinterpret_cast<uint32_t *>(base + l.slide_flags);
+    p->given = reinterpret_cast<float *>(base + l.given);
+    p->dist = reinterpret_cast<double *>(base + l.dist);
+    p->other = reinterpret_cast<double *>(base + l.other);
+    p->grounded = base + l.grounded;
+    p->grounded_out = base + l.grounded_out;
+    p->push = base + l.push;
+    return CLAPGPU_OK;
+}
 
+int clapgpu::move_slice(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_world *w, const clapgpu_geoms *statics,
+                        const clapgpu_trimesh *meshes, double dt_sec, const clapgpu_move *m, uint32_t at, uint32_t n,
+                        const MoveParts &p, bool push)
+{
+    const size_t o = at;
+    uint32_t *slide_body = p.slide_body + o, *slide_flags = p.slide_flags + o;
+    float *given = p.given + 3 * o;
+    uint8_t *grounded = p.grounded + o, *grounded_out = p.grounded_out + o;
+    uint32_t *words = p.words;
     hipStream_t s = as_stream(stream);
     const dim3 grid((n + MB - 1) / MB);
     int rc;
     // ---- phys_body_ground_collide(body, !ch->airborne), :454 ----
     if (bp && (rc = clapgpu_bp_index(stream, bp, b->n, b->aabb))) return rc;
     const uint32_t n_words = b->n ? b->n : 1, lanes = n > n_words ? n : n_words;
-    hipLaunchKernelGGL(k_move_begin, dim3((lanes + MB - 1) / MB), dim3(MB), 0, s, n, m->airborne, grounded, n_words, words);
+    hipLaunchKernelGGL(k_move_begin, dim3((lanes + MB - 1) / MB), dim3(MB), 0, s, n, m->airborne + o, grounded, n_words, words);
     CLAPGPU_LAUNCH_CHECK("k_move_begin");
-    rc = clapgpu_bodies_ground_collide_on(stream, bp, b, statics, meshes, n, m->body, m->ray_off, grounded, grounded_out,
-                                          m->normal, dist, m->collision, m->flags, words, other, true);
+    rc = clapgpu_bodies_ground_collide_on(stream, bp, b, statics, meshes, n, m->body + o, m->ray_off + o, grounded, grounded_out,
+                                          m->normal + 3 * o, p.dist + o, m->collision + o, m->flags + o, words, p.other + o, true);
     if (rc) return rc;
     // ---- :464-532 ----
     MoveK k;
-    k.n = n; k.body = m->body; k.motion = m->motion; k.state = m->state; k.jump = m->jump; k.jump_params = m->jump_params;
-    k.velocity = m->velocity; k.normal = m->normal; k.airborne = m->airborne; k.request = m->request; k.applied = m->applied;
-    k.first_frac = m->first_frac; k.push_hit = m->push_hit; k.flags = m->flags; k.grounded_out = grounded_out;
+    k.n = n; k.body = m->body + o; k.motion = m->motion + 2 * o; k.state = m->state + o; k.jump = m->jump + o;
+    k.jump_params = m->jump_params + 2 * o; k.velocity = m->velocity + 3 * o; k.normal = m->normal + 3 * o;
+    k.airborne = m->airborne + o; k.request = m->request + o; k.applied = m->applied + o;
+    k.first_frac = m->first_frac + 2 * o; k.push_hit = m->push_hit + 6 * o; k.flags = m->flags + o; k.grounded_out = grounded_out;
     k.slide_body = slide_body; k.slide_flags = slide_flags; k.given = given;
     hipLaunchKernelGGL(k_move_decide, grid, dim3(MB), 0, s, k, (float)w->gravity[1], dt_sec);
     CLAPGPU_LAUNCH_CHECK("k_move_decide");
@@ -232,17 +253,39 @@ extern "C" int clapgpu_characters_move(void *stream, clapgpu_bp *bp, const clapg
     if (!(dt_sec < 1e-6)) {
         if (bp && (rc = clapgpu_bp_index(stream, bp, b->n, b->aabb))) return rc;      // the ground snaps moved boxes
         clapgpu_slide sl;
-        sl.n = n; sl.body = slide_body; sl.velocity = m->velocity; sl.airborne = m->airborne; sl.first_frac = m->first_frac;
-        sl.push_hit = m->push_hit; sl.flags = slide_flags;
+        sl.n = n; sl.body = slide_body; sl.velocity = m->velocity + 3 * o; sl.airborne = m->airborne + o;
+        sl.first_frac = m->first_frac + 2 * o; sl.push_hit = m->push_hit + 6 * o; sl.flags = slide_flags;
         rc = clapgpu_characters_slide(stream, bp, b, statics, meshes, dt_sec, &sl, words);
         if (rc) return rc;
-        rc = clapgpu_bodies_push(stream, b, w, n, slide_body, given, m->push_hit, slide_flags, nullptr, base + l.push);
-        if (rc) return rc;
+        if (push) {
+            rc = clapgpu_bodies_push(stream, b, w, n, slide_body, given, m->push_hit + 6 * o, slide_flags, nullptr, p.push);
+            if (rc) return rc;
+        }
     }
-    hipLaunchKernelGGL(k_move_finish, grid, dim3(MB), 0, s, n, slide_body, slide_flags, m->flags, m->applied, m->entity,
-                       reinterpret_cast<const float4 *>(m->yaw_quat), m->entity ? e->n : 0u,
+    return CLAPGPU_OK;
+}
+
+int clapgpu::move_finish(void *stream, const clapgpu_entities *e, const clapgpu_move *m, const MoveParts &p)
+{
+    const uint32_t n = m->n;
+    hipLaunchKernelGGL(k_move_finish, dim3((n + MB - 1) / MB), dim3(MB), 0, as_stream(stream), n, p.slide_body, p.slide_flags,
+                       m->flags, m->applied, m->entity, reinterpret_cast<const float4 *>(m->yaw_quat), m->entity ? e->n : 0u,
                        m->entity ? reinterpret_cast<float4 *>(const_cast<float *>(e->rot)) : nullptr,
                        m->entity ? e->flags : nullptr);
     CLAPGPU_LAUNCH_CHECK("k_move_finish");
     return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_characters_move(void *stream, clapgpu_bp *bp, const clapgpu_bodies *b, const clapgpu_world *w,
+                                       const clapgpu_geoms *statics, const clapgpu_trimesh *meshes, const clapgpu_entities *e,
+                                       double dt_sec, const clapgpu_move *m, void *scratch)
+{
+    int rc = move_check(bp, b, w, statics, e, m);
+    if (rc) return rc;
+    if (m->n == 0) return CLAPGPU_OK;
+    if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 255u)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    MoveParts p;
+    if ((rc = move_parts(scratch, b->n, m->n, &p))) return rc;
+    if ((rc = move_slice(stream, bp, b, w, statics, meshes, dt_sec, m, 0, m->n, p, true))) return rc;
+    return move_finish(stream, e, m, p);
 }

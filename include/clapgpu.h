@@ -58,7 +58,7 @@ void clapgpu_test_fail_after(int launches);
 /* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
  * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
  * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
-#define CLAPGPU_ABI_VERSION 42u
+#define CLAPGPU_ABI_VERSION 43u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -1033,7 +1033,7 @@ int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, 
  * (dBodySetPosition, then pos / axis / aabb / geom record as clapgpu_bodies_aabb writes them).  Out:
  * grounded_out[k] = the return value, dist[k] (unchanged on a miss), hit[k], flags[k].  Every ray sees the poses from
  * before the call (the reference moves the characters one at a time): CLAPGPU_RAY_MOVED_TARGET marks a ray whose hit
- * body moved in this call -- redo those in list order.  INVALID and UNRESOLVED rays move nothing (grounded_out 0).
+ * body moved in this call -- clapgpu_characters_move_ordered gives the whole move in list order.  INVALID and UNRESOLVED rays move nothing (grounded_out 0).
  * A body listed more than once: all its rays get CLAPGPU_RAY_INVALID and grounded_out 0, and it does not move.
  * scratch: [b->n] uint32 of device memory, overwritten.  bp: NULL or an index over (b->n, b->aabb); cleared on return.
  * meshes (may be NULL): as clapgpu_ray_cast takes it, by the same triangle test, with the same launch more and the same
@@ -1191,7 +1191,8 @@ int  clapgpu_sweep_capsules_grid(void *stream, clapgpu_bp *bp, const clapgpu_bod
  *                               -- both move nothing and keep velocity[k]; first_frac 1, push_hit -1
  *   CLAPGPU_SLIDE_MOVED_TARGET  a body that gave this mover's probe a contact at any step is itself a mover of this
  *                               batch that ended somewhere else.  The flag is a SUPERSET of that: with contacts from
- *                               several movers of the batch it is set without asking whether they moved.  The mover has moved: redo those in list order
+ *                               several movers of the batch it is set without asking whether they moved.  The mover has moved; the call
+ *                               that moves a crowd in list order is clapgpu_characters_move_ordered
  * scratch: [b->n] uint32 of device memory, overwritten.  bp: NULL or an index over (b->n, b->aabb); cleared on return
  * (bodies moved) unless dt_sec < 1e-6.  No host synchronisation, no allocation.
  */
@@ -1218,7 +1219,8 @@ int  clapgpu_characters_slide(void *stream, clapgpu_bp *bp, const clapgpu_bodies
  *   push_hit[k][6], flags[k] (may be NULL: all 0)   as clapgpu_characters_slide left them
  * The force of slot (k, q) on body h = push_hit[k][q] is (double)(pusher_mass * velocity[k][j]), the product formed in
  * float.  A slot with h < 0 or h >= b->n pushes nothing; a mover with pusher[k] >= b->n or flags[k] != 0 pushes nothing
- * (an INVALID, UNRESOLVED or MOVED_TARGET mover is redone by the host, pushes included).  The same body may stand in
+ * (an INVALID or UNRESOLVED mover is redone by the host, pushes included; clapgpu_characters_move_ordered leaves no
+ * MOVED_TARGET mover).  The same body may stand in
  * many slots and under many movers.  Every pushed body h:
  *   b->facc[h][j] += each force, one fp64 add per push, in ascending (k, q) order -- the reference's sequential sum, bit
  *                 for bit, whatever the scheduling (no atomics on the doubles: the slots are sorted by (h, k, q) and one
@@ -1454,7 +1456,8 @@ int clapgpu_characters_update_clock(void *stream, const clapgpu_characters *c, c
  *      e->rot[entity[k]] = yaw_quat[k] and e->flags[entity[k]] |= CLAPGPU_E_DIRTY (entity3d_rotate, :313).
  * One batch: every ground ray sees the poses from before the call, every slide the poses after all ground snaps.  The
  * reference moves one character at a time: flags[k] = the ray's CLAPGPU_RAY_* | the slide's CLAPGPU_SLIDE_* << 8, and
- * the MOVED_TARGET bit of either stage marks the movers to redo in list order.  A body listed more than once is INVALID
+ * the MOVED_TARGET bit of either stage marks the movers this batch got wrong; clapgpu_characters_move_ordered (below)
+ * moves a crowd in list order and leaves none.  A body listed more than once is INVALID
  * in both stages and stays (its normal[k] may hold its ray's).
  * Launches: the index (bp given), a launch that writes grounded[], the ground rays (+ the mesh pass) and their apply,
  * k_move_decide, the index again, the slide's, the push's, k_move_finish.  No allocation, no host synchronisation: a
@@ -1504,6 +1507,75 @@ int    clapgpu_characters_move(void *stream, clapgpu_bp *bp, const clapgpu_bodie
                                const clapgpu_geoms *statics, const clapgpu_trimesh *meshes,
                                const clapgpu_entities *e /* NULL without the hand-off */,
                                double dt_sec /* raw frame delta */, const clapgpu_move *m, void *scratch);
+
+/*
+ * clapgpu_characters_order / clapgpu_characters_move_ordered (ABI 43): a crowd moved in list order.  The reference moves
+ * one character at a time: each sees every earlier one where it ended up and every later one where it still stands.
+ * clapgpu_characters_move_ordered gives, bit for bit, what clapgpu_characters_move gives when it is called once per mover
+ * in list order -- every array of m and every array of b, facc, bflags and the auto-disable counters included -- and moves
+ * together the movers that cannot reach each other.  No mover of an ordered call carries a MOVED_TARGET bit.
+ *
+ * Reach box of mover k: six doubles in the layout of clapgpu_bodies.aabb, from the inputs of the call before anything
+ * moves; it holds everything the three stages of mover k can read of another geom or write of its own body, whatever
+ * branch the decision takes (the proof stands next to the kernel, clap_amd/csrc/order.hip).  With bb = b->aabb[body[k]],
+ * every operation in fp64, in this order, without FMA contraction (tests/orderref.py restates it bit for bit):
+ *   roff = ray_off[k] - 0.05;  ray_len = yoffset - roff + 1e-3;  rl = ray_len > 0 ? ray_len : 0   (also for NaN)
+ *   start = (double)(float)(pos.y - roff);  end = start - rl * 2
+ *   a0 = |vx| + |vy| + |vz|;  A = a0 + |(double)(float)gravity[1]| * dt_sec;  A not finite: A = a0;  still not: A = 0
+ *   B = 3 * (|dx| + |dz|);  not finite: B = 0;        S = A > B ? A : B
+ *   dtc = dt_sec < 1e-6 ? 0 : dt_sec > 1 / 30 ? 1 / 30 : dt_sec;      T = S * dtc;  not finite: T = 0
+ *   mag = fmax over T, |bb[0..5]|, |start|, |end|, rl (fmax skips NaN);      pad = mag * 2^-20 + 1e-6
+ *   gx = T + pad;  gy = rl + T + pad
+ *   x: [bb[0] - gx, bb[1] + gx]    z: [bb[4] - gx, bb[5] + gx]
+ *   y: [min(bb[2] - gy, end - pad), max(bb[3] + gy, start + pad)]   (a NaN ray end leaves the box's own bound)
+ * A is the airborne branch after gravity and the walker on a zero normal (the given velocity), B the walking branch; a
+ * jump and a state below IDLE do not slide; a delta that is not finite is CLAPGPU_SLIDE_INVALID and moves nothing.
+ * Over-estimating only costs levels.
+ * Conflict: movers i < j (positions in the list) conflict when their reach boxes overlap (closed).
+ * Level: level[j] = 0 without an earlier conflicting mover, else 1 + max level[i] over the earlier movers i that conflict
+ * with j: the longest path, unique, whatever the scheduling.  n_levels = 1 + max level (0 for n == 0).
+ * Two special cases.  A body listed more than once (and a body[k] >= b->n, whose reach box is NaN) is INVALID in both
+ * stages as in the plain call and moves nothing: every such listing is level 0 and conflicts with nobody.  A mover whose
+ * reach box is not finite (a NaN or infinite box row, an infinite ray) STANDS ALONE: it conflicts with every other leveled
+ * mover, so it has a level to itself -- a body whose box says nothing can still cast a valid ray or slide from a finite
+ * position, and nothing bounds what it meets.  The pair search is not given such boxes; the level pass walks n lanes of up
+ * to n steps per round while there is one.
+ * Ordered move: for L = 0 .. n_levels - 1, stages 1 to 5 of clapgpu_characters_move without the push over the movers of
+ * level L in list order (each level takes its own clapgpu_bp_index calls and clears the per-body words, as the plain call
+ * does); then ONE clapgpu_bodies_push over all n movers in list order, so facc is the reference's sequential sum in (k, q)
+ * order; then the flags and the rotation hand-off.  Why this is the one-at-a-time loop: movers of one level cannot touch
+ * each other; a mover's earlier conflicts are done and its later ones have not started; a mover that does not conflict
+ * with it cannot be seen by any of its stages; and no stage reads what the push writes (facc, bflags, the auto-disable
+ * counters: the ground apply and the slide apply of bodies.hip touch pos, lvel, axis, aabb and the geom record alone).
+ *
+ * clapgpu_characters_order moves nothing: it reads m's body, ray_off, motion and velocity and b's aabb, pos and yoffset,
+ * writes reach[n][6] and level[n] (device) and summary[4] (host): n_levels, pair_total, order_bp's status
+ * (clapgpu_bp_status), the relaxation rounds that ran.  pair_total counts the overlapping pairs of leveled boxes, listings
+ * of one body included.  order_bp: a second clapgpu_bp of either kind, created with n_static == 0 and n_max >= n; the
+ * conflicts are clapgpu_bp_collide's pairs over the reach boxes, the levels a relaxation over them (atomicMax(level[j],
+ * level[i] + 1) per pair and round until a round changes nothing, launched in chunks of 8 rounds).
+ * BOTH CALLS SYNCHRONISE THE STREAM, for the pair count, the convergence of the rounds and the level count only; neither
+ * can be captured in a graph, and neither is a stage of clapgpu_frame.
+ * CLAPGPU_ERR_INVALID_ARGUMENTS before any HIP call: what clapgpu_characters_move refuses (clapgpu_characters_order asks
+ * only for what it reads, and for reach, level and summary), a NULL order_bp, a missing b->aabb, a NULL n_levels.
+ * CLAPGPU_ERR_TOO_LARGE, from either call BEFORE ANY BODY HAS MOVED: pair_total > pair_capacity (summary[1] says how many;
+ * retry with more room), or order_bp's status bit 0 (a reach box larger than its top cell; that bit is sticky: retry with
+ * another object of a larger cell).  n == 0 returns CLAPGPU_OK, launches nothing and gives n_levels 0.
+ * A line of characters at touching distance costs one level per character: the reference's own sequential nature.
+ * scratch: *_scratch_bytes bytes of device memory, 256-byte aligned, overwritten; both helpers return 0 for n == 0, the
+ * ordered move's also when clapgpu_characters_move_scratch_bytes does.  level (ordered move) may be NULL.
+ */
+size_t clapgpu_characters_order_scratch_bytes(uint32_t n, uint32_t pair_capacity);
+int    clapgpu_characters_order(void *stream, clapgpu_bp *order_bp, const clapgpu_bodies *b, const clapgpu_world *w,
+                                double dt_sec, const clapgpu_move *m, uint32_t pair_capacity,
+                                double *reach /* [n][6] out */, uint32_t *level /* [n] out */,
+                                uint32_t *summary /* host [4]: n_levels, pair_total, order_bp status, rounds */, void *scratch);
+size_t clapgpu_characters_move_ordered_scratch_bytes(uint32_t n_bodies, uint32_t n, uint32_t pair_capacity);
+int    clapgpu_characters_move_ordered(void *stream, clapgpu_bp *bp, clapgpu_bp *order_bp, const clapgpu_bodies *b,
+                                       const clapgpu_world *w, const clapgpu_geoms *statics, const clapgpu_trimesh *meshes,
+                                       const clapgpu_entities *e, double dt_sec, const clapgpu_move *m, uint32_t pair_capacity,
+                                       uint32_t *level /* [n] device out, may be NULL */, uint32_t *n_levels /* host out */,
+                                       void *scratch);
 
 /* ======================================================================== */
 /* Clustered lighting: lights x screen tiles bitmask (core/light.c)           */
