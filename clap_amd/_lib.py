@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 OK = 0
 ERR_NOMEM = -1
@@ -352,6 +352,7 @@ SYMBOLS = {
     "clapgpu_bp_invalidate": (C.c_int, [C.c_void_p, C.c_void_p]),
     "clapgpu_bp_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "clapgpu_bp_index_status": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "clapgpu_bp_leveled_index": (C.c_int, [C.c_void_p, C.c_int]),
     "clapgpu_ray_cast": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Geoms), C.POINTER(Geoms), C.c_void_p, C.c_uint32,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clapgpu_bodies_ground_collide": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(Geoms), C.c_void_p,

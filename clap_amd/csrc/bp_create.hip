@@ -113,6 +113,20 @@ extern "C" uint32_t clapgpu_bp_cell_slot(const clapgpu_bp *bp, uint32_t level, i
     return bp->levels == 1 ? cell_slot(cx, cy, cz, bp->k.mask) : level_slot(level, cx, cy, cz, bp->k.mask);
 }
 
+// the switch of a leveled object's index; off as calloc leaves it.  Host state only: whatever index the object holds was
+// made for the other setting and is dropped
+extern "C" int clapgpu_bp_leveled_index(clapgpu_bp *bp, int on)
+{
+    if (!bp) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (bp->levels == 1) return CLAPGPU_OK;
+    bp->leveled_index = on != 0;
+    bp->indexed = false;
+    return CLAPGPU_OK;
+}
+
+// geoms_dev.h's scene_grid: a leveled object whose index is switched off: queries through it scan, indexed or not
+__attribute__((visibility("hidden"))) bool clapgpu_bp_scans(const clapgpu_bp *bp) { return bp->levels > 1 && !bp->leveled_index; }
+
 extern "C" void clapgpu_bp_destroy(clapgpu_bp *bp)
 {
     if (!bp) return;
@@ -141,8 +155,13 @@ __attribute__((visibility("hidden"))) unsigned long long *clapgpu_bp_contact_tic
 __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp *bp, uint32_t n, const double *aabb,
                                                                  BpGridView *v)
 {
-    if (!bp || bp->levels > 1 || !bp->indexed || bp->indexed_n != n || (aabb && bp->indexed_aabb != aabb)) return false;
-    v->n = n; v->n_static = bp->n_static; v->cell = bp->cell; v->mask = bp->k.mask; v->n_large = bp->n_large;
+    if (!bp || clapgpu_bp_scans(bp) || !bp->indexed || bp->indexed_n != n || (aabb && bp->indexed_aabb != aabb)) return false;
+    v->n = n; v->n_static = bp->n_static; v->cell = bp->cell; v->mask = bp->k.mask;
+    // a leveled object: the queries read the statics image of one level (bp_levels.h's query_statics_level)
+    v->levels = bp->levels;
+    v->s_level = query_statics_level(bp->levels);
+    v->large_first = bp->levels > 1 ? bp->large_start[v->s_level] : 0u;
+    v->n_large = bp->levels > 1 ? bp->large_start[v->s_level + 1] - v->large_first : bp->n_large;
     v->cell_range = bp->k.cell_range;
     v->recs = bp->k.recs;
     v->s_start = bp->k.s_start;
@@ -157,8 +176,8 @@ __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp
 extern "C" int clapgpu_bp_index_status(void *stream, clapgpu_bp *bp, uint32_t *status)
 {
     if (!bp || !status || !bp->indexed) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    *status = bp->levels > 1 ? 4u : 0u;                                  // leveled: no index was built, queries scan every geom
-    if (!bp->indexed_n || bp->levels > 1) return CLAPGPU_OK;
+    *status = clapgpu_bp_scans(bp) ? 4u : 0u;                            // leveled, switched off: no index was built, queries scan every geom
+    if (!bp->indexed_n || clapgpu_bp_scans(bp)) return CLAPGPU_OK;
     uint64_t w = 0;
     uint32_t epochs[2] = { 0, 0 };
     hipStream_t s = as_stream(stream);

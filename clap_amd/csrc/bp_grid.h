@@ -109,6 +109,10 @@ struct BpGridView {
     const uint64_t *index;               // INDEX_WORDS control words of the index
     const uint32_t *ctrl;                // the object's control words (epochs)
     double s_bounds[6];                  // union of the registered (not large) statics' boxes; min > max: none
+    // a leveled object (bp_levels.h; 1: none of this is read): cell is level 0's, the bodies' records carry their level,
+    // s_start holds one CSR of buckets + 1 starts per level, and the queries read level s_level's
+    uint32_t levels, s_level;
+    uint32_t large_first;                // the large statics are s_lrecs[large_first .. large_first + n_large) (level s_level's; one level: 0)
 };
 
 } // namespace clapgpu
@@ -118,6 +122,8 @@ struct BpGridView {
 struct clapgpu_bp;
 // geoms_dev.h's scene_grid, for rays.hip and slide.hip: true when `bp` holds an index over exactly (n, aabb) (aabb == nullptr: any array of n boxes); fills *v
 __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp *bp, uint32_t n, const double *aabb, clapgpu::BpGridView *v);
+// ... and whether `bp` (not NULL) is a leveled object with its index switched off (clapgpu_bp_leveled_index): it never holds a view
+__attribute__((visibility("hidden"))) bool clapgpu_bp_scans(const clapgpu_bp *bp);
 // contacts.hip (k_contacts_geoms_both): the one-launch form keeps its ticket + counts in the object's control words
 __attribute__((visibility("hidden"))) unsigned long long *clapgpu_bp_contact_ticket(clapgpu_bp *bp);
 // bodies.hip: the bin arrays for a step that is about to write and bin the n boxes of `aabb`, recorded as pre-binned

@@ -55,4 +55,19 @@ __host__ __device__ __forceinline__ void coarse_cells(double a0, double a1, doub
     if (*hi > *lo + 2) *hi = *lo + 2;
 }
 
+// The level S whose statics image the QUERIES through a leveled index read (grid_query_dev.h), counted down from the top
+// level (an object of fewer levels: level 0).  0 would be the top level, whose cell is the one a one-level object for
+// the same world would have been given, so the statics would cost a query what they cost it there: a block of 4^3 top
+// cells holds many small statics, and a query walks them all.  Two below: at 262 144 mixed bodies on six levels and
+// 5 000 statics of 0.1 .. 3 units, 65 536 ground rays take 862 us against 2 423 us, 65 536 sweeps 6.1 ms against 7.2 ms
+// (one below: 1 114 us / 6.2 ms, three below: 838 us / 6.0 ms; profiles/bp_levels_index/).  The price: a static that
+// spans more than 64 blocks of the finer level is in the large list, which every query tests.  Results do not depend on
+// S (every visitor tests each candidate itself); change it only with a measurement (tools/bp_levels_index_time.py),
+// written down there.
+constexpr uint32_t BPL_QUERY_STATICS_BELOW_TOP = 2;
+__host__ __device__ __forceinline__ uint32_t query_statics_level(uint32_t levels)
+{
+    return levels - 1u > BPL_QUERY_STATICS_BELOW_TOP ? levels - 1u - BPL_QUERY_STATICS_BELOW_TOP : 0u;
+}
+
 } // namespace clapgpu

@@ -211,11 +211,18 @@ __attribute__((visibility("hidden"))) int clapgpu_bpl_bin(hipStream_t s, const B
     return CLAPGPU_OK;
 }
 
+__attribute__((visibility("hidden"))) int clapgpu_bpl_scatter(hipStream_t s, const BplK &q)
+{
+    hipLaunchKernelGGL(k_bpl_scatter, dim3((q.k.n + PB - 1) / PB), dim3(PB), 0, s, q);
+    CLAPGPU_LAUNCH_CHECK("k_bpl_scatter");
+    return CLAPGPU_OK;
+}
+
 __attribute__((visibility("hidden"))) int clapgpu_bpl_pairs(hipStream_t s, const BplK &q)
 {
     const dim3 grid((q.k.n + PB - 1) / PB);
-    hipLaunchKernelGGL(k_bpl_scatter, grid, dim3(PB), 0, s, q);
-    CLAPGPU_LAUNCH_CHECK("k_bpl_scatter");
+    const int rc = clapgpu_bpl_scatter(s, q);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_bpl_search, grid, dim3(PB), 0, s, q);
     CLAPGPU_LAUNCH_CHECK("k_bpl_search");
     hipLaunchKernelGGL(k_bpl_emit, dim3(q.k.n_tiles), dim3(BP_EMIT_TILE), 0, s, q.k);

@@ -56,13 +56,16 @@ struct BplK {
 } // namespace clapgpu
 
 // bp_levels.hip, for clapgpu_bp_collide on a leveled object: launch 1 (bin), and launches 3 to 5 (scatter, search, emit);
-// launch 2 in between is broadphase.hip's k_bp_cells, which reads slots and knows no level
+// launch 2 in between is broadphase.hip's k_bp_cells, which reads slots and knows no level.  clapgpu_bp_index with the
+// leveled index switched on runs launch 1, k_bp_cells and launch 3 alone (clapgpu_bpl_scatter).
 __attribute__((visibility("hidden"))) int clapgpu_bpl_bin(hipStream_t s, const clapgpu::BplK &q);
+__attribute__((visibility("hidden"))) int clapgpu_bpl_scatter(hipStream_t s, const clapgpu::BplK &q);
 __attribute__((visibility("hidden"))) int clapgpu_bpl_pairs(hipStream_t s, const clapgpu::BplK &q);
 
 struct clapgpu_bp {
     uint32_t n_max, buckets, n_static, n_large, n_tiles;
     uint32_t levels;               // 1: the one-level grid of broadphase.hip; more: bp_levels.hip's kernels
+    bool leveled_index;            // clapgpu_bp_leveled_index: levels > 1 and clapgpu_bp_index builds an index (off: queries scan)
     uint32_t large_start[CLAPGPU_BP_LEVELS_MAX + 1];
     double cell;
     void *dev;                     // one allocation

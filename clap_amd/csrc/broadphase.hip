@@ -462,12 +462,13 @@ void k_bp_emit(BpK k)
     }
 }
 
-// clapgpu_bp_index's fourth launch: the indexed boxes' bounds and "an edge exceeds `cell`" into the index's own control
-// words (bp_grid.h), which the host set to all ones in front of it.  The sticky bit 0 of CTRL_STATUS is not this flag: it
-// reports any oversized box since the object was made, this one the boxes of the current index only.
+// clapgpu_bp_index's fourth launch: the indexed boxes' bounds and "an edge exceeds `limit`" into the index's own control
+// words (bp_grid.h), which the host set to all ones in front of it.  limit: the cell of a one-level object, the top
+// level's cell of a leveled one.  The sticky bit 0 of CTRL_STATUS is not this flag: it reports any oversized box since the
+// object was made, this one the boxes of the current index only.
 constexpr int BP_BOUNDS_BLOCKS = 512;
 __global__ __launch_bounds__(PB)
-void k_bp_index_bounds(BpK k)
+void k_bp_index_bounds(BpK k, double limit)
 {
     __shared__ double red[6][PB / WAVE];
     __shared__ uint32_t big[PB / WAVE];
@@ -477,7 +478,7 @@ void k_bp_index_bounds(BpK k)
     for (uint32_t i = blockIdx.x * PB + threadIdx.x; i < k.n; i += gridDim.x * PB) {
         double bb[6];
         load_box(k.aabb, i, bb);
-        if (box_oversized(bb, k.cell)) over = 1;
+        if (box_oversized(bb, limit)) over = 1;
         // finite coordinates only: a geom at infinity or NaN never hits (ray_colliders_dev.h), and the bounds stay finite
         for (int a = 0; a < 3; a++) {
             if (isfinite(bb[2 * a])) m[a] = fmin(m[a], bb[2 * a]);
@@ -635,19 +636,33 @@ __attribute__((visibility("hidden"))) int clapgpu_bp_prebin(void *stream, clapgp
 // bins the same boxes once more after its scatter.  The next collide -- eager, or captured in a graph whose collide has
 // no bin launch (FrameLoop.capture with prebin) -- then finds the counters it expects.  Ranks inside a cell may come out
 // in another order; the collide's lists are canonical whatever order the atomics took.
+// A leveled object whose index is switched on (clapgpu_bp_leveled_index) runs the same four launches with bp_levels.hip's
+// bin and scatter around k_bp_cells; it is never pre-binned, so nothing is binned back, and the bounds launch tests the
+// edges against the top level's cell.  Switched off (as created) it launches nothing and the queries scan.
 extern "C" int clapgpu_bp_index(void *stream, clapgpu_bp *bp, uint32_t n, const double *aabb)
 {
     if (!bp || (n && !aabb)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (n > bp->n_max) return CLAPGPU_ERR_TOO_LARGE;
     bp->indexed = false;
-    if (bp->levels > 1) {                                        // no leveled index yet: nothing is launched, queries scan
+    if (bp->levels > 1 && !bp->leveled_index) {                  // no index asked for: nothing is launched, queries scan
         bp->indexed = true; bp->indexed_aabb = aabb; bp->indexed_n = n;       // (clapgpu_bp_index_status: bit 2)
         return CLAPGPU_OK;
     }
     hipStream_t s = as_stream(stream);
     const BpK k = grid_k(bp, n, aabb);
     CLAPGPU_HIP(hipMemsetAsync(k.ctrl + CTRL_INDEX_WORD, 0xff, INDEX_WORDS * sizeof(uint64_t), s));
-    if (n) {
+    const uint32_t bounds_blocks = (n + PB - 1) / PB < BP_BOUNDS_BLOCKS ? (n + PB - 1) / PB : BP_BOUNDS_BLOCKS;
+    if (n && bp->levels > 1) {
+        const BplK q = bpl_k(bp, k);
+        int rc = clapgpu_bpl_bin(s, q);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_bp_cells, dim3((bp->buckets + BP_CELLS_BLOCK / WAVE - 1) / (BP_CELLS_BLOCK / WAVE)), dim3(BP_CELLS_BLOCK), 0, s, k);
+        CLAPGPU_LAUNCH_CHECK("k_bp_cells");
+        rc = clapgpu_bpl_scatter(s, q);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_bp_index_bounds, dim3(bounds_blocks), dim3(PB), 0, s, k, ldexp(bp->cell, (int)bp->levels - 1));
+        CLAPGPU_LAUNCH_CHECK("k_bp_index_bounds");
+    } else if (n) {
         bool prebinned;
         int rc = build_grid(stream, bp, k, false, &prebinned);
         if (rc) return rc;
@@ -655,8 +670,7 @@ extern "C" int clapgpu_bp_index(void *stream, clapgpu_bp *bp, uint32_t n, const 
             rc = launch_bin(s, k);
             if (rc) return rc;
         }
-        const uint32_t blocks = (n + PB - 1) / PB;
-        hipLaunchKernelGGL(k_bp_index_bounds, dim3(blocks < BP_BOUNDS_BLOCKS ? blocks : BP_BOUNDS_BLOCKS), dim3(PB), 0, s, k);
+        hipLaunchKernelGGL(k_bp_index_bounds, dim3(bounds_blocks), dim3(PB), 0, s, k, k.cell);
         CLAPGPU_LAUNCH_CHECK("k_bp_index_bounds");
     } else {
         int rc = clapgpu_bp_invalidate(stream, bp);              // no boxes: every cell is empty, as k_bp_cells leaves them

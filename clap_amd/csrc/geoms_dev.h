@@ -64,14 +64,15 @@ static inline bool body_geoms(const clapgpu_bodies *b, clapgpu_geoms *g)
 
 // The index of a scene's query.  meshes (or NULL) must be built for n_static statics.  bp == NULL: *grid = false.
 // Otherwise bp must be indexed over exactly (n, aabb) (aabb == NULL: any n boxes) and created with n_static statics:
-// *v is its view and *grid = true.  A leveled bp (clapgpu_bp_create_levels) has no index the queries can read: *grid =
-// false, the scan they take for bp == NULL.
+// *v is its view and *grid = true.  A leveled bp (clapgpu_bp_create_levels) whose index is switched off
+// (clapgpu_bp_leveled_index; as created) has no index the queries can read: *grid = false, the scan they take for
+// bp == NULL.  Switched on it is held to the same rule as a one-level object.
 static inline int scene_grid(const clapgpu_bp *bp, uint32_t n, const double *aabb, uint32_t n_static, const clapgpu_trimesh *meshes,
                              clapgpu::BpGridView *v, bool *grid)
 {
     *grid = false;
     if (meshes && clapgpu::trimesh_set(meshes).n_statics != n_static) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (!bp || clapgpu_bp_levels(bp) > 1) return CLAPGPU_OK;
+    if (!bp || clapgpu_bp_scans(bp)) return CLAPGPU_OK;
     if (!clapgpu_bp_grid_view(bp, n, aabb, v) || v->n_static != n_static) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     *grid = true;
     return CLAPGPU_OK;

@@ -96,10 +96,17 @@ __device__ __forceinline__ void scan_all(const CastK &k, const Ray &r, uint32_t 
 }
 
 // false: the clipped segment has more pieces than a scan of every geom has candidates per lane (far-flung boxes); the
-// caller scans instead, which also bounds the time one wavefront can spend on a ray
+// caller scans instead, which also bounds the time one wavefront can spend on a ray.
+// LEVELED (g.levels > 1): the bounds are grown by the top level's cell, the large list of the statics' level is visited
+// once, and every level cuts the clipped segment into pieces of at most ITS cell and visits its own cells along them,
+// the statics on their level's pieces alone; the limit holds the pieces of all levels together.
+template <bool LEVELED>
 __device__ bool scan_grid(const CastK &k, const Ray &r, uint32_t skip_key, Best &b)
 {
     const BpGridView &g = k.g;
+    const uint32_t levels = grid_levels<LEVELED>(g);
+    double top = g.cell;                                                     // the coarsest cell
+    for (uint32_t L = 1; L < levels; L++) top *= 2.0;
 
     // the scene's bounds: indexed boxes joined with the registered statics, grown by a cell
     double bnd[6];
@@ -109,8 +116,8 @@ __device__ bool scan_grid(const CastK &k, const Ray &r, uint32_t skip_key, Best 
             lo = fmin(lo, order_value(g.index[a]));
             hi = fmax(hi, order_value(~g.index[3 + a]));
         }
-        bnd[2 * a] = lo - g.cell;
-        bnd[2 * a + 1] = hi + g.cell;
+        bnd[2 * a] = lo - top;
+        bnd[2 * a + 1] = hi + top;
     }
     const bool any = bnd[0] <= bnd[1] && bnd[2] <= bnd[3] && bnd[4] <= bnd[5];   // else: nothing but the large statics
     const double t0 = any ? segment_enters(r, bnd) : INFINITY;
@@ -120,46 +127,54 @@ __device__ bool scan_grid(const CastK &k, const Ray &r, uint32_t skip_key, Best 
         if (r.u[a] != 0) t1 = fmin(t1, fmax((bnd[2 * a] - r.s[a]) / r.u[a], (bnd[2 * a + 1] - r.s[a]) / r.u[a]));
     if (t1 < t0) t1 = t0;
     const double span = pieces ? t1 - t0 : 0.0;
-    const double np_d = ceil(span / g.cell);
+    double c = g.cell, np_d = ceil(span / c);
+    for (uint32_t L = 1; L < levels; L++) { c *= 2.0; np_d += ceil(span / c); }
     // the bounds are finite (k_bp_index_bounds takes finite coordinates only), so is span; the limit keeps a ray through
     // a sparse, far-flung scene from costing more than the scan
     const double limit = 64.0 + (double)(k.bodies.n + k.statics.n) / 256.0;
     if (!(np_d <= limit)) return false;
-    const uint32_t np = !pieces ? 0u : np_d < 1.0 ? 1u : (uint32_t)np_d;
 
     auto test = [&](bool valid, bool is_static, uint32_t i) {
         if (!valid) return;
         if (is_static) test_geom(r, k.statics, i, KEY_STATIC | i, skip_key, b, k.meshed);
         else test_geom(r, k.bodies, i, i, skip_key, b, k.meshed);
     };
-    grid_visit_large(g, test);
-    GridRange prev;                                                          // the previous piece's: none
-    for (uint32_t j = 0; j < np; j++) {
-        const double ta = t0 + span * ((double)j / np), tb = (j + 1 == np) ? t1 : t0 + span * ((double)(j + 1) / np);
-        double lo[3], hi[3];
-        for (int a = 0; a < 3; a++) {
-            const double pa = r.s[a] + ta * r.u[a], pb = r.s[a] + tb * r.u[a];
-            lo[a] = fmin(pa, pb); hi[a] = fmax(pa, pb);
+    grid_visit_large<LEVELED>(g, test);
+    c = g.cell;
+    for (uint32_t L = 0; L < levels; L++, c *= 2.0) {
+        const double npl_d = ceil(span / c);
+        const uint32_t np = !pieces ? 0u : npl_d < 1.0 ? 1u : (uint32_t)npl_d;
+        GridRange prev;                                                      // the previous piece's: none
+        for (uint32_t j = 0; j < np; j++) {
+            const double ta = t0 + span * ((double)j / np), tb = (j + 1 == np) ? t1 : t0 + span * ((double)(j + 1) / np);
+            double lo[3], hi[3];
+            for (int a = 0; a < 3; a++) {
+                const double pa = r.s[a] + ta * r.u[a], pb = r.s[a] + tb * r.u[a];
+                lo[a] = fmin(pa, pb); hi[a] = fmax(pa, pb);
+            }
+            const GridRange piece = grid_range(c, lo, hi);
+            grid_visit<LEVELED>(g, L, grid_level_statics<LEVELED>(g, L), piece, &prev, test);   // what the last piece looked up is skipped
+            prev = piece;
         }
-        const GridRange piece = grid_range(g, lo, hi);
-        grid_visit(g, piece, &prev, test);                                   // what the last piece looked up is skipped
-        prev = piece;
     }
     return true;
 }
 
-// one ray on the whole wave: the best hit (every lane) and the ray's flags
+// one ray on the whole wave: the best hit (every lane) and the ray's flags.  LEVELED: k.g is a leveled index (the host
+// picks the kernel by it, so a one-level index and the scan run the code they ran)
+template <bool LEVELED>
 __device__ __forceinline__ uint32_t cast(const CastK &k, const Ray &r, uint32_t skip_key, Best &b)
 {
     b.depth = INFINITY; b.key = KEY_NONE; b.other = INFINITY;
     for (int a = 0; a < 3; a++) { b.pos[a] = 0; b.normal[a] = 0; }
     // the grid, unless: no index; the index may not be used (grid_usable); or more pieces than the scan's work
-    if (!k.grid || !grid_usable(k.g) || !scan_grid(k, r, skip_key, b)) scan_all(k, r, skip_key, b);
+    if (!k.grid || !grid_usable(k.g) || !scan_grid<LEVELED>(k, r, skip_key, b)) scan_all(k, r, skip_key, b);
     reduce_best(b);
     return unresolved(b.other, r.len, b.key, b.depth);
 }
 
 // other: NULL, or [n] where a mesh pass follows: the first entry into an OTHER static without a mesh, for its flags
+template <bool LEVELED>
 __global__ __launch_bounds__(RB)
 void k_ray_cast(CastK k, uint32_t n, const double *ray, const int32_t *skip, double *dist, int32_t *hit, double *contact,
                 uint32_t *flags, double *other)
@@ -173,7 +188,7 @@ void k_ray_cast(CastK k, uint32_t n, const double *ray, const int32_t *skip, dou
         return;
     }
     Best b;
-    const uint32_t f = cast(k, r, skip_key_of(skip ? skip[i] : -1), b);
+    const uint32_t f = cast<LEVELED>(k, r, skip_key_of(skip ? skip[i] : -1), b);
     if (lane == 0) {
         hit[i] = hit_of(b.key);
         if (b.key != KEY_NONE) {
@@ -190,6 +205,7 @@ void k_ray_cast(CastK k, uint32_t n, const double *ray, const int32_t *skip, dou
 // moved[body]: bit 0 = the apply launch will move it (unless it is listed twice), bits 1.. = rays cast for it.
 // other != NULL: a mesh pass follows and decides; this launch writes the hit so far, its normal (when the flags so far are
 // clear: the mesh pass can only clear them) and `other`
+template <bool LEVELED>
 __global__ __launch_bounds__(RB)
 void k_ground_rays(CastK k, uint32_t n, const double *pos, const double *yoffset, const uint32_t *body, const double *ray_off,
                    const uint8_t *grounded, uint8_t *grounded_out, float *normal, double *dist, int32_t *hit, uint32_t *flags,
@@ -212,7 +228,7 @@ void k_ground_rays(CastK k, uint32_t n, const double *pos, const double *yoffset
         f = CLAPGPU_RAY_INVALID;
         b.key = KEY_NONE;
     } else {
-        f = cast(k, r, i, b);
+        f = cast<LEVELED>(k, r, i, b);
     }
     if (lane == 0) {
         if (other && !(f & CLAPGPU_RAY_INVALID)) {                           // ground_decide's stores of the hit, restated
@@ -244,6 +260,9 @@ static int cast_scene(CastK &k, clapgpu_bp *bp, const clapgpu_geoms *bodies, con
     k.meshed = meshes ? trimesh_set(meshes).static_mesh : nullptr;
     return scene_grid(bp, bodies->n, body_aabb, statics->n, meshes, &k.g, &k.grid);
 }
+
+// the kernels of a leveled index are instantiations of their own: the others keep their code and their registers
+static bool leveled(const CastK &k) { return k.grid && k.g.levels > 1; }
 
 // ------------------------------------------------------------------------------------------------- the two passes
 // `other` between the first pass and the mesh pass of a call over n > 0 rays: the caller's [n] doubles (move.hip), or
@@ -291,8 +310,8 @@ extern "C" int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geom
     Between b;
     rc = take_between(s, meshes && flags, n_rays, nullptr, b);              // no flags asked for: `other` is not needed
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ray_cast, dim3((n_rays + RB / WAVE - 1) / (RB / WAVE)), dim3(RB), 0, s, k, n_rays, ray, skip, dist, hit,
-                       contact, flags, b.other);
+    hipLaunchKernelGGL(leveled(k) ? k_ray_cast<true> : k_ray_cast<false>, dim3((n_rays + RB / WAVE - 1) / (RB / WAVE)), dim3(RB), 0,
+                       s, k, n_rays, ray, skip, dist, hit, contact, flags, b.other);
     MeshPass p;
     memset(&p, 0, sizeof(p));
     p.n = n_rays; p.ray = ray; p.skip = skip; p.dist = dist; p.contact = contact; p.hit = hit; p.flags = flags;
@@ -326,8 +345,9 @@ __attribute__((visibility("hidden"))) int clapgpu_bodies_ground_collide_on(void 
     Between bt;
     rc = take_between(s, meshes != nullptr, n, other, bt);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ground_rays, dim3((n + RB / WAVE - 1) / (RB / WAVE)), dim3(RB), 0, s, k, n, b->pos, b->yoffset, body,
-                       ray_off, grounded, grounded_out, normal, dist, hit, flags, scratch, bt.other);
+    hipLaunchKernelGGL(leveled(k) ? k_ground_rays<true> : k_ground_rays<false>, dim3((n + RB / WAVE - 1) / (RB / WAVE)), dim3(RB), 0,
+                       s, k, n, b->pos, b->yoffset, body, ray_off, grounded, grounded_out, normal, dist, hit, flags, scratch,
+                       bt.other);
     MeshPass p;                                                              // the decision on the merged hit
     memset(&p, 0, sizeof(p));
     p.n = n; p.dist = dist; p.hit = hit; p.flags = flags;

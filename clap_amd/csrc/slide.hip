@@ -102,21 +102,28 @@ __device__ __forceinline__ void gather_all(const SlideScene &k, uint32_t self, c
         append(list, count, body_meets(k, base + lane, self, lo, hi), 0x80000000u | (base + lane));
 }
 
-// the swept box's cells, their blocks' statics and the large statics; false: more lookups than a scan tests geoms per lane
+// the swept box's cells, their blocks' statics and the large statics; false: more lookups than a scan tests geoms per lane.
+// LEVELED (g.levels > 1): the swept box's cells of every level and the blocks of the statics' level; the limit holds the
+// lookups of all levels together, so a large mover among small bodies scans
+template <bool LEVELED>
 __device__ bool gather_grid(const SlideScene &k, uint32_t self, const double (&lo)[3], const double (&hi)[3],
                             uint32_t *list, uint32_t &count, bool &other)
 {
     const BpGridView &g = k.g;
+    const uint32_t levels = grid_levels<LEVELED>(g);
     count = 0;
     other = false;
-    const GridRange range = grid_range(g, lo, hi);
-    if (!(grid_lookups(g, range) <= 64.0 + (double)(k.bodies.n + k.statics.n) / 64.0)) return false;
+    double c = g.cell, lookups = grid_lookups(g, grid_range(c, lo, hi), grid_level_statics<LEVELED>(g, 0));
+    for (uint32_t L = 1; L < levels; L++) { c *= 2.0; lookups += grid_lookups(g, grid_range(c, lo, hi), grid_level_statics<LEVELED>(g, L)); }
+    if (!(lookups <= 64.0 + (double)(k.bodies.n + k.statics.n) / 64.0)) return false;
     auto take = [&](bool valid, bool is_static, uint32_t i) {
         const bool pred = valid && (is_static ? static_meets(k, i, lo, hi, other) : body_meets(k, i, self, lo, hi));
         append(list, count, pred, is_static ? i : 0x80000000u | i);
     };
-    grid_visit_large(g, take);
-    grid_visit(g, range, nullptr, take);
+    grid_visit_large<LEVELED>(g, take);
+    c = g.cell;
+    for (uint32_t L = 0; L < levels; L++, c *= 2.0)
+        grid_visit<LEVELED>(g, L, grid_level_statics<LEVELED>(g, L), grid_range(c, lo, hi), nullptr, take);
     return true;
 }
 
@@ -154,8 +161,9 @@ __device__ __forceinline__ void sort_unique(uint32_t *list, uint32_t &count)
 
 // One sweep of `probe` (body `self`, at the position it starts from, its box there `bb`) along delta, |delta| =
 // delta_len >= 1e-6f and finite: gather, then march.  list: SLIDE_CAND words of this wavefront's LDS.  Returns
-// CLAPGPU_SLIDE_UNRESOLVED or 0; frac / normal / hit as phys_body_sweep_capsule leaves them.
-template <bool MESH, typename T>
+// CLAPGPU_SLIDE_UNRESOLVED or 0; frac / normal / hit as phys_body_sweep_capsule leaves them.  LEVELED: k.g is a leveled
+// index (the host picks the kernel by it, so a one-level index and the scan run the code they ran).
+template <bool MESH, bool LEVELED, typename T>
 __device__ __forceinline__ uint32_t sweep_once(const SlideScene &k, phd::Geom &probe, const double (&bb)[6], uint32_t self,
                                                const float (&delta)[3], float delta_len, uint32_t *list, const SweepLds &L,
                                                T &&touched, float &frac, float (&normal)[3], int32_t &hit)
@@ -167,7 +175,7 @@ __device__ __forceinline__ uint32_t sweep_once(const SlideScene &k, phd::Geom &p
     // the grid, unless: no index; the index may not be used (grid_usable); or too many cells
     const bool grid = k.grid && grid_usable(k.g);
     wave_lds_fence();                                                        // the list's last readers are done
-    if (grid && gather_grid(k, self, lo, hi, list, count, other)) {
+    if (grid && gather_grid<LEVELED>(k, self, lo, hi, list, count, other)) {
         if (count <= SLIDE_CAND) {
             wave_lds_fence();
             sort_unique(list, count);
@@ -201,7 +209,7 @@ __device__ __forceinline__ float vec3_len(const float (&v)[3])
     return sqrtf(p);
 }
 
-template <bool MESH>
+template <bool MESH, bool LEVELED>
 __global__ __launch_bounds__(SB)
 void k_sweep_grid(SlideScene k, uint32_t n_sweeps, const uint32_t *sweep_body, const float *delta_in, float *frac_out,
                   float *normal_out, int32_t *hit_out, uint32_t *flags)
@@ -232,7 +240,7 @@ void k_sweep_grid(SlideScene k, uint32_t n_sweeps, const uint32_t *sweep_body, c
             else
                 phd::geom_aabb(probe.pos, probe.radius, probe.length, probe.axis, bb);
             const SweepLds lds = { stk, ltri, lslot };
-            f = sweep_once<MESH>(k, probe, bb, self, delta, delta_len, lists[threadIdx.x / WAVE], lds, [](uint32_t) {}, frac,
+            f = sweep_once<MESH, LEVELED>(k, probe, bb, self, delta, delta_len, lists[threadIdx.x / WAVE], lds, [](uint32_t) {}, frac,
                                  normal, hit);
         }
     }
@@ -275,7 +283,7 @@ void k_slide_mark(uint32_t n, const uint32_t *body, uint32_t n_bodies, uint32_t 
 
 // dt: the clamped frame delta.  stash[body][3]: where the mover ends, for the apply launch (the body's lvel, which that
 // launch zeroes).  Nothing any sweep reads is written here: every mover sees the others where they were before the call.
-template <bool MESH>
+template <bool MESH, bool LEVELED>
 __global__ __launch_bounds__(SB)
 void k_slide_decide(SlideScene k, SlideK s, double dt, uint32_t *scratch, double *stash)
 {
@@ -326,7 +334,7 @@ void k_slide_decide(SlideScene k, SlideK s, double dt, uint32_t *scratch, double
                 phd::geom_aabb(p, probe.radius, probe.length, probe.axis, bb);
                 float frac, normal[3];
                 int32_t hit;
-                f |= sweep_once<MESH>(k, probe, bb, self, delta, len, lists[threadIdx.x / WAVE], lds,
+                f |= sweep_once<MESH, LEVELED>(k, probe, bb, self, delta, len, lists[threadIdx.x / WAVE], lds,
                                       [&](uint32_t id) {
                                           if ((scratch[id] >> 1) != 1u) return;      // no mover of this batch
                                           if (t_id == CAND_NONE) t_id = id;
@@ -419,11 +427,13 @@ extern "C" int clapgpu_sweep_capsules_grid(void *stream, clapgpu_bp *bp, const c
     if (n_sweeps && (!sweep_body || !delta || !frac || !normal || !hit)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (n_sweeps == 0) return CLAPGPU_OK;
     hipStream_t s = as_stream(stream);
+    const bool leveled = k.grid && k.g.levels > 1;     // instantiations of their own: the others keep their code and registers
     if (meshes)
-        hipLaunchKernelGGL(k_sweep_grid<true>, dim3(n_sweeps), dim3(WAVE), 0, s, k, n_sweeps, sweep_body, delta, frac, normal, hit, flags);
-    else
-        hipLaunchKernelGGL(k_sweep_grid<false>, dim3((n_sweeps + SB / WAVE - 1) / (SB / WAVE)), dim3(SB), 0, s, k, n_sweeps,
+        hipLaunchKernelGGL((leveled ? k_sweep_grid<true, true> : k_sweep_grid<true, false>), dim3(n_sweeps), dim3(WAVE), 0, s, k, n_sweeps,
                            sweep_body, delta, frac, normal, hit, flags);
+    else
+        hipLaunchKernelGGL((leveled ? k_sweep_grid<false, true> : k_sweep_grid<false, false>), dim3((n_sweeps + SB / WAVE - 1) / (SB / WAVE)),
+                           dim3(SB), 0, s, k, n_sweeps, sweep_body, delta, frac, normal, hit, flags);
     CLAPGPU_LAUNCH_CHECK("k_sweep_grid");
     return CLAPGPU_OK;
 }
@@ -450,11 +460,13 @@ extern "C" int clapgpu_characters_slide(void *stream, clapgpu_bp *bp, const clap
     SlideK sk;
     sk.n = sl->n; sk.body = sl->body; sk.velocity = sl->velocity; sk.airborne = sl->airborne; sk.first_frac = sl->first_frac;
     sk.push_hit = sl->push_hit; sk.flags = sl->flags;
+    const bool leveled = k.grid && k.g.levels > 1;
     if (meshes)
-        hipLaunchKernelGGL(k_slide_decide<true>, dim3(sl->n), dim3(WAVE), 0, s, k, sk, dt_sec, scratch, b->lvel);
+        hipLaunchKernelGGL((leveled ? k_slide_decide<true, true> : k_slide_decide<true, false>), dim3(sl->n), dim3(WAVE), 0, s, k, sk,
+                           dt_sec, scratch, b->lvel);
     else
-        hipLaunchKernelGGL(k_slide_decide<false>, dim3((sl->n + SB / WAVE - 1) / (SB / WAVE)), dim3(SB), 0, s, k, sk, dt_sec,
-                           scratch, b->lvel);
+        hipLaunchKernelGGL((leveled ? k_slide_decide<false, true> : k_slide_decide<false, false>), dim3((sl->n + SB / WAVE - 1) / (SB / WAVE)),
+                           dim3(SB), 0, s, k, sk, dt_sec, scratch, b->lvel);
     CLAPGPU_LAUNCH_CHECK("k_slide_decide");
     rc = clapgpu_bodies_slide_apply(stream, b, sl->n, sl->body, sl->flags, scratch);
     if (rc) return rc;

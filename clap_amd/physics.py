@@ -18,12 +18,12 @@ from .characters import CharacterMoves  # noqa: F401  (physics.CharacterMoves: t
 
 class PhysWorld:
     def __init__(self, bodies, statics=None, pair_capacity=None, device="cuda:0", static_pair_capacity=None, geom_records=True,
-                 forces=False, bp_levels=1):
+                 forces=False, bp_levels=1, leveled_index=False):
         """bodies: dict from synth.sphere_bodies() / synth.capsule_bodies(); statics: float64 [ns, 6]
         (minx,maxx,miny,maxy,minz,maxz), host array: binned once by clapgpu_bp_create.  forces: give the bodies a force
         accumulator (clapgpu_bodies.facc, zeros or bodies["facc"]): the step consumes it, bodies_push adds to it.
         bp_levels > 1: a multi-level broadphase grid (clapgpu_bp_create_levels) whose level-0 cell is bodies["cell"], for
-        bodies of mixed sizes: same pair lists; queries through it scan every geom."""
+        bodies of mixed sizes: same pair lists; queries through it scan every geom unless leveled_index (bp_leveled_index)."""
         self.device = dev = torch.device(device)
         self.n = n = int(bodies["n"])
         t = lambda k, dt: upload(bodies[k], dt, dev)
@@ -80,6 +80,8 @@ class PhysWorld:
         else:
             _lib.check(_lib.lib().clapgpu_bp_create(C.byref(self._bp), n, self.cell, self.n_static, st_ptr), "clapgpu_bp_create")
         self.statics_ptr = _lib.lib().clapgpu_bp_static_aabb(self._bp)     # device copy owned by the broadphase object
+        if leveled_index:
+            self.bp_leveled_index(True)
         # what the methods below allocate on demand (the alloc_* methods) or keep from their last call
         self.material = self.static_material = None                        # set_materials / contacts_static, or assigned
         self._static_geoms = self._static_keep = None                      # static_geoms / set_static_geoms
@@ -530,6 +532,12 @@ class PhysWorld:
     def bp_index(self):
         """The broadphase grid of the bodies' CURRENT boxes (clapgpu_bp_index): what ray_cast(grid=True) looks up."""
         _lib.check(_lib.lib().clapgpu_bp_index(_stream(), self._bp, self.n, _ptr(self.aabb)), "clapgpu_bp_index")
+
+    def bp_leveled_index(self, on):
+        """Switch the index of a leveled broadphase object on or off (clapgpu_bp_leveled_index; off as created).  On:
+        bp_index() builds an index over all levels and the queries read it; off: bp_index() launches nothing and they scan
+        every geom.  Either way the index held is dropped: bp_index() again.  A one-level world: accepted, no effect."""
+        _lib.check(_lib.lib().clapgpu_bp_leveled_index(self._bp, 1 if on else 0), "clapgpu_bp_leveled_index")
 
     def bp_index_status(self):
         st = C.c_uint32(0)

@@ -58,7 +58,7 @@ void clapgpu_test_fail_after(int launches);
 /* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
  * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
  * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
-#define CLAPGPU_ABI_VERSION 43u
+#define CLAPGPU_ABI_VERSION 44u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -879,7 +879,8 @@ int clapgpu_contacts_sphere_box(void *stream, const clapgpu_bodies *b, uint32_t 
  * takes a clapgpu_bp takes either kind, and the outputs of clapgpu_bp_collide keep their contract word for word.
  * levels == 1 is the object of clapgpu_bp_create (which stays the call it is); levels == 0 or above
  * CLAPGPU_BP_LEVELS_MAX, or levels > 1 with n_max > 2^28: CLAPGPU_ERR_INVALID_ARGUMENTS.  A leveled object is never
- * pre-binned (clapgpu_bodies_step_prebin runs the plain step) and holds no index: see clapgpu_bp_index.
+ * pre-binned (clapgpu_bodies_step_prebin runs the plain step) and holds no index unless it is asked to
+ * (clapgpu_bp_leveled_index, ABI 44): see clapgpu_bp_index.
  *   clapgpu_bp_levels     the levels of the object (0 for NULL)
  *   clapgpu_bp_cell_slot  host only, no device work: the cell slot of cell (cx, cy, cz) of `level` in this object (for
  *                         tests and tools); 0xffffffff for a level the object does not have
@@ -976,9 +977,27 @@ int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_g
  * index whose count has moved on scans every geom instead (same results, brute-force time) -- index after replays.
  * clapgpu_bp_index_status: host sync; bit 0: an indexed box's edge exceeds `cell` (this index only, unlike the sticky
  * bit 0 of clapgpu_bp_status); bit 1: the boxes were binned again since the index (a replayed collide or prebinning
- * step); bit 2 (value 4): the object is leveled (clapgpu_bp_create_levels with levels > 1): clapgpu_bp_index launched
- * nothing and every query through it scans every geom, as with bp == NULL.  In all three cases rays through this index
- * scan every geom.  CLAPGPU_ERR_INVALID_ARGUMENTS when not indexed.
+ * step); bit 2 (value 4): the object is leveled (clapgpu_bp_create_levels with levels > 1) and its index is switched
+ * off: clapgpu_bp_index launched nothing and every query through it scans every geom, as with bp == NULL.  In all
+ * three cases rays through this index scan every geom.  CLAPGPU_ERR_INVALID_ARGUMENTS when not indexed.
+ *
+ * clapgpu_bp_leveled_index (ABI 44): the switch of a leveled object's index; state of the object, off when it is
+ * created.  Host only: launches nothing, does not synchronise.  Setting it, on or off, drops the index the object
+ * holds: clapgpu_bp_index_status returns CLAPGPU_ERR_INVALID_ARGUMENTS until the next clapgpu_bp_index, as after
+ * clapgpu_bp_invalidate.  A one-level object: CLAPGPU_OK, nothing changes.  bp == NULL: CLAPGPU_ERR_INVALID_ARGUMENTS.
+ * Off: the object is the leveled object described above, bit 2 included.  On: clapgpu_bp_index runs four launches --
+ * the leveled bin, cells and scatter of clapgpu_bp_collide and the bounds reduction, its edge test against the TOP
+ * level's cell, cell * 2^(levels - 1) -- and clapgpu_bp_index_status reports bits 0 and 1 as for a one-level object
+ * (bit 0: an edge above the top level's cell), never bit 2.  Every query that takes a bp then reads that index, and
+ * every call that clears a one-level index's record clears this one.  The lookup rule: for a query box [lo, hi] every
+ * level L is looked up with its own cell c_L = cell * 2^L, in the cells floor((lo - g) / c_L) .. floor((hi + g) / c_L)
+ * per axis, g = c_L / 2 * (1 + 1e-9); a body of level L has edges of at most c_L and is binned by its centre, so those
+ * cells hold every body of that level whose box meets the query; a record counts only when its (level, cell) is the
+ * one looked up, because cells of all levels share slots.  The statics are read from ONE level's registration, two
+ * below the top (every static is registered on every level; which level is a measured choice and changes no
+ * result).  Rays cut their segment into pieces of c_L per level;
+ * the caps that send a far-flung ray or a large swept box to the scan hold the lookups of all levels together, so a
+ * large mover among small bodies scans.  Results are the scan's, bit for bit, either way.
  *
  * clapgpu_ray_cast: ray k = ray[k][8] (start xyz, direction xyz of any length, normalised as dGeomRaySet does, length,
  * pad) against every body (a geom of `bodies`) and static (`statics`), as dCreateRay + dGeomRaySetClosestHit +
@@ -1021,6 +1040,7 @@ int clapgpu_sweep_capsules(void *stream, const clapgpu_geoms *A, const clapgpu_g
 #define CLAPGPU_RAY_MOVED_TARGET 4u   /* clapgpu_bodies_ground_collide: the hit body was itself moved by this batch */
 int clapgpu_bp_index(void *stream, clapgpu_bp *bp, uint32_t n, const double *aabb);
 int clapgpu_bp_index_status(void *stream, clapgpu_bp *bp, uint32_t *status);
+int clapgpu_bp_leveled_index(clapgpu_bp *bp, int on);
 int clapgpu_ray_cast(void *stream, clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
                      const clapgpu_trimesh *meshes, uint32_t n_rays, const double *ray, const int32_t *skip,
                      double *dist, int32_t *hit, double *contact, uint32_t *flags);
