@@ -71,6 +71,7 @@ static int create(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t levels
     const StaticsImage im = levels == 1 ? bp_statics_image(nb, cell, n_static, static_aabb)
                                         : bp_statics_concat(bp_statics_level_images(nb, cell, levels, n_static, static_aabb), &large_start);
     bp->n_large = im.n_large;
+    bp->n_entries = im.start.back();
     memcpy(bp->large_start, large_start.data(), large_start.size() * sizeof(uint32_t));
     memcpy(bp->s_bounds, im.bounds, sizeof(bp->s_bounds));
 
@@ -131,6 +132,7 @@ extern "C" void clapgpu_bp_destroy(clapgpu_bp *bp)
 {
     if (!bp) return;
     if (bp->dev) (void)hipFree(bp->dev);
+    if (bp->dev2) (void)hipFree(bp->dev2);                       // clapgpu_bp_statics_update's images
     free(bp);
 }
 

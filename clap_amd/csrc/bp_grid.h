@@ -2,7 +2,7 @@
 // that the five k_bp_* launches (broadphase.hip) and the pre-binning body step (bodies.hip) bin with and the device
 // queries look cells up with (grid_query_dev.h, for rays.hip and slide.hip), the record and the control words of a
 // clapgpu_bp, a read-only view of an INDEXED clapgpu_bp (clapgpu_bp_index), and the hidden accessors of the broadphase
-// code (broadphase.hip, bp_create.hip) that hand these out.
+// code (broadphase.hip, bp_create.hip, bp_restatic.hip) that hand these out.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -117,8 +117,8 @@ struct BpGridView {
 
 } // namespace clapgpu
 
-// ---- the broadphase's hidden accessors: struct clapgpu_bp (bp_object.h) is written and read in broadphase.hip and
-// bp_create.hip alone
+// ---- the broadphase's hidden accessors: struct clapgpu_bp (bp_object.h) is written and read in broadphase.hip,
+// bp_create.hip and bp_restatic.hip alone
 struct clapgpu_bp;
 // geoms_dev.h's scene_grid, for rays.hip and slide.hip: true when `bp` holds an index over exactly (n, aabb) (aabb == nullptr: any array of n boxes); fills *v
 __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp *bp, uint32_t n, const double *aabb, clapgpu::BpGridView *v);

@@ -1,7 +1,9 @@
 // bp_object.h -- struct clapgpu_bp and the kernel arguments made from it.  PRIVATE to the broadphase translation
 // units: bp_create.hip makes and hands out the object, broadphase.hip runs its kernels and keeps its bookkeeping,
-// bp_levels.hip holds the kernels of a leveled object (it sees the kernel arguments, never the object).
-// struct clapgpu_bp is written and read in the first two files alone; others go through the hidden accessors of bp_grid.h.
+// bp_restatic.hip registers its static boxes again (clapgpu_bp_statics_update: the statics image in a second
+// allocation, the s_* pointers and counts swapped to it) and reads an image back, bp_levels.hip holds the kernels of a
+// leveled object (it sees the kernel arguments, never the object).
+// struct clapgpu_bp is written and read in the first three files alone; others go through the hidden accessors of bp_grid.h.
 #pragma once
 #include "common.h"
 #include "bp_grid.h"
@@ -28,7 +30,7 @@ struct BpK {
     uint64_t *lb_cells;                  // [buckets / 4] look-back words of the block-start scan (k_bp_cells)
     uint32_t *ctrl;                      // [CTRL_WORDS]
     uint32_t n_tiles;
-    // statics (binned on the host at create time)
+    // statics (binned on the host at create time; again on the device by clapgpu_bp_statics_update, which repoints these)
     const uint32_t *s_start;             // [buckets + 1]
     const uint32_t *s_entries;
     const double *s_aabb;
@@ -79,4 +81,10 @@ struct clapgpu_bp {
     const double *indexed_aabb;
     uint32_t indexed_n;
     double s_bounds[6];            // union of the statics registered per block (not the large list); min > max: none
+    uint32_t n_entries;            // registrations of the statics image k.s_entries / k.s_recs (all levels)
+    // clapgpu_bp_statics_update (bp_restatic.hip): the allocation its images stand in (none until the first update; the
+    // create-time image inside `dev` is then no longer pointed at), its room, and the slot of the two k.s_* point into
+    void *dev2;
+    uint32_t cap_entries, cap_large;
+    int slot;
 };

@@ -539,6 +539,21 @@ class PhysWorld:
         every geom.  Either way the index held is dropped: bp_index() again.  A one-level world: accepted, no effect."""
         _lib.check(_lib.lib().clapgpu_bp_leveled_index(self._bp, 1 if on else 0), "clapgpu_bp_leveled_index")
 
+    def update_statics(self, aabb):
+        """The statics moved (dGeomSetPosition on a geom without a body): their new boxes, float64 [n_static, 6] as at
+        construction, a host array or a device tensor, registered again on the device (clapgpu_bp_statics_update).
+        statics_ptr and every static geom description built on it keep their address and hold the new boxes.  Synchronises
+        the stream; drops the index and a recorded prebin; a graph captured from frames of this world must be captured
+        again.  Meshes are left to pose_static_meshes.  The order for a moving static that owns a mesh: update_statics
+        (the box must hold the posed mesh), then pose_static_meshes, then bp_index."""
+        a = upload(aabb, np.float64, self.device, (-1, 6))
+        if a.dtype != torch.float64 or a.dim() != 2 or tuple(a.shape) != (self.n_static, 6):
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "update_statics", f"float64 [{self.n_static}, 6] expected")
+        _lib.check(_lib.lib().clapgpu_bp_statics_update(_stream(), self._bp, self.n_static, _ptr(a) if self.n_static else None),
+                   "clapgpu_bp_statics_update")
+        if self.n_static:
+            self._statics_host = a.cpu().numpy()
+
     def bp_index_status(self):
         st = C.c_uint32(0)
         _lib.check(_lib.lib().clapgpu_bp_index_status(_stream(), self._bp, C.byref(st)), "clapgpu_bp_index_status")

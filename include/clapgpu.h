@@ -58,7 +58,7 @@ void clapgpu_test_fail_after(int launches);
 /* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
  * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
  * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
-#define CLAPGPU_ABI_VERSION 44u
+#define CLAPGPU_ABI_VERSION 45u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -865,8 +865,9 @@ int clapgpu_contacts_sphere_box(void *stream, const clapgpu_bodies *b, uint32_t 
  * four launches.  Bodies are binned by their AABB centre into a hash grid of 4x4x4-cell blocks (cell >= the
  * largest body AABB edge); one wavefront per block tests the block's own bodies against the block + its halo
  * staged in LDS, and against the static geoms registered for that block.
- *   clapgpu_bp_create   n_max bodies; statics: n_static AABBs in HOST memory (copied; binned once: statics do
- *                       not move; those spanning more than 64 blocks are kept in a list every block tests)
+ *   clapgpu_bp_create   n_max bodies; statics: n_static AABBs in HOST memory (copied and binned on the host; a static
+ *                       that moves is registered again by clapgpu_bp_statics_update; those spanning more than 64
+ *                       blocks are kept in a list every block tests)
  *   clapgpu_bp_collide  aabb: device [n][6] (clapgpu_bodies.aabb).  pairs / static_pairs are ascending (i, j), i < j resp. (body, static);
  *                       *_total = number found (device uint32), at most `capacity` written (when a total
  *                       exceeds its capacity the written part is incomplete).  static outputs may be NULL.
@@ -899,6 +900,53 @@ int  clapgpu_bp_collide(void *stream, clapgpu_bp *bp, uint32_t n, const double *
                         uint32_t *static_pairs, uint32_t static_capacity, uint32_t *static_pair_total);
 int  clapgpu_bp_status(void *stream, clapgpu_bp *bp, uint32_t *status);
 const double *clapgpu_bp_static_aabb(const clapgpu_bp *bp);            /* the device copy of the static AABBs */
+
+/*
+ * Moving statics (ABI 45): dGeomSetPosition on a geom without a body (phys_body_set_position / phys_body_move /
+ * phys_body_rotate_xform, physics.c:208-240) -- ODE's hash space bins every geom again at every dSpaceCollide; here the
+ * caller says which boxes are the new ones.
+ *
+ * clapgpu_bp_statics_update re-registers the static boxes of `bp` on the device: static_aabb is DEVICE memory,
+ * [n_static][6] as at create, n_static the count the object was created with (another count, a NULL bp or a NULL array:
+ * CLAPGPU_ERR_INVALID_ARGUMENTS; 0 statics: CLAPGPU_OK, nothing done).  After the call the object is, for every caller,
+ * the object clapgpu_bp_create[_levels] would have made from the same (n_max, cell, levels) and the new boxes: the same
+ * registrations per block bucket and level, the same large lists, the same bounds.  clapgpu_bp_static_aabb(bp) holds the
+ * new boxes AT THE SAME ADDRESS, so every clapgpu_geoms.aabb built on it stays valid.  static_aabb may be that very
+ * pointer (boxes rewritten in place by a kernel of the caller's, in stream order before the call); otherwise it must not
+ * overlap it.
+ *
+ * The call SYNCHRONISES the stream, twice (as clapgpu_characters_move_ordered does): once for the counts that size the new
+ * image, once at its end.  Work of other streams that reads the object must have finished.  The images stand in a second
+ * device allocation of the object, made by the first update, grown geometrically when an update needs more and freed by
+ * clapgpu_bp_destroy; the image of clapgpu_bp_create is then no longer used.  An object that is never updated is the
+ * object it was before ABI 45.
+ *
+ * Transactional: the object changes only after every launch and copy of the update has been issued without error and
+ * waited for, the copy into clapgpu_bp_static_aabb(bp) being the last of them; an error in between is returned and the
+ * object goes on answering with the old statics (from an in-place update its box array, the caller's, is the new one).
+ *
+ * What the call drops: the index (clapgpu_bp_index; its view describes the old statics: a query through the grid is
+ * refused until the next clapgpu_bp_index, as after clapgpu_bp_invalidate) and a recorded prebin
+ * (clapgpu_bodies_step_prebin; undone as clapgpu_bp_invalidate undoes it).  What stays: the sticky status bits, the bin
+ * epoch, the leveled-index switch, the contact ticket word.  A HIP graph captured from calls that use the object holds
+ * the old image's addresses and counts BY VALUE: capture it again after an update (this is not detected).
+ * A static that owns a mesh: update its box first, then clapgpu_trimesh_pose, then clapgpu_bp_index.
+ *
+ * For tests and tools, in the spirit of clapgpu_bp_cell_slot:
+ *   clapgpu_bp_statics_sizes  host state only (any output may be NULL): the block buckets, the registrations of all
+ *                             levels, the large statics of all levels, where each level's part of the large list
+ *                             starts (levels + 1 values used; all zero for a one-level object), the bounds of the
+ *                             registered boxes (min xyz, max xyz; min > max: none)
+ *   clapgpu_bp_statics_read   host sync; the image into HOST arrays (any may be NULL): start [levels * (buckets + 1)],
+ *                             entries [n_entries], large [n_large], entry_boxes [n_entries][6], large_boxes
+ *                             [n_large][6].  CLAPGPU_ERR_UNKNOWN when a record does not carry its entry's index or its
+ *                             cell words are not zero.
+ */
+int clapgpu_bp_statics_update(void *stream, clapgpu_bp *bp, uint32_t n_static, const double *static_aabb);
+int clapgpu_bp_statics_sizes(const clapgpu_bp *bp, uint32_t *buckets, uint32_t *n_entries, uint32_t *n_large,
+                             uint32_t large_start[CLAPGPU_BP_LEVELS_MAX + 1], double bounds[6]);
+int clapgpu_bp_statics_read(void *stream, const clapgpu_bp *bp, uint32_t *start, uint32_t *entries, uint32_t *large,
+                            double *entry_boxes, double *large_boxes);
 
 /*
  * near_callback (physics.c:399-449) on candidate pairs (ia in A, ib in B; g1 = A's geom): dCollide for spheres,
@@ -1087,8 +1135,8 @@ int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bo
  * clapgpu_trimesh_pose: new pos / quat (device arrays as above) for every mesh, then the same bake and rebuild as create.
  * clapgpu_trimesh_status: host sync; *depth = the tree's height (edges from the root to the deepest leaf; at most 62,
  * 0 without triangles), *n_tris = the triangles of all meshes.
- * A static's broadphase AABB (clapgpu_bp_create) must hold its posed mesh: the mesh contacts below only see pairs the
- * broadphase found.
+ * A static's broadphase AABB must hold its posed mesh: the mesh contacts below only see pairs the broadphase found.  A
+ * mesh that leaves the box it was created with: give the static its new box first (clapgpu_bp_statics_update), then pose.
  */
 typedef struct clapgpu_trimesh_desc {
     uint32_t        n_meshes, n_statics;
