@@ -1,6 +1,6 @@
-// bp_create.hip -- the clapgpu_bp object: its statics binned on the host (bp_statics.h), its one device allocation carved
-// into the arrays of BpK, and what the object hands out (status words, the ray cast's view of an index, the contact
-// ticket).  No kernel: the launches are broadphase.hip's.
+// bp_create.hip -- the clapgpu_bp object: its statics binned on the host (bp_statics.h) and adopted (bp_object.h's
+// bp_adopt_statics), its one device allocation carved into the arrays of BpK, and what the object hands out (status
+// words, the ray cast's view of an index, the contact ticket).  No kernel: the launches are broadphase.hip's.
 #include <stdlib.h>
 #include <type_traits>
 #include "bp_object.h"
@@ -67,17 +67,13 @@ static int create(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t levels
     bp->n_max = n_max; bp->buckets = nb; bp->cell = cell; bp->n_static = n_static;
     bp->n_tiles = (n + BP_EMIT_TILE - 1) / BP_EMIT_TILE;
     bp->levels = levels;
-    std::vector<uint32_t> large_start{ 0u, 0u };
+    std::vector<uint32_t> large_start{ 0u };
     const StaticsImage im = levels == 1 ? bp_statics_image(nb, cell, n_static, static_aabb)
                                         : bp_statics_concat(bp_statics_level_images(nb, cell, levels, n_static, static_aabb), &large_start);
-    bp->n_large = im.n_large;
-    bp->n_entries = im.start.back();
-    memcpy(bp->large_start, large_start.data(), large_start.size() * sizeof(uint32_t));
-    memcpy(bp->s_bounds, im.bounds, sizeof(bp->s_bounds));
+    if (levels == 1) large_start.push_back(im.n_large);                  // [l + 1]: the large statics up to the end of level l
 
     BpK &k = bp->k;                                                      // zero: calloc
-    k.cell = cell; k.mask = nb - 1;
-    k.n_large = bp->n_large; k.n_static = n_static;
+    k.cell = cell; k.mask = nb - 1; k.n_static = n_static;
     const size_t bytes = carve(k, nullptr, n, nb, bp->n_tiles, n_static, static_aabb, im);
     if (hipMalloc(&bp->dev, bytes) != hipSuccess) {
         (void)hipGetLastError();
@@ -91,6 +87,7 @@ static int create(clapgpu_bp **out, uint32_t n_max, double cell, uint32_t levels
         free(bp);
         return CLAPGPU_ERR_UNKNOWN;
     }
+    bp_adopt_statics(bp, k.s_start, k.s_entries, k.s_large, k.s_recs, k.s_lrecs, im.start.back(), large_start.data() + 1, im.bounds);
     *out = bp;
     return CLAPGPU_OK;
 }
@@ -132,7 +129,7 @@ extern "C" void clapgpu_bp_destroy(clapgpu_bp *bp)
 {
     if (!bp) return;
     if (bp->dev) (void)hipFree(bp->dev);
-    if (bp->dev2) (void)hipFree(bp->dev2);                       // clapgpu_bp_statics_update's images
+    if (bp->st.dev2) (void)hipFree(bp->st.dev2);                 // clapgpu_bp_statics_update's images
     free(bp);
 }
 
@@ -162,8 +159,8 @@ __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp
     // a leveled object: the queries read the statics image of one level (bp_levels.h's query_statics_level)
     v->levels = bp->levels;
     v->s_level = query_statics_level(bp->levels);
-    v->large_first = bp->levels > 1 ? bp->large_start[v->s_level] : 0u;
-    v->n_large = bp->levels > 1 ? bp->large_start[v->s_level + 1] - v->large_first : bp->n_large;
+    v->large_first = bp->levels > 1 ? bp->st.large_start[v->s_level] : 0u;
+    v->n_large = bp->levels > 1 ? bp->st.large_start[v->s_level + 1] - v->large_first : bp->st.n_large;
     v->cell_range = bp->k.cell_range;
     v->recs = bp->k.recs;
     v->s_start = bp->k.s_start;
@@ -171,7 +168,7 @@ __attribute__((visibility("hidden"))) bool clapgpu_bp_grid_view(const clapgpu_bp
     v->s_lrecs = bp->k.s_lrecs;
     v->index = reinterpret_cast<const uint64_t *>(bp->k.ctrl + CTRL_INDEX_WORD);
     v->ctrl = bp->k.ctrl;
-    memcpy(v->s_bounds, bp->s_bounds, sizeof(v->s_bounds));
+    memcpy(v->s_bounds, bp->st.bounds, sizeof(v->s_bounds));
     return true;
 }
 

@@ -23,6 +23,10 @@ __host__ __device__ __forceinline__ int32_t cell_coord(double x, double cell)
     return (int32_t)c;
 }
 
+// Half a cell and a relative margin against the rounding of the sums it enters: what a static's registration (bp_statics.h),
+// a query's range (grid_query_dev.h) and a finer body's coarse lookup (bp_levels.h) grow a box by.  They must agree.
+__host__ __device__ __forceinline__ double half_cell_grown(double c) { return c * 0.5 * (1.0 + 1e-9); }
+
 __host__ __device__ __forceinline__ uint32_t cell_slot(int32_t cx, int32_t cy, int32_t cz, uint32_t mask)
 {
     return block_hash(cx >> 2, cy >> 2, cz >> 2, mask) << 6 | (uint32_t)(cx & 3) | (uint32_t)(cy & 3) << 2 | (uint32_t)(cz & 3) << 4;

@@ -45,11 +45,11 @@ __host__ __device__ __forceinline__ uint32_t level_slot(uint32_t level, int32_t 
 }
 
 // The cells [lo, hi] of one axis that a finer body's extent [a0, a1] looks up on a coarser level of cell size c.  The
-// half cell is grown by the 1e-9 the statics' registration grows it by (bp_statics.h): a rounded centre cannot drop a
-// touching partner.  Never more than 3 cells (above); the clamp only bounds the walk of a box that is not a number.
+// half cell is half_cell_grown (bp_grid.h), the one the statics' registration grows a box by: a rounded centre cannot
+// drop a touching partner.  Never more than 3 cells (above); the clamp only bounds the walk of a box that is not a number.
 __host__ __device__ __forceinline__ void coarse_cells(double a0, double a1, double c, int32_t *lo, int32_t *hi)
 {
-    const double grow = c * 0.5 * (1.0 + 1e-9);
+    const double grow = half_cell_grown(c);
     *lo = cell_coord(a0 - grow, c);
     *hi = cell_coord(a1 + grow, c);
     if (*hi > *lo + 2) *hi = *lo + 2;

@@ -1,8 +1,7 @@
 // bp_object.h -- struct clapgpu_bp and the kernel arguments made from it.  PRIVATE to the broadphase translation
 // units: bp_create.hip makes and hands out the object, broadphase.hip runs its kernels and keeps its bookkeeping,
-// bp_restatic.hip registers its static boxes again (clapgpu_bp_statics_update: the statics image in a second
-// allocation, the s_* pointers and counts swapped to it) and reads an image back, bp_levels.hip holds the kernels of a
-// leveled object (it sees the kernel arguments, never the object).
+// bp_restatic.hip registers its static boxes again (clapgpu_bp_statics_update) and reads an image back, bp_levels.hip
+// holds the kernels of a leveled object (it sees the kernel arguments, never the object).
 // struct clapgpu_bp is written and read in the first three files alone; others go through the hidden accessors of bp_grid.h.
 #pragma once
 #include "common.h"
@@ -55,6 +54,18 @@ struct BplK {
     uint32_t large_start[CLAPGPU_BP_LEVELS_MAX + 1];
 };
 
+// The statics image the object answers with (its arrays: the k.s_* but k.s_aabb), written by bp_adopt_statics alone ...
+struct BpStatics {
+    uint32_t n_entries, n_large;                   // of k.s_entries / k.s_recs and k.s_large / k.s_lrecs (n_large is k.n_large)
+    uint32_t large_start[CLAPGPU_BP_LEVELS_MAX + 1];   // level l's large statics: [l] .. [l + 1]; ONE level: all zero (clapgpu.h)
+    double bounds[6];                              // union of the registered (not large) boxes: min xyz, max xyz; min > max: none
+    // ... and where clapgpu_bp_statics_update builds the next: its allocation (none until the first update; the create-time
+    // image inside `dev` is then no longer pointed at), the allocation's room, and the slot of its two that k.s_* point into
+    void *dev2;
+    uint32_t cap_entries, cap_large;
+    int slot;
+};
+
 } // namespace clapgpu
 
 // bp_levels.hip, for clapgpu_bp_collide on a leveled object: launch 1 (bin), and launches 3 to 5 (scatter, search, emit);
@@ -65,10 +76,9 @@ __attribute__((visibility("hidden"))) int clapgpu_bpl_scatter(hipStream_t s, con
 __attribute__((visibility("hidden"))) int clapgpu_bpl_pairs(hipStream_t s, const clapgpu::BplK &q);
 
 struct clapgpu_bp {
-    uint32_t n_max, buckets, n_static, n_large, n_tiles;
+    uint32_t n_max, buckets, n_static, n_tiles;
     uint32_t levels;               // 1: the one-level grid of broadphase.hip; more: bp_levels.hip's kernels
     bool leveled_index;            // clapgpu_bp_leveled_index: levels > 1 and clapgpu_bp_index builds an index (off: queries scan)
-    uint32_t large_start[CLAPGPU_BP_LEVELS_MAX + 1];
     double cell;
     void *dev;                     // one allocation
     clapgpu::BpK k;                // device pointers filled in
@@ -80,11 +90,19 @@ struct clapgpu_bp {
     bool indexed;
     const double *indexed_aabb;
     uint32_t indexed_n;
-    double s_bounds[6];            // union of the statics registered per block (not the large list); min > max: none
-    uint32_t n_entries;            // registrations of the statics image k.s_entries / k.s_recs (all levels)
-    // clapgpu_bp_statics_update (bp_restatic.hip): the allocation its images stand in (none until the first update; the
-    // create-time image inside `dev` is then no longer pointed at), its room, and the slot of the two k.s_* point into
-    void *dev2;
-    uint32_t cap_entries, cap_large;
-    int slot;
+    clapgpu::BpStatics st;
 };
+
+// The object answers with this image (create's and every update's): its arrays, registrations, large ends per level, bounds
+static inline void bp_adopt_statics(clapgpu_bp *bp, const uint32_t *start, const uint32_t *entries, const uint32_t *large,
+                                    const clapgpu::GridRec *recs, const clapgpu::GridRec *lrecs, uint32_t n_entries,
+                                    const uint32_t *large_end, const double *bounds)
+{
+    clapgpu::BpK &k = bp->k;
+    k.s_start = start; k.s_entries = entries; k.s_large = large; k.s_recs = recs; k.s_lrecs = lrecs;
+    bp->st.n_entries = n_entries;
+    bp->st.n_large = k.n_large = large_end[bp->levels - 1];
+    if (bp->levels > 1)                                                  // a one-level object keeps large_start all zero
+        for (uint32_t l = 0; l < bp->levels; l++) bp->st.large_start[l + 1] = large_end[l];
+    for (int a = 0; a < 6; a++) bp->st.bounds[a] = bounds[a];
+}

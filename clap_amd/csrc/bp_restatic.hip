@@ -1,12 +1,12 @@
 // bp_restatic.hip -- clapgpu_bp_statics_update: the static boxes of a clapgpu_bp registered again, on the device, and the
-// read-back of a statics image (clapgpu_bp_statics_sizes / _read).  The image rule is the host's, bp_statics.h, stated
-// there; the kernels below reproduce that image array for array from boxes in device memory.  An object that is never
-// updated runs none of this: the create-time image inside its first allocation stays what its kernels read.
+// read-back of a statics image (clapgpu_bp_statics_sizes / _read).  The rule for one static on one level is bp_statics.h's,
+// host and device: the host binning there and the kernels below both call it and make the same image array for array.  An
+// object that is never updated runs none of this: the create-time image inside its first allocation stays what its kernels read.
 //
 // One update, four launches over the object's SECOND allocation (made on the first update, grown geometrically):
-//   k_rs_count   one wavefront per (level, static): large or not (the host's running product with its sticky flag); the
-//                blocks of a registered static, one per lane (at most 64), hashed; the first lane of each distinct
-//                bucket counts it; the bounds of the registered boxes as order keys (atomicMax on zeroed words)
+//   k_rs_count   one wavefront per (level, static): large or not; the blocks of a registered static, one per lane (at
+//                most 64), hashed (both: the rule's); the first lane of each distinct bucket counts it; the bounds of
+//                the registered boxes as order keys (atomicMax on zeroed words)
 //   k_rs_scan    one workgroup: the bucket counts of all levels scanned end to end into the starts, the large flags
 //                compacted per level, in static order, into the large list and its records; the totals for the host
 //   -- the totals come to the host here (one copy, one synchronisation).  They fit the allocation's room, or a larger
@@ -19,8 +19,10 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 #include "bp_object.h"
+#include "bp_statics.h"
 
 namespace clapgpu {
 
@@ -66,36 +68,21 @@ __device__ __forceinline__ void zero_rec(GridRec *r)
     store_rec(r, z, 0u);
 }
 
-// A static on level l as the whole wavefront sees it: large (wave-uniform), or this lane's block of its <= 64 blocks:
-// mine: the lane has a block and no lower lane's block falls in the same bucket h.  bp_statics_image's loop body per
-// static, its x-fastest block order laid over the lanes.
+// A static on level l as the whole wavefront sees it: large (wave-uniform), or lane u's block u of its <= 64 blocks:
+// mine: the lane has a block and no lower lane's block falls in the same bucket h (the host's first-met test).
 struct RsBlocks { bool large, mine; uint32_t h; };
-__device__ __forceinline__ RsBlocks static_blocks(const RsK &q, uint32_t l, const double (&bb)[6], int lane)
+__device__ __forceinline__ RsBlocks lane_block(const RsK &q, uint32_t l, const double (&bb)[6], int lane)
 {
-    double c = q.cell;
-    for (uint32_t i = 0; i < l; i++) c *= 2.0;                           // bp_statics_level_images' cell of level l
-    const double grow = c * 0.5 * (1.0 + 1e-9);                          // bp_statics.h's grow
-    int32_t lo[3], hi[3];
-    RsBlocks r = { false, false, 0u };
-    unsigned long long blocks = 1;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        lo[a] = cell_coord(bb[2 * a] - grow, c) >> 2;
-        hi[a] = cell_coord(bb[2 * a + 1] + grow, c) >> 2;
-        if (!(bb[2 * a] <= bb[2 * a + 1])) r.large = true;
-        blocks *= (unsigned long long)(hi[a] - lo[a] + 1);
-        if (blocks > 64) r.large = true;
-    }
+    const StaticBlocks b = static_blocks(bb, level_cell(q.cell, l));
+    RsBlocks r = { b.large, false, 0u };
     if (r.large) return r;
-    const uint32_t nb = (uint32_t)blocks, nx = (uint32_t)(hi[0] - lo[0] + 1), ny = (uint32_t)(hi[1] - lo[1] + 1);
-    const bool has = (uint32_t)lane < nb;
-    const uint32_t u = has ? (uint32_t)lane : 0u;
-    r.h = block_hash(lo[0] + (int32_t)(u % nx), lo[1] + (int32_t)((u / nx) % ny), lo[2] + (int32_t)(u / (nx * ny)), q.buckets - 1);
+    const bool has = (uint32_t)lane < b.nb;
+    r.h = static_block_bucket(b, has ? (uint32_t)lane : 0u, q.buckets - 1);
     bool dup = false;
 #pragma unroll
     for (int i = 0; i < WAVE - 1; i++) {                                 // all lanes shuffle; lane i's bucket against the lanes above it
         const uint32_t hi_ = __shfl(r.h, i);
-        dup |= i < lane && (uint32_t)i < nb && hi_ == r.h;
+        dup |= i < lane && (uint32_t)i < b.nb && hi_ == r.h;
     }
     r.mine = has && !dup;
     return r;
@@ -119,7 +106,7 @@ void k_rs_count(RsK q)
     const int lane = lane_id();
     double bb[6];
     load_box(q.aabb, s, bb);
-    const RsBlocks r = static_blocks(q, l, bb, lane);
+    const RsBlocks r = lane_block(q, l, bb, lane);
     if (r.large) {
         if (lane == 0) q.flag[l * q.n_static + s] = 1;
         return;
@@ -198,7 +185,7 @@ void k_rs_fill(RsK q)
     if (!wave_item(q.levels * q.n_static, q.n_static, &l, &s)) return;
     double bb[6];
     load_box(q.aabb, s, bb);
-    const RsBlocks r = static_blocks(q, l, bb, lane_id());
+    const RsBlocks r = lane_block(q, l, bb, lane_id());
     if (r.large || !r.mine) return;
     const uint32_t at = q.start[(size_t)l * (q.buckets + 1) + r.h] + atomicAdd(&q.cnt[(size_t)l * q.buckets + r.h], 1u);
     if (at < q.cap_entries) { q.tmp[at] = s; q.tmp_bucket[at] = l * q.buckets + r.h; }
@@ -227,96 +214,78 @@ void k_rs_order(RsK q)
     store_rec(q.recs + s0 + rank, bb, v);
 }
 
-// The second allocation, carved: the work arrays first (zeroed in front of every count), then the two image slots
-struct RsLayout {
-    size_t cnt, flag, head, work_end, tmp, tmp_bucket;
-    struct { size_t start, entries, large, recs, lrecs; } slot[2];
-    size_t bytes;
-};
+// The second allocation, carved as bp_create.hip carves the first, every array stated once: the work arrays (zeroed in front of
+// every count, up to work_end), then two image slots of at's room.  No at.dev2: sized only; else q points into it, at at.slot.
+struct RsCarved { RsK q; size_t work_end, bytes; };
 
-static RsLayout rs_layout(const clapgpu_bp *bp, uint32_t cap_e, uint32_t cap_l)
+static RsCarved rs_carve(const clapgpu_bp *bp, const BpStatics &at, const double *aabb)
 {
-    RsLayout y;
+    RsCarved y{};
+    RsK &q = y.q;
+    const uint32_t cap_e = q.cap_entries = at.cap_entries, cap_l = q.cap_large = at.cap_large;
+    q.n_static = bp->n_static; q.levels = bp->levels; q.buckets = bp->buckets; q.cell = bp->cell; q.aabb = aabb;
     Carve c;
-    y.cnt = c.take(sizeof(uint32_t) * (size_t)bp->levels * bp->buckets);
-    y.flag = c.take((size_t)bp->levels * bp->n_static);
-    y.head = c.take(sizeof(RsHead));
+    auto arr = [&](auto *&member, size_t count) {
+        const size_t off = c.take(sizeof(*member) * count);
+        if (at.dev2) member = reinterpret_cast<std::remove_reference_t<decltype(member)>>(static_cast<char *>(at.dev2) + off);
+    };
+    arr(q.cnt, (size_t)bp->levels * bp->buckets);
+    arr(q.flag, (size_t)bp->levels * bp->n_static);
+    arr(q.head, 1);
     y.work_end = c.bytes();
-    y.tmp = c.take(sizeof(uint32_t) * (size_t)cap_e);
-    y.tmp_bucket = c.take(sizeof(uint32_t) * (size_t)cap_e);
+    arr(q.tmp, cap_e);
+    arr(q.tmp_bucket, cap_e);
     for (int i = 0; i < 2; i++) {
-        y.slot[i].start = c.take(sizeof(uint32_t) * (size_t)bp->levels * (bp->buckets + 1));
-        y.slot[i].entries = c.take(sizeof(uint32_t) * (size_t)cap_e);
-        y.slot[i].large = c.take(sizeof(uint32_t) * (size_t)cap_l);
-        y.slot[i].recs = c.take(sizeof(GridRec) * (size_t)cap_e);
-        y.slot[i].lrecs = c.take(sizeof(GridRec) * (size_t)cap_l);
+        RsK other{};                                                     // the slot that is not asked for: sized, not pointed at
+        RsK &t = i == at.slot ? q : other;
+        arr(t.start, (size_t)bp->levels * (bp->buckets + 1));
+        arr(t.entries, cap_e);
+        arr(t.large, cap_l);
+        arr(t.recs, cap_e);
+        arr(t.lrecs, cap_l);
     }
     y.bytes = c.bytes();
     return y;
 }
 
-static RsK rs_k(const clapgpu_bp *bp, char *base, const RsLayout &y, int slot, const double *aabb, uint32_t cap_e, uint32_t cap_l)
-{
-    RsK q{};
-    q.cap_entries = cap_e; q.cap_large = cap_l;
-    q.n_static = bp->n_static; q.levels = bp->levels; q.buckets = bp->buckets; q.cell = bp->cell; q.aabb = aabb;
-    q.cnt = reinterpret_cast<uint32_t *>(base + y.cnt);
-    q.flag = reinterpret_cast<uint8_t *>(base + y.flag);
-    q.head = reinterpret_cast<RsHead *>(base + y.head);
-    q.tmp = reinterpret_cast<uint32_t *>(base + y.tmp);
-    q.tmp_bucket = reinterpret_cast<uint32_t *>(base + y.tmp_bucket);
-    q.start = reinterpret_cast<uint32_t *>(base + y.slot[slot].start);
-    q.entries = reinterpret_cast<uint32_t *>(base + y.slot[slot].entries);
-    q.large = reinterpret_cast<uint32_t *>(base + y.slot[slot].large);
-    q.recs = reinterpret_cast<GridRec *>(base + y.slot[slot].recs);
-    q.lrecs = reinterpret_cast<GridRec *>(base + y.slot[slot].lrecs);
-    return q;
-}
-
 static uint32_t wave_blocks(uint32_t items) { return (items + RB / WAVE - 1) / (RB / WAVE); }
 
 // launches 1 and 2
-static int launch_count(hipStream_t s, char *base, const RsLayout &y, const RsK &q)
+static int launch_count(hipStream_t s, void *base, const RsCarved &y)
 {
     CLAPGPU_HIP(hipMemsetAsync(base, 0, y.work_end, s));
-    hipLaunchKernelGGL(k_rs_count, dim3(wave_blocks(q.levels * q.n_static)), dim3(RB), 0, s, q);
+    hipLaunchKernelGGL(k_rs_count, dim3(wave_blocks(y.q.levels * y.q.n_static)), dim3(RB), 0, s, y.q);
     CLAPGPU_LAUNCH_CHECK("k_rs_count");
-    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(RS_SCAN), 0, s, q);
+    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(RS_SCAN), 0, s, y.q);
     CLAPGPU_LAUNCH_CHECK("k_rs_scan");
     return CLAPGPU_OK;
 }
 
-// Everything of an update that can fail.  *dev / *cap_e / *cap_l / *slot: the allocation, its room and the slot the new
-// image stands in; the caller frees *dev when it is not the object's and this returns an error.
-static int rebuild(hipStream_t s, const clapgpu_bp *bp, const double *aabb, void **dev, uint32_t *cap_e, uint32_t *cap_l, int *slot,
-                   RsHead *head)
+// Everything of an update that can fail.  *nx (in: the object's, its slot the other one): the allocation, its room and
+// the slot the new image stands in; the caller frees nx->dev2 when it is not the object's and this returns an error.
+static int rebuild(hipStream_t s, const clapgpu_bp *bp, const double *aabb, BpStatics *nx, RsHead *head)
 {
     auto room = [](uint32_t have, uint32_t need) { return need > have ? (need > 2 * have ? need : 2 * have) : have; };
-    if (!*dev) {                                                         // the first update: room for an image like the current one
-        *cap_e = room(64, bp->n_entries + bp->n_entries / 2);
-        *cap_l = room(64, bp->n_large + bp->n_large / 2);
-        *slot = 0;
-        CLAPGPU_HIP(hipMalloc(dev, rs_layout(bp, *cap_e, *cap_l).bytes));
-    }
-    RsLayout y = rs_layout(bp, *cap_e, *cap_l);
-    RsK q = rs_k(bp, static_cast<char *>(*dev), y, *slot, aabb, *cap_e, *cap_l);
-    int rc = launch_count(s, static_cast<char *>(*dev), y, q);
+    auto fresh = [&](uint32_t cap_e, uint32_t cap_l) {                   // the bytes of a fresh allocation: the image goes to its slot 0
+        nx->dev2 = nullptr; nx->cap_entries = cap_e; nx->cap_large = cap_l; nx->slot = 0;
+        return rs_carve(bp, *nx, aabb).bytes;
+    };
+    if (!nx->dev2)                                                       // the first update: room for an image like the current one
+        CLAPGPU_HIP(hipMalloc(&nx->dev2, fresh(room(64, nx->n_entries + nx->n_entries / 2), room(64, nx->n_large + nx->n_large / 2))));
+    RsCarved y = rs_carve(bp, *nx, aabb);
+    int rc = launch_count(s, nx->dev2, y);
     if (rc) return rc;
-    CLAPGPU_HIP(hipMemcpyAsync(head, q.head, sizeof(*head), hipMemcpyDeviceToHost, s));
+    CLAPGPU_HIP(hipMemcpyAsync(head, y.q.head, sizeof(*head), hipMemcpyDeviceToHost, s));
     CLAPGPU_HIP(hipStreamSynchronize(s));
     const uint32_t n_large = head->large_end[bp->levels - 1];
-    if (head->n_entries > *cap_e || n_large > *cap_l) {                  // grow: another allocation, counted again (no second wait: the counts are known)
-        if (*dev != bp->dev2) { (void)hipFree(*dev); }
-        *dev = nullptr;
-        *cap_e = room(*cap_e, head->n_entries);
-        *cap_l = room(*cap_l, n_large);
-        *slot = 0;
-        y = rs_layout(bp, *cap_e, *cap_l);
-        CLAPGPU_HIP(hipMalloc(dev, y.bytes));
-        q = rs_k(bp, static_cast<char *>(*dev), y, 0, aabb, *cap_e, *cap_l);
-        rc = launch_count(s, static_cast<char *>(*dev), y, q);
+    if (head->n_entries > nx->cap_entries || n_large > nx->cap_large) {  // grow: another allocation, counted again (no second wait: the counts are known)
+        if (nx->dev2 != bp->st.dev2) { (void)hipFree(nx->dev2); }
+        CLAPGPU_HIP(hipMalloc(&nx->dev2, fresh(room(nx->cap_entries, head->n_entries), room(nx->cap_large, n_large))));
+        y = rs_carve(bp, *nx, aabb);
+        rc = launch_count(s, nx->dev2, y);
         if (rc) return rc;
     }
+    RsK &q = y.q;
     hipLaunchKernelGGL(k_rs_fill, dim3(wave_blocks(q.levels * q.n_static)), dim3(RB), 0, s, q);
     CLAPGPU_LAUNCH_CHECK("k_rs_fill");
     q.n_entries = head->n_entries;
@@ -343,33 +312,24 @@ extern "C" int clapgpu_bp_statics_update(void *stream, clapgpu_bp *bp, uint32_t 
     // the index describes the old statics (its view's s_* fields and bounds), an unconsumed prebin goes with it
     int rc = clapgpu_bp_invalidate(stream, bp);
     if (rc) return rc;
-    void *dev = bp->dev2;
-    uint32_t cap_e = bp->cap_entries, cap_l = bp->cap_large;
-    int slot = bp->dev2 ? 1 - bp->slot : 0;
-    RsHead head;
-    rc = rebuild(as_stream(stream), bp, static_aabb, &dev, &cap_e, &cap_l, &slot, &head);
+    BpStatics &st = bp->st, nx = st;
+    nx.slot = st.dev2 ? 1 - st.slot : 0;
+    RsHead rs;
+    rc = rebuild(as_stream(stream), bp, static_aabb, &nx, &rs);
     if (rc) {
-        if (dev && dev != bp->dev2) (void)hipFree(dev);
+        if (nx.dev2 && nx.dev2 != st.dev2) (void)hipFree(nx.dev2);
         return rc;
     }
     // ---- nothing below fails: the object becomes the object of the new boxes
-    if (dev != bp->dev2) {
-        if (bp->dev2) (void)hipFree(bp->dev2);
-        bp->dev2 = dev; bp->cap_entries = cap_e; bp->cap_large = cap_l;
-    }
-    bp->slot = slot;
-    const RsLayout y = rs_layout(bp, cap_e, cap_l);
-    const RsK q = rs_k(bp, static_cast<char *>(dev), y, slot, static_aabb, cap_e, cap_l);
-    BpK &k = bp->k;
-    k.s_start = q.start; k.s_entries = q.entries; k.s_large = q.large; k.s_recs = q.recs; k.s_lrecs = q.lrecs;
-    bp->n_entries = head.n_entries;
-    if (bp->levels > 1)                                                  // a one-level object keeps the zeros of its create
-        for (uint32_t l = 0; l < bp->levels; l++) bp->large_start[l + 1] = head.large_end[l];
-    bp->n_large = k.n_large = head.large_end[bp->levels - 1];
+    if (st.dev2 && st.dev2 != nx.dev2) (void)hipFree(st.dev2);
+    st = nx;                                                             // the allocation, its room and the slot; the rest: below
+    double bounds[6];
     for (int a = 0; a < 3; a++) {
-        bp->s_bounds[a] = head.bounds[a] ? order_value(~head.bounds[a]) : INFINITY;
-        bp->s_bounds[3 + a] = head.bounds[3 + a] ? order_value(head.bounds[3 + a]) : -INFINITY;
+        bounds[a] = rs.bounds[a] ? order_value(~rs.bounds[a]) : INFINITY;
+        bounds[3 + a] = rs.bounds[3 + a] ? order_value(rs.bounds[3 + a]) : -INFINITY;
     }
+    const RsK q = rs_carve(bp, st, static_aabb).q;
+    bp_adopt_statics(bp, q.start, q.entries, q.large, q.recs, q.lrecs, rs.n_entries, rs.large_end, bounds);
     return CLAPGPU_OK;
 }
 
@@ -378,10 +338,10 @@ extern "C" int clapgpu_bp_statics_sizes(const clapgpu_bp *bp, uint32_t *buckets,
 {
     if (!bp) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (buckets) *buckets = bp->buckets;
-    if (n_entries) *n_entries = bp->n_entries;
-    if (n_large) *n_large = bp->n_large;
-    if (large_start) memcpy(large_start, bp->large_start, sizeof(bp->large_start));
-    if (bounds) memcpy(bounds, bp->s_bounds, sizeof(bp->s_bounds));
+    if (n_entries) *n_entries = bp->st.n_entries;
+    if (n_large) *n_large = bp->st.n_large;
+    if (large_start) memcpy(large_start, bp->st.large_start, sizeof(bp->st.large_start));
+    if (bounds) memcpy(bounds, bp->st.bounds, sizeof(bp->st.bounds));
     return CLAPGPU_OK;
 }
 
@@ -391,8 +351,8 @@ extern "C" int clapgpu_bp_statics_read(void *stream, const clapgpu_bp *bp, uint3
     if (!bp) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     hipStream_t s = as_stream(stream);
     const BpK &k = bp->k;
-    std::vector<uint32_t> idx[2] = { std::vector<uint32_t>(bp->n_entries), std::vector<uint32_t>(bp->n_large) };
-    std::vector<GridRec> recs[2] = { std::vector<GridRec>(bp->n_entries), std::vector<GridRec>(bp->n_large) };
+    std::vector<uint32_t> idx[2] = { std::vector<uint32_t>(bp->st.n_entries), std::vector<uint32_t>(bp->st.n_large) };
+    std::vector<GridRec> recs[2] = { std::vector<GridRec>(bp->st.n_entries), std::vector<GridRec>(bp->st.n_large) };
     const uint32_t *d_idx[2] = { k.s_entries, k.s_large };
     const GridRec *d_recs[2] = { k.s_recs, k.s_lrecs };
     if (start)

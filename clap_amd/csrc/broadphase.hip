@@ -542,7 +542,7 @@ static BplK bpl_k(const clapgpu_bp *bp, const BpK &k)
 {
     BplK q;
     q.k = k; q.levels = bp->levels;
-    for (uint32_t l = 0; l <= CLAPGPU_BP_LEVELS_MAX; l++) q.large_start[l] = bp->large_start[l];
+    for (uint32_t l = 0; l <= CLAPGPU_BP_LEVELS_MAX; l++) q.large_start[l] = bp->st.large_start[l];
     return q;
 }
 

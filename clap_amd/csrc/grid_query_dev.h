@@ -5,8 +5,8 @@
 // Why the range of a box is complete.  An indexed body is binned by the centre of its box (box_cell) and, while
 // grid_usable holds, no box edge exceeds `cell`: the centre of a body whose box meets [lo, hi] lies within cell / 2 of
 // it on every axis.  cell_coord is monotone, so that centre's cell is one of cell_coord(lo - grow) ..
-// cell_coord(hi + grow) with grow = cell / 2 * (1 + 1e-9), the relative 1e-9 against the rounding of the sums.  A
-// static is registered (clapgpu_bp_create) in every block its box grown by the same half cell reaches, or, when those
+// cell_coord(hi + grow) with grow = half_cell_grown(cell) (bp_grid.h: its margin is against the rounding of the sums).  A
+// static is registered (bp_statics.h's rule) in every block its box grown by the same half cell reaches, or, when those
 // are too many, in the large list: the blocks of the range and the large list hold every static whose box meets
 // [lo, hi].  Cells and blocks are hashed into buckets, so a lookup may return records of other cells (rejected here by
 // the cell coordinates a body's record carries) and statics of other blocks, and a static comes once per block it is
@@ -14,7 +14,7 @@
 //
 // A LEVELED index (g.levels > 1: clapgpu_bp_leveled_index; bp_levels.h).  Bodies: every level L = 0 .. levels - 1 is
 // looked up with its own cell c_L = cell * 2^L: the cells cell_coord(lo - grow, c_L) .. cell_coord(hi + grow, c_L) with
-// grow = c_L / 2 * (1 + 1e-9), each at level_slot(L, ...).  That range holds every candidate of level L for the reason
+// grow = half_cell_grown(c_L), each at level_slot(L, ...).  That range holds every candidate of level L for the reason
 // bp_levels.h gives for a coarser partner: a body of level L has edges of at most c_L and is binned by its centre --
 // while no box exceeds the top level's cell, which is what INDEX_OVERSIZE reports for a leveled index, and grid_usable
 // is false then.  A slot is shared across levels, and a record of another level in the slot CAN be a candidate -- of
@@ -47,7 +47,7 @@ struct GridRange {                                      // cells and blocks lo .
 // the cells of size `cell`, and their blocks, that hold every candidate of the box [lo, hi] (see above)
 __device__ __forceinline__ GridRange grid_range(double cell, const double (&lo)[3], const double (&hi)[3])
 {
-    const double grow = cell * 0.5 * (1.0 + 1e-9);
+    const double grow = half_cell_grown(cell);
     GridRange r;
     for (int a = 0; a < 3; a++) {
         r.c_lo[a] = cell_coord(lo[a] - grow, cell);
