@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 45
+ABI_VERSION = 46
 
 OK = 0
 ERR_NOMEM = -1
@@ -196,6 +196,33 @@ class CharactersMove(C.Structure):
 CS_START, CS_WAKING, CS_IDLE, CS_MOVING, CS_JUMP_START, CS_JUMPING, CS_FALLING, CS_NONE = 0, 1, 2, 3, 4, 5, 6, 0xff
 
 
+# character states and animation queues (include/clapgpu.h, "Character states and animation queues")
+ANIQ_MAX = 4
+ANI_END_NONE, ANI_END_IDLE, ANI_END_START_MOTION, ANI_END_ANY_TO_JUMP, ANI_END_HOST = 0, 1, 2, 3, 0xff
+(ANI_IDLE, ANI_START_TO_IDLE, ANI_MOTION_STOP, ANI_JUMP_TO_IDLE, ANI_FALL_TO_IDLE, ANI_MOTION, ANI_MOTION_START,
+ ANI_JUMP_TO_MOTION, ANI_IDLE_TO_JUMP, ANI_MOTION_TO_JUMP, ANI_JUMP, ANI_FALL, ANI_NAMES) = range(13)
+# the names character.c pushes, in the order of the ANI_* slots (animation_by_name of each fills name_anim)
+ANI_NAME_LIST = ("idle", "start_to_idle", "motion_stop", "jump_to_idle", "fall_to_idle", "motion", "motion_start",
+                 "jump_to_motion", "idle_to_jump", "motion_to_jump", "jump", "fall")
+ANIQ_ENDED, ANIQ_STARTED, ANIQ_ADVANCED, ANIQ_CB_IDLE, ANIQ_CB_START_MOTION, ANIQ_CB_ANY_TO_JUMP, ANIQ_HOST, ANIQ_OVERFLOW = (
+    1, 2, 4, 8, 16, 32, 64, 128)
+ANIQ_STATE_SHIFT = 8
+
+
+class AniqEntry(C.Structure):
+    """clapgpu_aniq_entry (include/clapgpu.h): one struct queued_animation."""
+    _fields_ = [("animation", C.c_uint16), ("repeat", C.c_uint8), ("end", C.c_uint8), ("speed", C.c_float)]
+
+
+class Aniq(C.Structure):
+    """clapgpu_aniq (include/clapgpu.h): one animated model's character states and animation queues."""
+    _fields_ = [("n", C.c_uint32), ("n_anims", C.c_uint32), ("name_anim", C.c_void_p), ("time_end", C.c_void_p),
+                ("queue", C.c_void_p), ("len", C.c_void_p), ("cur", C.c_void_p), ("cleared", C.c_void_p),
+                ("ani_time", C.c_void_p), ("state", C.c_void_p), ("airborne", C.c_void_p), ("velocity", C.c_void_p),
+                ("ch_motion", C.c_void_p), ("jump_params", C.c_void_p), ("mover", C.c_void_p), ("pose_anim", C.c_void_p),
+                ("frame_time", C.c_void_p), ("events", C.c_void_p)]
+
+
 def characters_move_scratch_bytes(n_bodies, n):
     """clapgpu_characters_move_scratch_bytes: bytes of device scratch clapgpu_characters_move takes (needs a device)."""
     return int(lib().clapgpu_characters_move_scratch_bytes(int(n_bodies), int(n)))
@@ -260,7 +287,8 @@ class FrameDesc(C.Structure):
                 ("island_scratch", C.c_void_p), ("island", C.c_void_p), ("island_woken", C.c_void_p),
                 ("solver", C.POINTER(Solver)), ("solve_scratch", C.c_void_p), ("solve_rows_capacity", C.c_uint32),
                 ("solve_status", C.c_void_p),
-                ("move", C.POINTER(CharactersMove)), ("move_dt_sec", C.c_double), ("move_scratch", C.c_void_p)]
+                ("move", C.POINTER(CharactersMove)), ("move_dt_sec", C.c_double), ("move_scratch", C.c_void_p),
+                ("aniq", C.POINTER(Aniq))]
 
 
 LIGHTS_MAX = 128
@@ -272,7 +300,7 @@ STRUCTS = {
     "clapgpu_animations": Animations, "clapgpu_pose_batch": PoseBatch, "clapgpu_skin_batch": SkinBatch,
     "clapgpu_world": World, "clapgpu_bodies": Bodies, "clapgpu_geoms": Geoms, "clapgpu_trimesh_desc": TrimeshDesc,
     "clapgpu_slide": Slide, "clapgpu_move": CharactersMove, "clapgpu_characters": Characters, "clapgpu_lights": Lights,
-    "clapgpu_solver": Solver, "clapgpu_frame": FrameDesc,
+    "clapgpu_solver": Solver, "clapgpu_aniq_entry": AniqEntry, "clapgpu_aniq": Aniq, "clapgpu_frame": FrameDesc,
 }
 
 
@@ -379,6 +407,8 @@ SYMBOLS = {
     "clapgpu_characters_move_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
     "clapgpu_characters_move": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.POINTER(Geoms),
                                           C.c_void_p, C.POINTER(Entities), C.c_double, C.POINTER(CharactersMove), C.c_void_p]),
+    "clapgpu_characters_state": (C.c_int, [C.c_void_p, C.POINTER(Aniq), C.POINTER(CharactersMove), C.c_double, C.c_void_p]),
+    "clapgpu_animation_queue_time": (C.c_int, [C.c_void_p, C.POINTER(Aniq), C.c_double, C.c_void_p]),
     "clapgpu_characters_order_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
     "clapgpu_characters_order": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.c_double,
                                            C.POINTER(CharactersMove), C.c_uint32, C.c_void_p, C.c_void_p,

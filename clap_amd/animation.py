@@ -5,6 +5,9 @@
 once; ``CharacterBatch.animated_update`` is the batched ``animated_update`` (model.c:1563-1592:
 host time base -> channels_transform + one_joint_transform on the GPU) and
 ``CharacterBatch.skin`` the compute form of the skinning loop of shaders/model.vert:32-48.
+``AnimationQueues`` holds what ``character_set_state`` and ``animation_next`` keep per character -- the state, the
+queue of ``struct queued_animation``, ``e->animation``, ``ani_cleared``, ``ani_time`` -- for
+``clapgpu_characters_state`` and ``clapgpu_animation_queue_time`` (the queue clock in place of the plain one).
 """
 import ctypes as C
 
@@ -253,3 +256,91 @@ class CharacterBatch:
 
     def skin_algorithmic_bytes(self):
         return 68 * self.n_out_verts + 64 * self.model.nr_joints * self.n
+
+
+QUEUE_ENTRY = np.dtype([("animation", "<u2"), ("repeat", "u1"), ("end", "u1"), ("speed", "<f4")])      # clapgpu_aniq_entry
+
+
+def name_table(names):
+    """name_anim of a model whose animations are called `names`: animation_by_name (model.c:1426-1434, the first match)
+    of each of the twelve names character.c pushes, -1 where the model has none."""
+    names = list(names)
+    return np.asarray([names.index(k) if k in names else -1 for k in _lib.ANI_NAME_LIST], np.int32)
+
+
+class AnimationQueues:
+    """The character states and animation queues of one animated model (clapgpu_aniq), on the device.
+
+    n characters in the order of `batch` (a CharacterBatch: the queue clock then writes its anim / frame_time, which the
+    pose reads) or, without one, of arrays of its own.  name_anim [12]: name_table() of the model; time_end [n_anims].
+    moves (a CharacterMoves) without `mover`: character c is mover c, and state, airborne, velocity and jump_params ARE the
+    move's arrays, so the next frame's move reads the state these calls left.  mover [n]: index into the movers of the
+    CharacterMoves given to characters_state(), -1 for none; the four arrays are then this object's own.
+    set() uploads what the host decides: queue [n, 4] of QUEUE_ENTRY, len, cur, cleared, ani_time, state, airborne,
+    velocity [n, 3], ch_motion [n, 2], jump_params [n, 2]."""
+
+    _IN = dict(len=(np.uint8, ()), cur=(np.int8, ()), cleared=(np.uint8, ()), ani_time=(np.float64, ()), state=(np.uint8, ()),
+               airborne=(np.uint8, ()), velocity=(np.float32, (3,)), ch_motion=(np.float32, (2,)), jump_params=(np.float32, (2,)))
+    _TORCH = {np.uint8: torch.uint8, np.int8: torch.int8, np.float64: torch.float64, np.float32: torch.float32}
+
+    def __init__(self, n, name_anim, time_end, device="cuda:0", batch=None, moves=None, mover=None, **state):
+        self.device = dev = torch.device(device) if batch is None else batch.device
+        self.n = n = int(n)
+        self.batch, self.moves = batch, moves
+        rows = max(n, 1)                                     # no null address when n is 0
+        if batch is not None and batch.n != n:
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "AnimationQueues", "batch: a CharacterBatch of n characters")
+        shared = moves is not None and mover is None
+        if shared and moves.n != n:
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "AnimationQueues", "moves without mover: n movers")
+        self.name_anim = upload(name_anim, np.int32, dev, (_lib.ANI_NAMES,))
+        te = np.ascontiguousarray(time_end, np.float32).reshape(-1)
+        self.n_anims = len(te)
+        self.time_end = upload(te if len(te) else np.zeros(1, np.float32), np.float32, dev)
+        self.queue = device_array((rows, 2 * _lib.ANIQ_MAX), torch.int32, dev)
+        for k, (dt, tail) in self._IN.items():
+            if shared and k in ("state", "airborne", "velocity", "jump_params"):
+                setattr(self, k, getattr(moves, k))
+            else:
+                setattr(self, k, device_array((rows,) + tail, self._TORCH[dt], dev))
+        self.mover = None if mover is None else upload(mover, np.int32, dev, (-1,))
+        self.pose_anim = batch.anim if batch is not None else device_array(rows, torch.int32, dev)
+        self.frame_time = batch.frame_time if batch is not None else device_array(rows, torch.float32, dev)
+        self.events = device_array(rows, torch.int32, dev)
+        self.now_dev = device_array(1, torch.float64, dev)
+        self._desc = _lib.Aniq(n, self.n_anims, *[_ptr(getattr(self, k)) for k in
+                                                   ("name_anim", "time_end", "queue", "len", "cur", "cleared", "ani_time",
+                                                    "state", "airborne", "velocity", "ch_motion", "jump_params", "mover",
+                                                    "pose_anim", "frame_time", "events")])
+        self.set(**state)
+
+    def set(self, queue=None, **arrays):
+        if queue is not None and self.n:
+            q = np.ascontiguousarray(queue, QUEUE_ENTRY).reshape(self.n, _lib.ANIQ_MAX)
+            self.queue[:self.n].copy_(upload(q.view(np.uint32).reshape(self.n, 2 * _lib.ANIQ_MAX), np.uint32, self.device))
+        for k, a in arrays.items():
+            dt, tail = self._IN[k]
+            if self.n:
+                getattr(self, k)[:self.n].copy_(upload(a, dt, self.device, (-1,) + tail))
+
+    def characters_state(self, moves, now):
+        """clapgpu_characters_state behind moves' clapgpu_characters_move; now None: read from self.now_dev"""
+        rc = _lib.lib().clapgpu_characters_state(_stream(), C.byref(self._desc), C.byref(moves._desc),
+                                                 0.0 if now is None else float(now), _ptr(self.now_dev) if now is None else None)
+        _lib.check(rc, "clapgpu_characters_state")
+
+    def queue_time(self, now):
+        """clapgpu_animation_queue_time: animated_update's clock, advance and callbacks; now None: self.now_dev"""
+        rc = _lib.lib().clapgpu_animation_queue_time(_stream(), C.byref(self._desc), 0.0 if now is None else float(now),
+                                                     _ptr(self.now_dev) if now is None else None)
+        _lib.check(rc, "clapgpu_animation_queue_time")
+
+    def download(self):
+        torch.cuda.synchronize(self.device)
+        n = self.n
+        out = {k: getattr(self, k)[:n].cpu().numpy() for k in ("len", "cur", "cleared", "ani_time", "state", "airborne",
+                                                                "velocity", "ch_motion", "jump_params", "frame_time")}
+        out["queue"] = self.queue[:n].cpu().numpy().view(np.uint32).reshape(n, 2 * _lib.ANIQ_MAX).view(QUEUE_ENTRY)
+        out["pose_anim"] = self.pose_anim[:n].cpu().numpy().view(np.uint32)
+        out["events"] = self.events[:n].cpu().numpy().view(np.uint32)
+        return out

@@ -6,6 +6,11 @@
 // rebuild, animated_update; particles_update) -> light grid -> render-pass glue (visible list, LOD pick).
 // Nothing is read back.  Every part is optional (NULL).  The caller keeps the time base
 // (clapgpu_phys_step_schedule) and passes the number of substeps.
+// With f->aniq (ABI 46) the host is not needed between the move and the pose either: character_set_state follows the move
+// (clapgpu_characters_state), and animated_update's clock is the queue clock (clapgpu_animation_queue_time: frame time,
+// animation_next, the end callbacks), a launch of its own behind the character hooks -- character_update reads airborne
+// before animated_update's callback can set it, so the fused k_characters_update_clock would race.  Chain B (below) is
+// then forked behind that launch instead of at the head of the frame.
 //
 // Round 4: the frame as THREE CHAINS (opt-in: CLAPGPU_FRAME_OVERLAP).  What the reference runs in list order has only these
 // data dependences:
@@ -35,26 +40,28 @@ using namespace clapgpu;
 #define FR(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
 
 namespace {
-struct FrameStreams { int dev; hipStream_t b, c; hipEvent_t fork, join_b, join_c; };
-thread_local FrameStreams g_fs = { -1, nullptr, nullptr, nullptr, nullptr, nullptr };
+struct FrameStreams { int dev; hipStream_t b, c; hipEvent_t fork, join_b, join_c, fork_b; };
+thread_local FrameStreams g_fs = { -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
 
 int frame_streams(FrameStreams **out)
 {
     int dev = 0;
     CLAPGPU_HIP(hipGetDevice(&dev));
     if (g_fs.dev != dev) {                                       // per thread and device, for the life of the process
-        FrameStreams n = { dev, nullptr, nullptr, nullptr, nullptr, nullptr };
+        FrameStreams n = { dev, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
         hipError_t err = hipStreamCreateWithFlags(&n.b, hipStreamNonBlocking);
         if (err == hipSuccess) err = hipStreamCreateWithFlags(&n.c, hipStreamNonBlocking);
         if (err == hipSuccess) err = hipEventCreateWithFlags(&n.fork, hipEventDisableTiming);
         if (err == hipSuccess) err = hipEventCreateWithFlags(&n.join_b, hipEventDisableTiming);
         if (err == hipSuccess) err = hipEventCreateWithFlags(&n.join_c, hipEventDisableTiming);
+        if (err == hipSuccess) err = hipEventCreateWithFlags(&n.fork_b, hipEventDisableTiming);
         if (err != hipSuccess) {                                 // nothing half-made is kept (or leaked)
             if (n.b) (void)hipStreamDestroy(n.b);
             if (n.c) (void)hipStreamDestroy(n.c);
             if (n.fork) (void)hipEventDestroy(n.fork);
             if (n.join_b) (void)hipEventDestroy(n.join_b);
             if (n.join_c) (void)hipEventDestroy(n.join_c);
+            if (n.fork_b) (void)hipEventDestroy(n.fork_b);
             return hip_fail(err, "clapgpu_frame_issue: helper streams");
         }
         g_fs = n;
@@ -69,7 +76,7 @@ int frame_streams(FrameStreams **out)
 // skinning and particles work that is still writing (and, under stream capture, must not leave forked streams unjoined:
 // EndCapture would fail and invalidate the capture).
 static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t substeps, bool overlap, FrameStreams *fs,
-                      void *sb, void *sc, bool *joined);
+                      void *sb, void *sc, bool *b_forked, bool *joined);
 
 extern "C" int clapgpu_frame_issue(void *stream, const clapgpu_frame *f, double now, uint32_t substeps)
 {
@@ -77,20 +84,27 @@ extern "C" int clapgpu_frame_issue(void *stream, const clapgpu_frame *f, double 
     const bool animated = f->skeleton && f->animations && f->pose;
     const bool particles = f->particles && f->view_mx;
     const bool overlap = (f->flags & CLAPGPU_FRAME_OVERLAP) && (animated || particles);
+    if (f->aniq) {                                               // the queues drive the pose: asked before anything is issued
+        if (!animated || f->pose->anim != f->aniq->pose_anim || f->pose->frame_time != f->aniq->frame_time ||
+            f->pose->n_chars != f->aniq->n)
+            return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    }
     void *sb = stream, *sc = stream;                             // chains B and C: the caller's stream unless they overlap
     FrameStreams *fs = nullptr;
+    bool b_forked = false;                                       // with aniq chain B is forked later, behind the queue clock
     if (overlap) {
         FR(frame_streams(&fs));
         CLAPGPU_HIP(hipEventRecord(fs->fork, as_stream(stream)));
-        if (animated) {
+        if (animated) sb = fs->b;
+        if (animated && !f->aniq) {
             const hipError_t err = hipStreamWaitEvent(fs->b, fs->fork, 0);
             if (err != hipSuccess) return hip_fail(err, "clapgpu_frame_issue: fork");      // nothing forked yet
-            sb = fs->b;
+            b_forked = true;
         }
         if (particles) {
             const hipError_t err = hipStreamWaitEvent(fs->c, fs->fork, 0);
             if (err != hipSuccess) {
-                if (animated) {                                  // b is forked already: join it before giving up
+                if (b_forked) {                                  // b is forked already: join it before giving up
                     (void)hipEventRecord(fs->join_b, fs->b);
                     (void)hipStreamWaitEvent(as_stream(stream), fs->join_b, 0);
                 }
@@ -100,16 +114,16 @@ extern "C" int clapgpu_frame_issue(void *stream, const clapgpu_frame *f, double 
         }
     }
     bool joined = false;
-    const int rc = frame_body(stream, f, now, substeps, overlap, fs, sb, sc, &joined);
+    const int rc = frame_body(stream, f, now, substeps, overlap, fs, sb, sc, &b_forked, &joined);
     if (overlap && !joined) {                                    // an early exit: the one join every path goes through
-        if (animated) { (void)hipEventRecord(fs->join_b, fs->b); (void)hipStreamWaitEvent(as_stream(stream), fs->join_b, 0); }
+        if (b_forked) { (void)hipEventRecord(fs->join_b, fs->b); (void)hipStreamWaitEvent(as_stream(stream), fs->join_b, 0); }
         if (particles) { (void)hipEventRecord(fs->join_c, fs->c); (void)hipStreamWaitEvent(as_stream(stream), fs->join_c, 0); }
     }
     return rc;
 }
 
 static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t substeps, bool overlap, FrameStreams *fs,
-                      void *sb, void *sc, bool *joined)
+                      void *sb, void *sc, bool *b_forked, bool *joined)
 {
     const clapgpu_entities *e = f->entities;
     const bool animated = f->skeleton && f->animations && f->pose;
@@ -125,10 +139,11 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
 
     // ---- chain B: animated_update -- clock, pose, palette; the vertex shader's skinning loop once per frame ----
     // one stream: the clock rides the character hooks' launch (two per-character passes over different state)
-    const bool clock_with_hooks = !overlap && animated && f->anim_clock && f->characters;
+    // (not with aniq: character_update reads airborne, which animated_update's callback sets behind it)
+    const bool clock_with_hooks = !overlap && animated && f->anim_clock && f->characters && !f->aniq;
     auto chain_b = [&]() -> int {
         if (!animated) return CLAPGPU_OK;
-        if (f->anim_clock && !clock_with_hooks) {
+        if (f->anim_clock && !clock_with_hooks && !f->aniq) {
             if (f->now_dev) FR(clapgpu_animation_time_dev(sb, f->anim_clock, f->now_dev));
             else FR(clapgpu_animation_time(sb, f->anim_clock, now));
         }
@@ -143,7 +158,7 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         return CLAPGPU_OK;
     };
     if (overlap) {                                               // issued first: their launches are in the queues while A's are made
-        FR(chain_b());
+        if (!f->aniq) FR(chain_b());
         FR(chain_c());
     }
 
@@ -152,6 +167,8 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         if (!f->bodies || !f->world || !f->static_geoms) return CLAPGPU_ERR_INVALID_ARGUMENTS;
         FR(clapgpu_characters_move(stream, f->bp, f->bodies, f->world, f->static_geoms, f->meshes, f->move->entity ? e : nullptr,
                                    f->move_dt_sec, f->move, f->move_scratch));
+        if (f->aniq)                                             // character_move's character_set_state, on the device
+            FR(clapgpu_characters_state(stream, f->aniq, f->move, now, f->now_dev));
     }
     // ---- phys_step: per substep broadphase x2, contacts, dWorldQuickStep's body stage (physics.c:746-771) ----
     if (f->bodies && f->world) {
@@ -210,6 +227,16 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         FR(clapgpu_characters_update_clock(stream, f->characters, e, f->bodies, f->anim_clock, now, f->now_dev));
     else if (f->characters)
         FR(clapgpu_characters_update(stream, f->characters, e, f->bodies));
+    // ---- animated_update's clock with the queues: behind the hooks, in list order; chain B starts here ----
+    if (f->aniq) {
+        FR(clapgpu_animation_queue_time(stream, f->aniq, now, f->now_dev));
+        if (overlap) {
+            CLAPGPU_HIP(hipEventRecord(fs->fork_b, as_stream(stream)));
+            CLAPGPU_HIP(hipStreamWaitEvent(fs->b, fs->fork_b, 0));
+            *b_forked = true;
+            FR(chain_b());
+        }
+    }
     // ---- default_update: phys_body_update of dynamic bodies (model.c:1659-1665), rotation push (1680-1687),
     //      light hand-off (1689-1694) ----
     if (f->bodies) {
@@ -229,7 +256,7 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
 
     if (overlap) {                                               // join
         *joined = true;                                          // (a failure inside these four calls cannot be joined any better by the caller)
-        if (animated) { CLAPGPU_HIP(hipEventRecord(fs->join_b, fs->b)); CLAPGPU_HIP(hipStreamWaitEvent(as_stream(stream), fs->join_b, 0)); }
+        if (*b_forked) { CLAPGPU_HIP(hipEventRecord(fs->join_b, fs->b)); CLAPGPU_HIP(hipStreamWaitEvent(as_stream(stream), fs->join_b, 0)); }
         if (particles) { CLAPGPU_HIP(hipEventRecord(fs->join_c, fs->c)); CLAPGPU_HIP(hipStreamWaitEvent(as_stream(stream), fs->join_c, 0)); }
         if (finish_pos) FR(clapgpu_joint_pos_world(stream, f->skeleton, f->pose));
     } else {

@@ -20,7 +20,7 @@ from . import entities as ent_mod
 class FrameLoop:
     def __init__(self, batch, cam, world=None, feed=None, body_links=None, lights=None, characters=None,
                  particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False, solve=False,
-                 move=None):
+                 move=None, aniq=None):
         """batch: EntityBatch.  world: PhysWorld (dynamic bodies write their entities through
         body_entity; character bodies have body_entity = -1).  feed: CharacterFeed.  body_links:
         (link_body, link_entity) of characters / static colliders whose rotation follows the entity.
@@ -35,9 +35,13 @@ class FrameLoop:
         act on the bodies (clapgpu_bodies_solve between the island pass and the step; implies islands).  move: a
         physics.CharacterMoves over `world`: character_move of those characters is the frame's first stage
         (clapgpu_characters_move, scene_characters_move of clap.c:589) with the frame's dt as its raw frame delta; the
-        host updates its arrays (CharacterMoves.set) between frames and reads its outputs after them."""
+        host updates its arrays (CharacterMoves.set) between frames and reads its outputs after them.  aniq: an
+        animation.AnimationQueues over `characters`: character_set_state follows the move on the device
+        (clapgpu_characters_state) and the queue clock (clapgpu_animation_queue_time) takes the place of the plain one,
+        so the frame needs no host between the move and the pose; the host reads aniq's events afterwards."""
         islands = islands or solve
         self.move, self.move_dt = move, 0.0
+        self.aniq = aniq
         self.solve = solve
         self.batch, self.world, self.feed, self.lights = batch, world, feed, lights
         self.characters, self.particles = characters, particles
@@ -145,6 +149,10 @@ class FrameLoop:
             f.pose = C.pointer(cb._pose_desc)
             if cb._skin_desc is not None:
                 f.skin = C.pointer(cb._skin_desc)
+        if self.aniq is not None:
+            if cb is None or self.aniq.batch is not cb:
+                raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "FrameLoop", "aniq: AnimationQueues(batch=characters)")
+            f.aniq = C.pointer(self.aniq._desc)
         if self.particles is not None:
             f.particles = C.pointer(self.particles._desc)
         b.alloc_lod()

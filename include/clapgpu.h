@@ -58,7 +58,7 @@ void clapgpu_test_fail_after(int launches);
 /* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
  * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
  * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
-#define CLAPGPU_ABI_VERSION 45u
+#define CLAPGPU_ABI_VERSION 46u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -604,6 +604,7 @@ typedef struct clapgpu_pose_batch {
  * not repeat are left to the host, which reads ended[] to run its queue logic and callbacks
  * (animation_end, frame_cb, ani_cleared).  Run before clapgpu_pose_update with the same frame_time
  * array.  time_end[a] = animation.time_end of the model's animation a; now = clap_get_current_time().
+ * (The whole queue logic on the device, callbacks included: clapgpu_animation_queue_time, ABI 46.)
  */
 typedef struct clapgpu_anim_clock {
     uint32_t        n_chars;
@@ -1496,7 +1497,8 @@ int clapgpu_characters_update_clock(void *stream, const clapgpu_characters *c, c
  * ENTITY3D_HAS_PHYSICS branch of character_apply_velocity with its pushes.  It is scene_characters_move's body
  * (clap.c:589), which runs before phys_step.  What stays with the host, from the outputs: the animation side of
  * character_set_state and ch->state itself (request), connect / disconnect (collision), character_set_moved (applied),
- * character_debug, dash and input handling, characters without a body (transform_move).  PARITY UNPINNED (ODE absent):
+ * character_debug, dash and input handling, characters without a body (transform_move).  (From ABI 46 the first of these
+ * can follow on the device: clapgpu_characters_state, below.)  PARITY UNPINNED (ODE absent):
  * the rule below is the library's own contract; tests/moveref.py restates it.
  *
  * Mover k, all arithmetic in float exactly as character.c writes it, no FMA, linmath's loops in their own order:
@@ -1692,6 +1694,129 @@ int clapgpu_lights_from_entities(void *stream, const clapgpu_entities *e, uint32
                                  const float *carrier_off, const clapgpu_lights *lights);
 
 /* ======================================================================== */
+/* Character states and animation queues (ABI 46)                            */
+/* ======================================================================== */
+
+/*
+ * character_set_state (character.c:316-426), animation_push_by_name / animation_next / animation_end (model.c:1443-1561),
+ * animated_update's control flow (model.c:1563-1592) and the three end callbacks the engine installs itself
+ * (character_idle, character_start_motion, character_any_to_jump, character.c:86-121), per character, on the device.
+ * The rule is stated once in clap_amd/csrc/aniq_dev.h and restated in tests/aniqref.py.
+ *
+ * The queue of a character (entity3d.aniq): up to CLAPGPU_ANIQ_MAX entries of 8 bytes.  struct queued_animation
+ * (model.h:352-361) maps to an entry as: animation -> animation, repeat -> repeat, speed -> speed, end -> a code
+ * (CLAPGPU_ANI_END_*: the function pointer's name; end_priv is always the character), delay is unused by the reference,
+ * sfx_state and frame_cb stay with the host (events: CLAPGPU_ANIQ_STARTED tells it when to reset sfx_state).
+ * Per character: len (aniq.da.nr_el), cur (e->animation, -1 allowed), cleared (e->ani_cleared), ani_time (e->ani_time).
+ * The joint cursors animation_start resets (model.c:1419-1422) have no device counterpart: clapgpu_pose_update
+ * brackets a key time without a cursor.
+ *
+ * name_anim[CLAPGPU_ANI_NAMES]: animation_by_name (model.c:1426-1434) of the model for each of the twelve names
+ * character.c pushes, -1 where the model has none; the host fills it once (device memory).
+ *
+ * Host-owned characters.  A call leaves a character untouched -- none of its arrays written but events, which gets
+ * CLAPGPU_ANIQ_HOST -- when, on entry, len == 0, len > CLAPGPU_ANIQ_MAX, cur < 0, cur >= len or an entry's animation >=
+ * n_anims (animation_next would push "idle" with a drand48 phase, model.c:1458-1469: that stream is the host's), or when
+ * the step would call an end code CLAPGPU_ANI_END_HOST, push a fifth entry (CLAPGPU_ANIQ_OVERFLOW is set too), push an
+ * animation >= n_anims, or advance an emptied queue ((cur + 1) % 0, model.c:1478).  The step runs on a copy in
+ * registers and commits only when none of these arose; the host then does for that character what it did before ABI 46.
+ *
+ * state, airborne, velocity and jump_params may be the very arrays of a clapgpu_move when mover is NULL (character c is
+ * mover c): the move of the next frame then reads the state this frame's calls left.
+ */
+#define CLAPGPU_ANIQ_MAX 4u
+#define CLAPGPU_ANI_END_NONE         0u
+#define CLAPGPU_ANI_END_IDLE         1u     /* character_idle, character.c:86-92 */
+#define CLAPGPU_ANI_END_START_MOTION 2u     /* character_start_motion, :94-99 */
+#define CLAPGPU_ANI_END_ANY_TO_JUMP  3u     /* character_any_to_jump, :103-121 */
+#define CLAPGPU_ANI_END_HOST         0xffu  /* a callback of the host's */
+/* the slots of name_anim[], in the order character.c first uses the names */
+#define CLAPGPU_ANI_IDLE           0u
+#define CLAPGPU_ANI_START_TO_IDLE  1u
+#define CLAPGPU_ANI_MOTION_STOP    2u
+#define CLAPGPU_ANI_JUMP_TO_IDLE   3u
+#define CLAPGPU_ANI_FALL_TO_IDLE   4u
+#define CLAPGPU_ANI_MOTION         5u
+#define CLAPGPU_ANI_MOTION_START   6u
+#define CLAPGPU_ANI_JUMP_TO_MOTION 7u
+#define CLAPGPU_ANI_IDLE_TO_JUMP   8u
+#define CLAPGPU_ANI_MOTION_TO_JUMP 9u
+#define CLAPGPU_ANI_JUMP           10u
+#define CLAPGPU_ANI_FALL           11u
+#define CLAPGPU_ANI_NAMES          12u
+/* events[c]: bits 0-7 are the last clapgpu_animation_queue_time's, bits 8-15 (the same bits << CLAPGPU_ANIQ_STATE_SHIFT)
+ * the last clapgpu_characters_state's, which clears the low byte: one word holds the frame's both steps */
+#define CLAPGPU_ANIQ_ENDED           (1u << 0)   /* frame_time >= time_end (model.c:1590) */
+#define CLAPGPU_ANIQ_STARTED         (1u << 1)   /* an animation_start ran: the host resets sfx_state */
+#define CLAPGPU_ANIQ_ADVANCED        (1u << 2)   /* cur = (cur + 1) % len (model.c:1478) */
+#define CLAPGPU_ANIQ_CB_IDLE         (1u << 3)
+#define CLAPGPU_ANIQ_CB_START_MOTION (1u << 4)
+#define CLAPGPU_ANIQ_CB_ANY_TO_JUMP  (1u << 5)
+#define CLAPGPU_ANIQ_HOST            (1u << 6)   /* untouched: the host does this step */
+#define CLAPGPU_ANIQ_OVERFLOW        (1u << 7)   /* ... because a push found CLAPGPU_ANIQ_MAX entries */
+#define CLAPGPU_ANIQ_STATE_SHIFT     8u
+
+typedef struct clapgpu_aniq_entry {
+    uint16_t animation;
+    uint8_t  repeat;
+    uint8_t  end;                  /* CLAPGPU_ANI_END_* */
+    float    speed;
+} clapgpu_aniq_entry;
+
+/* One animated model's characters, in the order of its clapgpu_anim_clock / clapgpu_pose_batch. */
+typedef struct clapgpu_aniq {
+    uint32_t            n;
+    uint32_t            n_anims;
+    const int32_t      *name_anim;     /* [CLAPGPU_ANI_NAMES] */
+    const float        *time_end;      /* [n_anims] animation.time_end */
+    clapgpu_aniq_entry *queue;         /* [n][CLAPGPU_ANIQ_MAX], 16-byte aligned */
+    uint8_t            *len;           /* [n] */
+    int8_t             *cur;           /* [n] */
+    uint8_t            *cleared;       /* [n] */
+    double             *ani_time;      /* [n] */
+    uint8_t            *state;         /* [n] ch->state, CLAPGPU_CS_* */
+    uint8_t            *airborne;      /* [n] ch->airborne */
+    float              *velocity;      /* [n][3] ch->velocity */
+    float              *ch_motion;     /* [n][2] ch->motion's x and z: persistent, written at character.c:499 */
+    const float        *jump_params;   /* [n][2] jump_forward, jump_upward */
+    const int32_t      *mover;         /* [n] index into the clapgpu_move, -1: none; NULL: character c is mover c */
+    /* out */
+    uint32_t           *pose_anim;     /* [n] queue[cur].animation: clapgpu_pose_batch.anim */
+    float              *frame_time;    /* [n] clapgpu_pose_batch.frame_time */
+    uint32_t           *events;        /* [n] CLAPGPU_ANIQ_* */
+} clapgpu_aniq;
+
+/*
+ * What character_move does with its request, directly behind clapgpu_characters_move: for every character with a mover
+ * k whose request[k] is not 0xff, ch_motion[c] = motion[k] when request[k] is JUMP_START, MOVING or IDLE (the grounded
+ * path writes ch->motion, character.c:499; FALLING keeps the old value), then character_set_state(request[k])
+ * (character.c:316-426) with every push, ignored return value, goto fail_fallback and end callback it makes.  Left out
+ * of case CS_MOVING: character_apply_velocity and character_set_moved (:350-351), which the move has done (applied[k]).
+ * airborne = 1 of :388 is written again (idempotent: the call can be used without the move).
+ * now: clap_get_current_time(), the frame's one clock (clap.c:212-237, 557): what animation_start stores; now_dev != NULL:
+ * read from that device double instead (a captured graph).  events[c] = the step's bits << CLAPGPU_ANIQ_STATE_SHIFT, 0 for
+ * a character without a mover or a request.  One lane per character, no host synchronisation, no allocation.
+ * CLAPGPU_ERR_INVALID_ARGUMENTS before any HIP call: q or m NULL; with q->n > 0 a missing array of q (mover, pose_anim,
+ * frame_time and time_end may be NULL here), a queue that is not 16-byte aligned, m->n > 0 without m->request or
+ * m->motion, a NULL mover with q->n > m->n.  A mover index outside [0, m->n) is no mover.  q->n == 0 launches nothing.
+ */
+int clapgpu_characters_state(void *stream, const clapgpu_aniq *q, const clapgpu_move *m, double now, const double *now_dev);
+
+/*
+ * animated_update (model.c:1563-1592) for the model's characters, in place of clapgpu_animation_time: per character
+ *   pose_anim[c]  = queue[cur].animation
+ *   frame_time[c] = (float)((now - ani_time[c]) * speed)          (double arithmetic, before the advance: channels_transform
+ *                                                                  runs before animation_next)
+ * and, when (now - ani_time[c]) * speed >= time_end[animation], animation_next (model.c:1454-1483) with its callbacks:
+ * a repeating entry restarts; another one has its end code called (nulled first), then ani_cleared clears and returns,
+ * or cur = (cur + 1) % len and animation_start.  frame_cb / frame_sfx stay with the host, which runs them from
+ * frame_time; they change no queue.  events[c] = (events[c] & 0xff00) | the step's bits.  A host-owned character's
+ * pose_anim and frame_time are not written either.  Arguments as above (every array but mover needed, and time_end);
+ * q->n == 0 launches nothing.
+ */
+int clapgpu_animation_queue_time(void *stream, const clapgpu_aniq *q, double now, const double *now_dev);
+
+/* ======================================================================== */
 /* One frame (core/clap.c:551-665)                                           */
 /* ======================================================================== */
 
@@ -1764,6 +1889,13 @@ typedef struct clapgpu_frame {
     const clapgpu_move *move;
     double    move_dt_sec;                     /* the raw frame delta, as clapgpu_characters_move takes it */
     void     *move_scratch;                    /* clapgpu_characters_move_scratch_bytes(bodies->n, move->n), 256-byte aligned */
+    /* character states and animation queues on the device (ABI 46); NULL: the frame as before, launch for launch.  Set:
+     * clapgpu_characters_state(aniq, move) follows the move stage (when move is set), and clapgpu_animation_queue_time
+     * takes the place of the clock (anim_clock is not read).  The queue clock is a launch of its own behind the character
+     * hooks, which read airborne before animated_update's callback can set it; under CLAPGPU_FRAME_OVERLAP the animation
+     * chain is forked behind it.  Needs skeleton, animations and pose, with pose->anim == aniq->pose_anim, pose->frame_time
+     * == aniq->frame_time and pose->n_chars == aniq->n: CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, before any launch */
+    const clapgpu_aniq *aniq;
 } clapgpu_frame;
 
 /* Default (0): everything on the caller's stream in the reference's order.  CLAPGPU_FRAME_OVERLAP: the frame's three
