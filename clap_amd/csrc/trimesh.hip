@@ -10,6 +10,8 @@
 //   k_tm_gather     the triangles and their (static, triangle of its mesh) in leaf order
 //   k_tm_hierarchy  Karras 2012: the binary radix tree over the sorted keys (all distinct: the index breaks ties)
 //   k_tm_boxes      bottom-up: each node's two child boxes (float, rounded outward) and its subtree height
+// The arithmetic of these (bake, Morton code, Karras rule, rounding) is in trimesh_build.h, shared with trimesh_parts.hip:
+// the set "in parts" of clapgpu_trimesh_create_parts, whose pose refits and sorts nothing but its parts.
 //
 // The mesh: model3d.collision_vx scaled by the entity's scale in float the way mat4x4_scale_aniso + mat4x4_mul_vec4
 // compute it (each row starts from 0.f and adds the products, so -0 becomes +0; w == 1), widened to double, then
@@ -22,35 +24,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include <rocprim/device/device_radix_sort.hpp>
-#include "common.h"
-#include "phys_dev.h"
-#include "bp_grid.h"
-#include "trimesh_dev.h"
-
-namespace clapgpu {
-
-constexpr int TB = 256;                                 // set-up kernels
-
-} // namespace clapgpu
-
-struct clapgpu_trimesh {
-    uint32_t n_meshes, n_statics, n_vx, n_tris;
-    uint32_t *static_index, *vx_first, *tri_first, *tri_mesh;
-    float *vx, *scale, *quat;
-    uint16_t *idx;
-    double *pos;
-    int32_t *static_mesh;                               // [n_statics]: the static's mesh or -1
-    double *tri, *stri;                                 // [T][9]: input order, leaf order
-    uint2 *skey;
-    uint64_t *keys[2];
-    clapgpu::Node *nodes;                               // [max(T - 1, 1)]
-    uint32_t *parent;                                   // [T - 1 + T]: of the internal nodes, then of the leaves
-    uint32_t *counter, *height;                         // [T - 1] each
-    uint64_t *bounds;                                   // [6]: centroid min xyz, max xyz as order keys
-    uint32_t *ctl;                                      // [0] check error, [1] tree height
-    void *sort_tmp;
-    size_t sort_bytes;
-};
+#include "trimesh_build.h"
 
 namespace clapgpu {
 
@@ -78,20 +52,6 @@ void k_tm_check(uint32_t M, uint32_t T, uint32_t n_statics, const uint32_t *stat
     }
 }
 
-// mat4x4_scale_aniso(identity, s, s, s) then mat4x4_mul_vec4 on (x, y, z, 1): each row from 0.f plus the four
-// products in order, then vec3_scale by 1 / w
-__device__ __forceinline__ void scaled(float s, const float *v, double (&o)[3])
-{
-    const float v4[4] = { v[0], v[1], v[2], 1.0f };
-    float r[4];
-    for (int j = 0; j < 4; j++) {
-        r[j] = 0.f;
-        for (int i = 0; i < 4; i++) r[j] += (i == j ? (j < 3 ? s : 1.0f) : 0.0f) * v4[i];
-    }
-    const float w = 1.0f / r[3];
-    for (int j = 0; j < 3; j++) o[j] = r[j] * w;
-}
-
 __global__ __launch_bounds__(TB)
 void k_tm_bake(uint32_t T, const uint32_t *tri_mesh, const uint32_t *vx_first, const float *vx, const uint16_t *idx,
                const float *scale, const double *pos, const float *quat, double *tri, uint64_t *bounds)
@@ -99,56 +59,12 @@ void k_tm_bake(uint32_t T, const uint32_t *tri_mesh, const uint32_t *vx_first, c
     const uint32_t t = blockIdx.x * TB + threadIdx.x;
     double c[3] = { NAN, NAN, NAN };
     if (t < T) {
-        const uint32_t m = tri_mesh[t];
-        const double q[4] = { quat[4 * (size_t)m + 3], quat[4 * (size_t)m], quat[4 * (size_t)m + 1], quat[4 * (size_t)m + 2] };
-        double R[12];
-        phd::q_to_R(q, R);
-        const double p[3] = { pos[3 * (size_t)m], pos[3 * (size_t)m + 1], pos[3 * (size_t)m + 2] };
-        const float s = scale[m];
         double w[9];
-        for (int k = 0; k < 3; k++) {
-            const float *v = vx + 3 * ((size_t)vx_first[m] + idx[3 * (size_t)t + k]);
-            double ms[3];
-            scaled(s, v, ms);
-            for (int a = 0; a < 3; a++)
-                w[3 * k + a] = R[4 * a] * ms[0] + R[4 * a + 1] * ms[1] + R[4 * a + 2] * ms[2] + p[a];
-        }
+        bake_tri(t, tri_mesh[t], vx_first, vx, idx, scale, pos, quat, w);
         for (int a = 0; a < 9; a++) tri[9 * (size_t)t + a] = w[a];
         for (int a = 0; a < 3; a++) c[a] = (w[a] + w[3 + a] + w[6 + a]) / 3.0;
     }
-    // the centroids' bounds: the wave's, then the workgroup's in LDS, then one atomic per workgroup and side (NaN
-    // centroids left out)
-    __shared__ double red[TB / WAVE][6];
-    const int wv = threadIdx.x / WAVE;
-    for (int a = 0; a < 3; a++) {
-        double lo = c[a] == c[a] ? c[a] : INFINITY, hi = c[a] == c[a] ? c[a] : -INFINITY;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            lo = fmin(lo, __shfl_xor(lo, o));
-            hi = fmax(hi, __shfl_xor(hi, o));
-        }
-        if (lane_id() == 0) { red[wv][a] = lo; red[wv][3 + a] = hi; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        double lo = red[0][a], hi = red[0][3 + a];
-        for (int k = 1; k < TB / WAVE; k++) { lo = fmin(lo, red[k][a]); hi = fmax(hi, red[k][3 + a]); }
-        if (lo <= hi) {
-            atomicMin((unsigned long long *)&bounds[a], (unsigned long long)order_key(lo));
-            atomicMax((unsigned long long *)&bounds[3 + a], (unsigned long long)order_key(hi));
-        }
-    }
-}
-
-__device__ __forceinline__ uint32_t spread10(uint32_t x)                // 10 bits -> every third bit
-{
-    x &= 0x3ffu;
-    x = (x | (x << 16)) & 0x030000ffu;
-    x = (x | (x << 8)) & 0x0300f00fu;
-    x = (x | (x << 4)) & 0x030c30c3u;
-    x = (x | (x << 2)) & 0x09249249u;
-    return x;
+    block_bounds(c, bounds);                            // the centroids' bounds (NaN centroids left out)
 }
 
 __global__ __launch_bounds__(TB)
@@ -156,17 +72,9 @@ void k_tm_morton(uint32_t T, const double *tri, const uint64_t *bounds, uint64_t
 {
     const uint32_t t = blockIdx.x * TB + threadIdx.x;
     if (t >= T) return;
-    uint32_t code = 0;
-    if (bounds[0] != ~0ull) {                           // else every centroid is NaN: code 0
-        for (int a = 0; a < 3; a++) {
-            const double lo = order_value(bounds[a]), hi = order_value(bounds[3 + a]);
-            const double c = (tri[9 * (size_t)t + a] + tri[9 * (size_t)t + 3 + a] + tri[9 * (size_t)t + 6 + a]) / 3.0;
-            double f = hi > lo ? (c - lo) / (hi - lo) : 0.0;
-            f = f >= 0.0 ? (f <= 1.0 ? f : 1.0) : 0.0;  // NaN: 0
-            const uint32_t q = (uint32_t)fmin(f * 1024.0, 1023.0);
-            code |= spread10(q) << (2 - a);
-        }
-    }
+    double c[3];
+    for (int a = 0; a < 3; a++) c[a] = (tri[9 * (size_t)t + a] + tri[9 * (size_t)t + 3 + a] + tri[9 * (size_t)t + 6 + a]) / 3.0;
+    const uint32_t code = morton30(c, bounds);          // every centroid NaN: code 0
     keys[t] = ((uint64_t)code << 32) | t;
 }
 
@@ -181,33 +89,14 @@ void k_tm_gather(uint32_t T, const uint64_t *keys, const double *tri, const uint
     skey[i] = make_uint2(static_index[m], t - tri_first[m]);
 }
 
-__device__ __forceinline__ int delta(const uint64_t *k, int64_t T, int64_t i, int64_t j)
-{
-    return (j < 0 || j >= T) ? -1 : __clzll((long long)(k[i] ^ k[j]));
-}
-
 // Karras 2012, "Maximizing parallelism in the construction of BVHs, octrees, and k-d trees", internal node i of T - 1
 __global__ __launch_bounds__(TB)
 void k_tm_hierarchy(uint32_t T, const uint64_t *k, Node *nodes, uint32_t *parent)
 {
     const int64_t i = blockIdx.x * (int64_t)TB + threadIdx.x, n = T;
     if (i >= n - 1) return;
-    const int d = delta(k, n, i, i + 1) - delta(k, n, i, i - 1) >= 0 ? 1 : -1;
-    const int dmin = delta(k, n, i, i - d);
-    int64_t lmax = 2;
-    while (delta(k, n, i, i + lmax * d) > dmin) lmax <<= 1;
-    int64_t l = 0;
-    for (int64_t t = lmax >> 1; t >= 1; t >>= 1)
-        if (delta(k, n, i, i + (l + t) * d) > dmin) l += t;
-    const int64_t j = i + l * d;
-    const int dnode = delta(k, n, i, j);
-    int64_t s = 0, t = l;
-    do {
-        t = (t + 1) >> 1;
-        if (delta(k, n, i, i + (s + t) * d) > dnode) s += t;
-    } while (t > 1);
-    const int64_t g = i + s * d + (d < 0 ? -1 : 0);
-    const int64_t lo = i < j ? i : j, hi = i < j ? j : i;
+    int64_t lo, hi, g;
+    karras_node(k, n, i, lo, hi, g);
     const uint32_t c0 = lo == g ? TM_LEAF | (uint32_t)g : (uint32_t)g;
     const uint32_t c1 = hi == g + 1 ? TM_LEAF | (uint32_t)(g + 1) : (uint32_t)(g + 1);
     nodes[i].child[0] = c0;
@@ -215,25 +104,6 @@ void k_tm_hierarchy(uint32_t T, const uint64_t *k, Node *nodes, uint32_t *parent
     nodes[i].pad[0] = nodes[i].pad[1] = 0;
     parent[(c0 & TM_LEAF) ? (n - 1) + (c0 & ~TM_LEAF) : c0] = (uint32_t)i;
     parent[(c1 & TM_LEAF) ? (n - 1) + (c1 & ~TM_LEAF) : c1] = (uint32_t)i;
-}
-
-__device__ __forceinline__ float round_down(double d)
-{
-    float f = (float)d;
-    if ((double)f > d) f = nextafterf(f, -INFINITY);
-    return f;
-}
-
-__device__ __forceinline__ float round_up(double d)
-{
-    float f = (float)d;
-    if ((double)f < d) f = nextafterf(f, INFINITY);
-    return f;
-}
-
-__device__ __forceinline__ float load_agent(const float *p)
-{
-    return __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
 // one thread per leaf climbs while it is the second child to arrive at a node
@@ -244,11 +114,7 @@ void k_tm_boxes(uint32_t T, const double *stri, Node *nodes, const uint32_t *par
     const uint32_t i = blockIdx.x * TB + threadIdx.x;
     if (i >= T) return;
     float b[6];
-    const double *v = stri + 9 * (size_t)i;
-    for (int a = 0; a < 3; a++) {
-        b[a] = round_down(fmin(fmin(v[a], v[3 + a]), v[6 + a]));
-        b[3 + a] = round_up(fmax(fmax(v[a], v[3 + a]), v[6 + a]));
-    }
+    leaf_box(stri + 9 * (size_t)i, b);
     if (T == 1) {                                       // a root holding the one leaf twice
         for (int a = 0; a < 6; a++) { nodes[0].box[a] = b[a]; nodes[0].box[6 + a] = b[a]; }
         nodes[0].child[0] = nodes[0].child[1] = TM_LEAF;
@@ -325,16 +191,12 @@ extern "C" void clapgpu_trimesh_destroy(clapgpu_trimesh *m)
                   m->height, m->bounds, m->ctl, m->sort_tmp };
     for (void *q : p)
         if (q) (void)hipFree(q);
+    parts_free(m);
     free(m);
 }
 
-template <typename T> static int dev_alloc(T *&p, size_t n)
-{
-    CLAPGPU_HIP(hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T)));
-    return CLAPGPU_OK;
-}
-
-extern "C" int clapgpu_trimesh_create(void *stream, clapgpu_trimesh **out, const clapgpu_trimesh_desc *d)
+// the arguments, the ranges, the copies and the device check of both kinds of set, then the kind's own build
+int clapgpu::trimesh_create(void *stream, clapgpu_trimesh **out, const clapgpu_trimesh_desc *d, bool parts)
 {
     if (!out || !d) return CLAPGPU_ERR_INVALID_ARGUMENTS;
     *out = nullptr;
@@ -352,28 +214,28 @@ extern "C" int clapgpu_trimesh_create(void *stream, clapgpu_trimesh **out, const
 #define TRY(x) do { rc = (x); if (rc) { clapgpu_trimesh_destroy(m); return rc; } } while (0)
     uint32_t *hf = static_cast<uint32_t *>(malloc(2 * ((size_t)M + 1) * sizeof(uint32_t)));
     if (!hf) { clapgpu_trimesh_destroy(m); return CLAPGPU_ERR_NOMEM; }
+    struct Hold { void *p; ~Hold() { free(p); } } hold{ hf };                  // the ranges live to the end: a set in parts reads them
     hf[0] = hf[M + 1] = 0;
     if (M) {                                                                   // the ranges, on the host: they size everything
         hipError_t e = hipMemcpyAsync(hf, d->vx_first, ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(hf + M + 1, d->tri_first, ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { free(hf); clapgpu_trimesh_destroy(m); return hip_fail(e, "clapgpu_trimesh_create: ranges"); }
+        if (e != hipSuccess) { clapgpu_trimesh_destroy(m); return hip_fail(e, "clapgpu_trimesh_create: ranges"); }
     }
     bool ok = hf[0] == 0 && hf[M + 1] == 0;
     for (uint32_t k = 0; k < M && ok; k++) ok = hf[k + 1] >= hf[k] && hf[M + 2 + k] >= hf[M + 1 + k];
     m->n_vx = hf[M];
     m->n_tris = hf[2 * M + 1];
-    free(hf);
     if (!ok || m->n_tris >= TM_LEAF) { clapgpu_trimesh_destroy(m); return CLAPGPU_ERR_INVALID_ARGUMENTS; }
     const size_t V = m->n_vx, T = m->n_tris;
     TRY(dev_alloc(m->static_index, M)); TRY(dev_alloc(m->vx_first, M + 1)); TRY(dev_alloc(m->tri_first, M + 1));
     TRY(dev_alloc(m->tri_mesh, T)); TRY(dev_alloc(m->vx, 3 * V)); TRY(dev_alloc(m->scale, M)); TRY(dev_alloc(m->quat, 4 * M));
     TRY(dev_alloc(m->idx, 3 * T)); TRY(dev_alloc(m->pos, 3 * M)); TRY(dev_alloc(m->static_mesh, m->n_statics));
-    TRY(dev_alloc(m->tri, 9 * T)); TRY(dev_alloc(m->stri, 9 * T)); TRY(dev_alloc(m->skey, T));
-    TRY(dev_alloc(m->keys[0], T)); TRY(dev_alloc(m->keys[1], T)); TRY(dev_alloc(m->nodes, T > 1 ? T - 1 : 1));
+    TRY(dev_alloc(m->tri, parts ? 0 : 9 * T)); TRY(dev_alloc(m->stri, 9 * T)); TRY(dev_alloc(m->skey, T));
+    TRY(dev_alloc(m->keys[0], parts ? 0 : T)); TRY(dev_alloc(m->keys[1], parts ? 0 : T)); TRY(dev_alloc(m->nodes, T > 1 ? T - 1 : 1));
     TRY(dev_alloc(m->parent, 2 * T)); TRY(dev_alloc(m->counter, T)); TRY(dev_alloc(m->height, T));
     TRY(dev_alloc(m->bounds, 6)); TRY(dev_alloc(m->ctl, 4));
-    if (T) {
+    if (T && !parts) {
         size_t bytes = 0;
         if (rocprim::radix_sort_keys(nullptr, bytes, m->keys[0], m->keys[1], (size_t)T, 0, 62, s) != hipSuccess)
             TRY(CLAPGPU_ERR_UNKNOWN);
@@ -411,20 +273,25 @@ extern "C" int clapgpu_trimesh_create(void *stream, clapgpu_trimesh **out, const
             return CLAPGPU_ERR_INVALID_ARGUMENTS;
         }
     }
-    TRY(build(s, m));
+    TRY(parts ? parts_build(s, m, hf + M + 1) : build(s, m));
 #undef TRY
     *out = m;
     return CLAPGPU_OK;
 }
 
+extern "C" int clapgpu_trimesh_create(void *stream, clapgpu_trimesh **out, const clapgpu_trimesh_desc *d)
+{
+    return trimesh_create(stream, out, d, false);
+}
+
 extern "C" int clapgpu_trimesh_pose(void *stream, clapgpu_trimesh *m, const double *pos, const float *quat)
 {
     if (!m || (m->n_meshes && (!pos || !quat))) return CLAPGPU_ERR_INVALID_ARGUMENTS;
-    if (m->n_meshes == 0) return CLAPGPU_OK;
     hipStream_t s = as_stream(stream);
+    if (m->n_meshes == 0) return m->parts ? parts_pose_all(s, m) : CLAPGPU_OK;
     CLAPGPU_HIP(hipMemcpyAsync(m->pos, pos, 24 * (size_t)m->n_meshes, hipMemcpyDeviceToDevice, s));
     CLAPGPU_HIP(hipMemcpyAsync(m->quat, quat, 16 * (size_t)m->n_meshes, hipMemcpyDeviceToDevice, s));
-    return build(s, m);
+    return m->parts ? parts_pose_all(s, m) : build(s, m);
 }
 
 extern "C" int clapgpu_trimesh_status(void *stream, const clapgpu_trimesh *m, uint32_t *depth, uint32_t *n_tris)
@@ -434,6 +301,11 @@ extern "C" int clapgpu_trimesh_status(void *stream, const clapgpu_trimesh *m, ui
     *depth = 0;
     if (m->n_tris == 0) return CLAPGPU_OK;
     hipStream_t s = as_stream(stream);
+    if (m->parts) {                                     // top plus deepest part: both fixed at creation
+        CLAPGPU_HIP(hipStreamSynchronize(s));
+        *depth = m->top_height + m->part_height;
+        return CLAPGPU_OK;
+    }
     CLAPGPU_HIP(hipMemcpyAsync(depth, m->ctl + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     CLAPGPU_HIP(hipStreamSynchronize(s));
     return CLAPGPU_OK;

@@ -15,6 +15,9 @@ from . import _lib
 from ._dev import device_array, ptr as _ptr, stream as _stream, upload
 from .characters import CharacterMoves  # noqa: F401  (physics.CharacterMoves: the name callers know it by)
 
+# a node of the static meshes' BVH as read_static_meshes returns it (trimesh_dev.h: 64 bytes)
+NODE = np.dtype([("box", np.float32, (2, 6)), ("child", np.uint32, 2), ("pad", np.uint32, 2)])
+
 
 class PhysWorld:
     def __init__(self, bodies, statics=None, pair_capacity=None, device="cuda:0", static_pair_capacity=None, geom_records=True,
@@ -545,7 +548,8 @@ class PhysWorld:
         statics_ptr and every static geom description built on it keep their address and hold the new boxes.  Synchronises
         the stream; drops the index and a recorded prebin; a graph captured from frames of this world must be captured
         again.  Meshes are left to pose_static_meshes.  The order for a moving static that owns a mesh: update_statics
-        (the box must hold the posed mesh), then pose_static_meshes, then bp_index."""
+        (the box must hold the posed mesh), then pose_static_meshes (or, on a set in parts, pose_static_meshes_some with
+        the moved meshes alone), then bp_index."""
         a = upload(aabb, np.float64, self.device, (-1, 6))
         if a.dtype != torch.float64 or a.dim() != 2 or tuple(a.shape) != (self.n_static, 6):
             raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "update_statics", f"float64 [{self.n_static}, 6] expected")
@@ -560,12 +564,15 @@ class PhysWorld:
         return st.value
 
     _meshes = None
+    _meshes_shape = (0, 0)                                             # (meshes, triangles) of the set
 
-    def set_static_meshes(self, static_index, vertices, indices, scale, pos, quat):
+    def set_static_meshes(self, static_index, vertices, indices, scale, pos, quat, parts=False):
         """The triangle meshes of trimesh statics (phys_geom_trimesh_new, physics.c:882-930): mesh m belongs to static
         static_index[m]; vertices[m] float [V, 3] in model space, indices[m] u16 [T, 3], scale[m] (entity->scale),
         pos[m] (entity position), quat[m] (entity rotation x, y, z, w).  From then on ray_cast and ground_collide
-        intersect those statics through their triangles (clapgpu_trimesh_create)."""
+        intersect those statics through their triangles (clapgpu_trimesh_create).  parts: the set in parts
+        (clapgpu_trimesh_create_parts), which answers the same bit for bit and takes pose_static_meshes_some; it pays where
+        few of many meshes move per frame (profiles/trimesh_parts/README.md)."""
         dev = self.device
         m = len(static_index)
         vx = [np.asarray(v, np.float32).reshape(-1, 3) for v in vertices]
@@ -574,16 +581,18 @@ class PhysWorld:
         tri_first = np.concatenate([[0], np.cumsum([len(i) for i in ix])]).astype(np.uint32)
         keep = dict(static_index=upload(static_index, np.uint32, dev),
                     vx_first=upload(vx_first, np.uint32, dev), tri_first=upload(tri_first, np.uint32, dev),
-                    vx=upload(np.concatenate(vx) if m else np.zeros((1, 3)), np.float32, dev),
-                    idx=upload(np.concatenate(ix) if m else np.zeros((1, 3)), np.uint16, dev),
+                    vx=upload(np.concatenate(vx) if vx_first[-1] else np.zeros((1, 3)), np.float32, dev),
+                    idx=upload(np.concatenate(ix) if tri_first[-1] else np.zeros((1, 3)), np.uint16, dev),
                     scale=upload(scale, np.float32, dev, (-1,)), pos=upload(pos, np.float64, dev, (-1, 3)),
                     quat=upload(quat, np.float32, dev, (-1, 4)))
         d = _lib.TrimeshDesc(m, self.n_static, *[(_ptr(keep[k]) if m else None) for k in
                                                   ("static_index", "vx_first", "tri_first", "vx", "idx", "scale", "pos", "quat")])
         out = C.c_void_p()
-        _lib.check(_lib.lib().clapgpu_trimesh_create(_stream(), C.byref(out), C.byref(d)), "clapgpu_trimesh_create")
+        name = "clapgpu_trimesh_create_parts" if parts else "clapgpu_trimesh_create"
+        _lib.check(getattr(_lib.lib(), name)(_stream(), C.byref(out), C.byref(d)), name)
         self._free_meshes()
         self._meshes, self._meshes_keep = out, keep
+        self._meshes_shape = (m, int(tri_first[-1]))
 
     def pose_static_meshes(self, pos, quat):
         """New poses of every mesh (entity position, rotation x, y, z, w): re-bake and rebuild (clapgpu_trimesh_pose)."""
@@ -591,6 +600,37 @@ class PhysWorld:
         p, q = upload(pos, np.float64, dev, (-1, 3)), upload(quat, np.float32, dev, (-1, 4))
         _lib.check(_lib.lib().clapgpu_trimesh_pose(_stream(), self._meshes, _ptr(p), _ptr(q)), "clapgpu_trimesh_pose")
         torch.cuda.current_stream().synchronize()
+
+    def pose_static_meshes_some(self, mesh, pos, quat):
+        """New poses of the listed meshes of a set in parts (mesh [k] indices, pos [k, 3], quat [k, 4]; host arrays or
+        device tensors): those meshes are baked and refit, the others untouched (clapgpu_trimesh_pose_meshes).  Does not
+        synchronise."""
+        dev = self.device
+        i, p, q = upload(mesh, np.uint32, dev, (-1,)), upload(pos, np.float64, dev, (-1, 3)), upload(quat, np.float32, dev, (-1, 4))
+        k = int(i.shape[0])
+        if p.shape[0] != k or q.shape[0] != k:
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "pose_static_meshes_some", f"{k} meshes, {p.shape[0]} positions, "
+                                    f"{q.shape[0]} rotations")
+        _lib.check(_lib.lib().clapgpu_trimesh_pose_meshes(_stream(), self._meshes, k, _ptr(i) if k else None, _ptr(p) if k else None,
+                                                          _ptr(q) if k else None), "clapgpu_trimesh_pose_meshes")
+
+    def static_meshes_parts_status(self):
+        """(in parts, top height, deepest part's height, sticky flags) of the mesh set (clapgpu_trimesh_parts_status)."""
+        out = (C.c_uint32 * 4)()
+        _lib.check(_lib.lib().clapgpu_trimesh_parts_status(_stream(), self._meshes, out), "clapgpu_trimesh_parts_status")
+        return bool(out[0]), out[1], out[2], out[3]
+
+    def read_static_meshes(self):
+        """The set's image on the host (clapgpu_trimesh_read): dict of nodes (structured: box [2, 6] float32, child [2],
+        pad [2] uint32), key [T, 2], tri [T, 9] in leaf order, and part_root [n_meshes] for a set in parts, else None."""
+        n_meshes, T = self._meshes_shape
+        nodes = np.zeros(max(T - 1, 1), NODE)
+        key, tri = np.zeros((T, 2), np.uint32), np.zeros((T, 9), np.float64)
+        root = np.zeros(n_meshes, np.uint32) if self.static_meshes_parts_status()[0] else None
+        hp = lambda a: a.ctypes.data if a is not None and a.size else None
+        _lib.check(_lib.lib().clapgpu_trimesh_read(_stream(), self._meshes, hp(nodes), hp(key), hp(tri), hp(root)),
+                   "clapgpu_trimesh_read")
+        return dict(nodes=nodes, key=key, tri=tri, part_root=root)
 
     def static_meshes_status(self):
         """(tree height, triangles) of the mesh set."""

@@ -58,7 +58,7 @@ void clapgpu_test_fail_after(int launches);
 /* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
  * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
  * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
-#define CLAPGPU_ABI_VERSION 46u
+#define CLAPGPU_ABI_VERSION 47u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -931,7 +931,8 @@ const double *clapgpu_bp_static_aabb(const clapgpu_bp *bp);            /* the de
  * (clapgpu_bodies_step_prebin; undone as clapgpu_bp_invalidate undoes it).  What stays: the sticky status bits, the bin
  * epoch, the leveled-index switch, the contact ticket word.  A HIP graph captured from calls that use the object holds
  * the old image's addresses and counts BY VALUE: capture it again after an update (this is not detected).
- * A static that owns a mesh: update its box first, then clapgpu_trimesh_pose, then clapgpu_bp_index.
+ * A static that owns a mesh: update its box first, then clapgpu_trimesh_pose, then clapgpu_bp_index.  Where few of the
+ * meshes move, a set of clapgpu_trimesh_create_parts takes clapgpu_trimesh_pose_meshes in its place: the moved meshes alone.
  *
  * For tests and tools, in the spirit of clapgpu_bp_cell_slot:
  *   clapgpu_bp_statics_sizes  host state only (any output may be NULL): the block buckets, the registrations of all
@@ -1138,6 +1139,7 @@ int clapgpu_bodies_ground_collide(void *stream, clapgpu_bp *bp, const clapgpu_bo
  * 0 without triangles), *n_tris = the triangles of all meshes.
  * A static's broadphase AABB must hold its posed mesh: the mesh contacts below only see pairs the broadphase found.  A
  * mesh that leaves the box it was created with: give the static its new box first (clapgpu_bp_statics_update), then pose.
+ * Where few of the meshes move, pose those alone: clapgpu_trimesh_pose_meshes on a set in parts (below).
  */
 typedef struct clapgpu_trimesh_desc {
     uint32_t        n_meshes, n_statics;
@@ -1153,6 +1155,51 @@ int  clapgpu_trimesh_create(void *stream, clapgpu_trimesh **out, const clapgpu_t
 int  clapgpu_trimesh_pose(void *stream, clapgpu_trimesh *mesh, const double *pos, const float *quat);
 int  clapgpu_trimesh_status(void *stream, const clapgpu_trimesh *mesh, uint32_t *depth, uint32_t *n_tris);
 void clapgpu_trimesh_destroy(clapgpu_trimesh *mesh);
+
+/*
+ * A mesh set "in parts" (ABI 47): the same object for every entry point that takes a clapgpu_trimesh, with the same
+ * answers bit for bit, built so that posing some meshes costs those meshes.  clapgpu_trimesh_create_parts takes the
+ * descriptor of clapgpu_trimesh_create, checks it the same way, returns the same errors in the same order and
+ * synchronises.  The node array (max(T - 1, 1) nodes of 64 B, the root at node 0) holds one subtree per PART (a mesh
+ * with a triangle) and a top tree over the parts:
+ *   a part        its leaf slots are [tri_first[m], tri_first[m + 1]); its k - 1 nodes are one BVH2 by the rule of the
+ *                 plain set over keys of the UNPOSED mesh (30-bit Morton code of the scaled model-space centroid within
+ *                 the mesh's own centroid bounds, the triangle's index below it).  A pose changes no key, leaf order or
+ *                 link of it.  A part of one triangle has no node: its root is the leaf link
+ *   the top tree  the parts sorted by (30-bit Morton code of the centre of the part's root box within the bounds of all
+ *                 such centres, a centre with a NaN: code 0; then mesh index); balanced: a node covering [lo, hi) splits
+ *                 at lo + (hi - lo + 1) / 2; height ceil(log2 P); with one part, node 0 is that part's root
+ * Boxes as in the plain set (float, rounded outward from the fp64 bake, a child box the exact union of what is below it).
+ * The image (nodes, slots, keys) is a function of the descriptor and the poses alone.  CLAPGPU_ERR_TOO_LARGE, no object:
+ * top height plus the deepest part's height above 62 (the walk's stack).  Neither height depends on a pose.
+ * clapgpu_trimesh_status reports their sum: an upper bound of the tree's height, which is what the stack needs (the
+ * balanced top has its leaves on two levels, so where the deepest part hangs from a shorter branch the walked height
+ * is one less).  clapgpu_trimesh_pose on a set in parts takes every mesh's pose, bakes and
+ * refits (no triangle is sorted) and clears the sticky flags below.
+ *
+ * clapgpu_trimesh_pose_meshes: mesh[n_moved], pos[n_moved][3], quat[n_moved][4] are DEVICE arrays; row k is the new pose
+ * of mesh mesh[k].  Afterwards the set is, byte for byte, the set clapgpu_trimesh_create_parts makes of the same
+ * descriptor with those poses replaced: the listed meshes' triangles are baked into their slots, their parts' boxes refit,
+ * the P part keys sorted and the top tree rebuilt; no triangle of another mesh is read.  No host synchronisation and no
+ * allocation: a captured graph may hold the call.  n_moved == 0: CLAPGPU_OK, nothing launched.  A listed mesh without
+ * triangles changes only its stored pose.  CLAPGPU_ERR_INVALID_ARGUMENTS before any HIP call: a NULL set, a plain set, a
+ * NULL array with n_moved > 0.  Sticky flags (until the next clapgpu_trimesh_pose): CLAPGPU_TRIMESH_POSE_RANGE a
+ * mesh[k] >= n_meshes (skipped); CLAPGPU_TRIMESH_POSE_TWICE a mesh listed more than once (its lowest list position wins).
+ * After an error the set may be half posed: a clapgpu_trimesh_pose that succeeds makes it whole.
+ *
+ * clapgpu_trimesh_parts_status: host sync; out[0] 1 for a set in parts else 0, out[1] the top tree's height, out[2] the
+ * deepest part's, out[3] the sticky flags.
+ * clapgpu_trimesh_read (tests and tools, either kind of set): host sync; into HOST arrays, each may be NULL: nodes
+ * [max(T - 1, 1)][64 B], key [T][2] (static, triangle of its mesh) and tri [T][9] in leaf order, part_root [n_meshes]
+ * (the part's root link, 0xffffffff for a mesh without triangles; must be NULL for a plain set).
+ */
+#define CLAPGPU_TRIMESH_POSE_RANGE 1u
+#define CLAPGPU_TRIMESH_POSE_TWICE 2u
+int  clapgpu_trimesh_create_parts(void *stream, clapgpu_trimesh **out, const clapgpu_trimesh_desc *d);
+int  clapgpu_trimesh_pose_meshes(void *stream, clapgpu_trimesh *set, uint32_t n_moved, const uint32_t *mesh, const double *pos,
+                                 const float *quat);
+int  clapgpu_trimesh_parts_status(void *stream, const clapgpu_trimesh *set, uint32_t out[4]);
+int  clapgpu_trimesh_read(void *stream, const clapgpu_trimesh *set, void *nodes, uint32_t *key, double *tri, uint32_t *part_root);
 
 /*
  * Contacts against the mesh set: near_callback's dCollide for (body, static) pairs whose static owns a mesh, and the
