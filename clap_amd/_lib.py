@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 47
+ABI_VERSION = 48
 
 OK = 0
 ERR_NOMEM = -1
@@ -118,6 +118,21 @@ class SkinBatch(C.Structure):
                 ("normal", C.c_void_p), ("joints", C.c_void_p), ("weights", C.c_void_p),
                 ("joint_transforms", C.c_void_p), ("out_position", C.c_void_p), ("out_normal", C.c_void_p),
                 ("out_w", C.c_void_p)]
+
+
+SKIN_LODS = 4
+SKIN_LOD_ALL = 0xFFFFFFFF
+SKIN_NOT_DRAWN = 0xFF
+SKINSEL_ENTITY_RANGE, SKINSEL_LOD_RANGE, SKINSEL_LIST_RANGE = 1, 2, 4
+
+
+class SkinSelect(C.Structure):
+    """clapgpu_skin_select (include/clapgpu.h): which characters clapgpu_skin_drawn skins, and which of their vertices."""
+    _fields_ = [("n_planes", C.c_uint32), ("n_entities", C.c_uint32), ("planes", C.c_void_p * (1 + EXTRA_VIEWS_MAX)),
+                ("entity", C.c_void_p), ("cur_lod", C.c_void_p), ("n_rows", C.c_uint32), ("n_lods", C.c_uint32),
+                ("row", C.c_void_p), ("lod_first", C.c_void_p), ("lod_count", C.c_void_p), ("list", C.c_void_p),
+                ("n_list", C.c_uint32), ("pad", C.c_uint32), ("skinned", C.c_void_p), ("chars", C.c_void_p),
+                ("count", C.c_void_p), ("status", C.c_void_p), ("scratch", C.c_void_p)]
 
 
 class World(C.Structure):
@@ -288,7 +303,7 @@ class FrameDesc(C.Structure):
                 ("solver", C.POINTER(Solver)), ("solve_scratch", C.c_void_p), ("solve_rows_capacity", C.c_uint32),
                 ("solve_status", C.c_void_p),
                 ("move", C.POINTER(CharactersMove)), ("move_dt_sec", C.c_double), ("move_scratch", C.c_void_p),
-                ("aniq", C.POINTER(Aniq))]
+                ("aniq", C.POINTER(Aniq)), ("skin_select", C.POINTER(SkinSelect))]
 
 
 LIGHTS_MAX = 128
@@ -298,6 +313,7 @@ STRUCTS = {
     "clapgpu_frustum": Frustum, "clapgpu_bv_query": BvQuery, "clapgpu_views": Views, "clapgpu_entities": Entities,
     "clapgpu_particles": Particles, "clapgpu_anim_clock": AnimClock, "clapgpu_skeleton": Skeleton,
     "clapgpu_animations": Animations, "clapgpu_pose_batch": PoseBatch, "clapgpu_skin_batch": SkinBatch,
+    "clapgpu_skin_select": SkinSelect,
     "clapgpu_world": World, "clapgpu_bodies": Bodies, "clapgpu_geoms": Geoms, "clapgpu_trimesh_desc": TrimeshDesc,
     "clapgpu_slide": Slide, "clapgpu_move": CharactersMove, "clapgpu_characters": Characters, "clapgpu_lights": Lights,
     "clapgpu_solver": Solver, "clapgpu_aniq_entry": AniqEntry, "clapgpu_aniq": Aniq, "clapgpu_frame": FrameDesc,
@@ -341,6 +357,8 @@ SYMBOLS = {
     "clapgpu_joint_pos_world": (C.c_int, [C.c_void_p, C.POINTER(Skeleton), C.POINTER(PoseBatch)]),
     "clapgpu_pose_update": (C.c_int, [C.c_void_p, C.POINTER(Skeleton), C.POINTER(Animations), C.POINTER(PoseBatch)]),
     "clapgpu_skin": (C.c_int, [C.c_void_p, C.POINTER(SkinBatch)]),
+    "clapgpu_skin_select_scratch_bytes": (C.c_size_t, [C.c_uint32]),
+    "clapgpu_skin_drawn": (C.c_int, [C.c_void_p, C.POINTER(SkinBatch), C.POINTER(SkinSelect)]),
     "clapgpu_phys_step_schedule": (C.c_int, [C.POINTER(C.c_double), C.c_double]),
     "clapgpu_world_defaults": (None, [C.POINTER(World)]),
     "clapgpu_bodies_step": (C.c_int, [C.c_void_p, C.POINTER(Bodies), C.POINTER(World), C.c_double]),

@@ -66,6 +66,27 @@ def skeleton_bind(invmx):
     return out
 
 
+def skin_lod_lists(index_buffers, n_verts, capacity=None, total=0):
+    """clapgpu_skin_lod_lists (include/clapgpu_scene.h; host only): the ascending distinct vertices each LOD's DT_USHORT
+    index buffer references -> (rc, lod_first [n_lods], lod_count [n_lods], list [capacity], total).  A LOD that references
+    every vertex gets SKIN_LOD_ALL and no entries.  capacity None: sized to fit.  total: entries already in a list these
+    are appended to (lod_first counts from there; `list` holds the new ones from index `total` on)."""
+    from . import snapshot
+    L = snapshot.lib()
+    bufs = [np.ascontiguousarray(b, np.uint16).reshape(-1) for b in index_buffers]
+    nl = len(bufs)
+    ptrs = (C.c_void_p * max(nl, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+    counts = np.asarray([b.size for b in bufs] or [0], np.uint32)
+    first, count = np.zeros(max(nl, 1), np.uint32), np.zeros(max(nl, 1), np.uint32)
+    if capacity is None:
+        capacity = int(total) + sum(min(b.size, int(n_verts)) for b in bufs)
+    lst = np.zeros(max(int(capacity), 1), np.uint32)
+    tot = C.c_uint32(int(total))
+    rc = L.clapgpu_skin_lod_lists(ptrs, counts.ctypes.data, nl, int(n_verts), lst.ctypes.data, int(capacity), C.byref(tot),
+                                  first.ctypes.data, count.ctypes.data)
+    return rc, first[:nl], count[:nl], lst[:int(capacity)], int(tot.value)
+
+
 class SkinnedModel:
     """Device copy of one model3d's skeleton, animations and (optionally) skinned mesh."""
 
@@ -240,6 +261,62 @@ class CharacterBatch:
         rc = _lib.lib().clapgpu_skin(_stream(), C.byref(self._skin_desc))
         _lib.check(rc, "clapgpu_skin")
 
+    # ---- skinning that follows the cull and the LOD (clapgpu_skin_drawn) ------------------------
+    def set_skin_select(self, planes, cur_lod=None, entity=None, row=None, lod_lists=None, n_entities=None):
+        """What skin_drawn() skins (clapgpu_skin_select, include/clapgpu.h).  planes: the mask planes (1 .. 5 device tensors
+        or uint64 arrays shaped like clapgpu_entities.vis_mask) -- a character is drawn when its entity's bit is set in
+        one of them; None: left to the frame (FrameLoop(skin_select=...) supplies its batch's planes and cur_lod).
+        cur_lod: int32 per entity (None: LOD 0).  entity: the characters' entity slots (None: the batch's entity_index;
+        without one character c is entity c).
+        lod_lists: (lod_first [n_rows, n_lods], lod_count [n_rows, n_lods], list) -- see skin_lod_lists(); row: the
+        characters' rows (None: row 0).  n_entities: entities a plane covers (default: every bit of its words)."""
+        if self._skin_desc is None:
+            raise ValueError("model has no skinned mesh")
+        dev, n = self.device, self.n
+        s = _lib.SkinSelect()
+        self._sel_planes = [] if planes is None else [
+            p if torch.is_tensor(p) else upload(np.ascontiguousarray(p, np.uint64).view(np.int64), np.int64, dev) for p in planes]
+        if len(self._sel_planes) > 1 + _lib.EXTRA_VIEWS_MAX:
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "set_skin_select", "at most 5 planes")
+        s.n_planes = len(self._sel_planes)
+        for k, p in enumerate(self._sel_planes):
+            s.planes[k] = _ptr(p)
+        if self._sel_planes:
+            s.n_entities = int(n_entities) if n_entities is not None else 64 * min(p.numel() for p in self._sel_planes)
+        self._sel_cur_lod = None if cur_lod is None else upload(cur_lod, np.int32, dev)
+        self._sel_entity = self.entity_index if entity is None else upload(entity, np.uint32, dev)
+        self._sel_row = None if row is None else upload(row, np.uint32, dev)
+        s.cur_lod, s.entity, s.row = _ptr(self._sel_cur_lod), _ptr(self._sel_entity), _ptr(self._sel_row)
+        self._sel_lists = self._sel_lists_host = None
+        self._sel_row_host = None if row is None else np.asarray(row, np.int64)
+        if lod_lists is not None:
+            first, count, lst = lod_lists
+            first = np.ascontiguousarray(first, np.uint32)
+            first = first.reshape(-1, first.shape[-1])
+            count = np.ascontiguousarray(count, np.uint32).reshape(first.shape)
+            lst = np.ascontiguousarray(lst, np.uint32).reshape(-1)
+            self._sel_lists = (upload(first, np.uint32, dev), upload(count, np.uint32, dev),
+                               upload(lst if lst.size else np.zeros(1, np.uint32), np.uint32, dev))
+            self._sel_lists_host = (first, count)
+            s.n_rows, s.n_lods = first.shape
+            s.lod_first, s.lod_count, s.list = (_ptr(t) for t in self._sel_lists)
+            s.n_list = int(lst.size)
+        self.skinned = device_array(max(n, 1), torch.uint8, dev, fill=_lib.SKIN_NOT_DRAWN)
+        self.sel_chars = device_array(max(n, 1), torch.int32, dev)
+        self.sel_count = device_array(1, torch.int32, dev)
+        self.sel_status = device_array(1, torch.int32, dev)
+        self._sel_scratch = device_array(int(_lib.lib().clapgpu_skin_select_scratch_bytes(n)), torch.uint8, dev)
+        s.skinned, s.chars, s.count, s.status = _ptr(self.skinned), _ptr(self.sel_chars), _ptr(self.sel_count), _ptr(self.sel_status)
+        s.scratch = _ptr(self._sel_scratch)
+        self._sel_desc = s
+
+    def skin_drawn(self):
+        """clapgpu_skin_drawn: skin the characters set_skin_select's planes draw, at their LODs' vertices."""
+        if getattr(self, "_sel_desc", None) is None:
+            raise ValueError("set_skin_select() first")
+        rc = _lib.lib().clapgpu_skin_drawn(_stream(), C.byref(self._skin_desc), C.byref(self._sel_desc))
+        _lib.check(rc, "clapgpu_skin_drawn")
+
     def download(self):
         torch.cuda.synchronize(self.device)
         out = dict(trs=self.trs.cpu().numpy(), joint_transforms=self.joint_transforms.cpu().numpy(),
@@ -249,6 +326,11 @@ class CharacterBatch:
             out["out_normal"] = self.out_normal.cpu().numpy()
             if self.out_w is not None:
                 out["out_w"] = self.out_w.cpu().numpy()
+            if getattr(self, "_sel_desc", None) is not None:
+                out["count"] = int(self.sel_count.cpu().numpy().view(np.uint32)[0])
+                out["status"] = int(self.sel_status.cpu().numpy().view(np.uint32)[0])
+                out["skinned"] = self.skinned.cpu().numpy()[:self.n]
+                out["chars"] = self.sel_chars.cpu().numpy().view(np.uint32)[:min(out["count"], self.n)]
         return out
 
     def pose_algorithmic_bytes(self):
@@ -256,6 +338,26 @@ class CharacterBatch:
 
     def skin_algorithmic_bytes(self):
         return 68 * self.n_out_verts + 64 * self.model.nr_joints * self.n
+
+    def skin_drawn_algorithmic_bytes(self, skinned):
+        """Bytes clapgpu_skin_drawn has to move for the downloaded `skinned` [n]: 68 B (72 with w) per written vertex, the
+        64 * J palette bytes per drawn character, 4 B per list entry read.  (A listed index past the mesh counts as read
+        and as written: the formula is for well-formed lists.)"""
+        skinned = np.asarray(skinned)[:self.n]
+        drawn = np.flatnonzero(skinned != _lib.SKIN_NOT_DRAWN)
+        verts = self.vert_count_host[drawn].astype(np.int64)
+        entries = np.zeros(drawn.size, np.int64)
+        lists = getattr(self, "_sel_lists_host", None)
+        if lists is not None:
+            first, count = lists
+            row = self._sel_row_host[drawn] if self._sel_row_host is not None else np.zeros(drawn.size, np.int64)
+            ok = row < first.shape[0]
+            f = first[np.where(ok, row, 0), skinned[drawn]]
+            listed = ok & (f != _lib.SKIN_LOD_ALL)
+            entries = np.where(listed, count[np.where(ok, row, 0), skinned[drawn]], 0).astype(np.int64)
+            verts = np.where(listed, entries, verts)
+        per_vertex = 72 if self._skin_desc.out_w else 68
+        return int(per_vertex * verts.sum() + 64 * self.model.nr_joints * drawn.size + 4 * entries.sum())
 
 
 QUEUE_ENTRY = np.dtype([("animation", "<u2"), ("repeat", "u1"), ("end", "u1"), ("speed", "<f4")])      # clapgpu_aniq_entry

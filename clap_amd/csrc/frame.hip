@@ -11,6 +11,9 @@
 // animation_next, the end callbacks), a launch of its own behind the character hooks -- character_update reads airborne
 // before animated_update's callback can set it, so the fused k_characters_update_clock would race.  Chain B (below) is
 // then forked behind that launch instead of at the head of the frame.
+// With f->skin_select (ABI 48) the skinning follows the cull and the LOD as the reference's vertex shader does: chain B
+// stops at the palette, and clapgpu_skin_drawn is the frame's last stage, behind the visible list and the LOD pick (and
+// behind the join), over the frame's own mask planes and cur_lod.
 //
 // Round 4: the frame as THREE CHAINS (opt-in: CLAPGPU_FRAME_OVERLAP).  What the reference runs in list order has only these
 // data dependences:
@@ -89,6 +92,12 @@ extern "C" int clapgpu_frame_issue(void *stream, const clapgpu_frame *f, double 
             f->pose->n_chars != f->aniq->n)
             return CLAPGPU_ERR_INVALID_ARGUMENTS;
     }
+    if (f->skin_select) {                                        // skinning what is drawn: a palette and a cull to follow
+        const clapgpu_entities *e = f->entities;
+        if (!f->skin || !animated || !f->frustum) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+        if (f->skin_select->n_planes == 0 && (!e->vis_mask || (e->views && e->views->n > CLAPGPU_EXTRA_VIEWS_MAX)))
+            return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    }
     void *sb = stream, *sc = stream;                             // chains B and C: the caller's stream unless they overlap
     FrameStreams *fs = nullptr;
     bool b_forked = false;                                       // with aniq chain B is forked later, behind the queue clock
@@ -148,7 +157,7 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
             else FR(clapgpu_animation_time(sb, f->anim_clock, now));
         }
         FR(clapgpu_pose_update(sb, f->skeleton, f->animations, &pose_b));
-        if (f->skin)
+        if (f->skin && !f->skin_select)                              // with skin_select: the frame's last stage, below
             FR(clapgpu_skin(sb, f->skin));
         return CLAPGPU_OK;
     };
@@ -275,6 +284,19 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         else
             FR(clapgpu_visible_compact(stream, e->vis_mask, e->vis_row_pop, e->n, f->index_base, f->visible, f->visible_count,
                                        f->visible_scratch));
+    }
+    // ---- the vertex shader's skinning loop for what the passes draw, at the LOD just picked (model.c:959-997) ----
+    if (f->skin_select) {
+        clapgpu_skin_select sel = *f->skin_select;
+        if (sel.n_planes == 0) {                                 // the frame's own planes: the main view's and the further views'
+            const uint32_t nx = e->views ? e->views->n : 0;
+            sel.planes[0] = e->vis_mask;
+            for (uint32_t v = 0; v < nx; v++) sel.planes[1 + v] = e->views->vis_mask[v];
+            sel.n_planes = 1 + nx;
+            sel.n_entities = e->n;
+        }
+        if (!sel.cur_lod) sel.cur_lod = f->cur_lod;
+        FR(clapgpu_skin_drawn(stream, f->skin, &sel));
     }
     return CLAPGPU_OK;
 }

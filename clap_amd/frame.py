@@ -20,7 +20,7 @@ from . import entities as ent_mod
 class FrameLoop:
     def __init__(self, batch, cam, world=None, feed=None, body_links=None, lights=None, characters=None,
                  particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False, solve=False,
-                 move=None, aniq=None):
+                 move=None, aniq=None, skin_select=None):
         """batch: EntityBatch.  world: PhysWorld (dynamic bodies write their entities through
         body_entity; character bodies have body_entity = -1).  feed: CharacterFeed.  body_links:
         (link_body, link_entity) of characters / static colliders whose rotation follows the entity.
@@ -38,10 +38,15 @@ class FrameLoop:
         host updates its arrays (CharacterMoves.set) between frames and reads its outputs after them.  aniq: an
         animation.AnimationQueues over `characters`: character_set_state follows the move on the device
         (clapgpu_characters_state) and the queue clock (clapgpu_animation_queue_time) takes the place of the plain one,
-        so the frame needs no host between the move and the pose; the host reads aniq's events afterwards."""
+        so the frame needs no host between the move and the pose; the host reads aniq's events afterwards.
+        skin_select: True, or the keyword arguments of CharacterBatch.set_skin_select (entity, row, lod_lists; planes
+        and cur_lod given there replace the frame's own): the frame skins what its passes draw -- clapgpu_skin_drawn as
+        its last stage, over the batch's main plane and the planes of its further views at the LODs just picked, in place
+        of clapgpu_skin.  None (the default): the plain call."""
         islands = islands or solve
         self.move, self.move_dt = move, 0.0
         self.aniq = aniq
+        self.skin_select = skin_select
         self.solve = solve
         self.batch, self.world, self.feed, self.lights = batch, world, feed, lights
         self.characters, self.particles = characters, particles
@@ -149,6 +154,13 @@ class FrameLoop:
             f.pose = C.pointer(cb._pose_desc)
             if cb._skin_desc is not None:
                 f.skin = C.pointer(cb._skin_desc)
+        if self.skin_select is not None and self.skin_select is not False:
+            if cb is None or cb._skin_desc is None:
+                raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "FrameLoop", "skin_select: characters with a skinned mesh")
+            kw = dict(self.skin_select) if isinstance(self.skin_select, dict) else {}
+            kw.setdefault("planes", None)                       # n_planes 0: clapgpu_frame_issue supplies the batch's planes
+            cb.set_skin_select(**kw)
+            f.skin_select = C.pointer(cb._sel_desc)
         if self.aniq is not None:
             if cb is None or self.aniq.batch is not cb:
                 raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "FrameLoop", "aniq: AnimationQueues(batch=characters)")

@@ -40,6 +40,11 @@ LOAD_SYMBOLS = {
     "clapgpu_load_scene": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]),
     "clapgpu_load_gltf": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t]),
 }
+# include/clapgpu_scene.h: the host helpers that take no scene
+SCENE_SYMBOLS = {
+    "clapgpu_skin_lod_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                         C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]),
+}
 
 _L = None
 
@@ -51,7 +56,7 @@ def lib():
             raise _lib.ClapGpuError(_lib.ERR_INIT_FAILED, "clap_amd.snapshot", f"{SCENE_LIB_PATH} is not built")
         _lib.lib()                                           # libclapgpu.so first: the scene library links against it
         L = C.CDLL(SCENE_LIB_PATH)
-        for name, (res, args) in {**SYMBOLS, **LOAD_SYMBOLS}.items():
+        for name, (res, args) in {**SYMBOLS, **LOAD_SYMBOLS, **SCENE_SYMBOLS}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _L = L

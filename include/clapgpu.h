@@ -58,7 +58,7 @@ void clapgpu_test_fail_after(int launches);
 /* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
  * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
  * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
-#define CLAPGPU_ABI_VERSION 47u
+#define CLAPGPU_ABI_VERSION 48u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -669,6 +669,70 @@ typedef struct clapgpu_skin_batch {
 } clapgpu_skin_batch;
 
 int clapgpu_skin(void *stream, const clapgpu_skin_batch *b);
+
+/*
+ * Skinning that follows the cull and the LOD (ABI 48).  The reference skins in its vertex shader, so only entities that
+ * pass _models_render's draw predicate in some pass (model.c:959-973) are skinned, and only the vertices the bound index
+ * buffer model->index[e->cur_lod] references (model.c:993-997, 1042; LOD_MAX = 4 index buffers over one vertex buffer,
+ * model.h:42).  clapgpu_skin_drawn(b, sel) skins that subset of what clapgpu_skin(b) skins.  THE RULE:
+ *
+ * Character c of the batch has entity slot s = entity[c] (entity == NULL: s = c).
+ *   Drawn.  c is drawn when bit s (bit s % 64 of word s / 64) is set in at least one of the n_planes mask planes; n_planes
+ *     is 1 .. 1 + CLAPGPU_EXTRA_VIEWS_MAX and a plane has the shape of clapgpu_entities.vis_mask for n_entities entities.
+ *     s >= n_entities: c is not drawn and CLAPGPU_SKINSEL_ENTITY_RANGE is set; nothing is read outside the planes.
+ *   Its LOD (of a drawn character; nothing is asked of the others).  l = cur_lod[s] (cur_lod == NULL: 0).  l < 0 or
+ *     l >= n_lods: LOD 0 is used and CLAPGPU_SKINSEL_LOD_RANGE is set.  n_lods <= CLAPGPU_SKIN_LODS; without rows
+ *     n_lods == 0 stands for CLAPGPU_SKIN_LODS.
+ *   Its vertices.  Row r = row[c] (row == NULL: 0) of the tables lod_first[n_rows][n_lods] and lod_count[n_rows][n_lods]
+ *     names list[lod_first[r][l] .. lod_first[r][l] + lod_count[r][l]): ascending, distinct LOCAL vertex indices (vertex v
+ *     of the character is vertex vert_first[c] + v of the pool).  lod_first == CLAPGPU_SKIN_LOD_ALL: the whole range
+ *     [0, vert_count[c]) with no list read (lod_count is not read).  n_rows == 0: no tables at all, every drawn character
+ *     is skinned whole.  A listed index >= vert_count[c] is skipped and sets CLAPGPU_SKINSEL_LIST_RANGE; so does the part
+ *     of a range that lies past list[n_list) (skipped: nothing is read outside the list) and a row[c] >= n_rows (that
+ *     character is skinned whole).
+ *   What is written.  For every drawn c and every vertex v it names, out_position, out_normal (and out_w when given) at
+ *     out_first[c] + v get exactly the bits clapgpu_skin writes there.  Every other byte of the three arrays keeps its value.
+ *   What is reported, by every call (n_chars != 0): skinned[c] = the LOD used, CLAPGPU_SKIN_NOT_DRAWN for a character that
+ *     is not drawn; chars[0 .. *count) = the drawn characters in ascending order, *count one device word.  *status is
+ *     sticky: the call ORs bits into it and never clears it (the caller zeroes it once).
+ *
+ * All pointers are device pointers except the struct itself.  scratch: clapgpu_skin_select_scratch_bytes(n_chars) bytes,
+ * 256-byte aligned, not shared with a call that may run at the same time.  No allocation and no host synchronisation: a
+ * captured graph can hold the call.  n_chars == 0: CLAPGPU_OK, nothing is launched.  CLAPGPU_ERR_INVALID_ARGUMENTS before
+ * any HIP call for a NULL batch, select or required array (the batch's as for clapgpu_skin; skinned, chars, count,
+ * status; lod_first and lod_count with rows; list with n_list != 0), n_planes outside its range or a NULL plane, n_lods
+ * outside 1 .. CLAPGPU_SKIN_LODS with rows (above it without), a scratch that is NULL or not 256-byte aligned; nr_joints
+ * as for clapgpu_skin (CLAPGPU_ERR_TOO_LARGE).
+ */
+#define CLAPGPU_SKIN_LODS              4u            /* LOD_MAX, model.h:42 */
+#define CLAPGPU_SKIN_LOD_ALL           0xffffffffu   /* lod_first: every vertex of the character, no list */
+#define CLAPGPU_SKIN_NOT_DRAWN         0xffu         /* skinned[c] of a character that is not drawn */
+#define CLAPGPU_SKINSEL_ENTITY_RANGE   (1u << 0)
+#define CLAPGPU_SKINSEL_LOD_RANGE      (1u << 1)
+#define CLAPGPU_SKINSEL_LIST_RANGE     (1u << 2)
+typedef struct clapgpu_skin_select {
+    uint32_t        n_planes;            /* 1 .. 1 + CLAPGPU_EXTRA_VIEWS_MAX (0 in a clapgpu_frame: the frame's own planes) */
+    uint32_t        n_entities;          /* entities a plane covers */
+    const uint64_t *planes[1 + CLAPGPU_EXTRA_VIEWS_MAX];
+    const uint32_t *entity;              /* [n_chars] or NULL */
+    const int32_t  *cur_lod;             /* [n_entities] or NULL */
+    uint32_t        n_rows;              /* rows of the LOD tables; 0: none */
+    uint32_t        n_lods;
+    const uint32_t *row;                 /* [n_chars] or NULL */
+    const uint32_t *lod_first;           /* [n_rows][n_lods] */
+    const uint32_t *lod_count;           /* [n_rows][n_lods] */
+    const uint32_t *list;                /* [n_list] */
+    uint32_t        n_list;
+    uint32_t        pad;
+    uint8_t        *skinned;             /* [n_chars] out */
+    uint32_t       *chars;               /* [n_chars] out */
+    uint32_t       *count;               /* [1] out */
+    uint32_t       *status;              /* [1] CLAPGPU_SKINSEL_*, sticky */
+    void           *scratch;
+} clapgpu_skin_select;
+
+size_t clapgpu_skin_select_scratch_bytes(uint32_t n_chars);
+int clapgpu_skin_drawn(void *stream, const clapgpu_skin_batch *b, const clapgpu_skin_select *sel);
 
 /* ======================================================================== */
 /* Rigid bodies: phys_step schedule, integrate, read-back, AABB broadphase   */
@@ -1943,6 +2007,13 @@ typedef struct clapgpu_frame {
      * chain is forked behind it.  Needs skeleton, animations and pose, with pose->anim == aniq->pose_anim, pose->frame_time
      * == aniq->frame_time and pose->n_chars == aniq->n: CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, before any launch */
     const clapgpu_aniq *aniq;
+    /* skinning that follows the cull and the LOD (ABI 48); NULL: the frame as before, launch for launch.  Set: the
+     * animation chain no longer issues clapgpu_skin, and clapgpu_skin_drawn(skin, skin_select) is the frame's LAST stage:
+     * behind the visible list and the LOD pick, and behind the join under CLAPGPU_FRAME_OVERLAP.  n_planes == 0 in the
+     * descriptor: the frame supplies the planes and n_entities itself -- entities->vis_mask and the planes of
+     * entities->views; cur_lod == NULL there: this descriptor's cur_lod is used when it has one.  Needs skin, pose (with
+     * skeleton and animations) and frustum: CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, before any launch */
+    const clapgpu_skin_select *skin_select;
 } clapgpu_frame;
 
 /* Default (0): everything on the caller's stream in the reference's order.  CLAPGPU_FRAME_OVERLAP: the frame's three

@@ -229,6 +229,20 @@ void         clapgpu_scene_set_lod_sync(clapgpu_scene *s, int by_caller);
 void         clapgpu_scene_lod_picked(clapgpu_scene *s, uint32_t slot, int lod);
 uint32_t     clapgpu_scene_draw_list(const clapgpu_scene *s, const uint32_t **slots, const int32_t **lods);
 
+/*
+ * The LOD lists clapgpu_skin_drawn takes (clapgpu.h: clapgpu_skin_select), from the engine's own index buffers.  Host
+ * only: no scene, no device.  index[l] / n_index[l]: the DT_USHORT index buffer model->index[l] of LOD l and its number of
+ * indices, l < n_lods <= CLAPGPU_SKIN_LODS; n_verts: the vertices of the model's one vertex buffer (1 .. 65536).
+ * Per LOD the ascending distinct vertex indices it references are APPENDED to list[] at *total (in: the entries already
+ * there; out: the entries there would be with room for all), lod_first[l] = where they start, lod_count[l] = how many:
+ * one row of clapgpu_skin_select's tables.  A LOD that references every vertex gets lod_first[l] = CLAPGPU_SKIN_LOD_ALL,
+ * lod_count[l] = n_verts and no entries; an empty LOD gets a count of 0.  Nothing is written at or past list[capacity]:
+ * the call then returns CLAPGPU_ERR_TOO_LARGE, with *total and both tables still reported, so that the caller can call
+ * again with room for *total.  An index >= n_verts: CLAPGPU_ERR_OUT_OF_BOUNDS, nothing written.
+ */
+int          clapgpu_skin_lod_lists(const uint16_t *const *index, const uint32_t *n_index, uint32_t n_lods, uint32_t n_verts,
+                                    uint32_t *list, uint32_t capacity, uint32_t *total, uint32_t *lod_first, uint32_t *lod_count);
+
 int          clapgpu_scene_layout_is_tiled(const clapgpu_scene *s);
 uint32_t     clapgpu_scene_slot_count(const clapgpu_scene *s);
 /* incremented every time mq_update rebuilds the layout: cached slots are stale when it changes */
