@@ -366,7 +366,7 @@ static int check_ranges(uint32_t n_ranges, uint32_t cap_pad, const uint32_t *bas
         const uint32_t np = n_pad ? n_pad[r] : cap_pad;
         if ((np & 63u) || np > cap_pad || (base[r] & 63u) || base[r] < end) return CLAPGPU_ERR_INVALID_ARGUMENTS;   /* ascending, disjoint */
         end = (uint64_t)base[r] + np;
-        if (end > 0xffffffffull) return CLAPGPU_ERR_TOO_LARGE;
+        if (end > 0x100000000ull) return CLAPGPU_ERR_TOO_LARGE;      /* end is one past the last id: 2^32 is the id 0xffffffff */
     }
     return CLAPGPU_OK;
 }

@@ -169,8 +169,11 @@ typedef struct clapgpu_bv_query {
  * (model.c:966-973; the test reads view->main only, view.c:296-337): two frusta a frame, more with more shadowed lights.
  * The rows' boxes are in registers when the main view is tested: a further view costs ~150 flops and 1/64 word per entity.
  * Every view v gets its own vis_mask / vis_row_pop plane (same shapes as clapgpu_entities'), written exactly as the main
- * plane is: bit i = entity i passes _models_render's draw predicate for that view.  Only read when the call has a main
- * frustum.  host_vis_mask: clapgpu_entities_update_tiles_hostio only -- device aliases of mapped host words the launch
+ * plane is: bit i = entity i passes _models_render's draw predicate for that view, ALIVE && VISIBLE && (SKIP_CULLING || its
+ * box is in that view's frustum).  CLAPGPU_E_SKIP_CULLING means the same in every plane: no view's planes are consulted for
+ * such an entity, its bit is ALIVE && VISIBLE in the main plane and in every further one.  In every plane the bits at or
+ * past n are zero, vis_row_pop[w] is the popcount of word w, and no vis_row_pop byte past ceil(n/64) is written.  Only read
+ * when the call has a main frustum.  host_vis_mask: clapgpu_entities_update_tiles_hostio only -- device aliases of mapped host words the launch
  * writes as well (NULL: not wanted); such a view's drawn entities count as read for the export policy (keep_mask).
  */
 #define CLAPGPU_EXTRA_VIEWS_MAX 4                          /* CASCADES_MAX, shader_constants.h:9 */
