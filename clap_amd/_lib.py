@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 48
+ABI_VERSION = 49
 
 OK = 0
 ERR_NOMEM = -1
@@ -64,6 +64,36 @@ class Views(C.Structure):
     _fields_ = [("n", C.c_uint32), ("pad", C.c_uint32), ("frustum", Frustum * EXTRA_VIEWS_MAX),
                 ("vis_mask", C.c_void_p * EXTRA_VIEWS_MAX), ("vis_row_pop", C.c_void_p * EXTRA_VIEWS_MAX),
                 ("host_vis_mask", C.c_void_p * EXTRA_VIEWS_MAX)]
+
+
+VIEW_SLOTS = 1 + EXTRA_VIEWS_MAX
+VIEW_FROM_POSE, VIEW_NDC_Z_ZERO_ONE = 1, 2
+
+
+class ViewSource(C.Structure):
+    """clapgpu_view_source (include/clapgpu.h): what one view is -- matrices, or a pose."""
+    _fields_ = [("view_mx", C.c_float * 16), ("proj_mx", C.c_float * 16), ("pos", C.c_float * 3), ("flags", C.c_uint32),
+                ("quat", C.c_float * 4)]
+
+
+class ViewsSource(C.Structure):
+    """clapgpu_views_source: slot 0 the main view, slot 1 + k further view k.  Lives in device memory."""
+    _fields_ = [("slot", ViewSource * VIEW_SLOTS)]
+
+
+class ViewState(C.Structure):
+    """clapgpu_view_state (include/clapgpu.h): what the kernels read of one view."""
+    _fields_ = [("frustum", Frustum), ("cull", C.c_uint32 * 8), ("view_mx", C.c_float * 16), ("proj_mx", C.c_float * 16),
+                ("mvp", C.c_float * 16), ("cam_pos", C.c_float * 3), ("pad", C.c_uint32)]
+
+
+class ViewsState(C.Structure):
+    """clapgpu_views_state: written by clapgpu_views_calc alone.  Lives in device memory."""
+    _fields_ = [("slot", ViewState * VIEW_SLOTS)]
+
+
+VIEWS_SOURCE_BYTES, VIEWS_STATE_BYTES = 800, 2320           # CLAPGPU_VIEWS_*_BYTES
+assert C.sizeof(ViewsSource) == VIEWS_SOURCE_BYTES and C.sizeof(ViewsState) == VIEWS_STATE_BYTES
 
 
 class Entities(C.Structure):
@@ -303,7 +333,8 @@ class FrameDesc(C.Structure):
                 ("solver", C.POINTER(Solver)), ("solve_scratch", C.c_void_p), ("solve_rows_capacity", C.c_uint32),
                 ("solve_status", C.c_void_p),
                 ("move", C.POINTER(CharactersMove)), ("move_dt_sec", C.c_double), ("move_scratch", C.c_void_p),
-                ("aniq", C.POINTER(Aniq)), ("skin_select", C.POINTER(SkinSelect))]
+                ("aniq", C.POINTER(Aniq)), ("skin_select", C.POINTER(SkinSelect)),
+                ("views_source", C.c_void_p), ("views_state", C.c_void_p)]
 
 
 LIGHTS_MAX = 128
@@ -316,6 +347,8 @@ STRUCTS = {
     "clapgpu_skin_select": SkinSelect,
     "clapgpu_world": World, "clapgpu_bodies": Bodies, "clapgpu_geoms": Geoms, "clapgpu_trimesh_desc": TrimeshDesc,
     "clapgpu_slide": Slide, "clapgpu_move": CharactersMove, "clapgpu_characters": Characters, "clapgpu_lights": Lights,
+    "clapgpu_view_source": ViewSource, "clapgpu_views_source": ViewsSource, "clapgpu_view_state": ViewState,
+    "clapgpu_views_state": ViewsState,
     "clapgpu_solver": Solver, "clapgpu_aniq_entry": AniqEntry, "clapgpu_aniq": Aniq, "clapgpu_frame": FrameDesc,
 }
 
@@ -486,6 +519,15 @@ SYMBOLS = {
                                        C.POINTER(C.c_uint32)]),
     "clapgpu_light_grid_compute": (C.c_int, [C.c_void_p, C.POINTER(Lights), C.POINTER(C.c_float),
                                              C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "clapgpu_views_calc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "clapgpu_entities_cull_views": (C.c_int, [C.c_void_p, C.POINTER(Entities), C.c_void_p]),
+    "clapgpu_entities_lod_views": (C.c_int, [C.c_void_p, C.POINTER(Entities), C.c_void_p, C.c_void_p, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_visible_compact_lod_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_light_grid_compute_views": (C.c_int, [C.c_void_p, C.POINTER(Lights), C.c_void_p, C.c_uint32, C.c_uint32,
+                                                   C.c_uint32, C.c_void_p]),
+    "clapgpu_particles_update_views": (C.c_int, [C.c_void_p, C.POINTER(Particles), C.c_void_p]),
     "clapgpu_lights_from_entities": (C.c_int, [C.c_void_p, C.POINTER(Entities), C.c_uint32, C.c_uint32, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.POINTER(Lights)]),
 }

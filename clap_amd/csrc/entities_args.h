@@ -46,9 +46,8 @@ static inline EntK to_kernel_args(const clapgpu_entities *e)
     return k;
 }
 
-// Kernel-side frustum: adds the per-axis extremes of the frustum corners (NaN if any corner is
-// NaN, so the comparison is false exactly when the reference's count cannot reach 8) and a flag
-// telling whether every plane component is finite.
+// Kernel-side frustum of a host frustum: adds the cull's constants (lmd::frustum_constants, the statement k_views_calc
+// shares).
 static inline lmd::FrustumK make_frustum_k(const clapgpu_frustum *frustum)
 {
     static_assert(sizeof(lmd::Frustum) == sizeof(clapgpu_frustum), "frustum layout");
@@ -56,23 +55,7 @@ static inline lmd::FrustumK make_frustum_k(const clapgpu_frustum *frustum)
     if (!frustum)
         return k;
     memcpy(&k.f, frustum, sizeof(k.f));
-    for (int ax = 0; ax < 3; ax++) {
-        float lo = INFINITY, hi = -INFINITY;
-        bool nan = false;
-        for (int i = 0; i < 8; i++) {
-            const float c = k.f.corners[i][ax];
-            nan = nan || (c != c);
-            lo = c < lo ? c : lo;
-            hi = c > hi ? c : hi;
-        }
-        k.cmin[ax] = nan ? NAN : lo;
-        k.cmax[ax] = nan ? NAN : hi;
-    }
-    k.finite = 1;
-    for (int i = 0; i < 6; i++)
-        for (int c = 0; c < 4; c++)
-            if (!(fabsf(k.f.planes[i][c]) <= 3.402823466e+38f))
-                k.finite = 0;
+    lmd::frustum_constants(k);
     return k;
 }
 

@@ -12,6 +12,7 @@
 #include <math.h>
 #include "common.h"
 #include "lm_dev.h"
+#include "views_dev.h"
 
 namespace clapgpu {
 
@@ -52,6 +53,18 @@ struct XViewsK {
     lmd::FrustumK fr[CLAPGPU_EXTRA_VIEWS_MAX];
 };
 
+// The same with the frusta left in device memory (the view block, views_dev.h): slot 1 + v of `st` is further view v.
+// Taken by clapgpu_entities_cull_views' kernel alone; the fused update kernels take an XViewsK.
+struct XViewsDevK {
+    uint32_t n, pad;
+    uint64_t *mask[CLAPGPU_EXTRA_VIEWS_MAX];
+    uint8_t  *pop[CLAPGPU_EXTRA_VIEWS_MAX];
+    uint64_t *o_mask[CLAPGPU_EXTRA_VIEWS_MAX];       // always NULL (no host mirror reads this path)
+    const clapgpu_views_state *st;
+};
+__device__ __forceinline__ const lmd::FrustumK &xview_frustum(const XViewsK &xv, uint32_t v) { return xv.fr[v]; }
+__device__ __forceinline__ const lmd::FrustumK &xview_frustum(const XViewsDevK &xv, uint32_t v) { return view_frustum_k(xv.st, 1 + v); }
+
 // The kernels that cull further views are the plain ones with an XViewsK as one more, trailing argument (a parameter pack
 // that is empty or that): the pointer process_row takes, for either.
 __device__ __forceinline__ const XViewsK *xviews_ptr() { return nullptr; }
@@ -87,7 +100,8 @@ __device__ __forceinline__ bool extra_view_test(const lmd::FrustumK &k, const fl
     return in;
 }
 
-__device__ __forceinline__ uint64_t cull_extra_views(const XViewsK &xv, const bool base, const uint32_t fl, const float (&bb)[6],
+template <class XVT>
+__device__ __forceinline__ uint64_t cull_extra_views(const XVT &xv, const bool base, const uint32_t fl, const float (&bb)[6],
                                                      const uint32_t word, const int lane)
 {
     uint64_t any = 0;
@@ -99,7 +113,7 @@ __device__ __forceinline__ uint64_t cull_extra_views(const XViewsK &xv, const bo
     for (int a = 0; a < 6; a++) box_finite = box_finite && (fabsf(bb[a]) <= 3.402823466e+38f);
     const bool tested = base && !(fl & CLAPGPU_E_SKIP_CULLING);
     for (uint32_t v = 0; v < xv.n; v++) {                        // uniform: a view's planes and extremes are scalar loads (NOT unrolled: 3x the code, 15 us slower)
-        const bool vis = tested ? extra_view_test(xv.fr[v], bb, lo, hi, box_finite) : base;
+        const bool vis = tested ? extra_view_test(xview_frustum(xv, v), bb, lo, hi, box_finite) : base;
         const uint64_t m = __ballot(vis);
         if (lane == 0) {
             xv.mask[v][word] = m;

@@ -14,6 +14,10 @@
 // With f->skin_select (ABI 48) the skinning follows the cull and the LOD as the reference's vertex shader does: chain B
 // stops at the palette, and clapgpu_skin_drawn is the frame's last stage, behind the visible list and the LOD pick (and
 // behind the join), over the frame's own mask planes and cur_lod.
+// With f->views_source / f->views_state (ABI 49) nothing about a view is a kernel argument: clapgpu_views_calc is the
+// frame's first launch, ahead of any fork, the entity update runs without its fused cull (the fused kernels take their
+// frustum by value and are not touched: entities.hip) with clapgpu_entities_cull_views behind it over the boxes it stored,
+// and particles, light grid and LOD pick read the block.  A captured frame then follows whatever the source holds.
 //
 // Round 4: the frame as THREE CHAINS (opt-in: CLAPGPU_FRAME_OVERLAP).  What the reference runs in list order has only these
 // data dependences:
@@ -37,6 +41,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "common.h"
+#include "views_dev.h"
 
 using namespace clapgpu;
 
@@ -84,8 +89,13 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
 extern "C" int clapgpu_frame_issue(void *stream, const clapgpu_frame *f, double now, uint32_t substeps)
 {
     if (!f || !f->entities) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if ((f->views_source != nullptr) != (f->views_state != nullptr) || (f->views_state && f->frustum) ||
+        (f->views_state && (!view_block_ok(f->views_source) || !view_block_ok(f->views_state))))
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (f->views_state && f->entities->views && f->entities->views->n > CLAPGPU_EXTRA_VIEWS_MAX)
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
     const bool animated = f->skeleton && f->animations && f->pose;
-    const bool particles = f->particles && f->view_mx;
+    const bool particles = f->particles && (f->view_mx || f->views_state);
     const bool overlap = (f->flags & CLAPGPU_FRAME_OVERLAP) && (animated || particles);
     if (f->aniq) {                                               // the queues drive the pose: asked before anything is issued
         if (!animated || f->pose->anim != f->aniq->pose_anim || f->pose->frame_time != f->aniq->frame_time ||
@@ -94,10 +104,12 @@ extern "C" int clapgpu_frame_issue(void *stream, const clapgpu_frame *f, double 
     }
     if (f->skin_select) {                                        // skinning what is drawn: a palette and a cull to follow
         const clapgpu_entities *e = f->entities;
-        if (!f->skin || !animated || !f->frustum) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+        if (!f->skin || !animated || !(f->frustum || f->views_state)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
         if (f->skin_select->n_planes == 0 && (!e->vis_mask || (e->views && e->views->n > CLAPGPU_EXTRA_VIEWS_MAX)))
             return CLAPGPU_ERR_INVALID_ARGUMENTS;
     }
+    if (f->views_state)                                          // the views of this frame: ahead of every reader, on every chain
+        FR(clapgpu_views_calc(stream, f->views_source, f->views_state, 1 + (f->entities->views ? f->entities->views->n : 0)));
     void *sb = stream, *sc = stream;                             // chains B and C: the caller's stream unless they overlap
     FrameStreams *fs = nullptr;
     bool b_forked = false;                                       // with aniq chain B is forked later, behind the queue clock
@@ -136,7 +148,8 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
 {
     const clapgpu_entities *e = f->entities;
     const bool animated = f->skeleton && f->animations && f->pose;
-    const bool particles = f->particles && f->view_mx;
+    const bool particles = f->particles && (f->view_mx || f->views_state);
+    const clapgpu_views_state *vs = f->views_state;             // NULL: the views are host values
     // joint positions need e->mx: with the chains apart k_pose stops at the model-space position
     clapgpu_pose_batch pose_b;
     bool finish_pos = false;
@@ -163,7 +176,8 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
     };
     // ---- chain C: particles_update hooks ----
     auto chain_c = [&]() -> int {
-        if (particles) FR(clapgpu_particles_update(sc, f->particles, f->view_mx));
+        if (particles && vs) FR(clapgpu_particles_update_views(sc, f->particles, vs));
+        else if (particles) FR(clapgpu_particles_update(sc, f->particles, f->view_mx));
         return CLAPGPU_OK;
     };
     if (overlap) {                                               // issued first: their launches are in the queues while A's are made
@@ -262,6 +276,8 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         FR(clapgpu_entities_update_tiles(stream, e, f->tile_row_start, f->n_tiles, 0, f->frustum));
     else
         FR(clapgpu_entities_update(stream, e, f->level_start, f->n_levels, 0, f->frustum));
+    if (vs)                                                      // f->frustum is NULL: the update above did not cull
+        FR(clapgpu_entities_cull_views(stream, e, vs));
 
     if (overlap) {                                               // join
         *joined = true;                                          // (a failure inside these four calls cannot be joined any better by the caller)
@@ -273,12 +289,17 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         FR(chain_c());
     }
     // ---- scene_update: light_grid_compute ----
-    if (f->lights && f->light_tiles && f->view_mx && f->proj_mx)
+    if (f->lights && f->light_tiles && vs)
+        FR(clapgpu_light_grid_compute_views(stream, f->lights, vs, f->light_width, f->light_height, f->light_cell, f->light_tiles));
+    else if (f->lights && f->light_tiles && f->view_mx && f->proj_mx)
         FR(clapgpu_light_grid_compute(stream, f->lights, f->view_mx, f->proj_mx, f->light_width, f->light_height, f->light_cell,
                                       f->light_tiles));
     // ---- render pass glue: ordered visible list + LOD pick ----
-    if (f->frustum && f->visible && f->visible_count && f->visible_scratch) {
-        if (f->cur_lod && f->draw_lod)                           // list + LODs in one launch
+    if ((f->frustum || vs) && f->visible && f->visible_count && f->visible_scratch) {
+        if (f->cur_lod && f->draw_lod && vs)
+            FR(clapgpu_visible_compact_lod_views(stream, e, f->index_base, vs, f->force_lod, f->cur_lod, f->visible,
+                                                 f->visible_count, f->draw_lod, f->visible_scratch));
+        else if (f->cur_lod && f->draw_lod)                      // list + LODs in one launch
             FR(clapgpu_visible_compact_lod(stream, e, f->index_base, f->cam_pos, f->force_lod, f->cur_lod, f->visible,
                                            f->visible_count, f->draw_lod, f->visible_scratch));
         else

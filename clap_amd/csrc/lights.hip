@@ -17,6 +17,7 @@
 #include <math.h>
 #include "common.h"
 #include "lm_dev.h"
+#include "views_dev.h"
 
 namespace clapgpu {
 
@@ -76,8 +77,7 @@ __device__ __forceinline__ bool disc_reaches(float sx, float sy, float r2, float
     return d00 < r2 || d10 < r2 || d01 < r2 || d11 < r2;
 }
 
-__global__ __launch_bounds__(LIGHT_BLOCK)
-void k_light_grid(LightGridArgs a)
+__device__ __forceinline__ void light_grid_pass(LightGridArgs a)
 {
     const int lane = lane_id();
     float ax, ay, ar, bx, by, br;
@@ -102,6 +102,23 @@ void k_light_grid(LightGridArgs a)
     }
     if (lane < LIGHT_TILES_PER_WAVE && first + lane < n_tiles)
         a.tiles[first + lane] = mine;
+}
+
+__global__ __launch_bounds__(LIGHT_BLOCK)
+void k_light_grid(LightGridArgs a)
+{
+    light_grid_pass(a);
+}
+
+// clapgpu_light_grid_compute_views: view, mvp and proj_mx[0] are slot 0's of the view block
+__global__ __launch_bounds__(LIGHT_BLOCK)
+void k_light_grid_views(LightGridArgs a, const clapgpu_views_state *st)
+{
+    const clapgpu_view_state &v = st->slot[0];
+#pragma unroll
+    for (int i = 0; i < 16; i++) { a.view[i] = v.view_mx[i]; a.mvp[i] = v.mvp[i]; }
+    a.fx = v.proj_mx[0];
+    light_grid_pass(a);
 }
 
 struct LightCarrierArgs {
@@ -180,14 +197,10 @@ static int check_lights(const clapgpu_lights *l)
     return CLAPGPU_OK;
 }
 
-extern "C" int clapgpu_light_grid_compute(void *stream, const clapgpu_lights *lights, const float view_mx[16],
-                                          const float proj_mx[16], uint32_t width, uint32_t height, uint32_t cell,
-                                          uint32_t *tiles)
+// view_mx / proj_mx: the host's matrices, or both NULL and `state` the view block
+static int light_grid_launch(void *stream, const clapgpu_lights *lights, const float *view_mx, const float *proj_mx,
+                             const clapgpu_views_state *state, uint32_t width, uint32_t height, uint32_t cell, uint32_t *tiles)
 {
-    int rc = check_lights(lights);
-    if (rc) return rc;
-    if (!view_mx || !proj_mx)
-        return CLAPGPU_ERR_INVALID_ARGUMENTS;
     uint32_t tw, th;
     clapgpu_light_grid_dims(width, height, cell, &tw, &th);
     if (!width || !height || !cell || !tw || !th)                   // light.c:46, 55, 93: nothing to do
@@ -199,20 +212,49 @@ extern "C" int clapgpu_light_grid_compute(void *stream, const clapgpu_lights *li
         return CLAPGPU_ERR_TOO_LARGE;
 
     LightGridArgs a;
+    memset(&a, 0, sizeof(a));
     a.nr_lights = lights->nr_lights;
     a.pos = lights->pos; a.color = lights->color; a.attenuation = lights->attenuation;
     a.is_dir = lights->is_dir; a.active = lights->active;
-    memcpy(a.view, view_mx, sizeof(a.view));
-    host_mat4_mul(a.mvp, proj_mx, view_mx);                         // light.c:98
-    a.fx = proj_mx[0];
+    if (!state) {
+        memcpy(a.view, view_mx, sizeof(a.view));
+        host_mat4_mul(a.mvp, proj_mx, view_mx);                     // light.c:98
+        a.fx = proj_mx[0];
+    }
     a.width = width; a.height = height; a.cell = cell; a.twidth = tw; a.theight = th;
     a.tiles = reinterpret_cast<uint4 *>(tiles);
     const uint32_t n_tiles = tw * th;
     constexpr uint32_t per_block = LIGHT_TILES_PER_WAVE * (LIGHT_BLOCK / WAVE);
-    hipLaunchKernelGGL(k_light_grid, dim3((n_tiles + per_block - 1) / per_block), dim3(LIGHT_BLOCK), 0,
-                       as_stream(stream), a);
-    CLAPGPU_LAUNCH_CHECK("k_light_grid");
+    const dim3 grid((n_tiles + per_block - 1) / per_block), block(LIGHT_BLOCK);
+    if (state) {
+        hipLaunchKernelGGL(k_light_grid_views, grid, block, 0, as_stream(stream), a, state);
+        CLAPGPU_LAUNCH_CHECK("k_light_grid_views");
+    } else {
+        hipLaunchKernelGGL(k_light_grid, grid, block, 0, as_stream(stream), a);
+        CLAPGPU_LAUNCH_CHECK("k_light_grid");
+    }
     return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_light_grid_compute(void *stream, const clapgpu_lights *lights, const float view_mx[16],
+                                          const float proj_mx[16], uint32_t width, uint32_t height, uint32_t cell,
+                                          uint32_t *tiles)
+{
+    int rc = check_lights(lights);
+    if (rc) return rc;
+    if (!view_mx || !proj_mx)
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    return light_grid_launch(stream, lights, view_mx, proj_mx, nullptr, width, height, cell, tiles);
+}
+
+extern "C" int clapgpu_light_grid_compute_views(void *stream, const clapgpu_lights *lights, const clapgpu_views_state *state,
+                                                uint32_t width, uint32_t height, uint32_t cell, uint32_t *tiles)
+{
+    if (!view_block_ok(state))
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    int rc = check_lights(lights);
+    if (rc) return rc;
+    return light_grid_launch(stream, lights, nullptr, nullptr, state, width, height, cell, tiles);
 }
 
 extern "C" int clapgpu_lights_from_entities(void *stream, const clapgpu_entities *e, uint32_t mode,

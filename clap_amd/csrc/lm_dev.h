@@ -339,4 +339,96 @@ LMD bool aabb_in_frustum_fast(const FrustumK &k, const float (&bb)[6])
     return true;
 }
 
+// ---- a view: the O(1)-per-frame arithmetic of the host entry points (runtime.hip) and of k_views_calc (views.hip) ----
+// Stated once, here, for both machines.  What an invalid operation leaves in a NaN's sign and payload is the machine's
+// (x86: 0xffc00000, gfx950: 0x7fc00000) and nothing reads it: whatever these functions store goes through one_nan.
+LMD float one_nan(float v) { return v != v ? __builtin_nanf("") : v; }
+
+// transform.c:132-138: I * R(quat), transpose the 3x3, translate_in_place(-pos)
+LMD void view_matrix(float (&out)[16], const float (&pos)[3], const float (&quat)[4])
+{
+    float m[16], r[16], t[16];
+    identity(m);
+    from_quat(r, quat[0], quat[1], quat[2], quat[3]);
+    mul(m, m, r);
+#pragma unroll
+    for (int i = 0; i < 16; i++) t[i] = m[i];
+#pragma unroll
+    for (int c = 0; c < 3; c++)                      // linmath.h:408-416
+#pragma unroll
+        for (int rr = 0; rr < 3; rr++)
+            t[4 * c + rr] = m[4 * rr + c];
+    // The negated position reaches translate_in_place as a value, not as a negation the device compiler can move: it
+    // turns 0 + (-x) m0 + (-y) m1 into (-(x m0)) - y m1, without the +0 that makes a zero sum +0 (a camera at the origin
+    // came out with -0 in the translation).  The host compiler does not; the barrier costs nothing.
+    float npos[3] = { -pos[0], -pos[1], -pos[2] };
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(npos[0]), "+v"(npos[1]), "+v"(npos[2]));
+#endif
+    translate_in_place(t, npos[0], npos[1], npos[2]);
+#pragma unroll
+    for (int i = 0; i < 16; i++) out[i] = one_nan(t[i]);
+}
+
+// view.c:248-289: mvp = proj * view, the planes and the corners
+LMD void frustum_calc(Frustum &out, float (&mvp)[16], const float (&v)[16], const float (&p)[16], bool ndc_z_zero_one)
+{
+    float inv[16];
+    mul(mvp, p, v);
+    invert(inv, mvp);
+    // planes = row3(mvp) +/- row{0,1,2}(mvp)  (view.c:271,275-280 via the transpose)
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float r0 = mvp[4 * k + 0], r1 = mvp[4 * k + 1], r2 = mvp[4 * k + 2], r3 = mvp[4 * k + 3];
+        out.planes[0][k] = one_nan(r3 + r0);
+        out.planes[1][k] = one_nan(r3 - r0);
+        out.planes[2][k] = one_nan(r3 + r1);
+        out.planes[3][k] = one_nan(r3 - r1);
+        out.planes[4][k] = one_nan(r3 + r2);
+        out.planes[5][k] = one_nan(r3 - r2);
+    }
+    const float zn = ndc_z_zero_one ? 0.f : -1.f;   // view.c:252-265
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const float sx = (i == 0 || i == 3 || i == 4 || i == 7) ? -1.f : 1.f;
+        const float sy = ((i & 3) < 2) ? -1.f : 1.f;
+        const float c[4] = { sx, sy, i < 4 ? zn : 1.f, 1.f };
+        float q[4];
+        mul_vec4(q, inv, c);
+        const float s = 1.f / q[3];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            out.corners[i][k] = one_nan(q[k] * s);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) mvp[i] = one_nan(mvp[i]);
+}
+
+// The cull's constants of a frustum (FrustumK above): per-axis extremes of the corners (NaN if any corner is NaN, so the
+// comparison is false exactly when the reference's count cannot reach 8) and "every plane component is finite".
+LMD void frustum_constants(FrustumK &k)
+{
+#pragma unroll
+    for (int ax = 0; ax < 3; ax++) {
+        float lo = __builtin_inff(), hi = -__builtin_inff();
+        bool nan = false;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const float c = k.f.corners[i][ax];
+            nan = nan || (c != c);
+            lo = c < lo ? c : lo;
+            hi = c > hi ? c : hi;
+        }
+        k.cmin[ax] = nan ? __builtin_nanf("") : lo;
+        k.cmax[ax] = nan ? __builtin_nanf("") : hi;
+    }
+    k.finite = 1;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if (!(__builtin_fabsf(k.f.planes[i][c]) <= 3.402823466e+38f))
+                k.finite = 0;
+}
+
 } // namespace lmd

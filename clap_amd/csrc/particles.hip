@@ -19,6 +19,7 @@
 #include <string.h>
 #include "common.h"
 #include "lm_dev.h"
+#include "views_dev.h"
 
 namespace clapgpu {
 
@@ -118,6 +119,32 @@ void k_particles_advect(PartK k, Mat4Arg view)
                 o[4 * c + r] = (c < 3 && r < 3) ? view.m[4 * r + c] : view.m[4 * c + r];
         o[12] = cx; o[13] = cy; o[14] = cz;
     }
+}
+
+// clapgpu_particles_update_views: the billboards alone, from slot 0's view matrix of the view block -- k_particles_advect
+// then runs with billboard_mx NULL.  One lane per system.  k_particles_advect writes system s's matrix from the lane of
+// particle sys[s].first when that particle is live and its row names s; the same test here, so the same systems are
+// written.  (A kernel of its own: k_particles_advect takes its matrix by value, and its body moved into a function that
+// both forms share came out with another instruction stream -- tools/isa_hashes.sh.)
+__global__ __launch_bounds__(PART_BLOCK)
+void k_particles_billboards_views(PartK k, const clapgpu_views_state *st)
+{
+    const uint32_t s = blockIdx.x * PART_BLOCK + threadIdx.x;
+    if (s >= k.n_sys) return;
+    const clapgpu_particle_system &ps = k.sys[s];
+    const uint32_t i = ps.first;
+    if (i >= k.n || ps.count == 0) return;
+    uint32_t named = k.row_sys[i >> 6];
+    if (named >= k.n_sys) named = 0;
+    if (named != s) return;
+    const float (&vm)[16] = st->slot[0].view_mx;
+    float *o = k.billboard_mx + 16 * (size_t)s;
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+            o[4 * c + r] = (c < 3 && r < 3) ? vm[4 * r + c] : vm[4 * c + r];     // particle.c:93-100
+    o[12] = ps.center[0]; o[13] = ps.center[1]; o[14] = ps.center[2];
 }
 
 // X_{n+m} = A^m X_n + C_m (mod 2^48): power of the affine map by squaring
@@ -304,10 +331,11 @@ using namespace clapgpu;
 
 static_assert(sizeof(clapgpu_particle_system) == 64, "clapgpu_particle_system layout");
 
-extern "C" int clapgpu_particles_update(void *stream, const clapgpu_particles *p, const float view_mx[16])
+// view_mx: the host's matrix, or NULL and `state` the view block
+static int particles_update(void *stream, const clapgpu_particles *p, const float *view_mx, const clapgpu_views_state *state)
 {
     if (!p || !p->sys || !p->row_sys || !p->pos || !p->vel || !p->rng_state || !p->respawn_mask ||
-        !p->respawn_row_pop || !p->respawn_list || !p->respawn_count || !view_mx)
+        !p->respawn_row_pop || !p->respawn_list || !p->respawn_count || (!view_mx && !state))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (p->n & 63u)
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
@@ -327,11 +355,20 @@ extern "C" int clapgpu_particles_update(void *stream, const clapgpu_particles *p
     k.n_sys = p->n_sys ? p->n_sys : 1;
     const bool row_path = p->n / WAVE <= (1u << 16) && (reinterpret_cast<uintptr_t>(p->respawn_row_pop) & 15u) == 0;
     k.groups = row_path ? p->respawn_groups : nullptr;
+    const dim3 grid((p->n + PART_BLOCK - 1) / PART_BLOCK), block(PART_BLOCK);
     Mat4Arg view;
-    memcpy(view.m, view_mx, sizeof(view.m));
-
-    hipLaunchKernelGGL(k_particles_advect, dim3((p->n + PART_BLOCK - 1) / PART_BLOCK), dim3(PART_BLOCK), 0,
-                       as_stream(stream), k, view);
+    memset(&view, 0, sizeof(view));
+    if (state) {                                                 // the billboards from the block, by a launch of their own
+        if (k.billboard_mx) {
+            hipLaunchKernelGGL(k_particles_billboards_views, dim3((k.n_sys + PART_BLOCK - 1) / PART_BLOCK), block, 0,
+                               as_stream(stream), k, state);
+            CLAPGPU_LAUNCH_CHECK("k_particles_billboards_views");
+        }
+        k.billboard_mx = nullptr;
+    } else {
+        memcpy(view.m, view_mx, sizeof(view.m));
+    }
+    hipLaunchKernelGGL(k_particles_advect, grid, block, 0, as_stream(stream), k, view);
     CLAPGPU_LAUNCH_CHECK("k_particles_advect");
     if (row_path) {
         const uint32_t waves = (p->n / WAVE + WAVE - 1) / WAVE, per_block = PART_BLOCK / WAVE;
@@ -348,4 +385,18 @@ extern "C" int clapgpu_particles_update(void *stream, const clapgpu_particles *p
                        p->respawn_list, p->respawn_count);
     CLAPGPU_LAUNCH_CHECK("k_particles_respawn");
     return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_particles_update(void *stream, const clapgpu_particles *p, const float view_mx[16])
+{
+    if (!view_mx)
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    return particles_update(stream, p, view_mx, nullptr);
+}
+
+extern "C" int clapgpu_particles_update_views(void *stream, const clapgpu_particles *p, const clapgpu_views_state *state)
+{
+    if (!view_block_ok(state))
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    return particles_update(stream, p, nullptr, state);
 }

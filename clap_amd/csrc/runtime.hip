@@ -190,19 +190,12 @@ extern "C" int clapgpu_stream_sync(void *stream)
 // Host-side per-frame constants.  Same arithmetic as the kernels (lm_dev.h).
 // ---------------------------------------------------------------------------
 
-// transform.c:132-138: I * R(quat), transpose the 3x3, translate_in_place(-pos)
+// transform.c:132-138 (lmd::view_matrix: the statement k_views_calc shares)
 extern "C" void clapgpu_view_matrix(const float pos[3], const float quat[4], float view_mx[16])
 {
-    float m[16], r[16];
-    lmd::identity(m);
-    lmd::from_quat(r, quat[0], quat[1], quat[2], quat[3]);
-    lmd::mul(m, m, r);
     float t[16];
-    for (int i = 0; i < 16; i++) t[i] = m[i];
-    for (int c = 0; c < 3; c++)                     // linmath.h:408-416
-        for (int rr = 0; rr < 3; rr++)
-            t[4 * c + rr] = m[4 * rr + c];
-    lmd::translate_in_place(t, -pos[0], -pos[1], -pos[2]);
+    const float p[3] = { pos[0], pos[1], pos[2] }, q[4] = { quat[0], quat[1], quat[2], quat[3] };
+    lmd::view_matrix(t, p, q);
     memcpy(view_mx, t, sizeof(t));
 }
 
@@ -241,34 +234,15 @@ extern "C" void clapgpu_perspective(float fov, float aspect, float n, float f,
     }
 }
 
-// view.c:248-289
+// view.c:248-289 (lmd::frustum_calc: the statement k_views_calc shares)
 extern "C" void clapgpu_frustum_calc(const float view_mx[16], const float proj_mx[16],
                                      int ndc_z_zero_one, clapgpu_frustum *out)
 {
-    float v[16], p[16], mvp[16], inv[16];
+    static_assert(sizeof(lmd::Frustum) == sizeof(clapgpu_frustum), "frustum layout");
+    float v[16], p[16], mvp[16];
     memcpy(v, view_mx, sizeof(v));
     memcpy(p, proj_mx, sizeof(p));
-    lmd::mul(mvp, p, v);
-    lmd::invert(inv, mvp);
-    // planes = row3(mvp) +/- row{0,1,2}(mvp)  (view.c:271,275-280 via the transpose)
-    for (int k = 0; k < 4; k++) {
-        const float r0 = mvp[4 * k + 0], r1 = mvp[4 * k + 1], r2 = mvp[4 * k + 2], r3 = mvp[4 * k + 3];
-        out->planes[0][k] = r3 + r0;
-        out->planes[1][k] = r3 - r0;
-        out->planes[2][k] = r3 + r1;
-        out->planes[3][k] = r3 - r1;
-        out->planes[4][k] = r3 + r2;
-        out->planes[5][k] = r3 - r2;
-    }
-    const float zn = ndc_z_zero_one ? 0.f : -1.f;  // view.c:252-265
-    for (int i = 0; i < 8; i++) {
-        const float sx = (i == 0 || i == 3 || i == 4 || i == 7) ? -1.f : 1.f;
-        const float sy = ((i & 3) < 2) ? -1.f : 1.f;
-        const float c[4] = { sx, sy, i < 4 ? zn : 1.f, 1.f };
-        float q[4];
-        lmd::mul_vec4(q, inv, c);
-        const float s = 1.f / q[3];
-        for (int k = 0; k < 4; k++)
-            out->corners[i][k] = q[k] * s;
-    }
+    lmd::Frustum f;
+    lmd::frustum_calc(f, mvp, v, p, ndc_z_zero_one != 0);
+    memcpy(out, &f, sizeof(f));
 }

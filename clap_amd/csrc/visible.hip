@@ -11,7 +11,14 @@
 namespace clapgpu {
 
 // Cull-only pass over stored AABBs (one per render pass in the reference).
-// XV: nothing, or the frame's further views (a trailing XViewsK): every view of the frame from one read of the boxes
+// XV: nothing, or the frame's further views (a trailing XViewsK): every view of the frame from one read of the boxes.
+// With a trailing XViewsDevK (clapgpu_entities_cull_views) every frustum lies in the view block: the main view's is slot
+// 0's and the argument `fr` is not read.  One body for the three, in the kernel itself: moved into a function the kernels
+// share, the two instantiations the parent had came out with other instruction streams (tools/isa_hashes.sh).
+__device__ __forceinline__ const lmd::FrustumK &main_frustum(const lmd::FrustumK &fr) { return fr; }
+__device__ __forceinline__ const lmd::FrustumK &main_frustum(const lmd::FrustumK &fr, const XViewsK &) { return fr; }
+__device__ __forceinline__ const lmd::FrustumK &main_frustum(const lmd::FrustumK &, const XViewsDevK &xv) { return view_frustum_k(xv.st, 0); }
+
 template <class... XV>
 __global__ __launch_bounds__(ENT_BLOCK)
 void k_entities_cull(const uint32_t *flags, const float *aabb, uint64_t *vis_mask, uint8_t *vis_row_pop,
@@ -29,7 +36,7 @@ void k_entities_cull(const uint32_t *flags, const float *aabb, uint64_t *vis_mas
         if (base && !(fl & CLAPGPU_E_SKIP_CULLING)) {
 #pragma unroll
             for (int k = 0; k < 6; k++) bb[k] = aabb[6 * (size_t)i + k];
-            vis = lmd::aabb_in_frustum_fast(fr, bb);
+            vis = lmd::aabb_in_frustum_fast(main_frustum(fr, xv...), bb);
         }
     }
     // a wavefront past the end: with further views it leaves here, ahead of their ballots and mask words; without, the
@@ -287,8 +294,8 @@ __device__ __forceinline__ int32_t lod_pick(const LodK &k, uint32_t i)
     return lod;
 }
 
-__global__ __launch_bounds__(ENT_BLOCK)
-void k_entities_lod(const uint32_t *visible, const uint32_t *count, uint32_t index_base, LodK lk, int32_t *draw_lod, uint32_t n)
+__device__ __forceinline__ void lod_pass(const uint32_t *visible, const uint32_t *count, const uint32_t index_base, const LodK &lk,
+                                         int32_t *draw_lod, const uint32_t n)
 {
     const uint32_t total = *count < n ? *count : n;                       // a count beyond the batch would walk off the list
     for (uint32_t k = blockIdx.x * ENT_BLOCK + threadIdx.x; k < total; k += gridDim.x * ENT_BLOCK) {
@@ -296,6 +303,21 @@ void k_entities_lod(const uint32_t *visible, const uint32_t *count, uint32_t ind
         if (i >= n) { draw_lod[k] = 0; continue; }                          // an id of another shard
         draw_lod[k] = lod_pick(lk, i);
     }
+}
+
+__global__ __launch_bounds__(ENT_BLOCK)
+void k_entities_lod(const uint32_t *visible, const uint32_t *count, uint32_t index_base, LodK lk, int32_t *draw_lod, uint32_t n)
+{
+    lod_pass(visible, count, index_base, lk, draw_lod, n);
+}
+
+// clapgpu_entities_lod_views: the camera position is slot 0's of the view block
+__global__ __launch_bounds__(ENT_BLOCK)
+void k_entities_lod_views(const uint32_t *visible, const uint32_t *count, uint32_t index_base, LodK lk, int32_t *draw_lod, uint32_t n,
+                          const clapgpu_views_state *st)
+{
+    lk.cx = st->slot[0].cam_pos[0]; lk.cy = st->slot[0].cam_pos[1]; lk.cz = st->slot[0].cam_pos[2];
+    lod_pass(visible, count, index_base, lk, draw_lod, n);
 }
 
 } // namespace clapgpu
@@ -319,6 +341,30 @@ extern "C" int clapgpu_entities_cull(void *stream, const clapgpu_entities *e, co
         hipLaunchKernelGGL(k_entities_cull<>, grid, block, 0, as_stream(stream), e->flags, e->aabb, e->vis_mask,
                            e->vis_row_pop, e->n, fr);
     CLAPGPU_LAUNCH_CHECK("k_entities_cull");
+    return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_entities_cull_views(void *stream, const clapgpu_entities *e, const clapgpu_views_state *state)
+{
+    if (!view_block_ok(state) || !e || !e->flags || !e->aabb || !e->vis_mask || !e->vis_row_pop)
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (e->n == 0)
+        return CLAPGPU_OK;
+    XViewsDevK xv;
+    memset(&xv, 0, sizeof(xv));
+    xv.st = state;
+    if (const clapgpu_views *v = e->views) {                     // as make_xviews_k, without the frusta
+        if (v->n > CLAPGPU_EXTRA_VIEWS_MAX) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+        xv.n = v->n;
+        for (uint32_t k = 0; k < v->n; k++) {
+            if (!v->vis_mask[k] || !v->vis_row_pop[k]) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+            xv.mask[k] = v->vis_mask[k]; xv.pop[k] = v->vis_row_pop[k];
+        }
+    }
+    const lmd::FrustumK unread = {};                             // every frustum is read from the block
+    hipLaunchKernelGGL(k_entities_cull<XViewsDevK>, dim3((e->n + ENT_BLOCK - 1) / ENT_BLOCK), dim3(ENT_BLOCK), 0, as_stream(stream),
+                       e->flags, e->aabb, e->vis_mask, e->vis_row_pop, e->n, unread, xv);
+    CLAPGPU_LAUNCH_CHECK("k_entities_cull<views>");
     return CLAPGPU_OK;
 }
 
@@ -446,6 +492,24 @@ extern "C" int clapgpu_entities_lod(void *stream, const clapgpu_entities *e, con
     return CLAPGPU_OK;
 }
 
+extern "C" int clapgpu_entities_lod_views(void *stream, const clapgpu_entities *e, const uint32_t *visible, const uint32_t *count,
+                                          uint32_t index_base, const clapgpu_views_state *state, const int32_t *force_lod,
+                                          int32_t *cur_lod, int32_t *draw_lod)
+{
+    if (!view_block_ok(state) || !e || !visible || !count || !cur_lod || !draw_lod || !e->aabb || !e->center ||
+        !e->pos_scale || !e->model || !e->model_table)
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (e->n == 0)
+        return CLAPGPU_OK;
+    uint32_t blocks = (e->n + ENT_BLOCK - 1) / ENT_BLOCK;
+    if (blocks > 2048) blocks = 2048;
+    const float unread[3] = { 0.f, 0.f, 0.f };                   // the kernel takes the position from the block
+    hipLaunchKernelGGL(k_entities_lod_views, dim3(blocks), dim3(ENT_BLOCK), 0, as_stream(stream), visible, count, index_base,
+                       lod_args(e, unread, force_lod, cur_lod), draw_lod, e->n, state);
+    CLAPGPU_LAUNCH_CHECK("k_entities_lod_views");
+    return CLAPGPU_OK;
+}
+
 // clapgpu_visible_compact + clapgpu_entities_lod of this batch's own entities: the render pass's list and its LODs by one
 // call.  Two launches: a single kernel that picks the LOD of every id as it writes it was built and measured (round 5,
 // profiles/r05_experiments/lod_in_expand.md) -- the expansion walks sixteen mask rows per wavefront one after the other,
@@ -461,4 +525,16 @@ extern "C" int clapgpu_visible_compact_lod(void *stream, const clapgpu_entities 
     int rc = clapgpu_visible_compact(stream, e->vis_mask, e->vis_row_pop, n, index_base, visible, count, scratch);
     if (rc) return rc;
     return clapgpu_entities_lod(stream, e, visible, count, index_base, cam_pos, force_lod, cur_lod, draw_lod);
+}
+
+extern "C" int clapgpu_visible_compact_lod_views(void *stream, const clapgpu_entities *e, uint32_t index_base,
+                                                 const clapgpu_views_state *state, const int32_t *force_lod, int32_t *cur_lod,
+                                                 uint32_t *visible, uint32_t *count, int32_t *draw_lod, void *scratch)
+{
+    if (!view_block_ok(state) || !e || !count || !cur_lod || !draw_lod || (e->n && (!e->vis_mask || !visible)) || !e->aabb ||
+        !e->center || !e->pos_scale || !e->model || !e->model_table)
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    int rc = clapgpu_visible_compact(stream, e->vis_mask, e->vis_row_pop, e->n, index_base, visible, count, scratch);
+    if (rc) return rc;
+    return clapgpu_entities_lod_views(stream, e, visible, count, index_base, state, force_lod, cur_lod, draw_lod);
 }

@@ -32,6 +32,15 @@ def view_calc_frustum(cam):
     return fr, view, proj
 
 
+def frustum_from_matrices(view_mx, proj_mx, ndc_z_zero_one=False):
+    """clapgpu_frustum_calc on the host."""
+    f32p = C.POINTER(C.c_float)
+    view, proj = np.ascontiguousarray(view_mx, np.float32).ravel(), np.ascontiguousarray(proj_mx, np.float32).ravel()
+    fr = _lib.Frustum()
+    _lib.lib().clapgpu_frustum_calc(view.ctypes.data_as(f32p), proj.ctypes.data_as(f32p), int(bool(ndc_z_zero_one)), C.byref(fr))
+    return fr
+
+
 def frustum_arrays(fr):
     return (np.ctypeslib.as_array(fr.planes).reshape(6, 4).copy(),
             np.ctypeslib.as_array(fr.corners).reshape(8, 4).copy())
@@ -96,11 +105,17 @@ class EntityBatch:
         self._desc.vis_row_pop = vis_row_pop.data_ptr()
 
     # ---- optional inputs ---------------------------------------------------------------
-    def set_views(self, frusta):
+    def set_views(self, frusta, matrices=None):
         """The frame's other frusta (one light view for the shadow passes, pipeline-builder.c:246-272): culled by the same
         launch as the main one, each into its own mask plane (view_masks[v], view_row_pops[v]).  frusta: up to
-        _lib.EXTRA_VIEWS_MAX _lib.Frustum; an empty list takes them off again."""
+        _lib.EXTRA_VIEWS_MAX _lib.Frustum; an empty list takes them off again.  matrices: per view the (view_mx, proj_mx,
+        ndc_z_zero_one) its frustum was computed from -- what a frame with its views in device memory
+        (FrameLoop(views_dev=True)) writes into slot 1 + v of the view block; frusta None: computed from them here."""
         dev = self.device
+        if frusta is None:
+            frusta = [frustum_from_matrices(*m) for m in matrices]
+        self.view_matrices = None if matrices is None else [
+            (np.array(v, np.float32).ravel(), np.array(p, np.float32).ravel(), bool(z)) for v, p, z in matrices]
         n_rows = (self.n + 63) // 64
         self._views = _lib.Views()
         self._views.n = len(frusta)
@@ -185,6 +200,12 @@ class EntityBatch:
         rc = _lib.lib().clapgpu_entities_cull(_stream(), C.byref(self._desc), C.byref(frustum))
         _lib.check(rc, "clapgpu_entities_cull")
 
+    def cull_views(self, views):
+        """cull() with every frustum read from a views.ViewBlock's state: the main plane from slot 0, plane v of
+        set_views from slot 1 + v (clapgpu_entities_cull_views)."""
+        rc = _lib.lib().clapgpu_entities_cull_views(_stream(), C.byref(self._desc), _ptr(views.state))
+        _lib.check(rc, "clapgpu_entities_cull_views")
+
     def compact_visible(self, index_base=0, two_pass=False):
         """Build the ascending visible-index list on the device (visible[:visible_count]).
         two_pass forces the large-n path (no per-row popcounts)."""
@@ -222,6 +243,26 @@ class EntityBatch:
                                                     _ptr(self.cur_lod), _ptr(self.visible), _ptr(self.visible_count),
                                                     _ptr(self.draw_lod), _ptr(self.scratch))
         _lib.check(rc, "clapgpu_visible_compact_lod")
+
+    def select_lod_views(self, views, force_lod=None):
+        """select_lod() with the camera position read from slot 0 of a views.ViewBlock's state."""
+        self.alloc_lod()
+        if force_lod is not None:
+            self.force_lod = upload(force_lod, np.int32, self.device)
+        rc = _lib.lib().clapgpu_entities_lod_views(_stream(), C.byref(self._desc), _ptr(self.visible), _ptr(self.visible_count),
+                                                   0, _ptr(views.state), _ptr(self.force_lod), _ptr(self.cur_lod),
+                                                   _ptr(self.draw_lod))
+        _lib.check(rc, "clapgpu_entities_lod_views")
+
+    def compact_visible_lod_views(self, views, force_lod=None, index_base=0):
+        """compact_visible_lod() with the camera position read from slot 0 of a views.ViewBlock's state."""
+        self.alloc_lod()
+        if force_lod is not None:
+            self.force_lod = upload(force_lod, np.int32, self.device)
+        rc = _lib.lib().clapgpu_visible_compact_lod_views(_stream(), C.byref(self._desc), index_base, _ptr(views.state),
+                                                          _ptr(self.force_lod), _ptr(self.cur_lod), _ptr(self.visible),
+                                                          _ptr(self.visible_count), _ptr(self.draw_lod), _ptr(self.scratch))
+        _lib.check(rc, "clapgpu_visible_compact_lod_views")
 
     def view_entity_in_frustum(self, idx):
         """Served from the precomputed visibility bitmask (host sync)."""

@@ -20,7 +20,7 @@ from . import entities as ent_mod
 class FrameLoop:
     def __init__(self, batch, cam, world=None, feed=None, body_links=None, lights=None, characters=None,
                  particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False, solve=False,
-                 move=None, aniq=None, skin_select=None):
+                 move=None, aniq=None, skin_select=None, views_dev=False):
         """batch: EntityBatch.  world: PhysWorld (dynamic bodies write their entities through
         body_entity; character bodies have body_entity = -1).  feed: CharacterFeed.  body_links:
         (link_body, link_entity) of characters / static colliders whose rotation follows the entity.
@@ -42,7 +42,12 @@ class FrameLoop:
         skin_select: True, or the keyword arguments of CharacterBatch.set_skin_select (entity, row, lod_lists; planes
         and cur_lod given there replace the frame's own): the frame skins what its passes draw -- clapgpu_skin_drawn as
         its last stage, over the batch's main plane and the planes of its further views at the LODs just picked, in place
-        of clapgpu_skin.  None (the default): the plain call."""
+        of clapgpu_skin.  None (the default): the plain call.  views_dev: the frame's views live in device memory (a
+        views.ViewBlock; clapgpu_frame.views_source / views_state): set_camera writes the pose into pinned host memory
+        and every frame copies it to the device ahead of its launches, the frame's first launch derives frustum,
+        matrices and camera position from it (clapgpu_views_calc) and cull, light grid, particles and LOD pick read
+        those, so neither set_camera nor a replayed graph needs a new descriptor.  Further views of the batch go into
+        slots 1.. from the matrices given to EntityBatch.set_views(..., matrices=)."""
         islands = islands or solve
         self.move, self.move_dt = move, 0.0
         self.aniq = aniq
@@ -55,6 +60,10 @@ class FrameLoop:
         self.overlap = False        # CLAPGPU_FRAME_OVERLAP: a caller may set it (three chains on three streams, frame.hip)
         self.prebin = prebin        # CLAPGPU_FRAME_PREBIN: the step bins its boxes for the next frame's broadphase (nothing else writes them)
         self._desc = None
+        self.views = None
+        if views_dev:
+            from .views import ViewBlock
+            self.views = ViewBlock(batch.device)
         if characters is not None:
             missing = bool(characters.model.anim_desc.packed_layout & 0x010)        # POSE_LAYOUT_MISSING (pose_pack.h)
             characters.set_outputs(trs=("trs" in pose_readers) or missing, joint_pos="joint_pos" in pose_readers)
@@ -62,8 +71,23 @@ class FrameLoop:
 
     def set_camera(self, cam):
         self.cam = cam
+        if self.views is not None:                          # the source block: the descriptor does not change
+            self.views.set_camera(0, cam)
+            return
         self.frustum, self.view_mx, self.proj_mx = ent_mod.view_calc_frustum(cam)
         self._desc = None                                   # frustum / matrices are part of the descriptor
+
+    def _further_views(self):
+        """Slots 1.. of the source block from the batch's further views (EntityBatch.set_views(..., matrices=))."""
+        from . import _lib
+        b = self.batch
+        extra = getattr(b, "view_matrices", None) or []
+        if len(getattr(b, "view_masks", [])) != len(extra):
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "FrameLoop",
+                                    "views_dev: EntityBatch.set_views(..., matrices=) for every further view")
+        for v, (vm, pm, z01) in enumerate(extra):
+            self.views.set_matrices(1 + v, vm, pm, ndc_z_zero_one=z01)
+        self._views_seen = getattr(b, "view_matrices", None)
 
     # ---- the clapgpu_frame descriptor ---------------------------------------------------
     def _build(self):
@@ -77,7 +101,11 @@ class FrameLoop:
             f.tile_row_start, f.n_tiles = b.tile_row_start.data_ptr(), b.n_tiles
         else:
             f.level_start, f.n_levels = b.level_start.ctypes.data, b.n_levels
-        f.frustum = C.pointer(self.frustum)
+        if self.views is not None:
+            self._further_views()
+            f.views_source, f.views_state = self.views.source.data_ptr(), self.views.state.data_ptr()
+        else:
+            f.frustum = C.pointer(self.frustum)
         if w is not None:
             f.bodies, f.world, f.bp = C.pointer(w._desc), C.pointer(w.world), w._bp
             f.pairs, f.pair_capacity, f.pair_total = w.pairs.data_ptr(), w.capacity, w.pair_total.data_ptr()
@@ -129,11 +157,12 @@ class FrameLoop:
                 f.n_body_links, f.link_body, f.link_entity = len(self.body_links[0]), lb.data_ptr(), le.data_ptr()
         if self.feed is not None:
             f.characters = C.pointer(self.feed._desc)
-        vm = np.ascontiguousarray(self.view_mx, np.float32)
-        pm = np.ascontiguousarray(self.proj_mx, np.float32)
-        keep += [vm, pm]
-        f.view_mx = vm.ctypes.data_as(C.POINTER(C.c_float))
-        f.proj_mx = pm.ctypes.data_as(C.POINTER(C.c_float))
+        if self.views is None:
+            vm = np.ascontiguousarray(self.view_mx, np.float32)
+            pm = np.ascontiguousarray(self.proj_mx, np.float32)
+            keep += [vm, pm]
+            f.view_mx = vm.ctypes.data_as(C.POINTER(C.c_float))
+            f.proj_mx = pm.ctypes.data_as(C.POINTER(C.c_float))
         ls = self.lights
         if ls is not None:
             d = ls._desc()
@@ -170,17 +199,20 @@ class FrameLoop:
         b.alloc_lod()
         f.index_base = 0
         f.visible, f.visible_count, f.visible_scratch = b.visible.data_ptr(), b.visible_count.data_ptr(), b.scratch.data_ptr()
-        f.cam_pos[:] = [float(v) for v in self.cam["cam_pos"]]
+        if self.views is None:
+            f.cam_pos[:] = [float(v) for v in self.cam["cam_pos"]]
         f.force_lod = b.force_lod.data_ptr() if b.force_lod is not None else None
         f.cur_lod, f.draw_lod = b.cur_lod.data_ptr(), b.draw_lod.data_ptr()
         self._desc, self._keep = f, keep
         return f
 
     def capture(self, dt=1.0 / 120.0, warmup_now=0.0):
-        """Record one frame (with one physics substep, the current camera) as a HIP graph.  Afterwards
-        clap_frame_replay(now) costs one graph launch instead of ~35 kernel launches: what a
-        testbed-sized scene, whose frame is launch latency, needs.  Re-capture after a camera change
-        (the frustum and view matrices are kernel arguments)."""
+        """Record one frame (with one physics substep) as a HIP graph.  Afterwards clap_frame_replay(now) costs one
+        graph launch instead of ~35 kernel launches: what a testbed-sized scene, whose frame is launch latency, needs.
+        With views_dev=True the graph follows the camera: set_camera() writes the pose into the pinned source block,
+        clap_frame_replay copies it to the device ahead of the replay, and the graph's first node (clapgpu_views_calc)
+        derives every view from it.  Without it the frustum, the matrices and the camera position are kernel arguments
+        frozen in the graph: re-capture after a camera change."""
         self.clap_frame(warmup_now, dt)                      # everything allocated, lazily created state exists
         torch.cuda.synchronize()
         self._now_host = torch.zeros(1, dtype=torch.float64).pin_memory()
@@ -195,6 +227,10 @@ class FrameLoop:
         self._now_host[0] = float(now)
         if self.characters is not None:
             self.characters.now_dev.copy_(self._now_host, non_blocking=True)
+        if self.views is not None:
+            if getattr(self.batch, "view_matrices", None) is not self._views_seen:
+                self._further_views()
+            self.views.upload()
         self._graph.replay()
 
     def clap_frame(self, now, dt):
@@ -213,6 +249,10 @@ class FrameLoop:
         # CLAPGPU_FRAME_OVERLAP: three chains on three streams (frame.hip); CLAPGPU_FRAME_PREBIN
         f.flags = (1 if self.overlap else 0) | (2 if self.prebin else 0)
         f.move_dt_sec = self.move_dt
+        if self.views is not None and now is not None:       # (under capture the copy is the replay's, not a graph node)
+            if getattr(self.batch, "view_matrices", None) is not self._views_seen:
+                self._further_views()                        # set_views since the last frame
+            self.views.upload()
         rc = _lib.lib().clapgpu_frame_issue(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(f),
                                             0.0 if now is None else float(now), int(steps))
         _lib.check(rc, "clapgpu_frame_issue")

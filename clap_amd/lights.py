@@ -155,6 +155,17 @@ class LightSet:
         _lib.check(rc, "clapgpu_light_grid_compute")
         return self.tiles
 
+    def grid_compute_views(self, views):
+        """grid_compute with view, mvp and proj_mx[0] read from slot 0 of a views.ViewBlock's state."""
+        self._upload()
+        if self.alloc_tiles() is None:
+            return None
+        desc = self._desc()
+        rc = _lib.lib().clapgpu_light_grid_compute_views(_stream(), C.byref(desc), views.state.data_ptr(), self.width,
+                                                         self.height, self.cell, self.tiles.data_ptr())
+        _lib.check(rc, "clapgpu_light_grid_compute_views")
+        return self.tiles
+
     def download_tiles(self):
         torch.cuda.synchronize(self.device)
         return self.tiles.cpu().numpy().view(np.uint32)

@@ -49,6 +49,11 @@ class ParticleBatch:
         rc = _lib.lib().clapgpu_particles_update(_stream(), C.byref(self._desc), v.ctypes.data_as(C.POINTER(C.c_float)))
         _lib.check(rc, "clapgpu_particles_update")
 
+    def particles_update_views(self, views):
+        """particles_update with the billboards' view matrix read from slot 0 of a views.ViewBlock's state."""
+        rc = _lib.lib().clapgpu_particles_update_views(_stream(), C.byref(self._desc), views.state.data_ptr())
+        _lib.check(rc, "clapgpu_particles_update_views")
+
     def particle_system_count(self, s):
         return int(self.sys_host["count"][s])
 

@@ -58,7 +58,7 @@ void clapgpu_test_fail_after(int launches);
 /* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
  * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
  * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
-#define CLAPGPU_ABI_VERSION 48u
+#define CLAPGPU_ABI_VERSION 49u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -1931,6 +1931,88 @@ int clapgpu_characters_state(void *stream, const clapgpu_aniq *q, const clapgpu_
 int clapgpu_animation_queue_time(void *stream, const clapgpu_aniq *q, double now, const double *now_dev);
 
 /* ======================================================================== */
+/* Views in device memory (ABI 49)                                           */
+/* ======================================================================== */
+
+/*
+ * Everything a frame knows about its views -- the frusta of the cull, the view and projection matrices of the light grid
+ * and the particles' billboards, the camera position of the LOD pick -- reaches the kernels above by value, from host
+ * memory, as kernel arguments; a captured graph holds them frozen.  The view block is the same knowledge in device memory:
+ *   clapgpu_views_source   what a view IS: matrices, or a pose.  Written by one small copy from the host or by a kernel
+ *                          of the caller's.
+ *   clapgpu_views_state    what the kernels READ: per slot the frustum, the matrices, the camera position and the cull's
+ *                          constants.  Written by clapgpu_views_calc alone.
+ * Slot 0 is the main view, slot 1 + k further view k in the order of clapgpu_views.  Both blocks are 16-byte aligned.
+ *
+ * THE RULE: clapgpu_views_calc does per slot the arithmetic of clapgpu_view_matrix (when FROM_POSE), mvp = proj * view
+ * and clapgpu_frustum_calc, by the same functions (csrc/lm_dev.h) in the same order, and every *_views entry point
+ * below gives the bits of its twin called with those host values.  Every NaN these functions store is the one quiet NaN
+ * 0x7fc00000, on the host and on the device: what an invalid operation (0 * inf of a singular mvp) leaves in the sign and
+ * payload of a NaN differs between the two machines and no consumer reads it.
+ * The camera controller (camera_update's pull-in rays, camera_target, the cascades' light views) is still the host's:
+ * it writes the source.  clapgpu_entities.bv (the bounding-volume pick's camera and control positions) stays
+ * host-valued too: it is an argument of the fused update kernel, which the view block does not reach.
+ */
+#define CLAPGPU_VIEW_SLOTS (1 + CLAPGPU_EXTRA_VIEWS_MAX)
+#define CLAPGPU_VIEW_FROM_POSE        1u     /* view matrix = clapgpu_view_matrix(pos, quat); view_mx is not read */
+#define CLAPGPU_VIEW_NDC_Z_ZERO_ONE   2u     /* the ndc_z_zero_one argument of clapgpu_frustum_calc */
+
+typedef struct clapgpu_view_source {
+    float    view_mx[16], proj_mx[16];
+    float    pos[3];                         /* the camera position the LOD pick uses (and the pose's, when FROM_POSE) */
+    uint32_t flags;                          /* CLAPGPU_VIEW_* */
+    float    quat[4];                        /* x y z w; read only when FROM_POSE */
+} clapgpu_view_source;
+typedef struct clapgpu_views_source {
+    clapgpu_view_source slot[CLAPGPU_VIEW_SLOTS];
+} clapgpu_views_source;
+
+typedef struct clapgpu_view_state {
+    clapgpu_frustum frustum;                 /* clapgpu_frustum_calc(view_mx, proj_mx, NDC_Z_ZERO_ONE) */
+    uint32_t cull[8];                        /* reserved to the library: the cull's constants (per-axis extremes of the
+                                              * corners, "every plane component finite") */
+    float    view_mx[16], proj_mx[16], mvp[16];
+    float    cam_pos[3];
+    uint32_t pad;
+} clapgpu_view_state;
+typedef struct clapgpu_views_state {
+    clapgpu_view_state slot[CLAPGPU_VIEW_SLOTS];
+} clapgpu_views_state;
+
+#define CLAPGPU_VIEWS_SOURCE_BYTES 800
+#define CLAPGPU_VIEWS_STATE_BYTES  2320
+#ifdef __cplusplus
+static_assert(sizeof(clapgpu_views_source) == CLAPGPU_VIEWS_SOURCE_BYTES && sizeof(clapgpu_views_state) == CLAPGPU_VIEWS_STATE_BYTES,
+              "the view block's layout is ABI");
+#else
+_Static_assert(sizeof(clapgpu_views_source) == CLAPGPU_VIEWS_SOURCE_BYTES && sizeof(clapgpu_views_state) == CLAPGPU_VIEWS_STATE_BYTES,
+               "the view block's layout is ABI");
+#endif
+
+/* state->slot[0 .. n_views-1] from source->slot[same]; the other slots are left untouched.  n_views is 1 ..
+ * CLAPGPU_VIEW_SLOTS.  One launch, no allocation, no host synchronisation: it can be captured.  A NULL or misaligned
+ * block or an n_views out of range: CLAPGPU_ERR_INVALID_ARGUMENTS before any HIP call (as for every entry point below). */
+int clapgpu_views_calc(void *stream, const clapgpu_views_source *source, clapgpu_views_state *state, uint32_t n_views);
+
+/* The twins: each takes the view block where its original takes host values, validates as its original does and leaves
+ * the bits its original leaves when called with the host-computed values of the same source. */
+/* clapgpu_entities_cull: the main plane from slot 0, plane k of e->views (mask pointers and n from the host struct)
+ * from slot 1 + k; e->views->frustum[] is not read */
+int clapgpu_entities_cull_views(void *stream, const clapgpu_entities *e, const clapgpu_views_state *state);
+/* clapgpu_entities_lod / clapgpu_visible_compact_lod: cam_pos from slot 0 */
+int clapgpu_entities_lod_views(void *stream, const clapgpu_entities *e, const uint32_t *visible, const uint32_t *count,
+                               uint32_t index_base, const clapgpu_views_state *state, const int32_t *force_lod,
+                               int32_t *cur_lod, int32_t *draw_lod);
+int clapgpu_visible_compact_lod_views(void *stream, const clapgpu_entities *e, uint32_t index_base,
+                                      const clapgpu_views_state *state, const int32_t *force_lod, int32_t *cur_lod,
+                                      uint32_t *visible, uint32_t *count, int32_t *draw_lod, void *scratch);
+/* clapgpu_light_grid_compute: view, mvp and proj_mx[0] from slot 0 */
+int clapgpu_light_grid_compute_views(void *stream, const clapgpu_lights *lights, const clapgpu_views_state *state,
+                                     uint32_t width, uint32_t height, uint32_t cell, uint32_t *tiles);
+/* clapgpu_particles_update: the billboards' view matrix from slot 0 */
+int clapgpu_particles_update_views(void *stream, const clapgpu_particles *p, const clapgpu_views_state *state);
+
+/* ======================================================================== */
 /* One frame (core/clap.c:551-665)                                           */
 /* ======================================================================== */
 
@@ -2017,6 +2099,17 @@ typedef struct clapgpu_frame {
      * entities->views; cur_lod == NULL there: this descriptor's cur_lod is used when it has one.  Needs skin, pose (with
      * skeleton and animations) and frustum: CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, before any launch */
     const clapgpu_skin_select *skin_select;
+    /* views in device memory (ABI 49); both NULL: the frame as before, launch for launch.  Both set (one alone, or
+     * views_state next to a non-NULL frustum: CLAPGPU_ERR_INVALID_ARGUMENTS before any launch): clapgpu_views_calc(
+     * views_source, views_state, 1 + entities->views->n) is the frame's FIRST launch on the caller's stream, ahead of any
+     * fork of CLAPGPU_FRAME_OVERLAP; the entity update runs without its fused cull and clapgpu_entities_cull_views follows
+     * it over the boxes it stored (the same masks: the fused kernel's frustum is a kernel argument); the light grid, the
+     * particles and the LOD pick use their *_views twins.  frustum (NULL), view_mx, proj_mx, cam_pos and
+     * entities->views->frustum[] are not read, and "the frame has a main view" (visible list, LOD pick, skin_select)
+     * means frustum || views_state.  A replayed graph of such a frame follows whatever was written into views_source
+     * before the replay.  entities->bv stays host-valued */
+    const clapgpu_views_source *views_source;  /* device */
+    clapgpu_views_state        *views_state;   /* device */
 } clapgpu_frame;
 
 /* Default (0): everything on the caller's stream in the reference's order.  CLAPGPU_FRAME_OVERLAP: the frame's three
