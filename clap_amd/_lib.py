@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 49
+ABI_VERSION = 50
 
 OK = 0
 ERR_NOMEM = -1
@@ -94,6 +94,25 @@ class ViewsState(C.Structure):
 
 VIEWS_SOURCE_BYTES, VIEWS_STATE_BYTES = 800, 2320           # CLAPGPU_VIEWS_*_BYTES
 assert C.sizeof(ViewsSource) == VIEWS_SOURCE_BYTES and C.sizeof(ViewsState) == VIEWS_STATE_BYTES
+
+
+CAMERA_IS_CHARACTER, CAMERA_HAS_HEAD_JOINT = 1, 2
+CAMERA_UNRESOLVED, CAMERA_CAPPED, CAMERA_INVALID = 1, 2, 4
+CAMERA_ITER_MAX = 16384
+
+
+class Camera(C.Structure):
+    """clapgpu_camera (include/clapgpu.h): the camera controller's block.  Lives in device memory."""
+    _fields_ = [("quat", C.c_float * 4), ("pos", C.c_float * 3), ("dist", C.c_float),
+                ("near_plane", C.c_float), ("far_plane", C.c_float), ("aspect", C.c_float), ("moved", C.c_uint32),
+                ("ctl_entity", C.c_uint32), ("ctl_skip", C.c_int32), ("flags", C.c_uint32), ("head_joint", C.c_uint32),
+                ("target", C.c_float * 3), ("updated", C.c_uint32), ("corner", C.c_float * 16),
+                ("iterations", C.c_uint32), ("status", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+CAMERA_BYTES = 160                                           # CLAPGPU_CAMERA_BYTES
+assert C.sizeof(Camera) == CAMERA_BYTES
+CAMERA_CAST_FN = C.CFUNCTYPE(C.c_uint32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double))
 
 
 class Entities(C.Structure):
@@ -334,7 +353,8 @@ class FrameDesc(C.Structure):
                 ("solve_status", C.c_void_p),
                 ("move", C.POINTER(CharactersMove)), ("move_dt_sec", C.c_double), ("move_scratch", C.c_void_p),
                 ("aniq", C.POINTER(Aniq)), ("skin_select", C.POINTER(SkinSelect)),
-                ("views_source", C.c_void_p), ("views_state", C.c_void_p)]
+                ("views_source", C.c_void_p), ("views_state", C.c_void_p),
+                ("camera", C.c_void_p), ("camera_bp", C.c_void_p)]
 
 
 LIGHTS_MAX = 128
@@ -348,7 +368,7 @@ STRUCTS = {
     "clapgpu_world": World, "clapgpu_bodies": Bodies, "clapgpu_geoms": Geoms, "clapgpu_trimesh_desc": TrimeshDesc,
     "clapgpu_slide": Slide, "clapgpu_move": CharactersMove, "clapgpu_characters": Characters, "clapgpu_lights": Lights,
     "clapgpu_view_source": ViewSource, "clapgpu_views_source": ViewsSource, "clapgpu_view_state": ViewState,
-    "clapgpu_views_state": ViewsState,
+    "clapgpu_views_state": ViewsState, "clapgpu_camera": Camera,
     "clapgpu_solver": Solver, "clapgpu_aniq_entry": AniqEntry, "clapgpu_aniq": Aniq, "clapgpu_frame": FrameDesc,
 }
 
@@ -520,6 +540,16 @@ SYMBOLS = {
     "clapgpu_light_grid_compute": (C.c_int, [C.c_void_p, C.POINTER(Lights), C.POINTER(C.c_float),
                                              C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "clapgpu_views_calc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "clapgpu_camera_calc": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Entities), C.c_void_p, C.c_void_p, C.POINTER(Geoms),
+                                      C.POINTER(Geoms), C.c_void_p, C.c_void_p]),
+    "clapgpu_camera_target": (None, [C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float)]),
+    "clapgpu_camera_rays": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float,
+                                   C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+    "clapgpu_camera_decide": (C.c_int, [C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "clapgpu_camera_update_host": (None, [C.POINTER(Camera), C.c_void_p, C.c_void_p]),
     "clapgpu_entities_cull_views": (C.c_int, [C.c_void_p, C.POINTER(Entities), C.c_void_p]),
     "clapgpu_entities_lod_views": (C.c_int, [C.c_void_p, C.POINTER(Entities), C.c_void_p, C.c_void_p, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

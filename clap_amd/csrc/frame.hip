@@ -18,6 +18,12 @@
 // frame's first launch, ahead of any fork, the entity update runs without its fused cull (the fused kernels take their
 // frustum by value and are not touched: entities.hip) with clapgpu_entities_cull_views behind it over the boxes it stored,
 // and particles, light grid and LOD pick read the block.  A captured frame then follows whatever the source holds.
+// With f->camera (ABI 50) the camera controller runs in the reference's place in the frame, scene_cameras_calc behind
+// scene_update (clap.c:614-616): the head clapgpu_views_calc stays (particles and the light grid see the camera the
+// previous frame left, as the reference's do) and, behind the join, clapgpu_joint_pos_world and the light grid, come
+// clapgpu_bp_index(camera_bp) when an index is asked for, clapgpu_camera_calc (camera.hip: camera_target, the pull-in rays
+// against this frame's colliders, the orbit; it writes slot 0 of the source), a second clapgpu_views_calc, and only then
+// the cull, which therefore moves from behind the update to here, the visible list, the LOD pick and skin_select.
 //
 // Round 4: the frame as THREE CHAINS (opt-in: CLAPGPU_FRAME_OVERLAP).  What the reference runs in list order has only these
 // data dependences:
@@ -42,6 +48,7 @@
 #include <string.h>
 #include "common.h"
 #include "views_dev.h"
+#include "geoms_dev.h"
 
 using namespace clapgpu;
 
@@ -94,6 +101,8 @@ extern "C" int clapgpu_frame_issue(void *stream, const clapgpu_frame *f, double 
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (f->views_state && f->entities->views && f->entities->views->n > CLAPGPU_EXTRA_VIEWS_MAX)
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    if (f->camera && (!f->views_state || !view_block_ok(f->camera) || (f->camera_bp && !f->bodies)))
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;                    // the camera writes the view block's source
     const bool animated = f->skeleton && f->animations && f->pose;
     const bool particles = f->particles && (f->view_mx || f->views_state);
     const bool overlap = (f->flags & CLAPGPU_FRAME_OVERLAP) && (animated || particles);
@@ -276,7 +285,7 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         FR(clapgpu_entities_update_tiles(stream, e, f->tile_row_start, f->n_tiles, 0, f->frustum));
     else
         FR(clapgpu_entities_update(stream, e, f->level_start, f->n_levels, 0, f->frustum));
-    if (vs)                                                      // f->frustum is NULL: the update above did not cull
+    if (vs && !f->camera)                                        // f->frustum is NULL: the update above did not cull
         FR(clapgpu_entities_cull_views(stream, e, vs));
 
     if (overlap) {                                               // join
@@ -294,6 +303,21 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
     else if (f->lights && f->light_tiles && f->view_mx && f->proj_mx)
         FR(clapgpu_light_grid_compute(stream, f->lights, f->view_mx, f->proj_mx, f->light_width, f->light_height, f->light_cell,
                                       f->light_tiles));
+    // ---- scene_cameras_calc (clap.c:616): camera_update on the device, this frame's views, and the cull they wait for ----
+    if (f->camera) {
+        clapgpu_geoms none, from_bodies;
+        memset(&none, 0, sizeof(none));
+        const clapgpu_geoms *bg = f->body_geoms;
+        if (!bg && f->bodies) {
+            if (!body_geoms(f->bodies, &from_bodies)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+            bg = &from_bodies;
+        }
+        if (f->camera_bp) FR(clapgpu_bp_index(stream, f->camera_bp, f->bodies->n, f->bodies->aabb));
+        FR(clapgpu_camera_calc(stream, f->camera, e, animated ? f->pose->joint_pos : nullptr, f->camera_bp, bg ? bg : &none,
+                               f->static_geoms ? f->static_geoms : &none, f->meshes, const_cast<clapgpu_views_source *>(f->views_source)));
+        FR(clapgpu_views_calc(stream, f->views_source, f->views_state, 1 + (e->views ? e->views->n : 0)));
+        FR(clapgpu_entities_cull_views(stream, e, vs));
+    }
     // ---- render pass glue: ordered visible list + LOD pick ----
     if ((f->frustum || vs) && f->visible && f->visible_count && f->visible_scratch) {
         if (f->cur_lod && f->draw_lod && vs)

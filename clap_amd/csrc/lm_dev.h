@@ -339,6 +339,26 @@ LMD bool aabb_in_frustum_fast(const FrustumK &k, const float (&bb)[6])
     return true;
 }
 
+// ---- libm cbrtf for the LOD pick (visible.hip) and the camera (below) ----
+// glibc 2.35 sysdeps/ieee754/flt-32/s_cbrtf.c restated (the reference calls libm cbrtf(),
+// model.c:1263): the float is rescaled by frexpf, a quadratic start and one Halley step run in
+// double, ldexpf rescales.  Bit-identical to libm on every one of 3.0e8 floats probed over the
+// whole normal range, which is what makes the integer LOD exact.
+LMD float cbrtf_glibc(float x)
+{
+    int xe;
+    const float xm = frexpf(fabsf(x), &xe);
+    if (xe == 0 && (x == 0.0f || x != x || isinf(x)))
+        return x + x;
+    const float u = (float)(0.492659620528969547 + (0.697570460207922770 - 0.191502161678719066 * (double)xm) * (double)xm);
+    const float t2 = u * u * u;
+    const int r = xe % 3;
+    const double f = r == -2 ? 1.0 / 1.5874010519681994748 : r == -1 ? 1.0 / 1.2599210498948731648
+                   : r == 0 ? 1.0 : r == 1 ? 1.2599210498948731648 : 1.5874010519681994748;
+    const float ym = (float)((double)u * ((double)t2 + 2.0 * (double)xm) / (2.0 * (double)t2 + (double)xm) * f);
+    return ldexpf(x > 0.0f ? ym : -ym, xe / 3);
+}
+
 // ---- a view: the O(1)-per-frame arithmetic of the host entry points (runtime.hip) and of k_views_calc (views.hip) ----
 // Stated once, here, for both machines.  What an invalid operation leaves in a NaN's sign and payload is the machine's
 // (x86: 0xffc00000, gfx950: 0x7fc00000) and nothing reads it: whatever these functions store goes through one_nan.
@@ -429,6 +449,155 @@ LMD void frustum_constants(FrustumK &k)
         for (int c = 0; c < 4; c++)
             if (!(__builtin_fabsf(k.f.planes[i][c]) <= 3.402823466e+38f))
                 k.finite = 0;
+}
+
+// ---- the camera controller: camera_update (core/camera.c:51-117, 174-246) over transform_orbit (transform.c:109-123) ----
+// Stated once, here, for k_camera_calc (camera.hip) and for the host's clapgpu_camera_* (runtime.hip): fp32 and fp64
+// where the reference has them, its order of operations, and whatever is stored goes through one_nan.  The rule is in
+// include/clapgpu.h ("The camera controller on the device").
+constexpr uint32_t CAMERA_IS_CHARACTER = 1u, CAMERA_HAS_HEAD_JOINT = 2u;          // CLAPGPU_CAMERA_* (flags)
+constexpr uint32_t CAMERA_UNRESOLVED = 1u, CAMERA_CAPPED = 2u;                    // CLAPGPU_CAMERA_* (status)
+constexpr uint32_t CAMERA_ITER_MAX = 16384u;
+
+// linmath.h:939-958: t = 2 cross(q.xyz, v); r = (v + q.w t) + cross(q.xyz, t)
+LMD void quat_mul_vec3(float (&r)[3], const float (&q)[4], const float (&v)[3])
+{
+    float t[3], u[3];
+    t[0] = q[1] * v[2] - q[2] * v[1];
+    t[1] = q[2] * v[0] - q[0] * v[2];
+    t[2] = q[0] * v[1] - q[1] * v[0];
+#pragma unroll
+    for (int i = 0; i < 3; i++) t[i] = t[i] * 2.f;
+    u[0] = q[1] * t[2] - q[2] * t[1];
+    u[1] = q[2] * t[0] - q[0] * t[2];
+    u[2] = q[0] * t[1] - q[1] * t[0];
+#pragma unroll
+    for (int i = 0; i < 3; i++) t[i] = t[i] * q[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) r[i] = v[i] + t[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) r[i] = r[i] + u[i];
+}
+
+// transform.c:116-123: pos = rotate((0, 0, len)) + target
+LMD void orbit(float (&pos)[3], const float (&quat)[4], const float (&target)[3], float len)
+{
+    const float start[3] = { 0.f, 0.f, len };
+    float r[3];
+    quat_mul_vec3(r, quat, start);
+#pragma unroll
+    for (int i = 0; i < 3; i++) pos[i] = one_nan(r[i] + target[i]);
+}
+
+// camera.c:174-206.  pos_scale / lo / hi / center: the control entity's position and scale, its MODEL box
+// (model_table) and its world centre; head: its head joint's world position (read when HAS_HEAD_JOINT)
+LMD void camera_target(float (&target)[3], float &dist, uint32_t flags, const float (&pos_scale)[4], const float (&lo)[3],
+                       const float (&hi)[3], const float (&center)[3], const float (&head)[3], float far_plane)
+{
+    const float s = pos_scale[3];                    // entity3d_aabb_X / Y / Z (model.c:1185-1198, 433-447)
+    const float X = fabsf(hi[0] - lo[0]) * s, Y = fabsf(hi[1] - lo[1]) * s, Z = fabsf(hi[2] - lo[2]) * s;
+    float height;
+    if (flags & CAMERA_IS_CHARACTER) {
+        height = Y;
+        if (flags & CAMERA_HAS_HEAD_JOINT) {
+            target[0] = head[0] + 0.0f;
+            target[1] = head[1] + height * 0.2f;
+            target[2] = head[2] + 0.0f;
+        } else {
+            target[0] = pos_scale[0];
+            target[1] = pos_scale[1] + height * 0.75f;
+            target[2] = pos_scale[2];
+        }
+    } else {
+        target[0] = center[0]; target[1] = center[1]; target[2] = center[2];
+        height = Y / 2.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) target[i] = one_nan(target[i]);
+    const float dist_cap = fmaxf(10.0f, cbrtf_glibc(X * Y * Z));               // entity3d_aabb_avg_edge, model.c:1261-1264
+    dist = one_nan(fminf(height * 3.0f, fminf(dist_cap, far_plane - 10.0f)));
+}
+
+// camera.c:68-91 and 56-57: the orbiting camera's four near-plane corners and the rays to them as clapgpu_ray_cast takes
+// them (start, direction, length, pad)
+LMD void camera_rays(float (&corner)[4][4], double (&ray)[4][8], const float (&quat)[4], const float (&target)[3], float dist,
+                     float near_plane, float aspect)
+{
+    const float w = near_plane, h = near_plane / aspect;
+    float pos[3], m[16], inv[16];
+    orbit(pos, quat, target, dist);
+    view_matrix(m, pos, quat);
+    invert(inv, m);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float r[4] = { (k & 1) ? -w : w, (k & 2) ? -h : h, 0.0f, 1.0f };
+#pragma unroll
+        for (int j = 0; j < 4; j++) {                // mat4x4_mul_vec4, linmath.h:308-316
+            float t = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; i++) t += E_(inv, i, j) * r[i];
+            corner[k][j] = one_nan(t);
+        }
+        float dir[3], p = 0.f;
+#pragma unroll
+        for (int i = 0; i < 3; i++) dir[i] = one_nan(corner[k][i] - target[i]);
+#pragma unroll
+        for (int i = 0; i < 3; i++) p += dir[i] * dir[i];
+#pragma unroll
+        for (int i = 0; i < 3; i++) { ray[k][i] = (double)target[i]; ray[k][3 + i] = (double)dir[i]; }
+        ray[k][6] = (double)one_nan(sqrtf(p));       // distance, camera.c:57
+        ray[k][7] = 0.0;
+    }
+}
+
+// camera.c:101-116: true = the position is good; false: next = the distance to try
+LMD bool camera_decide(double &min_scale, double &next, float dist, const bool (&hit)[4], const double (&depth)[4],
+                       const double (&ray)[4][8])
+{
+    min_scale = 1.0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (hit[k]) min_scale = fmin(min_scale, depth[k] / ray[k][6]);
+    if (min_scale < 0.99) {
+        next = (double)dist * min_scale;
+        return false;
+    }
+    return true;
+}
+
+struct CameraResult {
+    float pos[3], dist, target[3];
+    float corner[4][4];
+    uint32_t updated, iterations, status;
+};
+
+// camera.c:226-242 behind camera_target (target and dist of `o` are its).  cast(ray, hit, depth) casts the four rays and
+// returns CAMERA_UNRESOLVED or 0; it is not called when the control entity has no physics (phys_ray_cast returns NULL,
+// physics.c:536).  o.corner is written when o.iterations > 0.
+// The loop ends on every input: a continuing iteration multiplies a finite dist by less than 0.99 and the loop stops at
+// or below 0.1, at most ln(3.4e39) / -ln(0.99) ~ 9 040 iterations from the largest float; a NaN dist fails `> 0.1`; an
+// infinite one gives non-finite corners, whose rays are invalid and miss, so min_scale stays 1.  CAMERA_ITER_MAX can
+// therefore never bind; it is there so that no arithmetic argument stands between a kernel and its end.
+template <typename Cast>
+LMD void camera_update(CameraResult &o, const float (&quat)[4], float near_plane, float aspect, bool has_physics, Cast &&cast)
+{
+    const float cdist = o.dist;
+    double dist = cdist, next = 0.0, min_scale;
+    o.iterations = 0;
+    o.status = 0;
+    while (dist > 0.1) {
+        if (o.iterations == CAMERA_ITER_MAX) { o.status |= CAMERA_CAPPED; break; }
+        o.iterations++;
+        double ray[4][8], depth[4] = { 0.0, 0.0, 0.0, 0.0 };
+        bool hit[4] = { false, false, false, false };
+        camera_rays(o.corner, ray, quat, o.target, (float)dist, near_plane, aspect);
+        if (has_physics) o.status |= cast(ray, hit, depth);
+        if (camera_decide(min_scale, next, (float)dist, hit, depth, ray)) break;
+        dist = next;
+    }
+    o.updated = (double)cdist != dist ? 1u : 0u;     // camera.c:238
+    o.dist = one_nan((float)dist);
+    orbit(o.pos, quat, o.target, o.dist);
 }
 
 } // namespace lmd

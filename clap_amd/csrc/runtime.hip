@@ -246,3 +246,64 @@ extern "C" void clapgpu_frustum_calc(const float view_mx[16], const float proj_m
     lmd::frustum_calc(f, mvp, v, p, ndc_z_zero_one != 0);
     memcpy(out, &f, sizeof(f));
 }
+
+// camera.c:174-206, 68-91, 101-116, 226-242 (lmd::camera_*: the statements k_camera_calc shares)
+extern "C" void clapgpu_camera_target(uint32_t flags, const float pos_scale[4], const float lo[3], const float hi[3],
+                                      const float center[3], const float head[3], float far_plane, float target[3], float *dist)
+{
+    float ps[4], l[3], h[3], c[3], hd[3] = { 0.f, 0.f, 0.f }, t[3], d;
+    memcpy(ps, pos_scale, sizeof(ps)); memcpy(l, lo, sizeof(l)); memcpy(h, hi, sizeof(h)); memcpy(c, center, sizeof(c));
+    if (head && (flags & CLAPGPU_CAMERA_HAS_HEAD_JOINT)) memcpy(hd, head, sizeof(hd));
+    lmd::camera_target(t, d, flags, ps, l, h, c, hd, far_plane);
+    memcpy(target, t, sizeof(t));
+    *dist = d;
+}
+
+extern "C" void clapgpu_camera_rays(const float quat[4], const float target[3], float dist, float near_plane, float aspect,
+                                    float corner[16], double ray[32])
+{
+    float q[4], t[3], cn[4][4];
+    double r[4][8];
+    memcpy(q, quat, sizeof(q)); memcpy(t, target, sizeof(t));
+    lmd::camera_rays(cn, r, q, t, dist, near_plane, aspect);
+    memcpy(corner, cn, sizeof(cn));
+    memcpy(ray, r, sizeof(r));
+}
+
+extern "C" int clapgpu_camera_decide(float dist, const int32_t hit[4], const double depth[4], const double ray[32],
+                                     double *min_scale, double *next_dist)
+{
+    bool h[4];
+    double d[4], r[4][8], ms, next = 0.0;
+    for (int k = 0; k < 4; k++) { h[k] = hit[k] != 0; d[k] = depth[k]; }
+    memcpy(r, ray, sizeof(r));
+    const bool good = lmd::camera_decide(ms, next, dist, h, d, r);
+    *min_scale = ms;
+    if (!good) *next_dist = next;
+    return good ? 1 : 0;
+}
+
+extern "C" void clapgpu_camera_update_host(clapgpu_camera *cam, void *cast_fn, void *user)
+{
+    const clapgpu_camera_cast_fn cast = reinterpret_cast<clapgpu_camera_cast_fn>(cast_fn);
+    if (cam->moved == 0) { cam->status = 0; cam->iterations = 0; return; }
+    lmd::CameraResult o;
+    memcpy(o.target, cam->target, sizeof(o.target));
+    o.dist = cam->dist;
+    float q[4];
+    memcpy(q, cam->quat, sizeof(q));
+    auto cast4 = [&](const double (&ray)[4][8], bool (&hit)[4], double (&depth)[4]) -> uint32_t {
+        int32_t h[4] = { 0, 0, 0, 0 };
+        const uint32_t f = cast(user, &ray[0][0], h, depth);
+        for (int k = 0; k < 4; k++) hit[k] = h[k] != 0;
+        return (f & CLAPGPU_RAY_UNRESOLVED) ? CLAPGPU_CAMERA_UNRESOLVED : 0u;
+    };
+    lmd::camera_update(o, q, cam->near_plane, cam->aspect, cam->ctl_skip != -1, cast4);
+    memcpy(cam->pos, o.pos, sizeof(o.pos));
+    memcpy(cam->target, o.target, sizeof(o.target));
+    cam->dist = o.dist;
+    cam->updated = o.updated;
+    if (o.iterations) memcpy(cam->corner, o.corner, sizeof(o.corner));
+    cam->iterations = o.iterations;
+    cam->status = o.status;
+}

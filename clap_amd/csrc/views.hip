@@ -6,7 +6,8 @@
 // make_frustum_k call on the host -- so the block holds the host's bits, non-finite inputs included.
 //
 // A few hundred flops in a single wavefront: the launch is latency, not work.  What it buys is that nothing about a view
-// is a kernel argument any more, so a captured frame follows its camera.
+// is a kernel argument any more, so a captured frame follows its camera.  The source is the host's to write, or a
+// kernel's: slot 0's pose is k_camera_calc's (camera.hip) in a frame with clapgpu_frame.camera.
 #include "common.h"
 #include "lm_dev.h"
 #include "views_dev.h"

@@ -230,25 +230,6 @@ void k_visible_expand_rp(const uint64_t *vis_mask, const uint8_t *row_pop, uint3
 }
 
 // ---- per-pass LOD pick for the entities on the visible list (model.c:975-992) ----
-// glibc 2.35 sysdeps/ieee754/flt-32/s_cbrtf.c restated (the reference calls libm cbrtf(),
-// model.c:1263): the float is rescaled by frexpf, a quadratic start and one Halley step run in
-// double, ldexpf rescales.  Bit-identical to libm on every one of 3.0e8 floats probed over the
-// whole normal range, which is what makes the integer LOD exact.
-__device__ __forceinline__ float cbrtf_glibc(float x)
-{
-    int xe;
-    const float xm = frexpf(fabsf(x), &xe);
-    if (xe == 0 && (x == 0.0f || x != x || isinf(x)))
-        return x + x;
-    const float u = (float)(0.492659620528969547 + (0.697570460207922770 - 0.191502161678719066 * (double)xm) * (double)xm);
-    const float t2 = u * u * u;
-    const int r = xe % 3;
-    const double f = r == -2 ? 1.0 / 1.5874010519681994748 : r == -1 ? 1.0 / 1.2599210498948731648
-                   : r == 0 ? 1.0 : r == 1 ? 1.2599210498948731648 : 1.5874010519681994748;
-    const float ym = (float)((double)u * ((double)t2 + 2.0 * (double)xm) / (2.0 * (double)t2 + (double)xm) * f);
-    return ldexpf(x > 0.0f ? ym : -ym, xe / 3);
-}
-
 struct LodK {                       // what the pick reads (model.c:975-992) and writes
     float cx, cy, cz;
     const float *aabb, *center;
@@ -282,7 +263,7 @@ __device__ __forceinline__ int32_t lod_pick(const LodK &k, uint32_t i)
             const float4 lo = k.model_table[2 * mi], hi = k.model_table[2 * mi + 1];
             const float s = k.pos_scale[i].w;
             const float X = fabsf(hi.x - lo.x) * s, Y = fabsf(hi.y - lo.y) * s, Z = fabsf(hi.z - lo.z) * s;
-            const float side = cbrtf_glibc(X * Y * Z);                  // entity3d_aabb_avg_edge
+            const float side = lmd::cbrtf_glibc(X * Y * Z);                  // entity3d_aabb_avg_edge
             const float scale = (float)((double)fabsf(dd - side * side) / 3600.0);
             const uint32_t lm = __float_as_uint(hi.w);                  // lod_min | lod_max << 8
             const int lmin = (int)(lm & 0xffu), lmax = (int)((lm >> 8) & 0xffu);

@@ -20,7 +20,7 @@ from . import entities as ent_mod
 class FrameLoop:
     def __init__(self, batch, cam, world=None, feed=None, body_links=None, lights=None, characters=None,
                  particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False, solve=False,
-                 move=None, aniq=None, skin_select=None, views_dev=False):
+                 move=None, aniq=None, skin_select=None, views_dev=False, camera=None, camera_index=False):
         """batch: EntityBatch.  world: PhysWorld (dynamic bodies write their entities through
         body_entity; character bodies have body_entity = -1).  feed: CharacterFeed.  body_links:
         (link_body, link_entity) of characters / static colliders whose rotation follows the entity.
@@ -47,7 +47,13 @@ class FrameLoop:
         and every frame copies it to the device ahead of its launches, the frame's first launch derives frustum,
         matrices and camera position from it (clapgpu_views_calc) and cull, light grid, particles and LOD pick read
         those, so neither set_camera nor a replayed graph needs a new descriptor.  Further views of the batch go into
-        slots 1.. from the matrices given to EntityBatch.set_views(..., matrices=)."""
+        slots 1.. from the matrices given to EntityBatch.set_views(..., matrices=).  camera: a camera.CameraBlock (needs
+        views_dev): the camera controller runs on the device in the reference's place in the frame
+        (clapgpu_frame.camera: camera_target, the pull-in rays against `world`'s colliders, the orbit, then this frame's
+        views and the cull), so a following camera needs no read-back and a replayed graph follows the control entity.
+        The caller writes the block's inputs (CameraBlock.set + upload) whenever they change; the frame copies the view
+        source only after set_camera, since slot 0's pose is now the device's.  camera_index: the rays go through an
+        index of the world's broadphase grid built in the frame (clapgpu_frame.camera_bp) instead of scanning."""
         islands = islands or solve
         self.move, self.move_dt = move, 0.0
         self.aniq = aniq
@@ -61,6 +67,11 @@ class FrameLoop:
         self.prebin = prebin        # CLAPGPU_FRAME_PREBIN: the step bins its boxes for the next frame's broadphase (nothing else writes them)
         self._desc = None
         self.views = None
+        self.camera, self.camera_index = camera, camera_index
+        self._views_dirty = True
+        if camera is not None and not views_dev:
+            from . import _lib
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "FrameLoop", "camera: the camera writes the view block (views_dev=True)")
         if views_dev:
             from .views import ViewBlock
             self.views = ViewBlock(batch.device)
@@ -73,6 +84,7 @@ class FrameLoop:
         self.cam = cam
         if self.views is not None:                          # the source block: the descriptor does not change
             self.views.set_camera(0, cam)
+            self._views_dirty = True
             return
         self.frustum, self.view_mx, self.proj_mx = ent_mod.view_calc_frustum(cam)
         self._desc = None                                   # frustum / matrices are part of the descriptor
@@ -152,9 +164,20 @@ class FrameLoop:
                 if w._meshes is not None:
                     f.meshes = w._meshes
                 f.move, f.move_scratch = C.pointer(self.move._desc), self.move.scratch.data_ptr()
+            if self.camera is not None:                         # the rays' colliders (body geoms: the frame takes the bodies')
+                if not f.static_geoms and w.n_static:
+                    sg = w.static_geoms()
+                    keep.append(sg)
+                    f.static_geoms = C.pointer(sg)
+                if w._meshes is not None:
+                    f.meshes = w._meshes
+                if self.camera_index:
+                    f.camera_bp = w._bp
             if self.body_links is not None:
                 lb, le = w.upload_links(*self.body_links)
                 f.n_body_links, f.link_body, f.link_entity = len(self.body_links[0]), lb.data_ptr(), le.data_ptr()
+        if self.camera is not None:
+            f.camera = self.camera.dev.data_ptr()
         if self.feed is not None:
             f.characters = C.pointer(self.feed._desc)
         if self.views is None:
@@ -228,10 +251,18 @@ class FrameLoop:
         if self.characters is not None:
             self.characters.now_dev.copy_(self._now_host, non_blocking=True)
         if self.views is not None:
-            if getattr(self.batch, "view_matrices", None) is not self._views_seen:
-                self._further_views()
-            self.views.upload()
+            self._upload_views()
         self._graph.replay()
+
+    def _upload_views(self):
+        """The source block's copy ahead of a frame.  With a camera on the device slot 0's pose is the device's from the
+        first frame on: the copy is made only when the host changed the source (set_camera, set_views)."""
+        changed = getattr(self.batch, "view_matrices", None) is not self._views_seen
+        if changed:
+            self._further_views()                            # set_views since the last frame
+        if self.camera is None or self._views_dirty or changed:
+            self.views.upload()
+            self._views_dirty = False
 
     def clap_frame(self, now, dt):
         steps = self.world.phys_step_begin(dt) if self.world is not None else 0
@@ -250,9 +281,7 @@ class FrameLoop:
         f.flags = (1 if self.overlap else 0) | (2 if self.prebin else 0)
         f.move_dt_sec = self.move_dt
         if self.views is not None and now is not None:       # (under capture the copy is the replay's, not a graph node)
-            if getattr(self.batch, "view_matrices", None) is not self._views_seen:
-                self._further_views()                        # set_views since the last frame
-            self.views.upload()
+            self._upload_views()
         rc = _lib.lib().clapgpu_frame_issue(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(f),
                                             0.0 if now is None else float(now), int(steps))
         _lib.check(rc, "clapgpu_frame_issue")

@@ -58,7 +58,7 @@ void clapgpu_test_fail_after(int launches);
 /* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
  * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
  * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
-#define CLAPGPU_ABI_VERSION 49u
+#define CLAPGPU_ABI_VERSION 50u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -1949,9 +1949,10 @@ int clapgpu_animation_queue_time(void *stream, const clapgpu_aniq *q, double now
  * below gives the bits of its twin called with those host values.  Every NaN these functions store is the one quiet NaN
  * 0x7fc00000, on the host and on the device: what an invalid operation (0 * inf of a singular mvp) leaves in the sign and
  * payload of a NaN differs between the two machines and no consumer reads it.
- * The camera controller (camera_update's pull-in rays, camera_target, the cascades' light views) is still the host's:
- * it writes the source.  clapgpu_entities.bv (the bounding-volume pick's camera and control positions) stays
- * host-valued too: it is an argument of the fused update kernel, which the view block does not reach.
+ * The cascades' light views (view.c:195-246) are still the host's: it writes their slots of the source; the main view's
+ * pose can come from the camera controller on the device (clapgpu_camera_calc, ABI 50, below).  clapgpu_entities.bv (the
+ * bounding-volume pick's camera and control positions) stays host-valued too: it is an argument of the fused update
+ * kernel, which the view block does not reach.
  */
 #define CLAPGPU_VIEW_SLOTS (1 + CLAPGPU_EXTRA_VIEWS_MAX)
 #define CLAPGPU_VIEW_FROM_POSE        1u     /* view matrix = clapgpu_view_matrix(pos, quat); view_mx is not read */
@@ -2011,6 +2012,116 @@ int clapgpu_light_grid_compute_views(void *stream, const clapgpu_lights *lights,
                                      uint32_t width, uint32_t height, uint32_t cell, uint32_t *tiles);
 /* clapgpu_particles_update: the billboards' view matrix from slot 0 */
 int clapgpu_particles_update_views(void *stream, const clapgpu_particles *p, const clapgpu_views_state *state);
+
+/* ======================================================================== */
+/* The camera controller on the device (ABI 50)                              */
+/* ======================================================================== */
+
+/*
+ * camera_update (core/camera.c:208-246, called from scene_camera_calc, scene.c:1013) for a camera that follows a control
+ * entity: camera_target, the loop that casts four rays from the target to the near-plane corners of the orbiting camera
+ * and shortens the orbit until none is blocked, and transform_orbit.  camera_move (yaw and pitch from input) stays with
+ * the host: it writes quat.  clapgpu_camera is a block in DEVICE memory, 16-byte aligned; the host writes the inputs,
+ * clapgpu_camera_calc the outputs.
+ *
+ * THE RULE.  clapgpu_camera_calc does camera_update's arithmetic in its order, in fp32 and fp64 exactly where the
+ * reference has them, with no FMA contraction, by the functions the host twins below call (csrc/lm_dev.h), so the block
+ * holds the host's bits; every NaN stored is 0x7fc00000 (as for the view block).
+ *   moved == 0 (camera_has_moved() is false): status = 0 and iterations = 0 are written and nothing else; slot 0 of the
+ *       source is left alone.
+ *   camera_target (camera.c:174-206), for entity ctl_entity of `e`:
+ *       IS_CHARACTER: target = pos_scale.xyz; height = entity3d_aabb_Y = |model box Y| * pos_scale.w (model.c:1190,
+ *           model_table); HAS_HEAD_JOINT: target = joint_pos[head_joint].xyz + (0, height * 0.2f, 0), else
+ *           target.y += height * 0.75f
+ *       otherwise: target = center[ctl_entity], height = aabb_Y / 2.0f
+ *       dist_cap = fmaxf(10.0f, cbrtf(X * Y * Z)); dist = fminf(height * 3.0f, fminf(dist_cap, far_plane - 10.0f))
+ *   the loop (camera.c:232-236, 93-117, 68-91, 51-66), dist a double: while dist > 0.1 --
+ *       the pose is cloned and orbits: pos = quat * (0, 0, (float)dist) + target; the view matrix (clapgpu_view_matrix)
+ *       is inverted; corner[k] = inverse * (+-w, +-h, 0, 1) in the order (w,h) (-w,h) (w,-h) (-w,-h), w = near_plane,
+ *       h = near_plane / aspect; ray k starts at target, has direction corner[k].xyz - target (float) and length
+ *       (double)vec3_len(direction); a hit gives scale = depth / length, min_scale = fmin(...) from 1.0;
+ *       min_scale < 0.99: dist = (double)(float)dist * min_scale (camera_position_is_good takes dist as a float) and
+ *       round again, else stop
+ *   updated = ((double)dist_of_camera_target != dist) (camera.c:238), dist = (float)dist, pos = the final orbit;
+ *   pos and quat are then written into source->slot[0], whose flags must already hold CLAPGPU_VIEW_FROM_POSE; its
+ *   proj_mx and flags are left alone.
+ * THE RAYS are clapgpu_ray_cast's: the same colliders, tie rule and mesh test, with skip = ctl_skip; the result is, bit
+ * for bit, what a host gets by running the loop itself with one clapgpu_ray_cast of four rays (flags asked for) per
+ * iteration.  A ray flagged CLAPGPU_RAY_INVALID is a miss; one flagged CLAPGPU_RAY_UNRESOLVED counts by the hit it
+ * returned and sets CLAPGPU_CAMERA_UNRESOLVED.  ctl_skip == -1 says the control entity has no physics: phys_ray_cast
+ * returns NULL (physics.c:536), no ray is cast and none ever hits.
+ * TERMINATION is unconditional.  A continuing iteration multiplies a finite dist by less than 0.99 and the loop ends at
+ * or below 0.1: at most ln(3.4e39) / -ln(0.99) ~ 9 040 iterations from the largest float.  A NaN dist fails `> 0.1`;
+ * an infinite dist or a NaN quaternion gives non-finite corners, whose rays are INVALID and miss, so the loop stops after
+ * that iteration.  CLAPGPU_CAMERA_ITER_MAX therefore never binds on any input; the loop carries it (here and in
+ * clapgpu_camera_update_host) so that a kernel's end does not rest on an argument about rounding, and reports
+ * CLAPGPU_CAMERA_CAPPED if it ever did.
+ * What the host cannot see before a HIP call it cannot refuse: ctl_entity >= e->n, or HAS_HEAD_JOINT without joint_pos,
+ * is found by the kernel, which then writes status = CLAPGPU_CAMERA_INVALID and iterations = 0 and nothing else.
+ */
+#define CLAPGPU_CAMERA_IS_CHARACTER   1u     /* flags: entity3d_matches(control, ENTITY3D_IS_CHARACTER) */
+#define CLAPGPU_CAMERA_HAS_HEAD_JOINT 2u     /* flags: model3d_get_joint(model, JOINT_HEAD) succeeds */
+#define CLAPGPU_CAMERA_UNRESOLVED     1u     /* status: a ray of some iteration was CLAPGPU_RAY_UNRESOLVED */
+#define CLAPGPU_CAMERA_CAPPED         2u     /* status: the loop was cut at CLAPGPU_CAMERA_ITER_MAX (cannot happen, above) */
+#define CLAPGPU_CAMERA_INVALID        4u     /* status: ctl_entity out of range, or a head joint without joint_pos */
+#define CLAPGPU_CAMERA_ITER_MAX       16384u
+
+typedef struct clapgpu_camera {
+    /* in */
+    float    quat[4];                        /* c->xform.rotation (x y z w), after camera_move */
+    float    pos[3];                         /* in: c->xform.pos (not read: the orbit replaces it); out: the camera position */
+    float    dist;                           /* in: c->dist (not read: camera_target replaces it); out: c->dist */
+    float    near_plane, far_plane, aspect;
+    uint32_t moved;                          /* camera_has_moved() */
+    uint32_t ctl_entity;                     /* index into the frame's clapgpu_entities */
+    int32_t  ctl_skip;                       /* the rays' skip, as clapgpu_ray_cast codes it; -1: the control has no physics */
+    uint32_t flags;                          /* CLAPGPU_CAMERA_IS_CHARACTER | CLAPGPU_CAMERA_HAS_HEAD_JOINT */
+    uint32_t head_joint;                     /* index into the pose batch's joint_pos ([4] floats per joint) */
+    /* out */
+    float    target[3];
+    uint32_t updated;                        /* c->dist != dist, camera.c:238 */
+    float    corner[4][4];                   /* c->frustum_corner of the last iteration (untouched when there was none) */
+    uint32_t iterations, status;             /* calls of camera_position_is_good; CLAPGPU_CAMERA_* */
+    uint32_t pad[2];
+} clapgpu_camera;
+
+#define CLAPGPU_CAMERA_BYTES 160
+#ifdef __cplusplus
+static_assert(sizeof(clapgpu_camera) == CLAPGPU_CAMERA_BYTES, "the camera block's layout is ABI");
+#else
+_Static_assert(sizeof(clapgpu_camera) == CLAPGPU_CAMERA_BYTES, "the camera block's layout is ABI");
+#endif
+
+/* One launch (one workgroup of four wavefronts, a wavefront per corner ray), no allocation, no host synchronisation: it
+ * can be captured.  e: pos_scale, model, model_table and center are read.  joint_pos (may be NULL without a head joint):
+ * the pose batch's WORLD joint positions (clapgpu_pose_batch.joint_pos, behind clapgpu_joint_pos_world where the pose
+ * left model space).  bp, bodies, statics and meshes as clapgpu_ray_cast takes and validates them (bp NULL: every geom
+ * is scanned).  A NULL or misaligned cam or source, a NULL e / bodies / statics or an e without those four arrays:
+ * CLAPGPU_ERR_INVALID_ARGUMENTS before any HIP call. */
+int clapgpu_camera_calc(void *stream, clapgpu_camera *cam, const clapgpu_entities *e, const float *joint_pos,
+                        clapgpu_bp *bp, const clapgpu_geoms *bodies, const clapgpu_geoms *statics,
+                        const clapgpu_trimesh *meshes, clapgpu_views_source *source);
+
+/* The host twins: the kernel's own functions on the host's values (host memory throughout).
+ * clapgpu_camera_target: camera_target from the control entity's pos_scale[4], model box lo[3] / hi[3], world centre[3]
+ * and head joint position head[3] (read when HAS_HEAD_JOINT; may be NULL otherwise) -> target[3], *dist.
+ * clapgpu_camera_rays: one iteration's corners [4][4] and rays [4][8] (as clapgpu_ray_cast takes them) for the pose
+ * quat, target and dist.  clapgpu_camera_decide: from the four rays' answers (hit[k] != 0: a hit at depth[k]) and the
+ * rays cast, *min_scale and *next_dist; returns 1 when the position is good (the loop stops), 0 when the loop goes on
+ * with *next_dist. */
+void clapgpu_camera_target(uint32_t flags, const float pos_scale[4], const float lo[3], const float hi[3], const float center[3],
+                           const float head[3], float far_plane, float target[3], float *dist);
+void clapgpu_camera_rays(const float quat[4], const float target[3], float dist, float near_plane, float aspect,
+                         float corner[16], double ray[32]);
+int clapgpu_camera_decide(float dist, const int32_t hit[4], const double depth[4], const double ray[32], double *min_scale,
+                          double *next_dist);
+/* ... and the whole of camera_update behind camera_target on a HOST copy of the block (target and dist in, as
+ * clapgpu_camera_target left them): the loop with its cap, the final orbit, updated / iterations / status.  cast(user,
+ * ray[32], hit[4], depth[4]) answers one iteration's four rays (hit[k] != 0: a hit; preset to misses) and returns the OR
+ * of their CLAPGPU_RAY_* flags; it is not called when ctl_skip == -1.  moved == 0: as the kernel.  `cast` is a
+ * clapgpu_camera_cast_fn, passed as the object pointer POSIX lets a function pointer travel in. */
+typedef uint32_t (*clapgpu_camera_cast_fn)(void *user, const double *ray, int32_t *hit, double *depth);
+void clapgpu_camera_update_host(clapgpu_camera *cam, void *cast, void *user);
 
 /* ======================================================================== */
 /* One frame (core/clap.c:551-665)                                           */
@@ -2110,6 +2221,18 @@ typedef struct clapgpu_frame {
      * before the replay.  entities->bv stays host-valued */
     const clapgpu_views_source *views_source;  /* device */
     clapgpu_views_state        *views_state;   /* device */
+    /* the camera controller on the device (ABI 50); camera NULL: the frame as before, launch for launch (camera_bp is not
+     * read).  Set: it needs views_source and views_state (CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, before any launch),
+     * and writes slot 0 of views_source.  The rays see body_geoms, or the geoms of bodies when that is NULL, or no body,
+     * and static_geoms, or no static.  The head clapgpu_views_calc stays -- particles and the light grid read it: the
+     * camera the previous frame left, which is the reference's order (scene_update before scene_cameras_calc,
+     * clap.c:614-616) -- and clapgpu_entities_cull_views moves from behind the update to behind the camera: after the
+     * join, clapgpu_joint_pos_world and the light grid the frame issues clapgpu_bp_index(camera_bp, bodies->n,
+     * bodies->aabb) when camera_bp is set (it needs bodies then), clapgpu_camera_calc(camera, entities, pose->joint_pos,
+     * camera_bp, those geoms, meshes, views_source), a second clapgpu_views_calc, the cull, the visible
+     * list with the LOD pick, and skin_select.  Slots 1.. of the source keep what the host wrote */
+    clapgpu_camera             *camera;        /* device */
+    clapgpu_bp                 *camera_bp;     /* may be NULL: the rays scan every geom */
 } clapgpu_frame;
 
 /* Default (0): everything on the caller's stream in the reference's order.  CLAPGPU_FRAME_OVERLAP: the frame's three
