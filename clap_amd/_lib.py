@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 50
+ABI_VERSION = 51
 
 OK = 0
 ERR_NOMEM = -1
@@ -113,6 +113,32 @@ class Camera(C.Structure):
 CAMERA_BYTES = 160                                           # CLAPGPU_CAMERA_BYTES
 assert C.sizeof(Camera) == CAMERA_BYTES
 CAMERA_CAST_FN = C.CFUNCTYPE(C.c_uint32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double))
+
+
+CASCADES_MAX = 4
+CASCADES_Z_REVERSE, CASCADES_NDC_Z_ZERO_ONE, CASCADES_NEAR_BACKUP_FROM_BV = 1, 2, 4
+CASCADES_INVALID = 1
+CASCADES_NO_ENTITY = 0xFFFFFFFF
+
+
+class CascadeView(C.Structure):
+    """clapgpu_cascade_view (include/clapgpu.h): one light sub-view of the cascades block."""
+    _fields_ = [("view_mx", C.c_float * 16), ("inv_view_mx", C.c_float * 16), ("proj_mx", C.c_float * 16),
+                ("inv_proj_mx", C.c_float * 16), ("mvp", C.c_float * 16), ("near_plane", C.c_float), ("far_plane", C.c_float),
+                ("pad", C.c_uint32 * 2)]
+
+
+class Cascades(C.Structure):
+    """clapgpu_cascades (include/clapgpu.h): the shadow cascades' block.  Lives in device memory."""
+    _fields_ = [("light_dir", C.c_float * 3), ("nr_cascades", C.c_uint32), ("persp", C.c_float * 64),
+                ("near_backup", C.c_float), ("light_slot", C.c_uint32), ("flags", C.c_uint32), ("pad0", C.c_uint32),
+                ("cascade", CascadeView * CASCADES_MAX), ("view_mx", C.c_float * 16), ("inv_view_mx", C.c_float * 16),
+                ("near_backup_used", C.c_float), ("bv_entity", C.c_uint32), ("status", C.c_uint32), ("pad1", C.c_uint32),
+                ("cam_corners", C.c_float * 160)]
+
+
+CASCADE_VIEW_BYTES, CASCADES_BYTES = 336, 2416               # CLAPGPU_CASCADE*_BYTES
+assert C.sizeof(CascadeView) == CASCADE_VIEW_BYTES and C.sizeof(Cascades) == CASCADES_BYTES
 
 
 class Entities(C.Structure):
@@ -354,6 +380,7 @@ class FrameDesc(C.Structure):
                 ("move", C.POINTER(CharactersMove)), ("move_dt_sec", C.c_double), ("move_scratch", C.c_void_p),
                 ("aniq", C.POINTER(Aniq)), ("skin_select", C.POINTER(SkinSelect)),
                 ("views_source", C.c_void_p), ("views_state", C.c_void_p),
+                ("cascades", C.c_void_p), ("bv_result", C.c_void_p), ("bv_has_ctl", C.c_uint32), ("bv_ctl_entity", C.c_uint32),
                 ("camera", C.c_void_p), ("camera_bp", C.c_void_p)]
 
 
@@ -369,6 +396,7 @@ STRUCTS = {
     "clapgpu_slide": Slide, "clapgpu_move": CharactersMove, "clapgpu_characters": Characters, "clapgpu_lights": Lights,
     "clapgpu_view_source": ViewSource, "clapgpu_views_source": ViewsSource, "clapgpu_view_state": ViewState,
     "clapgpu_views_state": ViewsState, "clapgpu_camera": Camera,
+    "clapgpu_cascade_view": CascadeView, "clapgpu_cascades": Cascades,
     "clapgpu_solver": Solver, "clapgpu_aniq_entry": AniqEntry, "clapgpu_aniq": Aniq, "clapgpu_frame": FrameDesc,
 }
 
@@ -550,6 +578,13 @@ SYMBOLS = {
     "clapgpu_camera_decide": (C.c_int, [C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "clapgpu_camera_update_host": (None, [C.POINTER(Camera), C.c_void_p, C.c_void_p]),
+    "clapgpu_cascades_calc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Entities), C.c_void_p]),
+    "clapgpu_cascades_calc_host": (None, [C.POINTER(Cascades), C.POINTER(ViewsSource), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                          C.c_float, C.c_int]),
+    "clapgpu_cascades_near_backup": (C.c_float, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float]),
+    "clapgpu_cascades_persp": (None, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_int, C.POINTER(C.c_float)]),
+    "clapgpu_entities_bv_views": (C.c_int, [C.c_void_p, C.POINTER(Entities), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                            C.c_void_p]),
     "clapgpu_entities_cull_views": (C.c_int, [C.c_void_p, C.POINTER(Entities), C.c_void_p]),
     "clapgpu_entities_lod_views": (C.c_int, [C.c_void_p, C.POINTER(Entities), C.c_void_p, C.c_void_p, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -24,6 +24,11 @@
 // clapgpu_bp_index(camera_bp) when an index is asked for, clapgpu_camera_calc (camera.hip: camera_target, the pull-in rays
 // against this frame's colliders, the orbit; it writes slot 0 of the source), a second clapgpu_views_calc, and only then
 // the cull, which therefore moves from behind the update to here, the visible list, the LOD pick and skin_select.
+// With f->cascades (ABI 51) the rest of scene_camera_calc (scene.c:1015-1046) follows the camera there, so the tail takes
+// that shape whether or not f->camera is set: clapgpu_entities_bv_views (default_update's bounding-volume pick, when
+// bv_result is given; ahead of the camera, whose previous position it reads from the head views_calc), the camera,
+// clapgpu_cascades_calc (cascades.hip: the cascade sub-frusta, near_backup, the light's views; it writes the light's slot
+// of the source), the second clapgpu_views_calc, the cull, the list, the LOD pick and skin_select.
 //
 // Round 4: the frame as THREE CHAINS (opt-in: CLAPGPU_FRAME_OVERLAP).  What the reference runs in list order has only these
 // data dependences:
@@ -103,6 +108,8 @@ extern "C" int clapgpu_frame_issue(void *stream, const clapgpu_frame *f, double 
         return CLAPGPU_ERR_INVALID_ARGUMENTS;
     if (f->camera && (!f->views_state || !view_block_ok(f->camera) || (f->camera_bp && !f->bodies)))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;                    // the camera writes the view block's source
+    if (f->cascades && (!f->views_state || !view_block_ok(f->cascades) || !f->entities->views || f->entities->views->n < 1))
+        return CLAPGPU_ERR_INVALID_ARGUMENTS;                    // the fit writes the light's slot of the source
     const bool animated = f->skeleton && f->animations && f->pose;
     const bool particles = f->particles && (f->view_mx || f->views_state);
     const bool overlap = (f->flags & CLAPGPU_FRAME_OVERLAP) && (animated || particles);
@@ -285,7 +292,8 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         FR(clapgpu_entities_update_tiles(stream, e, f->tile_row_start, f->n_tiles, 0, f->frustum));
     else
         FR(clapgpu_entities_update(stream, e, f->level_start, f->n_levels, 0, f->frustum));
-    if (vs && !f->camera)                                        // f->frustum is NULL: the update above did not cull
+    const bool late_views = f->camera || f->cascades;            // scene_cameras_calc on the device: the cull waits for it
+    if (vs && !late_views)                                       // f->frustum is NULL: the update above did not cull
         FR(clapgpu_entities_cull_views(stream, e, vs));
 
     if (overlap) {                                               // join
@@ -303,7 +311,11 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
     else if (f->lights && f->light_tiles && f->view_mx && f->proj_mx)
         FR(clapgpu_light_grid_compute(stream, f->lights, f->view_mx, f->proj_mx, f->light_width, f->light_height, f->light_cell,
                                       f->light_tiles));
-    // ---- scene_cameras_calc (clap.c:616): camera_update on the device, this frame's views, and the cull they wait for ----
+    // ---- scene_cameras_calc (clap.c:616): camera_update and the cascades on the device, this frame's views, and the cull
+    //      they wait for.  The bounding-volume pick is default_update's: it sees the camera the previous frame left (the
+    //      head views_calc's cam_pos) and runs ahead of the camera ----
+    if (f->cascades && f->bv_result)
+        FR(clapgpu_entities_bv_views(stream, e, vs, f->bv_has_ctl, f->bv_ctl_entity, f->bv_result, nullptr));
     if (f->camera) {
         clapgpu_geoms none, from_bodies;
         memset(&none, 0, sizeof(none));
@@ -315,6 +327,10 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         if (f->camera_bp) FR(clapgpu_bp_index(stream, f->camera_bp, f->bodies->n, f->bodies->aabb));
         FR(clapgpu_camera_calc(stream, f->camera, e, animated ? f->pose->joint_pos : nullptr, f->camera_bp, bg ? bg : &none,
                                f->static_geoms ? f->static_geoms : &none, f->meshes, const_cast<clapgpu_views_source *>(f->views_source)));
+    }
+    if (f->cascades)
+        FR(clapgpu_cascades_calc(stream, f->cascades, const_cast<clapgpu_views_source *>(f->views_source), e, f->bv_result));
+    if (late_views) {
         FR(clapgpu_views_calc(stream, f->views_source, f->views_state, 1 + (e->views ? e->views->n : 0)));
         FR(clapgpu_entities_cull_views(stream, e, vs));
     }

@@ -600,4 +600,186 @@ LMD void camera_update(CameraResult &o, const float (&quat)[4], float near_plane
     orbit(o.pos, quat, o.target, o.dist);
 }
 
+// ---- the shadow cascades: scene_camera_calc behind camera_update (scene.c:1021-1046) over view_update_from_frustum
+// (view.c:129-163, 195-246) ----
+// Stated once, here, for k_cascades_calc (cascades.hip) and for the host's clapgpu_cascades_* beside it.  The rule is in
+// include/clapgpu.h ("The shadow cascades on the device").  Intermediate NaNs keep the machine's sign and payload: no
+// comparison reads them, and whatever is stored goes through one_nan.
+constexpr uint32_t CASCADES_Z_REVERSE = 1u, CASCADES_NDC_Z_ZERO_ONE = 2u, CASCADES_NEAR_BACKUP_FROM_BV = 4u;   // CLAPGPU_CASCADES_*
+
+// linmath.h:40-47: p = 0; p += b[i] * a[i]
+LMD float inner3(const float (&a)[3], const float (&b)[3])
+{
+    float p = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; i++) p += b[i] * a[i];
+    return p;
+}
+
+// linmath.h:58-62: k = 1.0 / len in double, rounded to float (r may be v)
+LMD void norm3(float (&r)[3], const float (&v)[3])
+{
+    const float k = (float)(1.0 / (double)sqrtf(inner3(v, v)));
+#pragma unroll
+    for (int i = 0; i < 3; i++) r[i] = v[i] * k;
+}
+
+// linmath.h:63-69: a NaN length is "true"
+LMD void norm3_safe(float (&r)[3], const float (&v)[3])
+{
+    if (sqrtf(inner3(v, v)) != 0.f) {
+        norm3(r, v);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 3; i++) r[i] = v[i];
+    }
+}
+
+// linmath.h:250-255
+LMD void cross3(float (&r)[3], const float (&a)[3], const float (&b)[3])
+{
+    r[0] = a[1] * b[2] - a[2] * b[1];
+    r[1] = a[2] * b[0] - a[0] * b[2];
+    r[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// linmath.h:777-817.  The negated forward vector and eye reach the matrix and translate_in_place as values (the barrier
+// of view_matrix, for its reason: a sum that loses its leading +0 turns a zero translation into -0)
+LMD void look_at(float (&m)[16], const float (&eye)[3], const float (&center)[3], const float (&up)[3])
+{
+    float f[3], s[3], t[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) f[i] = center[i] - eye[i];
+    norm3(f, f);
+    cross3(s, f, up);
+    norm3(s, s);
+    cross3(t, s, f);
+    float nf[3] = { -f[0], -f[1], -f[2] }, ne[3] = { -eye[0], -eye[1], -eye[2] };
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(nf[0]), "+v"(nf[1]), "+v"(nf[2]), "+v"(ne[0]), "+v"(ne[1]), "+v"(ne[2]));
+#endif
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        E_(m, c, 0) = s[c];
+        E_(m, c, 1) = t[c];
+        E_(m, c, 2) = nf[c];
+        E_(m, c, 3) = 0.f;
+    }
+    E_(m, 3, 0) = 0.f; E_(m, 3, 1) = 0.f; E_(m, 3, 2) = 0.f; E_(m, 3, 3) = 1.f;
+    translate_in_place(m, ne[0], ne[1], ne[2]);
+}
+
+// linmath.h:819-833 with up = (0, 1, 0): the literal inner product (inf * 0 is NaN, and NaN > 0.999f is false)
+LMD void look_at_safe(float (&m)[16], const float (&eye)[3], const float (&center)[3])
+{
+    const float up[3] = { 0.f, 1.f, 0.f }, other[3] = { 0.f, 0.f, -1.f };
+    float fw[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) fw[i] = center[i] - eye[i];
+    norm3(fw, fw);
+    const float dp = fabsf(inner3(fw, up));
+    if (dp > 0.999f) look_at(m, eye, center, other);
+    else look_at(m, eye, center, up);
+}
+
+// linmath.h:692-707 (NDC z in [-1, 1]) / 736-751 (NDC z in [0, 1])
+LMD void ortho(float (&M)[16], float l, float r, float b, float t, float n, float f, bool ndc_z_zero_one)
+{
+#pragma unroll
+    for (int i = 0; i < 16; i++) M[i] = 0.f;
+    E_(M, 0, 0) = 2.f / (r - l);
+    E_(M, 1, 1) = 2.f / (t - b);
+    E_(M, 2, 2) = ndc_z_zero_one ? -1.f / (f - n) : -2.f / (f - n);
+    E_(M, 3, 0) = -(r + l) / (r - l);
+    E_(M, 3, 1) = -(t + b) / (t - b);
+    E_(M, 3, 2) = ndc_z_zero_one ? -(n) / (f - n) : -(f + n) / (f - n);
+    E_(M, 3, 3) = 1.f;
+}
+
+// util.c:59-78 over eight vec4 corners (a stride of four floats): (x, y, z, 1) of each, through xlate when given
+// (mat4x4_mul_vec4_post, then * (1.0f / w)), folded from +-INFINITY by min(v, cur) / max(v, cur)
+LMD void corners_box(float (&bb)[6], const float (&corners)[8][4], const float (*xlate)[16])
+{
+    bb[0] = bb[1] = bb[2] = INFINITY;
+    bb[3] = bb[4] = bb[5] = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        float v[4] = { corners[i][0], corners[i][1], corners[i][2], 1.0f };
+        if (xlate) {
+            float q[4];
+            mul_vec4(q, *xlate, v);
+            const float s = 1.0f / q[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++) v[j] = q[j] * s;
+        }
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            bb[j] = tmin(v[j], bb[j]);
+            bb[3 + j] = tmax(v[j], bb[3 + j]);
+        }
+    }
+}
+
+// scene.c:1030-1037 for the bounding volume `env`: its MODEL box and scale (entity3d_aabb_X / Y / Z as camera_target).
+// interp.h:25-29: a * (1.0 - blend) + b * blend -- the complement, the first product and the sum are double, b * blend is
+// a float product
+LMD float near_backup(const float (&light_dir)[3], const float (&lo)[3], const float (&hi)[3], float scale)
+{
+    const float X = fabsf(hi[0] - lo[0]) * scale, Y = fabsf(hi[1] - lo[1]) * scale, Z = fabsf(hi[2] - lo[2]) * scale;
+    const float ex[3] = { 1.f, 0.f, 0.f }, ey[3] = { 0.f, 1.f, 0.f };
+    float d[3];
+    norm3_safe(d, light_dir);
+    const float blend = fabsf(inner3(d, ex));
+    const float xz_mix = (float)((double)Z * (1.0 - (double)blend) + (double)(X * blend));
+    const float ycos = fmaxf(fabsf(inner3(d, ey)), 0.2f);
+    const float q = xz_mix / ycos, edge = cbrtf_glibc(X * Y * Z);
+    return one_nan(q < edge ? q : edge);
+}
+
+// view.c:195-228: the light's view fitted to eight frustum corners
+LMD void cascade_fit(float (&view)[16], float (&inv_view)[16], const float (&corners)[8][4], const float (&light_dir)[3],
+                     float near_backup)
+{
+    float world[6], ctr[3], dir[3], eye[3], m[16], light[6];
+    corners_box(world, corners, nullptr);
+    box_center(ctr, world);
+    ctr[1] = world[1];
+    const float target[3] = { -light_dir[0], -light_dir[1], -light_dir[2] };      // view.c:242
+    norm3_safe(dir, target);
+    near_backup = fmaxf(near_backup, 1.0f);
+#pragma unroll
+    for (int i = 0; i < 3; i++) dir[i] = dir[i] * near_backup;
+#pragma unroll
+    for (int i = 0; i < 3; i++) eye[i] = dir[i] + ctr[i];
+    look_at_safe(m, eye, ctr);
+    corners_box(light, corners, &m);
+    const float len = fabsf(light[2] - light[5]);
+    const float k = (near_backup + len) / near_backup;
+#pragma unroll
+    for (int i = 0; i < 3; i++) dir[i] = dir[i] * k;
+#pragma unroll
+    for (int i = 0; i < 3; i++) eye[i] = dir[i] + ctr[i];
+    look_at_safe(m, eye, ctr);
+    invert(inv_view, m);
+#pragma unroll
+    for (int i = 0; i < 16; i++) { view[i] = one_nan(m[i]); inv_view[i] = one_nan(inv_view[i]); }
+}
+
+// view.c:129-146 (far_factor is 1.0): the cascade's orthographic projection over the camera sub-frustum in light space
+LMD void cascade_projection(float (&proj)[16], float (&inv_proj)[16], float (&mvp)[16], float &far_plane,
+                            const float (&view)[16], const float (&corners)[8][4], uint32_t flags)
+{
+    float bb[6];
+    corners_box(bb, corners, &view);
+    const float near_plane = 0.1f, far = -bb[2] * 1.0f;
+    const bool z01 = (flags & CASCADES_NDC_Z_ZERO_ONE) != 0;
+    if (flags & CASCADES_Z_REVERSE) ortho(proj, bb[0], bb[3], bb[1], bb[4], far, near_plane, z01);
+    else ortho(proj, bb[0], bb[3], bb[1], bb[4], near_plane, far, z01);
+    invert(inv_proj, proj);
+    mul(mvp, proj, view);
+    far_plane = one_nan(far);
+#pragma unroll
+    for (int i = 0; i < 16; i++) { proj[i] = one_nan(proj[i]); inv_proj[i] = one_nan(inv_proj[i]); mvp[i] = one_nan(mvp[i]); }
+}
+
 } // namespace lmd

@@ -206,6 +206,15 @@ class EntityBatch:
         rc = _lib.lib().clapgpu_entities_cull_views(_stream(), C.byref(self._desc), _ptr(views.state))
         _lib.check(rc, "clapgpu_entities_cull_views")
 
+    def bv_views(self, views, ctl_entity=None, result=None, inside_mask=None):
+        """default_update's bounding-volume pick over the boxes the last update stored, with the camera position read
+        from slot 0 of a views.ViewBlock's state and the control entity's from pos_scale (clapgpu_entities_bv_views).
+        result: a device int64 tensor of one key (as set_bv_query's bv_result), inside_mask: n / 64 int64 words."""
+        rc = _lib.lib().clapgpu_entities_bv_views(_stream(), C.byref(self._desc), _ptr(views.state),
+                                                  0 if ctl_entity is None else 1, 0 if ctl_entity is None else int(ctl_entity),
+                                                  _ptr(result), _ptr(inside_mask))
+        _lib.check(rc, "clapgpu_entities_bv_views")
+
     def compact_visible(self, index_base=0, two_pass=False):
         """Build the ascending visible-index list on the device (visible[:visible_count]).
         two_pass forces the large-n path (no per-row popcounts)."""

@@ -20,7 +20,8 @@ from . import entities as ent_mod
 class FrameLoop:
     def __init__(self, batch, cam, world=None, feed=None, body_links=None, lights=None, characters=None,
                  particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False, solve=False,
-                 move=None, aniq=None, skin_select=None, views_dev=False, camera=None, camera_index=False):
+                 move=None, aniq=None, skin_select=None, views_dev=False, camera=None, camera_index=False, cascades=None,
+                 bv_result=None, bv_ctl_entity=None):
         """batch: EntityBatch.  world: PhysWorld (dynamic bodies write their entities through
         body_entity; character bodies have body_entity = -1).  feed: CharacterFeed.  body_links:
         (link_body, link_entity) of characters / static colliders whose rotation follows the entity.
@@ -53,7 +54,16 @@ class FrameLoop:
         views and the cull), so a following camera needs no read-back and a replayed graph follows the control entity.
         The caller writes the block's inputs (CameraBlock.set + upload) whenever they change; the frame copies the view
         source only after set_camera, since slot 0's pose is now the device's.  camera_index: the rays go through an
-        index of the world's broadphase grid built in the frame (clapgpu_frame.camera_bp) instead of scanning."""
+        index of the world's broadphase grid built in the frame (clapgpu_frame.camera_bp) instead of scanning.
+        cascades: a cascades.CascadesBlock (needs views_dev and a further view of the batch in the block's light_slot):
+        the shadow light's views are fitted to the camera's cascade sub-frusta on the device behind the camera
+        (clapgpu_frame.cascades), the light's main view goes into its slot of the view source and the shadow planes are
+        culled against it, so the light follows the camera without a read-back, replayed graphs included.  The caller
+        writes the block's inputs (CascadesBlock.set + upload) whenever they change.  From the first frame on the light's
+        slot of the source is the device's: later copies of the source leave it out.  bv_result: a device int64 tensor
+        of one key: the frame runs default_update's bounding-volume pick (clapgpu_entities_bv_views, with bv_ctl_entity
+        as the control entity or None) ahead of the camera and the cascades read it when their block asks for
+        near_backup from the volume."""
         islands = islands or solve
         self.move, self.move_dt = move, 0.0
         self.aniq = aniq
@@ -69,6 +79,11 @@ class FrameLoop:
         self.views = None
         self.camera, self.camera_index = camera, camera_index
         self._views_dirty = True
+        self.cascades, self.bv_result, self.bv_ctl_entity = cascades, bv_result, bv_ctl_entity
+        self._light_slot_sent = False
+        if cascades is not None and not views_dev:
+            from . import _lib
+            raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "FrameLoop", "cascades: the fit writes the view block (views_dev=True)")
         if camera is not None and not views_dev:
             from . import _lib
             raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "FrameLoop", "camera: the camera writes the view block (views_dev=True)")
@@ -178,6 +193,12 @@ class FrameLoop:
                 f.n_body_links, f.link_body, f.link_entity = len(self.body_links[0]), lb.data_ptr(), le.data_ptr()
         if self.camera is not None:
             f.camera = self.camera.dev.data_ptr()
+        if self.cascades is not None:
+            f.cascades = self.cascades.dev.data_ptr()
+            if self.bv_result is not None:
+                f.bv_result = self.bv_result.data_ptr()
+                f.bv_has_ctl = 0 if self.bv_ctl_entity is None else 1
+                f.bv_ctl_entity = 0 if self.bv_ctl_entity is None else int(self.bv_ctl_entity)
         if self.feed is not None:
             f.characters = C.pointer(self.feed._desc)
         if self.views is None:
@@ -261,7 +282,15 @@ class FrameLoop:
         if changed:
             self._further_views()                            # set_views since the last frame
         if self.camera is None or self._views_dirty or changed:
-            self.views.upload()
+            if self.cascades is not None and self._light_slot_sent and not changed:   # the light's slot is the device's
+                from . import _lib
+                words = _lib.VIEWS_SOURCE_BYTES // _lib.VIEW_SLOTS // 4
+                at = int(self.cascades.host[0]["light_slot"]) * words
+                self.views.source[:at].copy_(self.views.host[:at], non_blocking=True)
+                self.views.source[at + words:].copy_(self.views.host[at + words:], non_blocking=True)
+            else:
+                self.views.upload()
+                self._light_slot_sent = True
             self._views_dirty = False
 
     def clap_frame(self, now, dt):

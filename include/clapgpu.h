@@ -58,7 +58,7 @@ void clapgpu_test_fail_after(int launches);
 /* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
  * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
  * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
-#define CLAPGPU_ABI_VERSION 50u
+#define CLAPGPU_ABI_VERSION 51u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -1949,10 +1949,10 @@ int clapgpu_animation_queue_time(void *stream, const clapgpu_aniq *q, double now
  * below gives the bits of its twin called with those host values.  Every NaN these functions store is the one quiet NaN
  * 0x7fc00000, on the host and on the device: what an invalid operation (0 * inf of a singular mvp) leaves in the sign and
  * payload of a NaN differs between the two machines and no consumer reads it.
- * The cascades' light views (view.c:195-246) are still the host's: it writes their slots of the source; the main view's
- * pose can come from the camera controller on the device (clapgpu_camera_calc, ABI 50, below).  clapgpu_entities.bv (the
- * bounding-volume pick's camera and control positions) stays host-valued too: it is an argument of the fused update
- * kernel, which the view block does not reach.
+ * The main view's pose can come from the camera controller on the device (clapgpu_camera_calc, ABI 50, below) and the
+ * shadow light's view from the cascades' fit (clapgpu_cascades_calc, ABI 51, below); the spotlights' views stay pose
+ * slots the host writes.  clapgpu_entities.bv (the bounding-volume pick's camera and control positions) is an argument
+ * of the fused update kernel, which the view block does not reach: clapgpu_entities_bv_views is its twin over the block.
  */
 #define CLAPGPU_VIEW_SLOTS (1 + CLAPGPU_EXTRA_VIEWS_MAX)
 #define CLAPGPU_VIEW_FROM_POSE        1u     /* view matrix = clapgpu_view_matrix(pos, quat); view_mx is not read */
@@ -2124,6 +2124,128 @@ typedef uint32_t (*clapgpu_camera_cast_fn)(void *user, const double *ray, int32_
 void clapgpu_camera_update_host(clapgpu_camera *cam, void *cast, void *user);
 
 /* ======================================================================== */
+/* The shadow cascades on the device (ABI 51)                                */
+/* ======================================================================== */
+
+/*
+ * What scene_camera_calc (scene.c:1004-1048) does behind camera_update: the camera's cascade sub-frusta
+ * (view_update_perspective_subviews, view.c:11-37), near_backup from the bounding volume this frame's default_update
+ * picked (scene.c:1021-1038, model.c:1703-1713), and the shadow light's views fitted to those frusta
+ * (view_update_from_frustum, view.c:195-246, 129-163).  clapgpu_cascades is a block in DEVICE memory, 16-byte aligned;
+ * the host writes the inputs, clapgpu_cascades_calc the outputs.  The inputs change with the window, the light and the
+ * render options, not with the camera: a frame whose camera is the device's needs no host between the camera and the
+ * shadow passes' cull, and a replayed graph's light view follows its camera.
+ *
+ * THE RULE.  clapgpu_cascades_calc does that arithmetic in the reference's order, in fp32 and fp64 exactly where the
+ * reference has them, with no FMA contraction, by the functions the host twins below call (csrc/lm_dev.h), so the block
+ * holds the host's bits; every NaN stored is 0x7fc00000 (as for the view block).  nr = nr_cascades, 0 meaning 4.
+ *   the camera's view matrix: slot 0 of `source` -- clapgpu_view_matrix(pos, quat) when its flags hold
+ *       CLAPGPU_VIEW_FROM_POSE, else its view_mx.
+ *   cam_corners[v], v < nr: the corners of clapgpu_frustum_calc(that matrix, persp[v], NDC_Z_ZERO_ONE); cam_corners[4]:
+ *       those of the main frustum, with slot 0's own proj_mx.  persp[] is the host's (clapgpu_cascades_persp): the
+ *       reference's mat4x4_perspective takes 1 / tan(fov / 2) through libm in double, which the device does not
+ *       reproduce bit for bit, and the four matrices change only with the window.  No libm function is called.
+ *   near_backup: the input field, or with NEAR_BACKUP_FROM_BV the value of scene.c:1030-1037 for the entity `env` of
+ *       *bv_result (the key of clapgpu_bv_query: 0 = no volume, near_backup 0; else env = 0xFFFFFFFF - low word):
+ *       X / Y / Z = |model box edge| * pos_scale.w (as camera_target); d = vec3_norm_safe(light_dir);
+ *       xz_mix = linf_interp(Z, X, fabsf(d . (1,0,0))) with the blend's complement and the sum in double;
+ *       ycos = fmaxf(fabsf(d . (0,1,0)), 0.2f); near_backup = min(xz_mix / ycos, cbrtf(X * Y * Z)), min the ternary
+ *       a < b ? a : b.  The inner products are the literal sums with their zero factors (inf * 0 is NaN, as there).
+ *   each fit (subview_update_from_target), once per cascade v < nr from cam_corners[v] and once for the light's main
+ *       view from cam_corners[4]: the world box of the eight corners from +-INFINITY by min(v, cur) / max(v, cur) as
+ *       ternaries; light_pos = aabb_center with y = the box's lowest; target = -light_dir through vec3_norm_safe, scaled
+ *       by fmaxf(near_backup, 1.0f); mat4x4_look_at_safe(light_pos + that, light_pos, (0,1,0)) -- the up vector becomes
+ *       (0,0,-1) where |forward . up| > 0.999f, vec3_norm takes 1.0 / len in double; the light-space box of the corners
+ *       under that matrix (mat4x4_mul_vec4_post, then * (1.0f / w)); the direction is scaled again by (near_backup +
+ *       |z extent|) / near_backup, the second look_at gives view_mx, mat4x4_invert inv_view_mx.
+ *   each cascade's projection (subview_projection_update): the light-space box of cam_corners[v] under view_mx;
+ *       near_plane = 0.1f, far_plane = -box.min.z; mat4x4_ortho_ndc_z_1 (NDC_Z_ZERO_ONE) or _2 over the box's x and y
+ *       with (near, far), or (far, near) under Z_REVERSE; inv_proj_mx = mat4x4_invert; mvp = proj_mx * view_mx
+ *       (UNIFORM_SHADOW_MVP, model.c:864-869; far_plane is UNIFORM_LIGHT_FAR).
+ *   the light's main view_mx is also written into source->slot[light_slot].view_mx; that slot's proj_mx, pos and flags
+ *       are left alone (view_update_from_frustum never writes light.view[0].main.proj_mx either).
+ * The reference fits every view->subview[] whatever nr_cascades is; nothing reads the surplus ones, and the device leaves
+ * cascade[v], and cam_corners[v], for nr <= v < 4 untouched.  The light sub-views' own frusta (view.c:145) are read by the
+ * debug UI alone and are not produced.
+ * What the host cannot see before a HIP call it cannot refuse: the flags, light_slot and nr_cascades live in the device
+ * block.  A light_slot outside 1 .. CLAPGPU_VIEW_SLOTS - 1, a light slot whose flags hold CLAPGPU_VIEW_FROM_POSE, an
+ * nr_cascades above 4, and with NEAR_BACKUP_FROM_BV a NULL bv_result or a key naming an entity at or past e->n: the
+ * kernel writes status = CLAPGPU_CASCADES_INVALID and nothing else.
+ */
+#define CLAPGPU_CASCADES_MAX                  4      /* CASCADES_MAX, shader_constants.h:9 */
+#define CLAPGPU_CASCADES_Z_REVERSE            1u     /* flags: the z_reverse of view.c:137 (!shadow_vsm) */
+#define CLAPGPU_CASCADES_NDC_Z_ZERO_ONE       2u     /* flags: renderer_get_caps()->ndc_z_zero_one */
+#define CLAPGPU_CASCADES_NEAR_BACKUP_FROM_BV  4u     /* flags: near_backup from *bv_result, not from the field */
+#define CLAPGPU_CASCADES_INVALID              1u     /* status */
+#define CLAPGPU_CASCADES_NO_ENTITY            0xFFFFFFFFu
+
+typedef struct clapgpu_cascade_view {        /* one light sub-view, out */
+    float    view_mx[16], inv_view_mx[16], proj_mx[16], inv_proj_mx[16];
+    float    mvp[16];                        /* proj_mx * view_mx */
+    float    near_plane, far_plane;
+    uint32_t pad[2];
+} clapgpu_cascade_view;
+
+typedef struct clapgpu_cascades {
+    /* in */
+    float    light_dir[3];                   /* s->light.dir[0..2] */
+    uint32_t nr_cascades;                    /* 1 .. 4; 0: 4 */
+    float    persp[CLAPGPU_CASCADES_MAX][16];/* the camera sub-frusta's projections (view.c:33): clapgpu_cascades_persp */
+    float    near_backup;                    /* used unless NEAR_BACKUP_FROM_BV */
+    uint32_t light_slot;                     /* 1 .. CLAPGPU_VIEW_SLOTS - 1: the source slot of the light's main view */
+    uint32_t flags;                          /* CLAPGPU_CASCADES_* */
+    uint32_t pad0;
+    /* out */
+    clapgpu_cascade_view cascade[CLAPGPU_CASCADES_MAX];
+    float    view_mx[16], inv_view_mx[16];   /* the light's main view */
+    float    near_backup_used;               /* scene.c's near_backup, before the fit's fmaxf(.., 1.0f) */
+    uint32_t bv_entity;                      /* the entity of *bv_result, or CLAPGPU_CASCADES_NO_ENTITY */
+    uint32_t status;                         /* 0 or CLAPGPU_CASCADES_INVALID */
+    uint32_t pad1;
+    float    cam_corners[CLAPGPU_CASCADES_MAX + 1][8][4];    /* the camera's sub-frusta's corners, [4]: the main frustum's */
+} clapgpu_cascades;
+
+#define CLAPGPU_CASCADE_VIEW_BYTES 336
+#define CLAPGPU_CASCADES_BYTES     2416
+#ifdef __cplusplus
+static_assert(sizeof(clapgpu_cascade_view) == CLAPGPU_CASCADE_VIEW_BYTES && sizeof(clapgpu_cascades) == CLAPGPU_CASCADES_BYTES,
+              "the cascades block's layout is ABI");
+#else
+_Static_assert(sizeof(clapgpu_cascade_view) == CLAPGPU_CASCADE_VIEW_BYTES && sizeof(clapgpu_cascades) == CLAPGPU_CASCADES_BYTES,
+               "the cascades block's layout is ABI");
+#endif
+
+/* One launch (one wavefront, a lane per fit), no allocation, no host synchronisation: it can be captured.  e: pos_scale,
+ * model and model_table are read when the key of *bv_result names an entity.  bv_result (device; may be NULL without
+ * NEAR_BACKUP_FROM_BV): what clapgpu_entities_bv_views or the update's fused pick left.  A NULL or misaligned c or source,
+ * a NULL e, or a bv_result next to an e without those three arrays: CLAPGPU_ERR_INVALID_ARGUMENTS before any HIP call. */
+int clapgpu_cascades_calc(void *stream, clapgpu_cascades *c, clapgpu_views_source *source, const clapgpu_entities *e,
+                          const uint64_t *bv_result);
+
+/* The host twins: the kernel's own functions on the host's values (host memory throughout).
+ * clapgpu_cascades_calc_host: the whole of clapgpu_cascades_calc on HOST copies of the block and the source.  The bounding
+ * volume is given by value: has_env == 0 is the key 0; else env's MODEL box and scale (near_backup is read from the field
+ * without NEAR_BACKUP_FROM_BV, as in the kernel); bv_entity is then set to 0, which the caller overwrites with the entity
+ * it meant.  clapgpu_cascades_near_backup: scene.c:1030-1037 alone.  clapgpu_cascades_persp: persp[] of the block from the
+ * main view's fov, aspect, near and far planes by the splits of view.c:13-26 (15, 50, 150, then far) and
+ * clapgpu_perspective. */
+void clapgpu_cascades_calc_host(clapgpu_cascades *c, clapgpu_views_source *source, const float env_box_lo[3],
+                                const float env_box_hi[3], float env_scale, int has_env);
+float clapgpu_cascades_near_backup(const float light_dir[3], const float env_box_lo[3], const float env_box_hi[3], float env_scale);
+void clapgpu_cascades_persp(float fov, float aspect, float near_plane, float far_plane, uint32_t nr_cascades, int ndc_z_zero_one,
+                            float persp[64]);
+
+/* The bounding-volume pick with its positions in device memory: the twin of the pick the fused update does for
+ * clapgpu_entities.bv, as a pass of its own over the boxes the update stored (it stands to the update as
+ * clapgpu_entities_cull_views stands to the fused cull).  The camera position is state->slot[0].cam_pos, the control
+ * position e->pos_scale[ctl_entity].xyz, read by the kernel; ctl_entity >= e->n with has_ctl set: no control.  *result
+ * (cleared on the stream first) and inside_mask get the bits the fused pick gives when clapgpu_bv_query holds those two
+ * positions; result may be NULL when inside_mask is given; both NULL: nothing is asked for and nothing is launched.  e:
+ * flags, aabb, model, model_table and pos_scale are read.  One launch, one wavefront per 64 entities; it can be captured. */
+int clapgpu_entities_bv_views(void *stream, const clapgpu_entities *e, const clapgpu_views_state *state, uint32_t has_ctl,
+                              uint32_t ctl_entity, uint64_t *result, uint64_t *inside_mask);
+
+/* ======================================================================== */
 /* One frame (core/clap.c:551-665)                                           */
 /* ======================================================================== */
 
@@ -2218,9 +2340,25 @@ typedef struct clapgpu_frame {
      * particles and the LOD pick use their *_views twins.  frustum (NULL), view_mx, proj_mx, cam_pos and
      * entities->views->frustum[] are not read, and "the frame has a main view" (visible list, LOD pick, skin_select)
      * means frustum || views_state.  A replayed graph of such a frame follows whatever was written into views_source
-     * before the replay.  entities->bv stays host-valued */
+     * before the replay.  entities->bv stays host-valued (its twin over the block: bv_result, below) */
     const clapgpu_views_source *views_source;  /* device */
     clapgpu_views_state        *views_state;   /* device */
+    /* the shadow cascades on the device (ABI 51); cascades NULL: the frame as before, launch for launch (the three fields
+     * behind it are not read).  Set: it needs views_source, views_state and entities->views with n >= 1 (the light's
+     * slot; light_slot itself lives in the device block: a slot the frame's views do not reach is fitted and not culled):
+     * CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, before any launch.  The tail of the frame takes the camera frame's shape
+     * whether or not `camera` is set -- the head clapgpu_views_calc stays, the update runs without its cull -- and
+     * behind the join, clapgpu_joint_pos_world and the light grid the frame issues, in this order:
+     * clapgpu_entities_bv_views(entities, views_state, bv_has_ctl, bv_ctl_entity, bv_result, NULL) when bv_result is set
+     * (the flag that asks for the volume lives in the device block, so "bv_result set" means "the frame runs the pick";
+     * it reads the head's cam_pos, the camera the previous frame left, which is the position default_update sees:
+     * scene_update runs before scene_cameras_calc); clapgpu_bp_index and clapgpu_camera_calc when `camera` is set;
+     * clapgpu_cascades_calc(cascades, views_source, entities, bv_result); the second clapgpu_views_calc over all slots;
+     * clapgpu_entities_cull_views, the visible list with the LOD pick, and skin_select.  bv_has_ctl / bv_ctl_entity are
+     * host values: camera->ctl_entity is in device memory */
+    clapgpu_cascades           *cascades;      /* device */
+    uint64_t                   *bv_result;     /* device, or NULL: no pick */
+    uint32_t                    bv_has_ctl, bv_ctl_entity;
     /* the camera controller on the device (ABI 50); camera NULL: the frame as before, launch for launch (camera_bp is not
      * read).  Set: it needs views_source and views_state (CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, before any launch),
      * and writes slot 0 of views_source.  The rays see body_geoms, or the geoms of bodies when that is NULL, or no body,
