@@ -82,6 +82,21 @@ def lib():
     return _lib
 
 
+SECOND_BUILD_NAMES = ("clapo_light_radius", "clapo_light_grid_dims", "clapo_light_grid_compute", "clapo_lights_from_entities",
+                      "clapo_particles_spawn", "clapo_particles_update", "clapo_particles_billboard")
+
+
+def second_build(path, names=SECOND_BUILD_NAMES):
+    """A second build of some of the restatement's sources (say, light.c and particles.c compiled with other floating-point
+    flags) opened beside the normal one: a plain CDLL whose functions get the normal library's prototypes.  Hand it to
+    light_grid_compute / particles_update as `L`; the tests use it to show that they can fail."""
+    L2, L = C.CDLL(path), lib()
+    for name in names:
+        f, f2 = getattr(L, name), getattr(L2, name)
+        f2.argtypes, f2.restype = f.argtypes, f.restype
+    return L2
+
+
 def _declare(L):
     L.clapo_view_matrix.argtypes = [F32P, F32P, F32P]
     L.clapo_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, F32P]
@@ -243,11 +258,11 @@ def particles_spawn(ps, rng_state):
     return pos, vel, st.value
 
 
-def particles_update(ps, pos, vel, rng_state):
-    """One frame in place.  Returns (respawn count, new rng state)."""
+def particles_update(ps, pos, vel, rng_state, L=None):
+    """One frame in place.  Returns (respawn count, new rng state).  L: a second_build() to run instead of the normal one."""
     st = C.c_uint64(rng_state)
     sys = np.ascontiguousarray(ps["sys"])
-    k = lib().clapo_particles_update(sys.ctypes.data, sys.shape[0], pos, vel, C.byref(st))
+    k = (L or lib()).clapo_particles_update(sys.ctypes.data, sys.shape[0], pos, vel, C.byref(st))
     return k, st.value
 
 
@@ -511,11 +526,12 @@ def light_radius(color, attenuation, is_dir=False):
                                           np.ascontiguousarray(attenuation, np.float32), int(is_dir)))
 
 
-def light_grid_compute(lights, view_mx, proj_mx, width, height, cell):
-    """lights: dict from clap_amd.synth.lights().  Returns tiles u32[theight][twidth][4]."""
+def light_grid_compute(lights, view_mx, proj_mx, width, height, cell, L=None):
+    """lights: dict from clap_amd.synth.lights().  Returns tiles u32[theight][twidth][4].  L: a second_build() to run
+    instead of the normal one."""
     tw, th = light_grid_dims(width, height, cell)
     tiles = np.zeros((th, tw, 4), np.uint32)
-    lib().clapo_light_grid_compute(int(lights["nr_lights"]), np.ascontiguousarray(lights["active"], np.uint32),
+    (L or lib()).clapo_light_grid_compute(int(lights["nr_lights"]), np.ascontiguousarray(lights["active"], np.uint32),
                                    np.ascontiguousarray(lights["is_dir"], np.int32),
                                    np.ascontiguousarray(lights["pos"], np.float32),
                                    np.ascontiguousarray(lights["color"], np.float32),

@@ -32,7 +32,7 @@
  * Usage: clap_ref <command> <in.clpio> <out.clpio>
  *   entities   default_update x frames, then view_entity_in_frustum
  *   pose       channels_transform + one_joint_transform per character
- *   particles  particles_update x frames (drand48 stream from a given state)
+ *   particles  particles_update x frames (drand48 stream from a given state; optional pos0 / vel0 to start from)
  *   bench_entities   time default_update + view_entity_in_frustum
  *   lod        entity3d_aabb_avg_edge + entity3d_set_lod
  *   lightgrid  light_grid_compute: lights x screen tiles -> RGBA32UI masks
@@ -443,6 +443,23 @@ static int cmd_particles(struct arrset *in, struct arrset *out)
             memcpy(o_vel0 + 3 * (off + i), p->velocity, 12);
         }
         off += ps[s].count;
+    }
+    if (arr_has(in, "pos0")) {                             /* chosen start: the spawned particles are moved there */
+        float *pos0 = arr_get(in, "pos0", NULL), *vel0 = arr_get(in, "vel0", NULL);   /* [total][3], list order */
+        off = 0;
+        for (uint32_t s = 0; s < n_sys; s++) {
+            particle *p;
+            uint64_t i = 0;
+            list_for_each_entry(p, &ps[s].particles, entry) {
+                memcpy(p->pos, pos0 + 3 * (off + i), 12);
+                memcpy(p->velocity, vel0 + 3 * (off + i), 12);
+                vec3_dup(ps[s].pos_array[i], p->pos);
+                i++;
+            }
+            off += ps[s].count;
+        }
+        memcpy(o_pos0, pos0, total * 12);
+        memcpy(o_vel0, vel0, total * 12);
     }
     {
         unsigned short z[3] = { 0, 0, 0 }, *old = seed48(z);

@@ -49,12 +49,32 @@ def test_oracle_matches_reference_fixture(name, golden_dir):
     assert 2 < set_bits < 100, "the fixture exercises both outcomes of the disc test"
 
 
+def _edge_cases():
+    """The chosen cases of tests/lightcases.py, families 1-4: disc edges, gate edges, degenerate radii, slots and words"""
+    import lightcases as lc
+    cases = [c for near, far, _found in lc.disc_edge_pairs() for c in (near, far)]
+    return cases + [c for c, _info in lc.gate_cases()] + list(lc.radius_cases()) + list(lc.slot_cases())
+
+
 @pytest.mark.skipif(not refrun.available(), reason="reference build (oracle/_ref) not present")
-@pytest.mark.parametrize("seed", range(6))
-def test_oracle_matches_reference_live(seed):
-    lights, cam, w, h, cell = _random_case(100 + seed)
-    tiles, _rad, vm, pm = refrun.lightgrid(lights, cam, w, h, cell)
-    assert np.array_equal(ob.light_grid_compute(lights, vm, pm, w, h, cell), tiles)
+@pytest.mark.parametrize("which", list(range(6)) + ["disc", "gate", "radius", "lone", "nr_lights", "dir", "released"])
+def test_oracle_matches_reference_live(which):
+    if isinstance(which, int):
+        lights, cam, w, h, cell = _random_case(100 + which)
+        tiles, _rad, vm, pm = refrun.lightgrid(lights, cam, w, h, cell)
+        assert np.array_equal(ob.light_grid_compute(lights, vm, pm, w, h, cell), tiles)
+        return
+    cases = [c for c in _edge_cases() if c["name"].startswith(which)]
+    assert cases
+    for c in cases:
+        L = c["lights"]
+        tiles, rad, vm, pm = refrun.lightgrid(L, c["cam"], c["width"], c["height"], c["cell"])
+        for mine, theirs in ((c["view"], vm), (c["proj"], pm)):
+            assert np.array_equal(mine.view(np.uint32), theirs.view(np.uint32)), f"{c['name']}: built under the reference's matrices"
+        assert np.array_equal(ob.light_grid_compute(L, vm, pm, c["width"], c["height"], c["cell"]), tiles), c["name"]
+        mine = np.asarray([ob.light_radius(L["color"][i], L["attenuation"][i], L["is_dir"][i]) for i in range(L["nr_lights"])], np.float32)
+        assert np.array_equal(np.isnan(mine), np.isnan(rad)) and np.array_equal(mine[~np.isnan(mine)], rad[~np.isnan(rad)]), \
+            f"{c['name']}: light_get_radius"
 
 
 def test_oracle_edge_cases():

@@ -86,11 +86,24 @@ def multi_frame(scene, seed, n_frames=3, dirty_frac=0.2):
     return frames
 
 
-def particle_fixture(name, ps, frames, view_mx, state=synth.DRAND48_DEFAULT_STATE):
-    ref = refrun.particles(ps, view_mx, state, frames)
+def particle_fixture(name, ps, frames, view_mx, state=synth.DRAND48_DEFAULT_STATE, pos0=None, vel0=None):
+    """pos0 / vel0: where the reference's particles are put after it spawned them (a chosen start); in_start_chosen says so."""
+    ref = refrun.particles(ps, view_mx, state, frames, pos0, vel0)
     save(name, in_sys=ps["sys"], in_row_sys=ps["row_sys"], in_n=np.asarray([ps["n"], ps["n_real"]], np.uint32),
          in_view_mx=np.asarray(view_mx, np.float32), in_rng_state=np.asarray([state], np.uint64),
-         **{"ref_" + k: v for k, v in ref.items()})
+         in_start_chosen=np.asarray([pos0 is not None], np.uint8), **{"ref_" + k: v for k, v in ref.items()})
+
+
+def light_edges_fixture(name, cases):
+    """Several 128-slot light cases (tests/lightcases.py) in one file, stacked along a leading axis: in_<field>[k], in_grid[k]
+    = (width, height, cell), the reference's own matrices ref_view_mx[k] / ref_proj_mx[k], and its tiles one case after
+    the other in ref_tiles[sum of tiles][4].  Inputs and recorded tiles only."""
+    ref = [refrun.lightgrid(c["lights"], c["cam"], c["width"], c["height"], c["cell"]) for c in cases]
+    d = {"in_" + f: np.stack([np.asarray(c["lights"][f]) for c in cases]) for f in ("pos", "color", "attenuation", "is_dir", "active")}
+    save(name, names=np.asarray(",".join(c["name"] for c in cases)),
+         in_grid=np.asarray([[c["width"], c["height"], c["cell"]] for c in cases], np.uint32),
+         ref_view_mx=np.stack([r[2] for r in ref]), ref_proj_mx=np.stack([r[3] for r in ref]),
+         ref_tiles=np.concatenate([r[0].reshape(-1, 4) for r in ref]), **d)
 
 
 SK_KEYS = ("parent", "invmx", "root_pose", "order")
@@ -172,6 +185,12 @@ def main():
     for dist, nm in ((synth.PART_DIST_CBRT, "cbrt"), (synth.PART_DIST_POW075, "pow075")):
         particle_fixture("particles_" + nm, synth.particle_systems(n_sys=3, count=100, radius=2.0, velocity=0.6,
                                                                     dist=dist, seed=6), 4, view)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import lightcases
+    import partcases
+    edge = partcases.fixture_case()                         # 256 and 257 respawns in one wave each, and dd == radius^2
+    particle_fixture("particles_edges_wave", edge["ps"], 2, view, state=partcases.STATE0, pos0=edge["pos"], vel0=edge["vel"])
+    light_edges_fixture("lightgrid_edges", lightcases.fixture_cases())
     for nm, skw, akw in (("pose_full", dict(), dict()),
                          ("pose_ragged", dict(unreachable=4), dict(missing_frac=0.3, ragged=True))):
         sk = synth.skeleton(24, 6, seed=8, **skw)
