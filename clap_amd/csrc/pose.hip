@@ -589,8 +589,9 @@ static int pose_launch(hipStream_t s, PoseArgs &a, bool missing, bool times_lds,
         if (v > 0 && (uint32_t)v < blocks) blocks = (uint32_t)v;
     }
     if (getenv("CLAPGPU_POSE_DEBUG"))
-        fprintf(stderr, "k_pose<%d, %d>: %u blocks resident (%u per CU), static LDS %zu + dynamic %u, %u program passes\n", LPC, BLOCK,
-                k.res, k.res / (uint32_t)d.n_cus, k.stat, dyn, want);
+        fprintf(stderr, "k_pose<%d, %d>: %u blocks resident (%u per CU), static LDS %zu + dynamic %u, %u program passes, "
+                "MISSING %d, TIMES_LDS %d, kp %u\n", LPC, BLOCK, k.res, k.res / (uint32_t)d.n_cus, k.stat, dyn, want,
+                (slot >> 1) & 1, slot & 1, a.pk_kp);
     void *args[] = { &a };
     (void)hipLaunchKernel(fn, dim3(blocks), dim3(BLOCK), args, dyn, s);      // its error: the launch check's
     CLAPGPU_LAUNCH_CHECK("k_pose");

@@ -26,13 +26,13 @@ pytestmark = pytest.mark.gpu
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "pose_*.npz")))
 
 
-def assert_pose_equal(out, trs, jt, jp, reach, what, trs_on=True, pos_on=True):
+def assert_pose_equal(out, trs, jt, jp, reach, what, trs_on=True, pos_on=True, key="pose"):
     """Every joint's T, R, S, its palette matrix and its world position: the reference's values."""
     if trs_on:
-        assert_trs_equal(out["trs"], trs, what + " T/R/S", key="pose T/R/S")
-    assert_mat4_equal(out["joint_transforms"][:, reach], jt[:, reach], what + " joint_transforms", key="pose joint_transforms")
+        assert_trs_equal(out["trs"], trs, what + " T/R/S", key=key + " T/R/S")
+    assert_mat4_equal(out["joint_transforms"][:, reach], jt[:, reach], what + " joint_transforms", key=key + " joint_transforms")
     if pos_on:
-        assert_vec_equal(out["joint_pos"][:, reach], jp[:, reach], what + " joint pos", key="pose joint_pos")
+        assert_vec_equal(out["joint_pos"][:, reach], jp[:, reach], what + " joint pos", key=key + " joint_pos")
 
 
 def oracle_pose(sk, anims, which, t, ent_mx, trs):
