@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 51
+ABI_VERSION = 52
 
 OK = 0
 ERR_NOMEM = -1
@@ -341,6 +341,20 @@ class Lights(C.Structure):
                 ("attenuation", C.c_void_p), ("is_dir", C.c_void_p), ("active", C.c_void_p)]
 
 
+SPOTS_INVALID = 1
+
+
+class Spots(C.Structure):
+    """clapgpu_spots (include/clapgpu.h): the lights that track an entity, their dir / cutoff slots and a status word."""
+    _fields_ = [("n", C.c_uint32), ("pad", C.c_uint32), ("carrier_entity", C.c_void_p), ("carrier_light", C.c_void_p),
+                ("carrier_off", C.c_void_p), ("carrier_view_slot", C.c_void_p), ("dir", C.c_void_p), ("cutoff", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
+SPOTS_BYTES = 64                                             # CLAPGPU_SPOTS_BYTES
+assert C.sizeof(Spots) == SPOTS_BYTES
+
+
 class Solver(C.Structure):
     """clapgpu_solver (include/clapgpu.h): quickstep's iteration count, SOR factor and global CFM; wide_rows: the rows from
     which an island is solved by a workgroup, level by level (0: never)."""
@@ -381,6 +395,8 @@ class FrameDesc(C.Structure):
                 ("aniq", C.POINTER(Aniq)), ("skin_select", C.POINTER(SkinSelect)),
                 ("views_source", C.c_void_p), ("views_state", C.c_void_p),
                 ("cascades", C.c_void_p), ("bv_result", C.c_void_p), ("bv_has_ctl", C.c_uint32), ("bv_ctl_entity", C.c_uint32),
+                ("spots", C.POINTER(Spots)), ("view_visible", C.c_void_p * EXTRA_VIEWS_MAX),
+                ("view_visible_count", C.c_void_p * EXTRA_VIEWS_MAX),
                 ("camera", C.c_void_p), ("camera_bp", C.c_void_p)]
 
 
@@ -397,7 +413,7 @@ STRUCTS = {
     "clapgpu_view_source": ViewSource, "clapgpu_views_source": ViewsSource, "clapgpu_view_state": ViewState,
     "clapgpu_views_state": ViewsState, "clapgpu_camera": Camera,
     "clapgpu_cascade_view": CascadeView, "clapgpu_cascades": Cascades,
-    "clapgpu_solver": Solver, "clapgpu_aniq_entry": AniqEntry, "clapgpu_aniq": Aniq, "clapgpu_frame": FrameDesc,
+    "clapgpu_spots": Spots, "clapgpu_solver": Solver, "clapgpu_aniq_entry": AniqEntry, "clapgpu_aniq": Aniq, "clapgpu_frame": FrameDesc,
 }
 
 
@@ -595,6 +611,10 @@ SYMBOLS = {
     "clapgpu_particles_update_views": (C.c_int, [C.c_void_p, C.POINTER(Particles), C.c_void_p]),
     "clapgpu_lights_from_entities": (C.c_int, [C.c_void_p, C.POINTER(Entities), C.c_uint32, C.c_uint32, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.POINTER(Lights)]),
+    "clapgpu_lights_update": (C.c_int, [C.c_void_p, C.POINTER(Entities), C.c_uint32, C.POINTER(Spots), C.POINTER(Lights),
+                                        C.c_void_p]),
+    "clapgpu_lights_update_host": (None, [C.POINTER(Entities), C.c_uint32, C.POINTER(Spots), C.POINTER(Lights), C.c_void_p]),
+    "clapgpu_spot_persp": (None, [C.c_float, C.c_int, C.POINTER(C.c_float)]),
 }
 
 _lib = None

@@ -29,6 +29,11 @@
 // bv_result is given; ahead of the camera, whose previous position it reads from the head views_calc), the camera,
 // clapgpu_cascades_calc (cascades.hip: the cascade sub-frusta, near_backup, the light's views; it writes the light's slot
 // of the source), the second clapgpu_views_calc, the cull, the list, the LOD pick and skin_select.
+// With f->spots (ABI 52) light_update (scene.c:1170, ahead of mq_update) runs where the reference has it: clapgpu_lights_update
+// directly before the light hand-off, behind the body read-back and the character hooks, which set DIRTY, and ahead of the
+// entity update, which clears it.  With a carrier_view_slot it writes a spot's pose into the source behind the head
+// views_calc, so the tail takes the cascades frame's shape: the second views_calc and the cull behind the join.  With
+// f->view_visible[v] the frame also compacts plane v of entities->views behind the main list: shadow pass v's list.
 //
 // Round 4: the frame as THREE CHAINS (opt-in: CLAPGPU_FRAME_OVERLAP).  What the reference runs in list order has only these
 // data dependences:
@@ -110,6 +115,17 @@ extern "C" int clapgpu_frame_issue(void *stream, const clapgpu_frame *f, double 
         return CLAPGPU_ERR_INVALID_ARGUMENTS;                    // the camera writes the view block's source
     if (f->cascades && (!f->views_state || !view_block_ok(f->cascades) || !f->entities->views || f->entities->views->n < 1))
         return CLAPGPU_ERR_INVALID_ARGUMENTS;                    // the fit writes the light's slot of the source
+    if (f->spots) {                                              // the tracked lights: slots to write, and a block for a spot's view
+        if (!f->lights || (f->spots->carrier_view_slot && !f->views_state)) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+        FR(spots_check(f->entities, f->spots, f->lights, f->views_source));
+    }
+    for (uint32_t v = 0; v < CLAPGPU_EXTRA_VIEWS_MAX; v++) {     // a shadow pass's list: a plane to compact, beside a main view
+        if (!f->view_visible[v]) continue;
+        const clapgpu_views *xv = f->entities->views;
+        if (!(f->frustum || f->views_state) || !xv || v >= xv->n || !xv->vis_mask[v] || !f->view_visible_count[v] ||
+            !f->visible_scratch)
+            return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    }
     const bool animated = f->skeleton && f->animations && f->pose;
     const bool particles = f->particles && (f->view_mx || f->views_state);
     const bool overlap = (f->flags & CLAPGPU_FRAME_OVERLAP) && (animated || particles);
@@ -284,6 +300,8 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         if (f->n_body_links)
             FR(clapgpu_bodies_rotate_from_entities(stream, f->bodies, e, 0, f->n_body_links, f->link_body, f->link_entity));
     }
+    if (f->spots)                                                // light_update (scene.c:1170): ahead of mq_update's hand-off
+        FR(clapgpu_lights_update(stream, e, 0, f->spots, f->lights, const_cast<clapgpu_views_source *>(f->views_source)));
     if (f->lights && f->n_light_carriers)
         FR(clapgpu_lights_from_entities(stream, e, 0, f->n_light_carriers, f->carrier_entity, f->carrier_light, f->carrier_offset,
                                         f->lights));
@@ -292,7 +310,8 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         FR(clapgpu_entities_update_tiles(stream, e, f->tile_row_start, f->n_tiles, 0, f->frustum));
     else
         FR(clapgpu_entities_update(stream, e, f->level_start, f->n_levels, 0, f->frustum));
-    const bool late_views = f->camera || f->cascades;            // scene_cameras_calc on the device: the cull waits for it
+    // scene_cameras_calc on the device, or a spot's view written above (behind the head views_calc): the cull waits for it
+    const bool late_views = f->camera || f->cascades || (f->spots && f->spots->carrier_view_slot);
     if (vs && !late_views)                                       // f->frustum is NULL: the update above did not cull
         FR(clapgpu_entities_cull_views(stream, e, vs));
 
@@ -346,6 +365,11 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
             FR(clapgpu_visible_compact(stream, e->vis_mask, e->vis_row_pop, e->n, f->index_base, f->visible, f->visible_count,
                                        f->visible_scratch));
     }
+    // ---- the shadow passes' lists (_models_render with view = &light->view[0]): no camera, no LOD pick (model.c:975) ----
+    for (uint32_t v = 0; v < CLAPGPU_EXTRA_VIEWS_MAX; v++)
+        if (f->view_visible[v])
+            FR(clapgpu_visible_compact(stream, e->views->vis_mask[v], e->views->vis_row_pop[v], e->n, f->index_base,
+                                       f->view_visible[v], f->view_visible_count[v], f->visible_scratch));
     // ---- the vertex shader's skinning loop for what the passes draw, at the LOD just picked (model.c:959-997) ----
     if (f->skin_select) {
         clapgpu_skin_select sel = *f->skin_select;

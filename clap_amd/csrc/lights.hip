@@ -162,6 +162,74 @@ void k_lights_from_entities(LightCarrierArgs a)
     }
 }
 
+struct SpotsArgs {
+    uint32_t        n, mode, n_entities, nr_lights;
+    const uint32_t *carrier_entity;
+    const int32_t  *carrier_light;
+    const float    *carrier_off;
+    const uint32_t *carrier_view_slot;                               // may be NULL: no carrier has a view
+    const float4   *pos_scale, *rot;
+    const uint32_t *flags;
+    const uint32_t *active;
+    const int32_t  *is_dir;
+    const float    *cutoff;
+    float          *light_pos, *dir;
+    uint32_t       *status;
+    clapgpu_views_source *source;
+};
+
+// light_update (light.c:462-471) over the tracked lights, on the plan of k_lights_from_entities: a lane per carrier
+// decides whether it applies and whether its view slot is valid, and records its index with an LDS atomicMax on its light
+// slot and, for a spotlight with a view, on its view slot; then a lane per light slot writes the winner's position and
+// direction and a lane per view slot the winner's pose.  The invalid verdict is an LDS word read behind the same barrier:
+// no global write precedes it.  Launch-bound by construction: one workgroup, a few hundred bytes.
+__global__ __launch_bounds__(CLAPGPU_LIGHTS_MAX)
+void k_lights_update(SpotsArgs a)
+{
+    __shared__ uint32_t last[CLAPGPU_LIGHTS_MAX];                    // 1 + index of the winning carrier, 0 = none
+    __shared__ uint32_t vlast[CLAPGPU_VIEW_SLOTS];                   // the same per view slot
+    __shared__ uint32_t invalid;
+    const uint32_t t = threadIdx.x;
+    last[t] = 0;
+    if (t < CLAPGPU_VIEW_SLOTS) vlast[t] = 0;
+    if (t == 0) invalid = 0;
+    __syncthreads();
+    for (uint32_t k = t; k < a.n; k += CLAPGPU_LIGHTS_MAX) {
+        const uint32_t vs = a.carrier_view_slot ? a.carrier_view_slot[k] : 0u;
+        if (vs && !spot_view_slot_ok(vs, a.source)) { atomicOr(&invalid, 1u); continue; }
+        const int32_t l = a.carrier_light[k];
+        if (!spot_carrier_applies(l, a.carrier_entity[k], a.nr_lights, a.n_entities, a.active, a.flags, a.mode)) continue;
+        atomicMax(&last[l], k + 1);
+        if (vs && lmd::light_is_spotlight(a.is_dir[l], a.cutoff[l])) atomicMax(&vlast[vs], k + 1);
+    }
+    __syncthreads();
+    if (invalid) {
+        if (t == 0) *a.status = CLAPGPU_SPOTS_INVALID;
+        return;
+    }
+    if (t == 0) *a.status = 0;
+    if (t < a.nr_lights && last[t]) {
+        const uint32_t k = last[t] - 1;
+        const uint32_t e = a.carrier_entity[k];
+        const float4 ps = a.pos_scale[e], q = a.rot[e];
+        const bool spot = lmd::light_is_spotlight(a.is_dir[t], a.cutoff[t]);
+        const float pos[3] = { ps.x, ps.y, ps.z }, rot[4] = { q.x, q.y, q.z, q.w };
+        const float off[3] = { a.carrier_off[3 * k], a.carrier_off[3 * k + 1], a.carrier_off[3 * k + 2] };
+        float lpos[3], dir[3] = { 0.f, 0.f, 0.f };
+        lmd::light_from_entity(lpos, dir, pos, off, rot, spot);
+        a.light_pos[3 * t] = lpos[0]; a.light_pos[3 * t + 1] = lpos[1]; a.light_pos[3 * t + 2] = lpos[2];
+        if (spot) { a.dir[3 * t] = dir[0]; a.dir[3 * t + 1] = dir[1]; a.dir[3 * t + 2] = dir[2]; }
+    }
+    if (t >= 1 && t < CLAPGPU_VIEW_SLOTS && vlast[t]) {              // view_update_from_angles reads e->xform: no light_off
+        const uint32_t e = a.carrier_entity[vlast[t] - 1];
+        const uint4 ps = reinterpret_cast<const uint4 *>(a.pos_scale)[e];       // the bits, NaNs included
+        const uint4 q = reinterpret_cast<const uint4 *>(a.rot)[e];
+        uint32_t *p = reinterpret_cast<uint32_t *>(a.source->slot[t].pos);
+        p[0] = ps.x; p[1] = ps.y; p[2] = ps.z;
+        *reinterpret_cast<uint4 *>(a.source->slot[t].quat) = q;
+    }
+}
+
 } // namespace clapgpu
 
 using namespace clapgpu;
@@ -277,5 +345,24 @@ extern "C" int clapgpu_lights_from_entities(void *stream, const clapgpu_entities
     a.parent = e->parent; a.flags = e->flags; a.active = lights->active; a.light_pos = lights->pos;
     hipLaunchKernelGGL(k_lights_from_entities, dim3(1), dim3(CLAPGPU_LIGHTS_MAX), 0, as_stream(stream), a);
     CLAPGPU_LAUNCH_CHECK("k_lights_from_entities");
+    return CLAPGPU_OK;
+}
+
+extern "C" int clapgpu_lights_update(void *stream, const clapgpu_entities *e, uint32_t mode, const clapgpu_spots *s,
+                                     const clapgpu_lights *lights, clapgpu_views_source *source)
+{
+    int rc = spots_check(e, s, lights, source);
+    if (rc) return rc;
+    if (s->n == 0 || lights->nr_lights == 0)
+        return CLAPGPU_OK;
+    SpotsArgs a;
+    a.n = s->n; a.mode = mode; a.n_entities = e->n; a.nr_lights = lights->nr_lights;
+    a.carrier_entity = s->carrier_entity; a.carrier_light = s->carrier_light; a.carrier_off = s->carrier_off;
+    a.carrier_view_slot = s->carrier_view_slot;
+    a.pos_scale = reinterpret_cast<const float4 *>(e->pos_scale); a.rot = reinterpret_cast<const float4 *>(e->rot);
+    a.flags = e->flags; a.active = lights->active; a.is_dir = lights->is_dir; a.cutoff = s->cutoff;
+    a.light_pos = lights->pos; a.dir = s->dir; a.status = s->status; a.source = s->carrier_view_slot ? source : nullptr;
+    hipLaunchKernelGGL(k_lights_update, dim3(1), dim3(CLAPGPU_LIGHTS_MAX), 0, as_stream(stream), a);
+    CLAPGPU_LAUNCH_CHECK("k_lights_update");
     return CLAPGPU_OK;
 }

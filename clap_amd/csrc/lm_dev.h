@@ -782,4 +782,25 @@ LMD void cascade_projection(float (&proj)[16], float (&inv_proj)[16], float (&mv
     for (int i = 0; i < 16; i++) { proj[i] = one_nan(proj[i]); inv_proj[i] = one_nan(inv_proj[i]); mvp[i] = one_nan(mvp[i]); }
 }
 
+// ---- a tracked light: light_update_from_entity (core/light.c:385-422) ----
+// Stated once, here, for k_lights_update (lights.hip) and for the host's clapgpu_lights_update_host (runtime.hip).  The
+// rule is in include/clapgpu.h ("Spotlights on the device").
+// light.c:516-522: the cutoff is compared as a double; a NaN cutoff is no spotlight
+LMD bool light_is_spotlight(int32_t is_dir, float cutoff) { return is_dir && (double)cutoff > 0.0; }
+
+// light.c:391-393: pos + light_off (the sum clapgpu_lights_from_entities stores); light.c:398-400, 508-514, spotlights
+// only: dir = (0,0,0) - rotate((0,0,1)) -- vec3_sub from a zero vector, so a -0 of the rotation becomes +0
+LMD void light_from_entity(float (&lpos)[3], float (&dir)[3], const float (&pos)[3], const float (&off)[3],
+                           const float (&rot)[4], bool spot)
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++) lpos[i] = pos[i] + off[i];
+    if (!spot) return;
+    const float fwd[3] = { 0.f, 0.f, 1.f };
+    float r[3];
+    quat_mul_vec3(r, rot, fwd);
+#pragma unroll
+    for (int i = 0; i < 3; i++) dir[i] = one_nan(0.0f - r[i]);
+}
+
 } // namespace lmd

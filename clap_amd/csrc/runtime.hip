@@ -7,6 +7,7 @@
 #include <atomic>
 #include "common.h"
 #include "lm_dev.h"
+#include "views_dev.h"
 
 #ifdef CLAPGPU_EXPERIMENT               // an A/B or sensitivity build (common.h): never loadable as the product
 #define ABI_EXPERIMENT_BIT 0x80000000u
@@ -232,6 +233,44 @@ extern "C" void clapgpu_perspective(float fov, float aspect, float n, float f,
         proj_mx[10] = -((f + n) / (f - n));
         proj_mx[14] = -((2.f * f * n) / (f - n));
     }
+}
+
+// light.c:462-471, 385-410 (lmd::light_from_entity, spot_carrier_applies, spot_view_slot_ok: the statements
+// k_lights_update shares), the carriers in list order: what the kernel's winners leave
+extern "C" void clapgpu_lights_update_host(const clapgpu_entities *e, uint32_t mode, const clapgpu_spots *s,
+                                           const clapgpu_lights *lights, clapgpu_views_source *source)
+{
+    if (spots_check(e, s, lights, source) || s->n == 0 || lights->nr_lights == 0) return;
+    for (uint32_t k = 0; s->carrier_view_slot && k < s->n; k++)
+        if (s->carrier_view_slot[k] && !spot_view_slot_ok(s->carrier_view_slot[k], source)) {
+            *s->status = CLAPGPU_SPOTS_INVALID;
+            return;
+        }
+    *s->status = 0;
+    for (uint32_t k = 0; k < s->n; k++) {
+        const int32_t l = s->carrier_light[k];
+        const uint32_t ent = s->carrier_entity[k];
+        if (!spot_carrier_applies(l, ent, lights->nr_lights, e->n, lights->active, e->flags, mode)) continue;
+        const bool spot = lmd::light_is_spotlight(lights->is_dir[l], s->cutoff[l]);
+        const float *ps = e->pos_scale + 4 * ent, *q = e->rot + 4 * ent, *o = s->carrier_off + 3 * k;
+        const float pos[3] = { ps[0], ps[1], ps[2] }, rot[4] = { q[0], q[1], q[2], q[3] }, off[3] = { o[0], o[1], o[2] };
+        float lpos[3], dir[3] = { 0.f, 0.f, 0.f };
+        lmd::light_from_entity(lpos, dir, pos, off, rot, spot);
+        memcpy(lights->pos + 3 * l, lpos, sizeof(lpos));
+        if (!spot) continue;
+        memcpy(s->dir + 3 * l, dir, sizeof(dir));
+        const uint32_t vs = s->carrier_view_slot ? s->carrier_view_slot[k] : 0u;
+        if (vs) {                                                    // the bits, NaNs included
+            memcpy(source->slot[vs].pos, ps, 3 * sizeof(float));
+            memcpy(source->slot[vs].quat, q, 4 * sizeof(float));
+        }
+    }
+}
+
+// light.c:404-408, view.c:178-193: fov = cutoff * zoom (1.0f), aspect = (float)1 / (float)1, planes 0.1f and 200.0f
+extern "C" void clapgpu_spot_persp(float cutoff, int ndc_z_zero_one, float proj[16])
+{
+    clapgpu_perspective(cutoff * 1.0f, 1.0f / 1.0f, 0.1f, 200.0f, ndc_z_zero_one, proj);
 }
 
 // view.c:248-289 (lmd::frustum_calc: the statement k_views_calc shares)

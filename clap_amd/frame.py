@@ -21,7 +21,7 @@ class FrameLoop:
     def __init__(self, batch, cam, world=None, feed=None, body_links=None, lights=None, characters=None,
                  particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False, solve=False,
                  move=None, aniq=None, skin_select=None, views_dev=False, camera=None, camera_index=False, cascades=None,
-                 bv_result=None, bv_ctl_entity=None):
+                 bv_result=None, bv_ctl_entity=None, view_lists=False):
         """batch: EntityBatch.  world: PhysWorld (dynamic bodies write their entities through
         body_entity; character bodies have body_entity = -1).  feed: CharacterFeed.  body_links:
         (link_body, link_entity) of characters / static colliders whose rotation follows the entity.
@@ -63,8 +63,16 @@ class FrameLoop:
         slot of the source is the device's: later copies of the source leave it out.  bv_result: a device int64 tensor
         of one key: the frame runs default_update's bounding-volume pick (clapgpu_entities_bv_views, with bv_ctl_entity
         as the control entity or None) ahead of the camera and the cascades read it when their block asks for
-        near_backup from the volume."""
+        near_backup from the volume.  A `lights` with tracked lights (LightSet.set_spots) makes the frame run light_update
+        on the device ahead of the light hand-off (clapgpu_frame.spots); with view slots (needs views_dev) the
+        spotlights' poses go into the view source and the shadow planes are culled against this frame's spot, replayed
+        graphs included; the batch's further view in such a slot gives its projection (EntityBatch.set_views(None,
+        matrices=[(any view matrix, lights.spot_persp(cutoff, z01), z01)])), and from the first frame on those slots of
+        the source are the device's.  view_lists: the frame also
+        writes the ordered list of every further view (clapgpu_frame.view_visible: batch.view_visible[v] /
+        batch.view_visible_count[v]), the shadow passes' lists."""
         islands = islands or solve
+        self.view_lists = view_lists
         self.move, self.move_dt = move, 0.0
         self.aniq = aniq
         self.skin_select = skin_select
@@ -112,8 +120,12 @@ class FrameLoop:
         if len(getattr(b, "view_masks", [])) != len(extra):
             raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "FrameLoop",
                                     "views_dev: EntityBatch.set_views(..., matrices=) for every further view")
+        spot_slots = self.lights.spot_view_slots() if self.lights is not None else []
         for v, (vm, pm, z01) in enumerate(extra):
-            self.views.set_matrices(1 + v, vm, pm, ndc_z_zero_one=z01)
+            if 1 + v in spot_slots:                         # a spotlight's view: a pose slot, its pose the device's
+                self.views.set_pose(1 + v, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0, 1.0), pm, ndc_z_zero_one=z01)
+            else:
+                self.views.set_matrices(1 + v, vm, pm, ndc_z_zero_one=z01)
         self._views_seen = getattr(b, "view_matrices", None)
 
     # ---- the clapgpu_frame descriptor ---------------------------------------------------
@@ -215,6 +227,12 @@ class FrameLoop:
             if ls._carriers and ls._carriers[0]:
                 n, ce, cl, co = ls._carriers
                 f.n_light_carriers, f.carrier_entity, f.carrier_light, f.carrier_offset = n, ce.data_ptr(), cl.data_ptr(), co.data_ptr()
+            if ls._spots:
+                if ls._spots[4] is not None and self.views is None:
+                    raise _lib.ClapGpuError(_lib.ERR_INVALID_ARGUMENTS, "FrameLoop", "spot views: the update writes the view block (views_dev=True)")
+                sp = ls._spots_desc()
+                keep.append(sp)
+                f.spots = C.pointer(sp)
             tiles = ls.alloc_tiles()
             if tiles is not None:
                 f.light_width, f.light_height, f.light_cell, f.light_tiles = ls.width, ls.height, ls.cell, tiles.data_ptr()
@@ -245,6 +263,14 @@ class FrameLoop:
         f.visible, f.visible_count, f.visible_scratch = b.visible.data_ptr(), b.visible_count.data_ptr(), b.scratch.data_ptr()
         if self.views is None:
             f.cam_pos[:] = [float(v) for v in self.cam["cam_pos"]]
+        if self.view_lists:                                     # the shadow passes' lists
+            from ._dev import device_array
+            nv = len(getattr(b, "view_masks", []))
+            if getattr(b, "view_visible", None) is None or len(b.view_visible) != nv:
+                b.view_visible = [device_array((max(b.n, 1),), torch.int32, b.device) for _ in range(nv)]
+                b.view_visible_count = [device_array((1,), torch.int32, b.device) for _ in range(nv)]
+            for v in range(nv):
+                f.view_visible[v], f.view_visible_count[v] = b.view_visible[v].data_ptr(), b.view_visible_count[v].data_ptr()
         f.force_lod = b.force_lod.data_ptr() if b.force_lod is not None else None
         f.cur_lod, f.draw_lod = b.cur_lod.data_ptr(), b.draw_lod.data_ptr()
         self._desc, self._keep = f, keep
@@ -282,12 +308,22 @@ class FrameLoop:
         if changed:
             self._further_views()                            # set_views since the last frame
         if self.camera is None or self._views_dirty or changed:
-            if self.cascades is not None and self._light_slot_sent and not changed:   # the light's slot is the device's
+            owned = set()                                    # slots that are the device's from the first frame on
+            if self._light_slot_sent and not changed:
+                if self.cascades is not None:
+                    owned.add(int(self.cascades.host[0]["light_slot"]))
+                if self.lights is not None:
+                    owned.update(self.lights.spot_view_slots())
+            if owned:
                 from . import _lib
                 words = _lib.VIEWS_SOURCE_BYTES // _lib.VIEW_SLOTS // 4
-                at = int(self.cascades.host[0]["light_slot"]) * words
-                self.views.source[:at].copy_(self.views.host[:at], non_blocking=True)
-                self.views.source[at + words:].copy_(self.views.host[at + words:], non_blocking=True)
+                first = None                                 # one copy per run of the host's slots
+                for v in range(_lib.VIEW_SLOTS + 1):
+                    if v < _lib.VIEW_SLOTS and v not in owned:
+                        first = v if first is None else first
+                    elif first is not None:
+                        self.views.source[first * words:v * words].copy_(self.views.host[first * words:v * words], non_blocking=True)
+                        first = None
             else:
                 self.views.upload()
                 self._light_slot_sent = True

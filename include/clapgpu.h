@@ -58,7 +58,7 @@ void clapgpu_test_fail_after(int launches);
 /* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
  * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
  * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
-#define CLAPGPU_ABI_VERSION 51u
+#define CLAPGPU_ABI_VERSION 52u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -1950,8 +1950,8 @@ int clapgpu_animation_queue_time(void *stream, const clapgpu_aniq *q, double now
  * 0x7fc00000, on the host and on the device: what an invalid operation (0 * inf of a singular mvp) leaves in the sign and
  * payload of a NaN differs between the two machines and no consumer reads it.
  * The main view's pose can come from the camera controller on the device (clapgpu_camera_calc, ABI 50, below) and the
- * shadow light's view from the cascades' fit (clapgpu_cascades_calc, ABI 51, below); the spotlights' views stay pose
- * slots the host writes.  clapgpu_entities.bv (the bounding-volume pick's camera and control positions) is an argument
+ * shadow light's view from the cascades' fit (clapgpu_cascades_calc, ABI 51, below), and a spotlight's view from the
+ * entity that carries it (clapgpu_lights_update, ABI 52, below).  clapgpu_entities.bv (the bounding-volume pick's camera and control positions) is an argument
  * of the fused update kernel, which the view block does not reach: clapgpu_entities_bv_views is its twin over the block.
  */
 #define CLAPGPU_VIEW_SLOTS (1 + CLAPGPU_EXTRA_VIEWS_MAX)
@@ -2246,6 +2246,87 @@ int clapgpu_entities_bv_views(void *stream, const clapgpu_entities *e, const cla
                               uint32_t ctl_entity, uint64_t *result, uint64_t *inside_mask);
 
 /* ======================================================================== */
+/* Spotlights on the device (ABI 52)                                         */
+/* ======================================================================== */
+
+/*
+ * light_update (core/light.c:462-471, called from scene_update ahead of mq_update, scene.c:1170) for the lights that
+ * track an entity: every light slot made from scene.json registers light_update_from_entity (light.c:385-422) on its
+ * entity's transform (scene.c:1626-1631), and when that transform has moved the callback writes the light's position,
+ * a spotlight's direction and the pose of a spotlight's own shadow view -- the view that culls the shadow passes when
+ * light 0 is a spotlight (scene.c:1043 skips the cascade fit then).  clapgpu_spots is a HOST struct of DEVICE pointers:
+ * the tracked lights in entity order, the slots' dir and cutoff (clapgpu_lights stays as it is: callers build it
+ * positionally), and one status word.  A frame whose spotlight rides a body, a character or an animated entity needs no
+ * host between the body read-back and the shadow passes' cull, and a replayed graph's spot view follows its carrier.
+ *
+ * THE RULE.  clapgpu_lights_update does the callback's arithmetic in its order, in fp32, with no FMA contraction, by
+ * the function its host twin calls (csrc/lm_dev.h), so the arrays hold the host's bits; every NaN stored in dir is
+ * 0x7fc00000 (as for the view block).
+ *   which carriers apply (light.c:464-467): carrier k applies iff 0 <= carrier_light[k] < nr_lights, carrier_entity[k] <
+ *       e->n, active[light] is set, and the entity's CLAPGPU_E_DIRTY is set (this mirror's transform_is_updated,
+ *       light.c:467) or mode has CLAPGPU_UPDATE_ALL_DIRTY.  There is NO parent test: light_update has none and the
+ *       transform it reads is the local one (light.c:391) -- this is where the call differs from
+ *       clapgpu_lights_from_entities.
+ *   who writes a slot (light.c:464: one callback per slot, the last registered): per light slot the last applying
+ *       carrier in list order writes it, and the same holds per view slot.
+ *   position (light.c:391-393, 473-480): lights->pos[l] = pos + carrier_off per component -- the bits
+ *       clapgpu_lights_from_entities leaves, so a carrier in both lists is written twice with one value.
+ *   the spotlight test (light.c:395, 516-522): is_dir[l] && (double)cutoff[l] > 0.0; a NaN cutoff is no spotlight.
+ *   direction, spotlights only (light.c:398-400, 508-514): r = quat_mul_vec3(rot[e], (0,0,1)) in linmath's order with
+ *       every product kept (inf * 0 stays NaN); dir[l][i] = 0.0f - r[i] -- vec3_sub from a zero vector, not a negation:
+ *       -0 becomes +0.
+ *   view pose, a spotlight with a nonzero view slot v (light.c:409, view_update_from_angles on e->xform):
+ *       source->slot[v].pos gets the entity's position bits (NOT + carrier_off) and source->slot[v].quat its rotation
+ *       bits, copies bit for bit, NaNs included; nothing else of the slot is touched.  The host writes that slot's
+ *       proj_mx once (clapgpu_spot_persp, light.c:404-408) and its flags once (CLAPGPU_VIEW_FROM_POSE, plus
+ *       NDC_Z_ZERO_ONE as the renderer has it).  A slot that is no spotlight writes no view: the callback has returned
+ *       by then (light.c:395-396).
+ * The copies of subview[0] into subview[1..3] and their dividers (light.c:418-421) are not produced: a consumer reads the
+ * slot's clapgpu_view_state for every cascade.  light_update_from_camera (light.c:430-460) has no user in the reference
+ * and none here.
+ * What the host cannot see before a HIP call it cannot refuse: carrier_view_slot[] and the slots' flags live in device
+ * memory.  If any carrier, applying or not, has a nonzero view slot outside 1 .. CLAPGPU_VIEW_SLOTS - 1, or one naming a
+ * slot whose flags lack CLAPGPU_VIEW_FROM_POSE, the kernel writes *status = CLAPGPU_SPOTS_INVALID and nothing else;
+ * otherwise *status = 0.
+ */
+#define CLAPGPU_SPOTS_INVALID 1u             /* status */
+
+typedef struct clapgpu_spots {
+    uint32_t        n, pad;             /* tracked lights, in entity order */
+    const uint32_t *carrier_entity;     /* [n] */
+    const int32_t  *carrier_light;      /* [n] */
+    const float    *carrier_off;        /* [3n] e->light_off */
+    const uint32_t *carrier_view_slot;  /* [n] 0: no view; 1 .. CLAPGPU_VIEW_SLOTS-1: the source slot of light.view[idx].main; may be NULL (all 0) */
+    float          *dir;                /* [3 * CLAPGPU_LIGHTS_MAX] light->dir, written */
+    const float    *cutoff;             /* [CLAPGPU_LIGHTS_MAX] light->cutoff, radians */
+    uint32_t       *status;             /* one device word: 0 or CLAPGPU_SPOTS_INVALID, written by every launch */
+} clapgpu_spots;
+
+#define CLAPGPU_SPOTS_BYTES 64
+#ifdef __cplusplus
+static_assert(sizeof(clapgpu_spots) == CLAPGPU_SPOTS_BYTES, "the spots descriptor's layout is ABI");
+#else
+_Static_assert(sizeof(clapgpu_spots) == CLAPGPU_SPOTS_BYTES, "the spots descriptor's layout is ABI");
+#endif
+
+/* One launch (one workgroup of CLAPGPU_LIGHTS_MAX lanes), no allocation, no host synchronisation: it can be captured.
+ * e: pos_scale, rot and flags are read.  source may be NULL iff s->carrier_view_slot is NULL.  Call BEFORE
+ * clapgpu_entities_update, which clears the dirty flags.  Refused with CLAPGPU_ERR_INVALID_ARGUMENTS before any HIP
+ * call: a NULL e / s / lights (or a lights without its arrays); an e without pos_scale / rot / flags; n > 0 with a NULL
+ * carrier_entity / carrier_light / carrier_off; a NULL dir / cutoff / status; a NULL or misaligned source next to a
+ * carrier_view_slot.  nr_lights > CLAPGPU_LIGHTS_MAX: CLAPGPU_ERR_TOO_LARGE.  n == 0 or nr_lights == 0: nothing is
+ * launched (status keeps its value) and CLAPGPU_OK. */
+int clapgpu_lights_update(void *stream, const clapgpu_entities *e, uint32_t mode, const clapgpu_spots *s,
+                          const clapgpu_lights *lights, clapgpu_views_source *source);
+/* The host twin: the kernel's own function on the host's values -- the same structs with HOST pointers, e's pos_scale /
+ * rot / flags as host arrays.  Arguments the device call refuses make it return without writing. */
+void clapgpu_lights_update_host(const clapgpu_entities *e, uint32_t mode, const clapgpu_spots *s,
+                                const clapgpu_lights *lights, clapgpu_views_source *source);
+/* A spotlight view's projection (light.c:404-408, view.c:178-193): clapgpu_perspective(cutoff * 1.0f, 1.0f / 1.0f, 0.1f,
+ * 200.0f, ndc_z_zero_one).  Host. */
+void clapgpu_spot_persp(float cutoff, int ndc_z_zero_one, float proj[16]);
+
+/* ======================================================================== */
 /* One frame (core/clap.c:551-665)                                           */
 /* ======================================================================== */
 
@@ -2359,6 +2440,25 @@ typedef struct clapgpu_frame {
     clapgpu_cascades           *cascades;      /* device */
     uint64_t                   *bv_result;     /* device, or NULL: no pick */
     uint32_t                    bv_has_ctl, bv_ctl_entity;
+    /* spotlights on the device (ABI 52); spots NULL: the frame as before, launch for launch.  Set: it needs lights, and
+     * with a spots->carrier_view_slot also views_source and views_state (CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, before
+     * any launch).  clapgpu_lights_update(entities, 0, spots, lights, views_source) is issued directly before the light
+     * hand-off: behind the body read-back and the character hooks, which set DIRTY, and ahead of the entity update, which
+     * clears it -- light_update before mq_update (scene.c:1170).  With a carrier_view_slot the tail takes the cascades
+     * frame's shape whether or not camera / cascades are set: the head clapgpu_views_calc stays, the update runs without
+     * its cull, and behind the join come the second clapgpu_views_calc over all slots, clapgpu_entities_cull_views, the
+     * list with the LOD pick and skin_select -- the shadow passes are culled against THIS frame's spot.  A spot's view
+     * slot equal to cascades->light_slot is the caller's contradiction (the reference never fits light 0 when it is a
+     * spotlight, scene.c:1043): both write the slot, the fit last.
+     * view_visible[v] set: behind the main list the frame issues clapgpu_visible_compact(views->vis_mask[v],
+     * views->vis_row_pop[v], n, index_base, view_visible[v], view_visible_count[v], visible_scratch): the ordered list of
+     * shadow pass v, which _models_render walks with view = &light->view[0].  No LOD is picked: a shadow pass has no
+     * camera (model.c:752-760, 975) and draws with the cur_lod the entity has.  It needs a main view (frustum or
+     * views_state), v < entities->views->n, view_visible_count[v] and visible_scratch: CLAPGPU_ERR_INVALID_ARGUMENTS
+     * otherwise, before any launch.
+     * (These fields stand in front of `camera`, as the cascades' do: the descriptor's version is CLAPGPU_ABI_VERSION.) */
+    const clapgpu_spots        *spots;
+    uint32_t *view_visible[CLAPGPU_EXTRA_VIEWS_MAX], *view_visible_count[CLAPGPU_EXTRA_VIEWS_MAX];
     /* the camera controller on the device (ABI 50); camera NULL: the frame as before, launch for launch (camera_bp is not
      * read).  Set: it needs views_source and views_state (CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, before any launch),
      * and writes slot 0 of views_source.  The rays see body_geoms, or the geoms of bodies when that is NULL, or no body,
