@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLAPGPU_LIB") or os.path.join(_HERE, "lib", "libclapgpu.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 52
+ABI_VERSION = 53
 
 OK = 0
 ERR_NOMEM = -1
@@ -355,6 +355,59 @@ SPOTS_BYTES = 64                                             # CLAPGPU_SPOTS_BYT
 assert C.sizeof(Spots) == SPOTS_BYTES
 
 
+DRAW_GROUP_SKIP_SHADOW = 1
+DRAW_IS_CHARACTER = 1
+DRAW_OUTLINE_EXCLUDE = 2
+DRAW_PASS_SHADOW = 1
+DRAW_PASS_HAS_ROPTS = 2
+DRAW_SET_BLOOM_INTENSITY = 1
+DRAW_SET_BLOOM_THRESHOLD = 2
+DRAW_CAPPED = 1
+DRAW_INVALID = 2
+DRAW_RECORD_BYTES = 192
+
+
+class DrawOrder(C.Structure):
+    """clapgpu_draw_order (include/clapgpu.h): the walk of model.c:784 / :959 flattened; device pointers."""
+    _fields_ = [("n_order", C.c_uint32), ("n_groups", C.c_uint32), ("order", C.c_void_p), ("group_start", C.c_void_p),
+                ("group_flags", C.c_void_p)]
+
+
+class DrawInputs(C.Structure):
+    """clapgpu_draw_inputs: per-entity arrays, any of them NULL."""
+    _fields_ = [("color", C.c_void_p), ("color_pt", C.c_void_p), ("bloom_intensity", C.c_void_p),
+                ("bloom_threshold", C.c_void_p), ("draw_flags", C.c_void_p), ("character", C.c_void_p)]
+
+
+class DrawPass(C.Structure):
+    """clapgpu_draw_pass: host values of one render pass."""
+    _fields_ = [("flags", C.c_uint32), ("bloom_intensity", C.c_float), ("bloom_threshold", C.c_float),
+                ("mq_nr_characters", C.c_uint32), ("index_base", C.c_uint32)]
+
+
+class DrawRecord(C.Structure):
+    """clapgpu_draw_record: 192 bytes, three 64-byte lines."""
+    _fields_ = [("mx", C.c_float * 16), ("inv_mx", C.c_float * 16), ("color", C.c_float * 4), ("bloom_intensity", C.c_float),
+                ("bloom_threshold", C.c_float), ("edge_mode", C.c_uint32), ("color_pt", C.c_int32), ("entity", C.c_uint32),
+                ("lod", C.c_int32), ("group", C.c_uint32), ("character", C.c_int32), ("flags", C.c_uint32),
+                ("zero", C.c_uint32 * 3)]
+
+
+assert C.sizeof(DrawRecord) == DRAW_RECORD_BYTES
+
+
+class FrameDrawPass(C.Structure):
+    """clapgpu_frame_draw_pass: one pass's outputs inside a frame."""
+    _fields_ = [("pass", DrawPass), ("capacity", C.c_uint32), ("records", C.c_void_p), ("count", C.c_void_p),
+                ("group_first", C.c_void_p), ("status", C.c_void_p)]
+
+
+class FrameDraw(C.Structure):
+    """clapgpu_frame_draw: the frame's draw records, the main pass and one block per further view."""
+    _fields_ = [("order", C.POINTER(DrawOrder)), ("inputs", C.POINTER(DrawInputs)), ("main", FrameDrawPass),
+                ("view", FrameDrawPass * EXTRA_VIEWS_MAX), ("scratch", C.c_void_p)]
+
+
 class Solver(C.Structure):
     """clapgpu_solver (include/clapgpu.h): quickstep's iteration count, SOR factor and global CFM; wide_rows: the rows from
     which an island is solved by a workgroup, level by level (0: never)."""
@@ -397,6 +450,7 @@ class FrameDesc(C.Structure):
                 ("cascades", C.c_void_p), ("bv_result", C.c_void_p), ("bv_has_ctl", C.c_uint32), ("bv_ctl_entity", C.c_uint32),
                 ("spots", C.POINTER(Spots)), ("view_visible", C.c_void_p * EXTRA_VIEWS_MAX),
                 ("view_visible_count", C.c_void_p * EXTRA_VIEWS_MAX),
+                ("draw", C.POINTER(FrameDraw)),
                 ("camera", C.c_void_p), ("camera_bp", C.c_void_p)]
 
 
@@ -413,7 +467,9 @@ STRUCTS = {
     "clapgpu_view_source": ViewSource, "clapgpu_views_source": ViewsSource, "clapgpu_view_state": ViewState,
     "clapgpu_views_state": ViewsState, "clapgpu_camera": Camera,
     "clapgpu_cascade_view": CascadeView, "clapgpu_cascades": Cascades,
-    "clapgpu_spots": Spots, "clapgpu_solver": Solver, "clapgpu_aniq_entry": AniqEntry, "clapgpu_aniq": Aniq, "clapgpu_frame": FrameDesc,
+    "clapgpu_spots": Spots, "clapgpu_draw_order": DrawOrder, "clapgpu_draw_inputs": DrawInputs, "clapgpu_draw_pass": DrawPass,
+    "clapgpu_draw_record": DrawRecord, "clapgpu_frame_draw_pass": FrameDrawPass, "clapgpu_frame_draw": FrameDraw,
+    "clapgpu_solver": Solver, "clapgpu_aniq_entry": AniqEntry, "clapgpu_aniq": Aniq, "clapgpu_frame": FrameDesc,
 }
 
 
@@ -615,6 +671,13 @@ SYMBOLS = {
                                         C.c_void_p]),
     "clapgpu_lights_update_host": (None, [C.POINTER(Entities), C.c_uint32, C.POINTER(Spots), C.POINTER(Lights), C.c_void_p]),
     "clapgpu_spot_persp": (None, [C.c_float, C.c_int, C.POINTER(C.c_float)]),
+    "clapgpu_draw_records_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "clapgpu_draw_records": (C.c_int, [C.c_void_p, C.POINTER(Entities), C.c_void_p, C.c_void_p, C.POINTER(DrawOrder),
+                                       C.POINTER(DrawInputs), C.POINTER(DrawPass), C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clapgpu_draw_records_host": (None, [C.POINTER(Entities), C.c_void_p, C.c_void_p, C.POINTER(DrawOrder),
+                                         C.POINTER(DrawInputs), C.POINTER(DrawPass), C.c_void_p, C.c_uint32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -34,6 +34,10 @@
 // entity update, which clears it.  With a carrier_view_slot it writes a spot's pose into the source behind the head
 // views_calc, so the tail takes the cascades frame's shape: the second views_calc and the cull behind the join.  With
 // f->view_visible[v] the frame also compacts plane v of entities->views behind the main list: shadow pass v's list.
+// With f->draw (ABI 53) the frame leaves what _models_render (model.c:742-1086) consumes: clapgpu_draw_records per pass.
+// pipeline_render runs the shadow passes before the model pass (pipeline-builder.c:246-272) and they have no camera, so
+// they draw with the cur_lod the last model pass left (model.c:975): the further views' records are issued behind the
+// cull and AHEAD of the visible list and the LOD pick, the main pass's behind the pick; skin_select stays last.
 //
 // Round 4: the frame as THREE CHAINS (opt-in: CLAPGPU_FRAME_OVERLAP).  What the reference runs in list order has only these
 // data dependences:
@@ -59,6 +63,7 @@
 #include "common.h"
 #include "views_dev.h"
 #include "geoms_dev.h"
+#include "draw_dev.h"
 
 using namespace clapgpu;
 
@@ -125,6 +130,26 @@ extern "C" int clapgpu_frame_issue(void *stream, const clapgpu_frame *f, double 
         if (!(f->frustum || f->views_state) || !xv || v >= xv->n || !xv->vis_mask[v] || !f->view_visible_count[v] ||
             !f->visible_scratch)
             return CLAPGPU_ERR_INVALID_ARGUMENTS;
+    }
+    if (f->draw) {                                               // the passes' records: a main view, and what the call itself asks
+        const clapgpu_frame_draw *d = f->draw;
+        const clapgpu_entities *e = f->entities;
+        if (!(f->frustum || f->views_state) || !d->order || !d->scratch || (reinterpret_cast<uintptr_t>(d->scratch) & 255u) ||
+            !e->vis_mask)
+            return CLAPGPU_ERR_INVALID_ARGUMENTS;
+        if ((reinterpret_cast<uintptr_t>(e->mx) | reinterpret_cast<uintptr_t>(e->inv_mx) |
+             reinterpret_cast<uintptr_t>(d->inputs ? d->inputs->color : nullptr)) & 15u)
+            return CLAPGPU_ERR_INVALID_ARGUMENTS;
+        if (d->main.count)
+            FR(draw_check(e, e->vis_mask, d->order, &d->main.pass, d->main.records, d->main.capacity, d->main.count,
+                          d->main.group_first, d->main.status));
+        for (uint32_t v = 0; v < CLAPGPU_EXTRA_VIEWS_MAX; v++) {
+            const clapgpu_frame_draw_pass *p = &d->view[v];
+            if (!p->count) continue;
+            if (!e->views || v >= e->views->n || !e->views->vis_mask[v]) return CLAPGPU_ERR_INVALID_ARGUMENTS;
+            FR(draw_check(e, e->views->vis_mask[v], d->order, &p->pass, p->records, p->capacity, p->count, p->group_first,
+                          p->status));
+        }
     }
     const bool animated = f->skeleton && f->animations && f->pose;
     const bool particles = f->particles && (f->view_mx || f->views_state);
@@ -353,6 +378,14 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         FR(clapgpu_views_calc(stream, f->views_source, f->views_state, 1 + (e->views ? e->views->n : 0)));
         FR(clapgpu_entities_cull_views(stream, e, vs));
     }
+    // ---- the shadow passes' draw records: ahead of the model pass, with the LODs the last one left (model.c:975) ----
+    if (f->draw)
+        for (uint32_t v = 0; v < CLAPGPU_EXTRA_VIEWS_MAX; v++) {
+            const clapgpu_frame_draw_pass *p = &f->draw->view[v];
+            if (p->count)
+                FR(clapgpu_draw_records(stream, e, e->views->vis_mask[v], f->cur_lod, f->draw->order, f->draw->inputs, &p->pass,
+                                        p->records, p->capacity, p->count, p->group_first, p->status, f->draw->scratch));
+        }
     // ---- render pass glue: ordered visible list + LOD pick ----
     if ((f->frustum || vs) && f->visible && f->visible_count && f->visible_scratch) {
         if (f->cur_lod && f->draw_lod && vs)
@@ -370,6 +403,12 @@ static int frame_body(void *stream, const clapgpu_frame *f, double now, uint32_t
         if (f->view_visible[v])
             FR(clapgpu_visible_compact(stream, e->views->vis_mask[v], e->views->vis_row_pop[v], e->n, f->index_base,
                                        f->view_visible[v], f->view_visible_count[v], f->visible_scratch));
+    // ---- the model pass's draw records: behind the LOD pick (model.c:975-997), this frame's cur_lod ----
+    if (f->draw && f->draw->main.count) {
+        const clapgpu_frame_draw_pass *p = &f->draw->main;
+        FR(clapgpu_draw_records(stream, e, e->vis_mask, f->cur_lod, f->draw->order, f->draw->inputs, &p->pass, p->records,
+                                p->capacity, p->count, p->group_first, p->status, f->draw->scratch));
+    }
     // ---- the vertex shader's skinning loop for what the passes draw, at the LOD just picked (model.c:959-997) ----
     if (f->skin_select) {
         clapgpu_skin_select sel = *f->skin_select;

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "lm_dev.h"
 #include "views_dev.h"
+#include "draw_dev.h"
 
 #ifdef CLAPGPU_EXPERIMENT               // an A/B or sensitivity build (common.h): never loadable as the product
 #define ABI_EXPERIMENT_BIT 0x80000000u
@@ -265,6 +266,50 @@ extern "C" void clapgpu_lights_update_host(const clapgpu_entities *e, uint32_t m
             memcpy(source->slot[vs].quat, q, 4 * sizeof(float));
         }
     }
+}
+
+// model.c:784-1050 (draw_dev.h: the statements the kernels of draw.hip share), txmodel by txmodel, entity by entity
+extern "C" void clapgpu_draw_records_host(const clapgpu_entities *e, const uint64_t *vis_mask, const int32_t *lod,
+                                          const clapgpu_draw_order *o, const clapgpu_draw_inputs *inputs,
+                                          const clapgpu_draw_pass *pass, clapgpu_draw_record *records, uint32_t capacity,
+                                          uint32_t *count, uint32_t *group_first, uint32_t *status)
+{
+    if (draw_check(e, vis_mask, o, pass, records, capacity, count, group_first, status)) return;
+    *count = 0;
+    *status = 0;
+    for (uint32_t g = 0; g <= o->n_groups; g++) group_first[g] = 0;
+    if (o->n_order == 0 || e->n == 0) return;
+    bool bad = o->group_start[0] != 0u || o->group_start[o->n_groups] != o->n_order;
+    for (uint32_t g = 0; g < o->n_groups && !bad; g++) bad = o->group_start[g] > o->group_start[g + 1];
+    for (uint32_t r = 0; r < o->n_order && !bad; r++) bad = o->order[r] >= e->n;
+    if (bad) { *status = CLAPGPU_DRAW_INVALID; return; }
+    clapgpu_draw_inputs in;
+    memset(&in, 0, sizeof(in));
+    if (inputs) in = *inputs;
+    uint32_t total = 0;
+    for (uint32_t g = 0; g < o->n_groups; g++) {
+        group_first[g] = total;
+        if (draw_group_skipped(o->group_flags[g], pass->flags)) continue;
+        uint32_t nr_characters = 0;
+        for (uint32_t r = o->group_start[g]; r < o->group_start[g + 1]; r++) {
+            const uint32_t i = o->order[r];
+            if (!draw_entity_drawn(vis_mask, e->flags, i)) continue;
+            if (draw_counts_character(in.draw_flags ? in.draw_flags[i] : 0u, pass->mq_nr_characters)) nr_characters++;
+            if (total < capacity) {
+                clapgpu_draw_record *rec = records + total;
+                const DrawTail t = draw_tail(in, *pass, lod, i, g, nr_characters);
+                memcpy(rec->mx, e->mx + 16 * (size_t)i, 64);
+                memcpy(rec->inv_mx, e->inv_mx + 16 * (size_t)i, 64);
+                if (in.color) memcpy(rec->color, in.color + 4 * (size_t)i, 16);
+                else memset(rec->color, 0, 16);
+                memcpy(&rec->bloom_intensity, t.w, sizeof(t.w));
+            }
+            total++;
+        }
+    }
+    group_first[o->n_groups] = total;
+    *count = total;
+    if (total > capacity) *status = CLAPGPU_DRAW_CAPPED;
 }
 
 // light.c:404-408, view.c:178-193: fov = cutoff * zoom (1.0f), aspect = (float)1 / (float)1, planes 0.1f and 200.0f

@@ -21,7 +21,7 @@ class FrameLoop:
     def __init__(self, batch, cam, world=None, feed=None, body_links=None, lights=None, characters=None,
                  particles=None, contacts=False, pose_readers=("trs", "joint_pos"), prebin=False, islands=False, solve=False,
                  move=None, aniq=None, skin_select=None, views_dev=False, camera=None, camera_index=False, cascades=None,
-                 bv_result=None, bv_ctl_entity=None, view_lists=False):
+                 bv_result=None, bv_ctl_entity=None, view_lists=False, draw=None):
         """batch: EntityBatch.  world: PhysWorld (dynamic bodies write their entities through
         body_entity; character bodies have body_entity = -1).  feed: CharacterFeed.  body_links:
         (link_body, link_entity) of characters / static colliders whose rotation follows the entity.
@@ -70,7 +70,10 @@ class FrameLoop:
         matrices=[(any view matrix, lights.spot_persp(cutoff, z01), z01)])), and from the first frame on those slots of
         the source are the device's.  view_lists: the frame also
         writes the ordered list of every further view (clapgpu_frame.view_visible: batch.view_visible[v] /
-        batch.view_visible_count[v]), the shadow passes' lists."""
+        batch.view_visible_count[v]), the shadow passes' lists.  draw: a draw.FrameDraw: the frame also leaves every
+        pass's draw records in render order (clapgpu_frame.draw) -- the further views' ahead of the LOD pick, with the
+        LODs the previous frame left, the main pass's behind it."""
+        self.draw = draw
         islands = islands or solve
         self.view_lists = view_lists
         self.move, self.move_dt = move, 0.0
@@ -273,6 +276,10 @@ class FrameLoop:
                 f.view_visible[v], f.view_visible_count[v] = b.view_visible[v].data_ptr(), b.view_visible_count[v].data_ptr()
         f.force_lod = b.force_lod.data_ptr() if b.force_lod is not None else None
         f.cur_lod, f.draw_lod = b.cur_lod.data_ptr(), b.draw_lod.data_ptr()
+        if self.draw is not None:                               # every pass's draw records
+            dd = self.draw.desc()
+            keep.append(dd)
+            f.draw = C.pointer(dd)
         self._desc, self._keep = f, keep
         return f
 

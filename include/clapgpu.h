@@ -58,7 +58,7 @@ void clapgpu_test_fail_after(int launches);
 /* ABI version: bumped whenever a signature or struct below changes.  CLAPGPU_ABI_VERSION is the version this header
  * describes; a caller compares clapgpu_abi_version() of the library it loaded with it before any other call and refuses
  * anything else (an experiment build reports its version with the top bit set, so it is refused too). */
-#define CLAPGPU_ABI_VERSION 52u
+#define CLAPGPU_ABI_VERSION 53u
 uint32_t clapgpu_abi_version(void);
 
 int clapgpu_malloc(void **dev, size_t bytes);
@@ -2327,6 +2327,170 @@ void clapgpu_lights_update_host(const clapgpu_entities *e, uint32_t mode, const 
 void clapgpu_spot_persp(float cutoff, int ndc_z_zero_one, float proj[16]);
 
 /* ======================================================================== */
+/* Draw records on the device (ABI 53)                                       */
+/* ======================================================================== */
+
+/*
+ * What _models_render (core/model.c:742-1086) sets per drawn entity, for one render pass, in the order it draws: txmodel
+ * by txmodel in list order (model.c:784) and inside a txmodel in the order of its entity list (model.c:959).  The
+ * frame's visible list is in device index order and carries no uniforms; clapgpu_draw_records leaves one fixed-size
+ * record per draw in the reference's order, and the range of every txmodel, so a renderer reads device buffers and no
+ * host pass walks what is drawn.
+ *
+ * clapgpu_draw_order is a HOST struct of DEVICE pointers, static while the topology stands (the caller builds it where
+ * it builds tile_row_start): the walk of model.c:784 / :959 flattened.  order[r] is the entity at render position r;
+ * entities that belong to no txmodel (padding lanes) are simply absent.  group_start[g] .. group_start[g + 1] are the
+ * positions of txmodel g: ascending, group_start[0] == 0, group_start[n_groups] == n_order; an empty group is legal.
+ * group_flags[g] has CLAPGPU_DRAW_GROUP_SKIP_SHADOW where model3d.skip_shadow is set.
+ *
+ * clapgpu_draw_inputs is a HOST struct of DEVICE pointers indexed by ENTITY, so that entity3d_color() and friends stay
+ * one store.  Any of them may be NULL: zeros then, and -1 for character.
+ *
+ * clapgpu_draw_pass holds HOST values: what models_render_options says about the pass.
+ *
+ * THE RULE, followed by the kernels and by the host twin through the same functions (csrc/draw_dev.h):
+ *   which groups draw (model.c:786): a group with CLAPGPU_DRAW_GROUP_SKIP_SHADOW emits nothing in a pass with
+ *       CLAPGPU_DRAW_PASS_SHADOW (opts->shader_override).
+ *   which positions draw (model.c:960-973): position r is drawn iff bit order[r] of vis_mask is set -- the planes hold
+ *       ALIVE && VISIBLE && (SKIP_CULLING || in the view's frustum) -- or, with vis_mask == NULL (the pass without a
+ *       view, model.c:969-970: `view &&`), iff flags[order[r]] has CLAPGPU_E_ALIVE and CLAPGPU_E_VISIBLE.  The records
+ *       are the drawn positions in ascending r.  (nr_ents, model.c:1049, is *count.)
+ *   group_first[g] is the number of records in front of group g; group_first[n_groups] == *count, the total.
+ *   mx, inv_mx (model.c:1027-1028), color and color_pt (model.c:1017-1018) are moved as 32-bit words: NaN payloads
+ *       survive, this is a copy and not arithmetic.
+ *   lod = lod[i] (model.c:993-997, 1042: e->cur_lod), or 0 with lod == NULL; character = character[i]; group = g;
+ *       entity = index_base + i.
+ *   bloom intensity (model.c:1000-1003): if (double)fabsf(e.bloom_intensity) > 1e-3 the entity's value, else with
+ *       CLAPGPU_DRAW_PASS_HAS_ROPTS (`else if (ropts)`) the pass's; in both cases CLAPGPU_DRAW_SET_BLOOM_INTENSITY is
+ *       set in the record's flags.  Otherwise the field is 0 and the bit clear: the reference leaves the uniform at
+ *       whatever the previous draw set, and a consumer has to know that.  The comparison is the reference's: the float
+ *       promoted to double against the double constant 1e-3, so (float)1e-3, which lies above it, passes and the float
+ *       below it does not; a NaN does not pass.
+ *   bloom threshold (model.c:1005-1008): the same rule, CLAPGPU_DRAW_SET_BLOOM_THRESHOLD.
+ *   edge_mode (model.c:1010-1016, shader_constants.h:57-62): CLAPGPU_DRAW_OUTLINE_EXCLUDE gives EDGE_EXCLUDE, 1u << 7;
+ *       with CLAPGPU_DRAW_IS_CHARACTER and mq_nr_characters != 0 it also gets (k & 15u), k the 1-based ordinal of this
+ *       draw among the DRAWN characters of its group in render order (nr_characters restarts per txmodel, model.c:956,
+ *       and counts only what passed the cull): the 16th drawn character of a txmodel gets 0, the 17th 1.
+ *   the three words at offset 180 are zero.
+ * Not produced: the LOD's buffer binds (a consumer compares lod with the record in front), joint_transforms (the
+ * record's character indexes the pose batch), the particle instance count.  Alpha-blended models are not sorted; the
+ * reference does not sort either.
+ *
+ * Capacity: records at or past `capacity` are not written; *count still holds the total, group_first is complete and
+ * *status has CLAPGPU_DRAW_CAPPED.  What the host cannot see it cannot refuse: an order[r] >= entities->n, a
+ * group_start that does not ascend, does not start at 0 or does not end at n_order give *status = CLAPGPU_DRAW_INVALID,
+ * *count = 0, group_first all zeros and nothing else written (the rule of CLAPGPU_SPOTS_INVALID).
+ */
+#define CLAPGPU_DRAW_GROUP_SKIP_SHADOW   1u  /* group_flags: model3d.skip_shadow */
+#define CLAPGPU_DRAW_IS_CHARACTER        1u  /* draw_flags: ENTITY3D_IS_CHARACTER */
+#define CLAPGPU_DRAW_OUTLINE_EXCLUDE     2u  /* draw_flags: e->outline_exclude */
+#define CLAPGPU_DRAW_PASS_SHADOW         1u  /* pass flags: opts->shader_override */
+#define CLAPGPU_DRAW_PASS_HAS_ROPTS      2u  /* pass flags: opts->render_options != NULL */
+#define CLAPGPU_DRAW_SET_BLOOM_INTENSITY 1u  /* record flags: this draw sets the uniform */
+#define CLAPGPU_DRAW_SET_BLOOM_THRESHOLD 2u
+#define CLAPGPU_DRAW_CAPPED              1u  /* status */
+#define CLAPGPU_DRAW_INVALID             2u  /* status */
+
+typedef struct clapgpu_draw_order {
+    uint32_t        n_order, n_groups;
+    const uint32_t *order;              /* [n_order] entity at render position r */
+    const uint32_t *group_start;        /* [n_groups + 1] */
+    const uint32_t *group_flags;        /* [n_groups] */
+} clapgpu_draw_order;
+
+typedef struct clapgpu_draw_inputs {
+    const float    *color;              /* [4n] e->color */
+    const int32_t  *color_pt;           /* [n] e->color_pt */
+    const float    *bloom_intensity;    /* [n] */
+    const float    *bloom_threshold;    /* [n] */
+    const uint32_t *draw_flags;         /* [n] CLAPGPU_DRAW_IS_CHARACTER | CLAPGPU_DRAW_OUTLINE_EXCLUDE */
+    const int32_t  *character;          /* [n] index into the pose batch, or -1 */
+} clapgpu_draw_inputs;
+
+typedef struct clapgpu_draw_pass {
+    uint32_t flags;                     /* CLAPGPU_DRAW_PASS_* */
+    float    bloom_intensity;           /* ropts->bloom_intensity */
+    float    bloom_threshold;           /* ropts->bloom_threshold */
+    uint32_t mq_nr_characters;          /* mq->nr_characters */
+    uint32_t index_base;
+} clapgpu_draw_pass;
+
+typedef struct clapgpu_draw_record {    /* three 64-byte lines */
+    float    mx[16];                    /*   0 UNIFORM_TRS */
+    float    inv_mx[16];                /*  64 UNIFORM_INVERSE_TRS */
+    float    color[4];                  /* 128 UNIFORM_IN_COLOR */
+    float    bloom_intensity;           /* 144 */
+    float    bloom_threshold;           /* 148 */
+    uint32_t edge_mode;                 /* 152 UNIFORM_EDGE_MODE */
+    int32_t  color_pt;                  /* 156 UNIFORM_COLOR_PASSTHROUGH */
+    uint32_t entity;                    /* 160 index_base + i */
+    int32_t  lod;                       /* 164 */
+    uint32_t group;                     /* 168 */
+    int32_t  character;                 /* 172 */
+    uint32_t flags;                     /* 176 CLAPGPU_DRAW_SET_* */
+    uint32_t zero[3];                   /* 180 */
+} clapgpu_draw_record;
+
+#define CLAPGPU_DRAW_RECORD_BYTES 192
+#ifdef __cplusplus
+#define CLAPGPU_DRAW_ASSERT(c) static_assert(c, "the draw record's layout is ABI")
+#else
+#define CLAPGPU_DRAW_ASSERT(c) _Static_assert(c, "the draw record's layout is ABI")
+#endif
+CLAPGPU_DRAW_ASSERT(sizeof(clapgpu_draw_record) == CLAPGPU_DRAW_RECORD_BYTES);
+CLAPGPU_DRAW_ASSERT(offsetof(clapgpu_draw_record, inv_mx) == 64 && offsetof(clapgpu_draw_record, color) == 128);
+CLAPGPU_DRAW_ASSERT(offsetof(clapgpu_draw_record, bloom_intensity) == 144 && offsetof(clapgpu_draw_record, bloom_threshold) == 148);
+CLAPGPU_DRAW_ASSERT(offsetof(clapgpu_draw_record, edge_mode) == 152 && offsetof(clapgpu_draw_record, color_pt) == 156);
+CLAPGPU_DRAW_ASSERT(offsetof(clapgpu_draw_record, entity) == 160 && offsetof(clapgpu_draw_record, lod) == 164);
+CLAPGPU_DRAW_ASSERT(offsetof(clapgpu_draw_record, group) == 168 && offsetof(clapgpu_draw_record, character) == 172);
+CLAPGPU_DRAW_ASSERT(offsetof(clapgpu_draw_record, flags) == 176 && offsetof(clapgpu_draw_record, zero) == 180);
+
+/* Bytes of device scratch (256-byte aligned) a call with these sizes needs: the render-space masks, their row counts and
+ * prefixes, the per-group character counts.  Never 0. */
+size_t clapgpu_draw_records_scratch_bytes(uint32_t n_order, uint32_t n_groups);
+/* Three launches (render-space masks; prefixes per group; record fill), no allocation, no host synchronisation: it can
+ * be captured.  entities: n, mx and inv_mx are read, and flags when vis_mask is NULL.  vis_mask: any entity-space plane
+ * of ceil(n / 64) words (entities->vis_mask, a plane of entities->views), or NULL: the pass without a view.  lod: the
+ * per-entity cur_lod array, NULL: 0.  inputs may be NULL (every array absent).  records: [capacity], 64-byte aligned.
+ * count, status: one device word each; group_first: [n_groups + 1] device words.  scratch: 256-byte aligned,
+ * clapgpu_draw_records_scratch_bytes(n_order, n_groups).  Refused with CLAPGPU_ERR_INVALID_ARGUMENTS before any HIP
+ * call: a NULL entities / order / pass / count / group_first / status; NULL records with capacity > 0; a misaligned
+ * records or scratch, or a NULL scratch; entities without mx / inv_mx (or without flags beside a NULL vis_mask);
+ * n_order > 0 with a NULL order->order or n_groups == 0; n_groups > 0 with a NULL group_start / group_flags.
+ * n_order == 0 or entities->n == 0 still leaves *count = 0, *status = 0 and a zeroed group_first. */
+int clapgpu_draw_records(void *stream, const clapgpu_entities *entities, const uint64_t *vis_mask, const int32_t *lod,
+                         const clapgpu_draw_order *order, const clapgpu_draw_inputs *inputs, const clapgpu_draw_pass *pass,
+                         clapgpu_draw_record *records, uint32_t capacity, uint32_t *count, uint32_t *group_first,
+                         uint32_t *status, void *scratch);
+/* The host twin: the kernels' own decision functions over HOST pointers (every struct as above with host arrays; no
+ * stream, no scratch).  Arguments the device call refuses make it return without writing. */
+void clapgpu_draw_records_host(const clapgpu_entities *entities, const uint64_t *vis_mask, const int32_t *lod,
+                               const clapgpu_draw_order *order, const clapgpu_draw_inputs *inputs, const clapgpu_draw_pass *pass,
+                               clapgpu_draw_record *records, uint32_t capacity, uint32_t *count, uint32_t *group_first,
+                               uint32_t *status);
+
+/* One pass's outputs inside a frame: the arguments of clapgpu_draw_records behind `inputs`.  A block with count == NULL
+ * is not issued.  NULL records with capacity == 0 and a count is legal: counts and ranges only. */
+typedef struct clapgpu_frame_draw_pass {
+    clapgpu_draw_pass    pass;
+    uint32_t             capacity;
+    clapgpu_draw_record *records;       /* device */
+    uint32_t            *count;         /* device */
+    uint32_t            *group_first;   /* device */
+    uint32_t            *status;        /* device */
+} clapgpu_frame_draw_pass;
+
+/* clapgpu_frame.draw: a HOST struct.  main is the model pass over entities->vis_mask; view[v] is the pass of further
+ * view v over entities->views->vis_mask[v] (the shadow passes).  scratch is shared: the passes run one after the other. */
+typedef struct clapgpu_frame_draw {
+    const clapgpu_draw_order  *order;
+    const clapgpu_draw_inputs *inputs;  /* may be NULL */
+    clapgpu_frame_draw_pass    main;
+    clapgpu_frame_draw_pass    view[CLAPGPU_EXTRA_VIEWS_MAX];
+    void                      *scratch; /* device, clapgpu_draw_records_scratch_bytes(order->n_order, order->n_groups) */
+} clapgpu_frame_draw;
+
+/* ======================================================================== */
 /* One frame (core/clap.c:551-665)                                           */
 /* ======================================================================== */
 
@@ -2459,6 +2623,16 @@ typedef struct clapgpu_frame {
      * (These fields stand in front of `camera`, as the cascades' do: the descriptor's version is CLAPGPU_ABI_VERSION.) */
     const clapgpu_spots        *spots;
     uint32_t *view_visible[CLAPGPU_EXTRA_VIEWS_MAX], *view_visible_count[CLAPGPU_EXTRA_VIEWS_MAX];
+    /* draw records on the device (ABI 53); draw NULL: the frame as before, launch for launch.  Set: it needs a main view
+     * (frustum or views_state), draw->order, draw->scratch, and for every further view's block with a count
+     * v < entities->views->n: CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, before any launch, as for anything
+     * clapgpu_draw_records itself refuses.  The further views' records are issued BEHIND THE CULL AND AHEAD OF the visible
+     * list and the LOD pick: pipeline_render runs the shadow passes before the model pass (pipeline-builder.c:246-272),
+     * and without a camera they draw with the cur_lod the last model pass left (model.c:975) -- clapgpu_draw_records(
+     * entities, views->vis_mask[v], cur_lod, order, inputs, &view[v].pass, ...).  The main pass's records are issued
+     * BEHIND the LOD pick, over entities->vis_mask with lod = cur_lod: this frame's LODs.  skin_select stays last.
+     * (The field stands in front of `camera`, as the spots' do.) */
+    const clapgpu_frame_draw   *draw;
     /* the camera controller on the device (ABI 50); camera NULL: the frame as before, launch for launch (camera_bp is not
      * read).  Set: it needs views_source and views_state (CLAPGPU_ERR_INVALID_ARGUMENTS otherwise, before any launch),
      * and writes slot 0 of views_source.  The rays see body_geoms, or the geoms of bodies when that is NULL, or no body,
